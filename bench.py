@@ -10,6 +10,12 @@ the C ABI (mpcx_allgather_u) on the solve stream; weak scaling.  Prints ONE JSON
                                                 # launch the ranks, then RANK/WORLD_SIZE come from the environment
   python bench.py --config 4 --gpus 8           # quadrotor N=50, 32768 per GPU (262144 on 8), 8 MiB all-gather
   python bench.py --workload ugv|osc8|vanderpol|osc6   # the NLMPC configs (3, 5, 1) under the same contract
+  python bench.py --full                        # also the legs around the headline: roofline and per-kernel times, CPU baseline,
+                                                # latency, pipelined streams, the NLMPC configs, the multi-GPU configs
+  python bench.py --dump-outputs DIR            # after the timed steps: what the last step returned, as DIR/<name>.npy (float64)
+
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit, ms_per_step, ...); everything
+else it can measure runs only with --full.
 """
 import argparse
 import hashlib
@@ -183,13 +189,18 @@ def main():
                     help="lmpc = quadrotor LMPC N=20 (config 2, the default); lmpc50 = N=50 (config 4); the others are NLMPC")
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU")
     ap.add_argument("--horizon", type=int, default=None, help="LMPC prediction horizon (overrides the workload's)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (0 = skip)")
-    ap.add_argument("--nlmpc-extra", type=int, default=1, help="default (LMPC) workload: append the NLMPC configs' quick figures as the `nlmpc` key (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what surrounds it: roofline and per-kernel times, CPU baseline, step latency, "
+                         "pipelined streams, the NLMPC configs' figures, the multi-GPU configs (off: the timed steps and the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (the arrays its caller receives) to DIR/<name>.npy, float64, 64 MB at most")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--nlmpc-extra", type=int, default=1, help="with --full, default (LMPC) workload: append the NLMPC configs' quick figures as the `nlmpc` key (0 = skip)")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the timed steps rotate over (each with its own controller handle, workspace and outputs); "
                          "1 = strictly serial steps (default: what `value`, the roofline and the rocprof trace refer to)")
     ap.add_argument("--pipeline-streams", type=int, default=3,
-                    help="extra leg after the timed region: the same steps rotated over this many streams, reported as "
+                    help="with --full, extra leg after the timed region: the same steps rotated over this many streams, reported as "
                          "`pipelined` (0 = skip)")
     args = ap.parse_args()
     workload, batch = CONFIGS[args.config] if args.config else ("lmpc", 4096)
@@ -268,6 +279,24 @@ def timed(step, steps, warmup, barrier, world, dev):
     return dt
 
 
+DUMP_LIMIT_BYTES = 63 << 20          # the arrays; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the result arrays of the last timed step, one <path>/<name>.npy each, in float64 (the integer fields convert
+    exactly).  Above 64 MB in all, every array keeps the same seeded sample of its rows, so that two builds still compare row for row."""
+    torch.cuda.synchronize()
+    host = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in arrays.items() if v is not None and not k.startswith("_")}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        for k, a in host.items():
+            rows = np.random.default_rng(0).choice(a.shape[0], max(1, a.shape[0] * DUMP_LIMIT_BYTES // total), replace=False)
+            host[k] = a[np.sort(rows)]
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def multi_gpu_configs(world, rank, local, dev, gather, barrier):
     """BASELINE.json's two multi-GPU configs in the line of the DEFAULT multi-GPU command (`bench.py --gpus N`, which weak-scales the headline
     config 2): config 4 (quadrotor LMPC N = 50, 32768 instances per rank) and config 5 (eight oscillators, 1024 per rank), batch-sharded with the
@@ -339,6 +368,24 @@ def run_lmpc(args, ph, B, steps, warmup, world, rank, local, dev, gather, barrie
         return r_k.cmd
 
     dt = timed(step, steps, warmup, barrier, world, dev)
+    if args.dump_outputs and rank == 0:
+        _, _, r_last, _, _, all_last = lanes[(counter[0] - 1) % ns]
+        dump_outputs(args.dump_outputs, dict(vars(r_last), cmd_allgather=all_last))
+    total = world * B * steps
+    out = {"metric": "MPC solves/sec (whole node) + p50 solve latency, quadrotor LMPC N=%d batch=%d" % (ph, B),
+           "value": total / dt, "unit": "solves/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+           "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "quadrotor_ex.cpp LMPC nx=12 nu=4 ny=12 ph=ch=%d, batch %d per GPU, "
+                                  "SplitMix64 x0/u0/yref (SURVEY 8d), maximum_iteration=250" % (ph, B),
+                      "parallelism": ("batch-sharded x%d, RCCL all-gather of u* (%d x 4 doubles) through mpcx_allgather_u"
+                                      % (world, world * B)) if gather else "single GPU",
+                      "rccl_ranks": gather.world if gather else 0, "streams": ns},
+           "solved_fraction": float((res.status == 0).double().mean())}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        return
     serial = None
     if gather:
         # The collective off the solve stream: step k's all-gather (latency-bound, tens of microseconds over xGMI) travels on a second
@@ -497,22 +544,11 @@ def run_lmpc(args, ph, B, steps, warmup, world, rank, local, dev, gather, barrie
                          f"figures from the first {n1} instances",
                "single_thread_value": n1 / rr["seconds"],
                "p50_ms": float(ps[len(ps) // 2] * 1e3), "p99_ms": float(ps[int(len(ps) * 0.99) - 1] * 1e3)}
-    total = world * B * steps
-    out = {"metric": "MPC solves/sec (whole node) + p50 solve latency, quadrotor LMPC N=%d batch=%d" % (ph, B),
-           "value": total / dt, "unit": "solves/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-           "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "quadrotor_ex.cpp LMPC nx=12 nu=4 ny=12 ph=ch=%d, batch %d per GPU, "
-                                  "SplitMix64 x0/u0/yref (SURVEY 8d), maximum_iteration=250" % (ph, B),
-                      "parallelism": ("batch-sharded x%d, RCCL all-gather of u* (%d x 4 doubles) through mpcx_allgather_u"
-                                      % (world, world * B)) if gather else "single GPU",
-                      "rccl_ranks": gather.world if gather else 0, "streams": ns},
-           "p50_step_latency_ms": lat_p50,
-           "p50_step_latency_graph_ms": lat_graph,
-           "pipelined": pipelined,
-           "allgather_overlapped": serial,
-           "solved_fraction": float((status == 0).mean()),
-           "roofline": roof, "cpu_baseline": cpu}
+    out.update({"p50_step_latency_ms": lat_p50,
+                "p50_step_latency_graph_ms": lat_graph,
+                "pipelined": pipelined,
+                "allgather_overlapped": serial,
+                "roofline": roof, "cpu_baseline": cpu})
     if mgc:
         out["multi_gpu_configs"] = mgc
     if world == 1 and args.nlmpc_extra:
@@ -545,6 +581,19 @@ def run_lmpc_hetero(args, ph, B, steps, warmup, world, rank, local, dev, gather,
 
     dt = timed(step, steps, warmup, barrier, world, dev)
     if rank != 0:
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(vars(res), cmd_allgather=all_k))
+    total = world * B * steps
+    out = {"metric": "MPC solves/sec (whole node), quadrotor LMPC N=%d, every instance its own controller, batch=%d" % (ph, B),
+           "value": total / dt, "unit": "solves/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+           "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "quadrotor LMPC nx=12 nu=4 ny=12 ph=ch=%d, %d controllers (quadrotor_variant: own dynamics, weights, limits), one "
+                                  "instance each per GPU, SplitMix64 x0/u0/yref" % (ph, B),
+                      "parallelism": ("batch-sharded x%d" % world) if gather else "single GPU", "rccl_ranks": gather.world if gather else 0},
+           "solved_fraction": float((res.status == 0).double().mean())}
+    if not args.full:
+        print(json.dumps(out))
         return
     ms = het.time_launches(b, mi, max(10, min(steps, 100)), stream)
     torch.cuda.synchronize()
@@ -593,14 +642,7 @@ def run_lmpc_hetero(args, ph, B, steps, warmup, world, rank, local, dev, gather,
                "sample": f"{done} solves in {t_all:.1f} s: {ncores} worker processes (one per host core), each on its own {per_core} instances of the same "
                          f"batch, every instance on the C oracle of its own controller (one controller object per problem, configured outside the "
                          f"timed loop; set-up per solve as LOptimizer::run)"}
-    total = world * B * steps
-    out = {"metric": "MPC solves/sec (whole node), quadrotor LMPC N=%d, every instance its own controller, batch=%d" % (ph, B),
-           "value": total / dt, "unit": "solves/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-           "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "quadrotor LMPC nx=12 nu=4 ny=12 ph=ch=%d, %d controllers (quadrotor_variant: own dynamics, weights, limits), one "
-                                  "instance each per GPU, SplitMix64 x0/u0/yref" % (ph, B),
-                      "parallelism": ("batch-sharded x%d" % world) if gather else "single GPU", "rccl_ranks": gather.world if gather else 0},
-           "solved_fraction": float((status == 0).mean()), "roofline": roof, "set_up": setup, "cpu_baseline": cpu}
+    out.update({"roofline": roof, "set_up": setup, "cpu_baseline": cpu})
     print(json.dumps(out))
 
 
@@ -724,6 +766,24 @@ def run_nlmpc(args, name, B, steps, warmup, world, rank, local, dev, gather, bar
     dt = timed(step, steps, warmup, barrier, world, dev)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(out, cmd_allgather=all_u))
+    st = out["solver_status"].cpu().numpy()
+    label = {"vanderpol": "vanderpol_ex.cpp NLMPC nx=2 nu=1 ph=10 ch=5 (config 1)",
+             "ugv": "ugv_ex.cpp NLMPC nx=4 nu=2 ph=ch=30, soft constraints (config 3)",
+             "osc6": "networked_oscillators_ex.cpp NLMPC 6 oscillators nx=12 nu=6 ph=20 ch=10 (the reference example)",
+             "osc8": "networked_oscillators_ex.cpp NLMPC 8 oscillators nx=16 nu=8 ph=30 ch=15 (config 5)"}[name]
+    o = {"metric": "MPC solves/sec (whole node), %s batch=%d" % (name, B), "value": world * B * steps / dt, "unit": "solves/s",
+         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
+         "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+         "config": {"workload": label + ", batch %d per GPU, cold starts" % B,
+                    "parallelism": ("batch-sharded x%d, RCCL all-gather of u* through mpcx_allgather_u" % world) if gather else "single GPU",
+                    "rccl_ranks": gather.world if gather else 0},
+         "solved_fraction": float(np.isin(st, (3, 4)).mean()),
+         "solver_status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)}}
+    if not args.full:
+        print(json.dumps(o))
+        return
     kern_ms = c.time_launches(b, max(1, min(steps, 5)), stream.cuda_stream)       # HIP events on the launch stream
     torch.cuda.synchronize()
     st = out["solver_status"].cpu().numpy(); it = out["iterations"].cpu().numpy().astype(np.float64)
@@ -760,19 +820,7 @@ def run_nlmpc(args, name, B, steps, warmup, world, rank, local, dev, gather, bar
                          f"instance(s) of the same batch; compiled baseline = the reference's callbacks restated in C "
                          f"(oracle/nlmpc_callbacks.c: forward / central differences as Objective.hpp:198-265, Constraints.hpp:641-905) "
                          f"driving SLSQP (scipy's compiled Kraft code, which NLopt's LD_SLSQP translates), cold starts, 150 iterations at most"}
-    label = {"vanderpol": "vanderpol_ex.cpp NLMPC nx=2 nu=1 ph=10 ch=5 (config 1)",
-             "ugv": "ugv_ex.cpp NLMPC nx=4 nu=2 ph=ch=30, soft constraints (config 3)",
-             "osc6": "networked_oscillators_ex.cpp NLMPC 6 oscillators nx=12 nu=6 ph=20 ch=10 (the reference example)",
-             "osc8": "networked_oscillators_ex.cpp NLMPC 8 oscillators nx=16 nu=8 ph=30 ch=15 (config 5)"}[name]
-    o = {"metric": "MPC solves/sec (whole node), %s batch=%d" % (name, B), "value": world * B * steps / dt, "unit": "solves/s",
-         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
-         "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-         "config": {"workload": label + ", batch %d per GPU, cold starts" % B,
-                    "parallelism": ("batch-sharded x%d, RCCL all-gather of u* through mpcx_allgather_u" % world) if gather else "single GPU",
-                    "rccl_ranks": gather.world if gather else 0},
-         "solved_fraction": float(np.isin(st, (3, 4)).mean()),
-         "solver_status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)},
-         "roofline": roof, "cpu_baseline": cpu}
+    o.update({"roofline": roof, "cpu_baseline": cpu})
     print(json.dumps(o))
 
 

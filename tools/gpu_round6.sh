@@ -25,17 +25,17 @@ timeout 600 tools/profile_sq.sh $T lmpchetero20_b4096 --workload lmpc-hetero --s
 timeout 600 tools/profile_sq.sh $T ugv_b256 --workload ugv --batch 256 --steps 3 --warmup 1 > $O/${T}_sq_ugv256.log 2>&1
 timeout 600 tools/profile_sq.sh $T osc8_b256 --workload osc8 --batch 256 --steps 3 --warmup 1 > $O/${T}_sq_osc8256.log 2>&1
 cp $O/${T}_pmc_traffic_*.json $O/${T}_sq_*.json $O/${T}_kernel_trace_stats_*.txt profiles/ 2>/dev/null
-( timeout 300 python bench.py --steps 200 --warmup 20 ) > $O/${T}_bench_lmpc20.json 2> $O/${T}_bench_lmpc20.err; cut -c1-300 $O/${T}_bench_lmpc20.json
-( MPCX_FORCE_DIST=1 timeout 400 python bench.py --steps 200 --warmup 20 --cpu-seconds 0 --pipeline-streams 0 --nlmpc-extra 0 ) 2> $O/${T}_bench_lmpc20_rccl1.err | grep "^{" > $O/${T}_bench_lmpc20_rccl1.json; cut -c1-200 $O/${T}_bench_lmpc20_rccl1.json
-( MPCX_FORCE_DIST=1 timeout 300 python bench.py --config 4 --steps 20 --warmup 3 --cpu-seconds 0 --pipeline-streams 0 ) 2> $O/${T}_bench_lmpc50_rccl1.err | grep "^{" > $O/${T}_bench_lmpc50_rccl1.json; cut -c1-200 $O/${T}_bench_lmpc50_rccl1.json
-( MPCX_FORCE_DIST=1 timeout 300 python bench.py --config 5 --cpu-seconds 0 ) 2> $O/${T}_bench_osc8_rccl1.err | grep "^{" > $O/${T}_bench_osc8_rccl1.json; cut -c1-200 $O/${T}_bench_osc8_rccl1.json
-( timeout 300 python bench.py --config 4 --steps 20 --warmup 3 --cpu-seconds 0 --pipeline-streams 0 ) > $O/${T}_bench_lmpc50.json 2> $O/${T}_bench_lmpc50.err; cut -c1-200 $O/${T}_bench_lmpc50.json
-( timeout 300 python bench.py --workload lmpc-hetero --steps 50 --warmup 5 ) > $O/${T}_bench_lmpchetero.json 2> $O/${T}_bench_lmpchetero.err; cut -c1-200 $O/${T}_bench_lmpchetero.json
+( timeout 300 python bench.py --full --steps 200 --warmup 20 ) > $O/${T}_bench_lmpc20.json 2> $O/${T}_bench_lmpc20.err; cut -c1-300 $O/${T}_bench_lmpc20.json
+( MPCX_FORCE_DIST=1 timeout 400 python bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --pipeline-streams 0 --nlmpc-extra 0 ) 2> $O/${T}_bench_lmpc20_rccl1.err | grep "^{" > $O/${T}_bench_lmpc20_rccl1.json; cut -c1-200 $O/${T}_bench_lmpc20_rccl1.json
+( MPCX_FORCE_DIST=1 timeout 300 python bench.py --full --config 4 --steps 20 --warmup 3 --cpu-seconds 0 --pipeline-streams 0 ) 2> $O/${T}_bench_lmpc50_rccl1.err | grep "^{" > $O/${T}_bench_lmpc50_rccl1.json; cut -c1-200 $O/${T}_bench_lmpc50_rccl1.json
+( MPCX_FORCE_DIST=1 timeout 300 python bench.py --full --config 5 --cpu-seconds 0 ) 2> $O/${T}_bench_osc8_rccl1.err | grep "^{" > $O/${T}_bench_osc8_rccl1.json; cut -c1-200 $O/${T}_bench_osc8_rccl1.json
+( timeout 300 python bench.py --full --config 4 --steps 20 --warmup 3 --cpu-seconds 0 --pipeline-streams 0 ) > $O/${T}_bench_lmpc50.json 2> $O/${T}_bench_lmpc50.err; cut -c1-200 $O/${T}_bench_lmpc50.json
+( timeout 300 python bench.py --full --workload lmpc-hetero --steps 50 --warmup 5 ) > $O/${T}_bench_lmpchetero.json 2> $O/${T}_bench_lmpchetero.err; cut -c1-200 $O/${T}_bench_lmpchetero.json
 for w in vanderpol ugv osc6 osc8; do
-  ( timeout 600 python bench.py --workload $w ) > $O/${T}_bench_$w.json 2> $O/${T}_bench_$w.err; cut -c1-200 $O/${T}_bench_$w.json
+  ( timeout 600 python bench.py --full --workload $w ) > $O/${T}_bench_$w.json 2> $O/${T}_bench_$w.err; cut -c1-200 $O/${T}_bench_$w.json
 done
 for wb in "ugv 256" "osc8 256"; do set -- $wb
-  ( timeout 300 python bench.py --workload $1 --batch $2 --cpu-seconds 0 --steps 5 --warmup 1 ) > $O/${T}_bench_$1_b$2.json 2> $O/${T}_bench_$1_b$2.err; cut -c1-200 $O/${T}_bench_$1_b$2.json
+  ( timeout 300 python bench.py --full --workload $1 --batch $2 --cpu-seconds 0 --steps 5 --warmup 1 ) > $O/${T}_bench_$1_b$2.json 2> $O/${T}_bench_$1_b$2.err; cut -c1-200 $O/${T}_bench_$1_b$2.json
 done
 # lmpc_solve_group cut short (tools/group_cut.sh built libmpcx_cut{0..3}.so before this call): what each part of its assemble phase costs a launch
 if [ -f libmpc_amd/libmpcx_cut0.so ]; then

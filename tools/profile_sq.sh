@@ -24,7 +24,7 @@ i=0
 for P in "${PASSES[@]}"; do
   D=/tmp/sq_${WL}_$i; rm -rf $D
   # a counter set the hardware cannot schedule makes rocprofv3 abort and then hang in its signal handler: bound every pass
-  timeout -k 5 150 rocprofv3 --kernel-trace --pmc $P -d $D --output-format csv -- python bench.py "$@" --cpu-seconds 0 --pipeline-streams 0 > $OUT/${TAG}_sq_${WL}_pass$i.log 2>&1 || echo "pass $i failed: $P"
+  timeout -k 5 150 rocprofv3 --kernel-trace --pmc $P -d $D --output-format csv -- python bench.py --full "$@" --cpu-seconds 0 --pipeline-streams 0 > $OUT/${TAG}_sq_${WL}_pass$i.log 2>&1 || echo "pass $i failed: $P"
   DIRS="$DIRS $D"; i=$((i+1))
   python tools/pmc_summary.py $DIRS > $OUT/${TAG}_sq_${WL}.json 2>/dev/null
 done
