@@ -17,6 +17,9 @@ namespace mpcx {
 
 constexpr int kMaxActive = 28;          // working-set capacity of the in-kernel polish
 constexpr int kSld = kMaxActive + 1;    // LDS row stride of the Schur complement
+// capacity of the fallback polish's working-set lists (indices, bounds, multipliers): up to nz rows, the most independent rows the condensed
+// problem can have; the Schur complement of a set of more than kMaxActive rows goes to a device buffer of one nz x nz slot per wavefront
+__host__ __device__ inline int ws_capacity(int nz) { return nz > kMaxActive ? nz : kMaxActive; }
 
 struct LmpcDev {
     int nx, nu, ndu, ny, ph, ch, nf, nz, mg;
@@ -98,8 +101,13 @@ int lmpc_kernel_variant(int ldz, int ldg);     // -1 if the dimensions are not c
 // which: bit 0 = assemble, bit 1 = polish-only solve, bit 2 = ADMM fallback (7 = the normal path;
 // single bits are for per-kernel timing).  fast_variant: -1 = generic assemble kernel, 0/1 = MFMA
 // assemble kernel with shared / per-instance-constant output reference.
+// pbuf / pslots: the fallback kernel's buffer for working sets of more than kMaxActive rows, pslots slots of nz x nz doubles
+// (lmpc_fallback_slots); its grid is then capped at pslots wavefronts.  Null: such sets are left to ADMM.
 int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream,
-                int which = 7, int fast_variant = -1);
+                int which = 7, int fast_variant = -1, double *pbuf = nullptr, int pslots = 0);
+// slots of that buffer to allocate for batches of up to `batch` instances: one per wavefront the fallback kernel launches, at most what fits in
+// a fixed budget (at least one workgroup's)
+int lmpc_fallback_slots(const LmpcDev &m, int batch);
 int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len);
 // src: rows x K column-major (rows a multiple of 16, K of 4) -> out[((t G + g) 64 + lane) 4 + e] = src[(4 (4 g + e) + kq) rows + 16 t + j] with lane = 16 kq + j,
 // G = ceil(K / 16) k-step groups per row tile t (zero beyond K): what one wavefront's MFMA A operands of four k-steps look like in registers

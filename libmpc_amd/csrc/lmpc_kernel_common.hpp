@@ -188,9 +188,8 @@ __device__ MPCX_FUSED_RECORD_INLINE void fused_record(const LmpcDev &M, const Lm
     const int nx = M.nx, nu = M.nu, ny = M.ny, kin = M.kin;
     const int ldz = M.ldz, ldg = M.ldg, ldy = M.ldy, rowsF = M.rowsF;
     const int variant = Bt.fused - 1;
-    // vin: the same k -> (x0 | lastU | yref | 1) map as lmpc_assemble_mfma
-    if (lane < kin) {
-        const int k = lane;
+    // vin: the same k -> (x0 | lastU | yref | 1) map as lmpc_assemble_mfma (kin may exceed the 64 lanes: nx + nu + ny past 60)
+    for (int k = lane; k < kin; k += 64) {
         double v = 0.0;
         if (k < M.nxp) { if (k < nx) v = gl(Bt.x0)[(size_t)b * nx + k]; }
         else if (k < M.nxp + M.nup) { const int c = k - M.nxp; if (c < nu) v = gl(Bt.u0)[(size_t)b * nu + c]; }

@@ -516,7 +516,7 @@ __global__ __launch_bounds__(256) void lmpc_assemble_mfma(const LmpcDev *__restr
 // =====================================================================================
 template <int CPZ, int CPG, bool ADMM, bool FUSED = false>
 __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
-                          double *stage, double *nt0, double *arena, gdw ws, const double *mf_lds = nullptr)
+                          double *stage, double *nt0, double *arena, gdw ws, const double *mf_lds = nullptr, gdw bigS = nullptr)
 {
     constexpr int NZS = 2 * CPZ, NGS = 2 * CPG;
     const int nx = M.nx, nu = M.nu, ny = M.ny, ndu = M.ndu, ph = M.ph;
@@ -654,11 +654,14 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
 #pragma unroll
     for (int s = 0; s < NGS; ++s) gw[s] = gt0[s];
 
+    // working sets of up to kMaxActive rows are factored in this LDS arena; larger ones (up to nz rows, the most independent rows there
+    // can be) in bigS, this wavefront's nz x nz slot of a device buffer (null: not available, such a set is left to ADMM)
+    const int wcap = ws_capacity(nz);
     double *S = arena;                               // Schur complement, kMaxActive x kSld
-    double *lam = S + kMaxActive * kSld;             // rhs -> multipliers
-    double *wsb = lam + kMaxActive;                  // bound values of the working set
-    double *dg0 = wsb + kMaxActive;                  // original diagonal (pivot scale)
-    int *wsidx = reinterpret_cast<int *>(dg0 + kMaxActive);
+    double *lam = S + kMaxActive * kSld;             // rhs -> multipliers [wcap]
+    double *wsb = lam + wcap;                        // bound values of the working set [wcap]
+    double *dg0 = wsb + wcap;                        // original diagonal (pivot scale) [wcap]
+    int *wsidx = reinterpret_cast<int *>(dg0 + wcap);     // [wcap]
     double dtol_last = 0;
     int na_last = 0, rounds_total = 0;
 
@@ -685,7 +688,7 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                 hsh = (hsh ^ __ballot(actb[s] > 0)) * 0x94D049BB133111EBull;
                 const int pos = na + __popcll(mk & lt_mask);
                 posb[s] = pos;
-                if (act && pos < kMaxActive) { wsidx[pos] = e; wsb[pos] = actb[s] < 0 ? lw[s] : uw[s]; }
+                if (act && pos < wcap) { wsidx[pos] = e; wsb[pos] = actb[s] < 0 ? lw[s] : uw[s]; }
                 na += __popcll(mk);
             }
 #pragma unroll
@@ -697,10 +700,10 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                 hsh = (hsh ^ __ballot(actg[s] > 0)) * 0x94D049BB133111EBull;
                 const int pos = na + __popcll(mk & lt_mask);
                 posg[s] = pos;
-                if (act && pos < kMaxActive) { wsidx[pos] = ldz + r; wsb[pos] = actg[s] < 0 ? lg[s] : ug[s]; }
+                if (act && pos < wcap) { wsidx[pos] = ldz + r; wsb[pos] = actg[s] < 0 ? lg[s] : ug[s]; }
                 na += __popcll(mk);
             }
-            if (na > kMaxActive) return false;
+            if (na > kMaxActive && (!bigS || na > nz)) return false;      // (more than nz rows are dependent: never a verified optimum)
             hsh |= 1ull;
             bool cyc = false;
 #pragma unroll
@@ -796,43 +799,50 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                 else if (na <= 12) reg_polish(std::integral_constant<int, 12>{});      // the slow instances live here: |A| of 9..12
                 else if (na <= kRegCap) reg_polish(std::integral_constant<int, kRegCap>{});
                 else {
-                for (int p = lane; p < na * na; p += 64) {
-                    const int a = p / na, c = p - a * na;
-                    S[a * kSld + c] = gY[(size_t)wsidx[a] * ldy + wsidx[c]];
-                }
-                if (lane < na) lam[lane] = nt0[wsidx[lane]] - wsb[lane];
-                wave_sync();
-                if (lane < na) dg0[lane] = S[lane * kSld + lane];
-                wave_sync();
-                for (int k = 0; k < na; ++k) {
-                    const double d = S[k * kSld + k];
-                    if (!(d > 1e-11 * dg0[k])) { dep_at = k; break; }
-                    const double sd = sqrt(d);
-                    if (lane > k && lane < na) S[lane * kSld + k] /= sd;
-                    if (lane == k) S[k * kSld + k] = sd;
-                    wave_sync();
-                    if (lane > k && lane < na) {
-                        const double lik = S[lane * kSld + k];
-                        for (int j = k + 1; j <= lane; ++j) S[lane * kSld + j] -= lik * S[j * kSld + k];
-                    }
-                    wave_sync();
-                }
-                if (dep_at < 0) {
-                    for (int k = 0; k < na; ++k) {
-                        const double yk = lam[k] / S[k * kSld + k];
-                        wave_sync();
-                        if (lane == k) lam[k] = yk;
-                        if (lane > k && lane < na) lam[lane] -= S[lane * kSld + k] * yk;
-                        wave_sync();
-                    }
-                    for (int k = na - 1; k >= 0; --k) {
-                        const double lk = lam[k] / S[k * kSld + k];
-                        wave_sync();
-                        if (lane == k) lam[k] = lk;
-                        if (lane < k) lam[lane] -= S[k * kSld + lane] * lk;
-                        wave_sync();
-                    }
-                }
+                    // row-by-row Cholesky S = L L' on the working set's rows of Y, then the two triangular solves for lam: in this
+                    // wavefront's LDS arena up to kMaxActive rows, in its slot of the device buffer beyond (there every lane-to-lane
+                    // hand-over goes through memory with a workgroup-scope fence: the stores must have landed before another lane reads)
+                    auto chol_solve = [&](auto Sp, const int sld, auto sync) {
+                        for (int p = lane; p < na * na; p += 64) {
+                            const int a = p / na, c = p - a * na;
+                            Sp[a * sld + c] = gY[(size_t)wsidx[a] * ldy + wsidx[c]];
+                        }
+                        for (int a = lane; a < na; a += 64) lam[a] = nt0[wsidx[a]] - wsb[a];
+                        sync();
+                        for (int a = lane; a < na; a += 64) dg0[a] = Sp[a * sld + a];
+                        sync();
+                        for (int k = 0; k < na; ++k) {
+                            const double d = Sp[k * sld + k];
+                            if (!(d > 1e-11 * dg0[k])) { dep_at = k; break; }
+                            const double sd = sqrt(d);
+                            for (int a = k + 1 + lane; a < na; a += 64) Sp[a * sld + k] /= sd;
+                            if (lane == 0) Sp[k * sld + k] = sd;
+                            sync();
+                            for (int a = k + 1 + lane; a < na; a += 64) {
+                                const double lik = Sp[a * sld + k];
+                                for (int j = k + 1; j <= a; ++j) Sp[a * sld + j] -= lik * Sp[j * sld + k];
+                            }
+                            sync();
+                        }
+                        if (dep_at < 0) {
+                            for (int k = 0; k < na; ++k) {
+                                const double yk = lam[k] / Sp[k * sld + k];
+                                wave_sync();
+                                if (lane == 0) lam[k] = yk;
+                                for (int a = k + 1 + lane; a < na; a += 64) lam[a] -= Sp[a * sld + k] * yk;
+                                wave_sync();
+                            }
+                            for (int k = na - 1; k >= 0; --k) {
+                                const double lk = lam[k] / Sp[k * sld + k];
+                                wave_sync();
+                                if (lane == 0) lam[k] = lk;
+                                for (int a = lane; a < k; a += 64) lam[a] -= Sp[k * sld + a] * lk;
+                                wave_sync();
+                            }
+                        }
+                    };
+                    if (na <= kMaxActive) chol_solve(S, kSld, [] { wave_sync(); });
+                    else chol_solve(bigS, na, [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); });
                 }
             }
             if (dep_at >= 0) {
@@ -1223,7 +1233,7 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
         double j = 0;
 #pragma unroll
         for (int s = 0; s < NZS; ++s) j = fma(f[s], w[s], j);
-        if (lane < na_last) j = fma(-lam[lane], wsb[lane], j);
+        for (int a = lane; a < na_last; a += 64) j = fma(-lam[a], wsb[a], j);
         cost = 0.5 * wave_sum(j) + c0;
     } else if (!ADMM && polished && !FUSED) {
         // cost from its definition (M.cost_direct: the identity above loses digits on an ill-conditioned Hessian), but not here:
@@ -1373,7 +1383,8 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
 // Fallback for the instances the polish-only kernel left unsolved (a handful in a thousand, or
 // everything when polish is switched off): ADMM iterations, then polish again.
 template <int CPZ, int CPG>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_solve_admm(const LmpcDev *__restrict__ Mp, const LmpcBatchDev Bt, double *wsbase)
+__global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_solve_admm(const LmpcDev *__restrict__ Mp, const LmpcBatchDev Bt, double *wsbase,
+                                                                        double *pbuf, const int pslots)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1391,6 +1402,9 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_solve_admm(const Lmp
     double *stage = smem + (size_t)wave * M.lds_per_wave;
     double *nt0 = stage + M.stage_len;
     double *arena = nt0 + M.ldy;
+    // this wavefront's slot for working sets of more than kMaxActive rows (the host caps the grid at pslots wavefronts)
+    const int slot = blockIdx.x * wpb + wave;
+    const gdw bigS = (pbuf && slot < pslots) ? glw(pbuf) + (size_t)slot * M.nz * M.nz : nullptr;
     if (Bt.chunked) {
         // after the polish-only kernel almost nothing is left: a wavefront looks at the flags of kFallbackChunk instances at
         // once (one load each, side by side) and only enters the solver for those still open -- an eighth of the wavefronts
@@ -1403,12 +1417,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_solve_admm(const Lmp
             while (todo) {
                 const int b = c0 + (int)__builtin_ctzll(todo);
                 todo &= todo - 1;
-                solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(wsbase) + (size_t)b * M.wsld);
+                solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(wsbase) + (size_t)b * M.wsld, nullptr, bigS);
             }
         }
     } else {
         for (int b = blockIdx.x * wpb + wave; b < Bt.batch; b += gridDim.x * wpb)
-            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(wsbase) + (size_t)b * M.wsld);
+            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(wsbase) + (size_t)b * M.wsld, nullptr, bigS);
     }
 }
 
@@ -1503,7 +1517,8 @@ __global__ __launch_bounds__(256) void lmpc_cost_mfma(const LmpcDev *__restrict_
 }
 
 template <int CPZ, int CPG>
-int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, hipStream_t stream, int which, int fast)
+int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, hipStream_t stream, int which, int fast,
+                   double *pbuf, int pslots)
 {
     const size_t lds = (size_t)kWavesPerBlock * m.lds_per_wave * sizeof(double);
     if (lds > lmpc_lds_limit()) return -2;
@@ -1561,7 +1576,11 @@ int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b
             if (blocks3 > cap) blocks3 = cap;
             if (blocks3 < 1) blocks3 = 1;
         }
-        hipLaunchKernelGGL(k3, dim3(blocks3), dim3(kWavesPerBlock * 64), lds, stream, m_dev, b3, ws);
+        if (pbuf && m.polish) {                  // one slot of the large-working-set buffer per wavefront (the kernel strides over the batch)
+            if (pslots < kWavesPerBlock) pbuf = nullptr;
+            else if (blocks3 > pslots / kWavesPerBlock) blocks3 = pslots / kWavesPerBlock;
+        }
+        hipLaunchKernelGGL(k3, dim3(blocks3), dim3(kWavesPerBlock * 64), lds, stream, m_dev, b3, ws, m.polish ? pbuf : nullptr, pslots);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -1598,7 +1617,8 @@ int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len)
     st = (st + 1) / 2 * 2;
     int a1 = (m.ph + 1) * (m.nx + 2 * m.ny) + (m.ph + 2) * m.nx + 2 * m.ph * m.nu + m.nu + (m.nx + m.nu) + m.ph * m.ndu + (m.ph + 2) / 2 + 8 +
              m.nx * m.nx + m.nx * m.nu + m.ny * m.nx + m.nx * m.ndu + m.ny * m.ndu;      // assemble_one's plan, model matrices last
-    int a2 = kMaxActive * kSld + 3 * kMaxActive + kMaxActive;      // S, lam, wsb, dg0, wsidx (ints)
+    const int wcap = ws_capacity(m.nz);
+    int a2 = kMaxActive * kSld + 3 * wcap + (wcap + 1) / 2;      // S, lam, wsb, dg0, wsidx (ints)
     int ar = a1 > a2 ? a1 : a2;
     ar = (ar + 1) / 2 * 2;
     // the active-set bitmaps are assembled in the nt0 slice
@@ -1610,13 +1630,24 @@ int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len)
     return st + ldy + ar;
 }
 
-int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, int which, int fast)
+int lmpc_fallback_slots(const LmpcDev &m, int batch)
+{
+    constexpr size_t kBudget = (size_t)256 << 20;           // bytes
+    const size_t per = (size_t)m.nz * m.nz * sizeof(double);
+    long long waves = ((long long)batch + kFallbackChunk * kWavesPerBlock - 1) / (kFallbackChunk * kWavesPerBlock) * kWavesPerBlock;
+    const long long fit = per ? (long long)(kBudget / per) / kWavesPerBlock * kWavesPerBlock : waves;
+    if (waves > fit) waves = fit;
+    if (waves > 256 * 8 * kWavesPerBlock) waves = 256 * 8 * kWavesPerBlock;
+    return (int)(waves < kWavesPerBlock ? kWavesPerBlock : waves);
+}
+
+int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, int which, int fast, double *pbuf, int pslots)
 {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (lmpc_kernel_variant(m.ldz, m.ldg)) {
-    case 1: return launch_variant<1, 1>(m, m_dev, b, ws, s, which, fast);
-    case 2: return launch_variant<2, 2>(m, m_dev, b, ws, s, which, fast);
-    case 4: return launch_variant<4, 4>(m, m_dev, b, ws, s, which, fast);
+    case 1: return launch_variant<1, 1>(m, m_dev, b, ws, s, which, fast, pbuf, pslots);
+    case 2: return launch_variant<2, 2>(m, m_dev, b, ws, s, which, fast, pbuf, pslots);
+    case 4: return launch_variant<4, 4>(m, m_dev, b, ws, s, which, fast, pbuf, pslots);
     default: return -2;
     }
 }

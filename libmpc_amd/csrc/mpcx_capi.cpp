@@ -66,6 +66,8 @@ struct mpcx_lmpc {
     int *pcounter = nullptr;            // work counters of the persistent fused kernel (eight ints of its own)
     int32_t *done = nullptr;            // [ws_cap] lmpc_solve_group: which instances it solved (the fallback kernel screens this instead of the records)
     size_t ws_cap = 0;                  // instances
+    double *pbuf = nullptr;             // the fallback kernel's slots for working sets of more than kMaxActive rows (pslots x nz x nz), sized with ws
+    int pslots = 0;
     explicit mpcx_lmpc(const mpcx_dims &d) : ctl(d) {}
 
     void release()
@@ -75,7 +77,8 @@ struct mpcx_lmpc {
         if (ws) (void)hipFree(ws);
         if (pcounter) (void)hipFree(pcounter);
         if (done) (void)hipFree(done);
-        ws = nullptr; pcounter = nullptr; done = nullptr; ws_cap = 0;
+        if (pbuf) (void)hipFree(pbuf);
+        ws = nullptr; pcounter = nullptr; done = nullptr; ws_cap = 0; pbuf = nullptr; pslots = 0;
         warm_batch = 0;                 // row numbering may have changed with the model
     }
     void release_staging()
@@ -236,6 +239,7 @@ struct mpcx_lmpc_hetero {
     mpcx::LmpcDev *models_d = nullptr;           // [count] device structs
     char *slab = nullptr, *slab_dev = nullptr;     // uploaded arrays / arrays the condensing kernel fills
     double *ws = nullptr; size_t ws_cap = 0;
+    double *pbuf = nullptr; int pslots = 0;      // as mpcx_lmpc's
     int active_words = 0, m_ref = 0;
     bool condensed_on_device = false;
     float setup_kernel_ms = 0, setup_total_ms = 0;   // the condensing kernel alone / the whole mpcx_lmpc_hetero_create
@@ -246,6 +250,7 @@ struct mpcx_lmpc_hetero {
         if (slab) (void)hipFree(slab);
         if (slab_dev) (void)hipFree(slab_dev);
         if (ws) (void)hipFree(ws);
+        if (pbuf) (void)hipFree(pbuf);
     }
 };
 
@@ -658,10 +663,14 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
         // grows only when a larger batch than ever before arrives (not capturable in a graph)
         if (h->ws) (void)hipFree(h->ws);
         if (h->done) (void)hipFree(h->done);
-        h->ws = nullptr; h->done = nullptr; h->ws_cap = 0;
+        if (h->pbuf) (void)hipFree(h->pbuf);
+        h->ws = nullptr; h->done = nullptr; h->ws_cap = 0; h->pbuf = nullptr; h->pslots = 0;
+        const int slots = mpcx::lmpc_fallback_slots(h->dev, b->batch);
         if (hipMalloc(reinterpret_cast<void **>(&h->ws), (size_t)b->batch * h->dev.wsld * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&h->done), (size_t)b->batch * sizeof(int32_t)) != hipSuccess)
+            hipMalloc(reinterpret_cast<void **>(&h->done), (size_t)b->batch * sizeof(int32_t)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&h->pbuf), (size_t)slots * h->dev.nz * h->dev.nz * sizeof(double)) != hipSuccess)
             return fail(MPCX_E_DEVICE, "workspace allocation failed");
+        h->pslots = slots;
         if (!h->pcounter) {
             if (hipMalloc(reinterpret_cast<void **>(&h->pcounter), 8 * sizeof(int)) != hipSuccess) return fail(MPCX_E_DEVICE, "workspace allocation failed");
             (void)hipMemset(h->pcounter, 0, 8 * sizeof(int));
@@ -677,7 +686,7 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
     }
     if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; B.done = h->done; }
     else if (fast >= 0 && h->dev.fused_ok && !B.dbg_cycles && h->use_fused == 1) { B.fused = fast + 1; B.pcounter = h->pcounter; }
-    int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 7, fast);
+    int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 7, fast, h->pbuf, h->pslots);
     if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
     if (lr != 0) return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     return MPCX_OK;
@@ -1036,12 +1045,16 @@ int mpcx_lmpc_hetero_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b,
     B.n_models = f->count; B.model_index = model_index;
     if ((size_t)b->batch > f->ws_cap) {
         if (f->ws) (void)hipFree(f->ws);
-        f->ws = nullptr; f->ws_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&f->ws), (size_t)b->batch * f->dev0.wsld * sizeof(double)) != hipSuccess)
+        if (f->pbuf) (void)hipFree(f->pbuf);
+        f->ws = nullptr; f->ws_cap = 0; f->pbuf = nullptr; f->pslots = 0;
+        const int slots = mpcx::lmpc_fallback_slots(f->dev0, b->batch);
+        if (hipMalloc(reinterpret_cast<void **>(&f->ws), (size_t)b->batch * f->dev0.wsld * sizeof(double)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&f->pbuf), (size_t)slots * f->dev0.nz * f->dev0.nz * sizeof(double)) != hipSuccess)
             return fail(MPCX_E_DEVICE, "workspace allocation failed");
+        f->pslots = slots;
         f->ws_cap = (size_t)b->batch;
     }
-    const int lr = mpcx::lmpc_launch(f->dev0, f->models_d, B, f->ws, stream, 7, -1);      // roll-out assemble, lean solve, ADMM fallback
+    const int lr = mpcx::lmpc_launch(f->dev0, f->models_d, B, f->ws, stream, 7, -1, f->pbuf, f->pslots);      // roll-out assemble, lean solve, ADMM fallback
     if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
     if (lr != 0) return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     return MPCX_OK;
@@ -1092,9 +1105,9 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
         if (which == 2 && h->dev.cost_direct) {
             // with pending costs the solve leaves w in t0's place: every timed launch needs a freshly assembled workspace
             for (int i = 0; i < repeats; i++) {
-                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 1, fast);
+                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 1, fast, h->pbuf, h->pslots);
                 (void)hipEventRecord(e0, s);
-                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 2, fast);
+                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 2, fast, h->pbuf, h->pslots);
                 (void)hipEventRecord(e1, s);
                 (void)hipEventSynchronize(e1);
                 float one = 0;
@@ -1103,7 +1116,7 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
             }
         } else {
             (void)hipEventRecord(e0, s);
-            for (int i = 0; i < repeats; i++) mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, which, fast);
+            for (int i = 0; i < repeats; i++) mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, which, fast, h->pbuf, h->pslots);
             (void)hipEventRecord(e1, s);
             (void)hipEventSynchronize(e1);
             (void)hipEventElapsedTime(&ms, e0, e1);

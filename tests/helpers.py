@@ -244,3 +244,176 @@ def assert_matches_oracle(r, ref, o_neq, o_ncon, rtol_cmd=1e-5, rtol_cost=1e-7, 
         same = (bl[:, o_neq:] == rl[:, o_neq:]).all(axis=1) & (bu[:, o_neq:] == ru[:, o_neq:]).all(axis=1)
         assert same[pol].all(), int(np.argmin(same | ~pol))
     return int((~pol).sum())
+
+
+# ---------------------------------------------------------------------------------------------
+# a family of controllers whose optima have large active sets (working sets past the lean kernels' 16 rows)
+# ---------------------------------------------------------------------------------------------
+def axes_spec(nax, ph, ch=None, vmax=0.8, umax=1.0, seed=0, perturb=0.0, ny_mode="eye", extra_states=0, zero_weight=False):
+    """`nax` double-integrator axes (position, velocity; dt = 0.1), one input each: inputs in +-umax over the control horizon,
+    velocities in +-vmax at every step, output weights 10 on positions and 1 on velocities, input weight 0.01, delta-u weight 0.1.
+    perturb: relative spread of the limits and weights drawn from `seed` (one controller of a heterogeneous bank).
+    ny_mode: "eye" (C = I), "select" (C picks the positions and the first velocity: ny < nx), "mix" (C = I plus nax rows
+    position + velocity of each axis: ny > nx; those outputs carry bounds too).  extra_states: states with no bounds, a stable
+    mode driven by the first position.  zero_weight: no input and delta-u weight and none on the last step's outputs -- the last
+    input then does not enter the cost and the condensed Hessian is singular (the set-up regularises it)."""
+    ch = ph if ch is None else ch
+    r = np.random.default_rng(seed)
+    jit = lambda n: 1.0 + perturb * r.uniform(-1.0, 1.0, size=n)
+    dt = 0.1
+    n2 = 2 * nax
+    nx, nu = n2 + extra_states, nax
+    A = np.eye(nx); B = np.zeros((nx, nu))
+    for a in range(nax):
+        A[2 * a, 2 * a + 1] = dt
+        B[2 * a, a] = 0.5 * dt * dt; B[2 * a + 1, a] = dt
+    for e in range(extra_states):
+        A[n2 + e, n2 + e] = 0.9 - 0.1 * e
+        A[n2 + e, 0] = 0.05
+    wpos = 10.0 * jit(nax); wvel = 1.0 * jit(nax)
+    ow_state = np.zeros(nx); ow_state[0:n2:2] = wpos; ow_state[1:n2:2] = wvel
+    if ny_mode == "eye":
+        Cm = np.eye(nx); OW = ow_state.copy()
+    elif ny_mode == "select":
+        rows = list(range(0, n2, 2)) + [1]
+        Cm = np.eye(nx)[rows]; OW = ow_state[rows]
+    elif ny_mode == "mix":
+        mix = np.zeros((nax, nx))
+        for a in range(nax):
+            mix[a, 2 * a] = 1.0; mix[a, 2 * a + 1] = 0.5
+        Cm = np.vstack([np.eye(nx), mix]); OW = np.concatenate([ow_state, np.full(nax, 0.5)])
+    else:
+        raise ValueError(ny_mode)
+    ny = Cm.shape[0]
+    OW = np.tile(OW[:, None], (1, ph))
+    UW = np.full((nu, ph), 0.01) * jit(nu)[:, None]
+    DUW = np.full((nu, ph), 0.1) * jit(nu)[:, None]
+    if zero_weight:
+        UW[:] = 0.0; DUW[:] = 0.0; OW[:, -1] = 0.0
+    um = umax * jit(nu); vm = vmax * jit(nax)
+    xmin = np.full(nx, -INF); xmax = np.full(nx, INF)
+    xmin[1:n2:2] = -vm; xmax[1:n2:2] = vm
+    ymin = np.full(ny, -INF); ymax = np.full(ny, INF)
+    if ny_mode == "mix":
+        ymin[nx:] = -4.0; ymax[nx:] = 4.0
+    return dict(dims=(nx, nu, 0, ny, ph, ch), A=A, B=B, C=Cm, OW=OW, UW=UW, DUW=DUW,
+                umin=-um, umax=um, xmin=xmin, xmax=xmax, ymin=ymin, ymax=ymax, nax=nax)
+
+
+def configure_axes(c, spec, maximum_iteration=4000):
+    """the controller of `spec` through reference-style calls (LMPC or OracleFrontEnd); references zero"""
+    from oracle.lmpc_oracle import default_params
+    nx, nu, ndu, ny, ph, ch = spec["dims"]
+    assert c.setStateSpaceModel(spec["A"], spec["B"], spec["C"])
+    assert c.setObjectiveWeights(spec["OW"], spec["UW"], spec["DUW"])
+    assert c.setInputBounds(spec["umin"], spec["umax"], (0, ch))
+    assert c.setStateBounds(spec["xmin"], spec["xmax"], (0, ph))
+    assert c.setOutputBounds(spec["ymin"], spec["ymax"], (0, ph))
+    assert c.setReferences(np.zeros(ny), np.zeros(nu), np.zeros(nu), (0, ph))
+    if isinstance(c, OracleFrontEnd):
+        c.o.params = default_params(maximum_iteration=maximum_iteration)
+    else:
+        from libmpc_amd import LParameters
+        c.setOptimizerParameters(LParameters(maximum_iteration=maximum_iteration))
+    return c
+
+
+def axes_oracle(spec, maximum_iteration=4000):
+    return configure_axes(OracleFrontEnd(*spec["dims"]), spec, maximum_iteration).o
+
+
+def axes_batch(spec, B, seed=2024):
+    """x0: positions U(-s, s) with s ~ U(0, 3) per instance, velocities U(-0.5, 0.5), extra states U(-0.5, 0.5);
+    lastU U(-0.5, 0.5) inside the input box; yref [B, ny] zero (the references of the set-up)"""
+    nx, nu, ndu, ny, ph, ch = spec["dims"]
+    nax = spec["nax"]
+    r = np.random.default_rng(seed)
+    s = r.uniform(0.0, 3.0, size=(B, 1))
+    x0 = r.uniform(-0.5, 0.5, size=(B, nx))
+    x0[:, 0:2 * nax:2] = s * r.uniform(-1.0, 1.0, size=(B, nax))
+    u0 = r.uniform(-0.5, 0.5, size=(B, nu)) * np.minimum(1.0, np.abs(spec["umax"]))[None, :]
+    return np.ascontiguousarray(x0), np.ascontiguousarray(u0), np.zeros((B, ny))
+
+
+def oracle_batch_parallel_spec(spec, x0, u0, yref=None, maximum_iteration=4000, workers=None):
+    """oracle_batch_parallel for any axes_spec controller: one cold oracle solve per instance over a thread pool, active bitmaps
+    included, plus 'n_active' (active inequality rows per instance) and 'violation': how far the oracle's sequence lies outside
+    the bounds.  Active rows are those with a nonzero multiplier; a row the oracle flags at its bound with a multiplier of exactly
+    zero (a degenerate optimum: it may or may not be in an optimal working set) is kept in 'active_*_flagged' and counted in
+    'n_flagged' only.  OSQP accepts a polished point whose residuals are no worse than the ADMM iterate's, so now and then a 'polished'
+    point misses an active row and crosses that bound by up to ADMM accuracy; such a point is not the exact optimum the kernels
+    are held to, and 'polished' is cleared there ('polished_raw' keeps the oracle's flag)."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    nx, nu, ndu, ny, ph, ch = spec["dims"]
+    B = len(x0)
+    yref = np.zeros((B, ny)) if yref is None else yref
+    workers = workers or max(1, min(16, (os.cpu_count() or 1)))
+    bounds = np.linspace(0, B, workers + 1).astype(int)
+    umax = np.abs(spec["umax"]); xlo, xhi, ylo, yhi = spec["xmin"], spec["xmax"], spec["ymin"], spec["ymax"]
+    zu, zd = np.zeros((nu, ph)), np.zeros((max(ndu, 0), ph))
+
+    def job(k):
+        o = axes_oracle(spec, maximum_iteration)
+        out = []
+        for b in range(bounds[k], bounds[k + 1]):
+            r = o.solve(x0[b], u0[b], np.tile(yref[b][:, None], (1, ph)), zu, zu, zd)
+            st, inp, outp = r["state"], r["input"], r["output"]
+            # (input rows checked without move blocking only: with ch < ph the bound columns map onto blocks of steps)
+            v = max(np.max(np.abs(inp[:ch]) - umax[None, :], initial=0.0) if ch == ph else 0.0,
+                    np.max(np.maximum(xlo[None, :] - st[1:], st[1:] - xhi[None, :]), initial=0.0),
+                    np.max(np.maximum(ylo[None, :] - outp[1:], outp[1:] - yhi[None, :]), initial=0.0))
+            out.append((b, r, max(v, 0.0)))
+        return out
+    with ThreadPoolExecutor(workers) as ex:
+        parts = [x for p_ in ex.map(job, range(workers)) for x in p_]
+    o = axes_oracle(spec, maximum_iteration)
+    res = {"neq": o.neq, "ncon": o.ncon, "nvar": o.nvar}
+    res["cmd"] = np.zeros((B, nu)); res["cost"] = np.zeros(B); res["violation"] = np.zeros(B)
+    for k in ("status", "solver_status", "iters", "polished"):
+        res[k] = np.zeros(B, dtype=np.int32)
+    for k in ("active_lower", "active_upper", "active_lower_flagged", "active_upper_flagged"):
+        res[k] = np.zeros((B, o.ncon), dtype=np.uint8)
+    for b, r, v in parts:
+        res["cmd"][b] = r["cmd"]; res["cost"][b] = r["cost"]; res["violation"][b] = v
+        for k in ("status", "solver_status", "iters", "polished"):
+            res[k][b] = r[k]
+        res["active_lower"][b] = r["active_lower"] & (r["y"] != 0); res["active_upper"][b] = r["active_upper"] & (r["y"] != 0)
+        res["active_lower_flagged"][b] = r["active_lower"]; res["active_upper_flagged"][b] = r["active_upper"]
+    # the box rows of step 0 bound the initial state and lastU, which are given, not decided: the condensed problem has no such rows and
+    # the kernels never report them, while OSQP, once x0 sits on a bound (closed loop), splits a multiplier between such a row and the
+    # initial-condition equality
+    na = nx + nu
+    for k in ("active_lower", "active_upper", "active_lower_flagged", "active_upper_flagged"):
+        res[k][:, o.neq:o.neq + na] = 0
+    res["polished_raw"] = res["polished"].copy()
+    res["polished"][res["violation"] > 1e-7] = 0
+    res["n_active"] = ((res["active_lower"][:, o.neq:] != 0) | (res["active_upper"][:, o.neq:] != 0)).sum(axis=1)
+    res["n_flagged"] = ((res["active_lower_flagged"][:, o.neq:] != 0) | (res["active_upper_flagged"][:, o.neq:] != 0)).sum(axis=1)
+    return res
+
+
+# the workloads of tests/test_lmpc_shapes*.py
+SHAPES_MAXIT = 4000
+SHAPES_MAIN = (3, 20, 1024)               # nax, ph, batch: working sets of 0 to ~60 rows, spread evenly
+# name -> (axes_spec arguments, kernel template variant, cost_direct)
+SHAPES_VARIANTS = {
+    "v1": (dict(nax=3, ph=20), 1, 0),                          # nz = 60
+    "v1_zero_weight": (dict(nax=3, ph=20, zero_weight=True), 1, 1),
+    "v2": (dict(nax=3, ph=50), 2, 0),                          # nz = 150
+    "v4": (dict(nax=6, ph=50), 4, 0),                          # nz = 300
+    "ldg": (dict(nax=2, ph=40, ny_mode="mix"), 2, 0),          # nz = 80, 160 bounded rows
+}
+SHAPES_EDGES = {
+    "nu1": dict(nax=1, ph=20),
+    "nu3": dict(nax=3, ph=10),
+    "nu5": dict(nax=5, ph=8),
+    "nx3": dict(nax=1, ph=20, extra_states=1),
+    "ny_lt_nx": dict(nax=3, ph=12, ny_mode="select"),
+    "ny_gt_nx": dict(nax=2, ph=15, ny_mode="mix"),
+    "ch_lt_ph": dict(nax=3, ph=20, ch=8),
+    "nz47": dict(nax=1, ph=47),
+    "nz48": dict(nax=1, ph=48),
+    "nz49": dict(nax=1, ph=49),
+    "kin72": dict(nax=2, ph=6, extra_states=28),               # nx = ny = 32, nu = 2
+}
