@@ -26,6 +26,9 @@ struct NlmpcWsLayout {
                                         // trajectories [kNlTrials x (ph+1) x ny]
     int sp;                             // sparse form of the sub-problem's rows: values [rows x kNlSparse], indices (int), counts (int)
     int total;
+    int wgh;                            // vector-valued user hooks on the workgroup form (NlmpcDev::wg_hook_waves > 0 only): room in front of
+                                        // scal for that form's hook buffers (nlmpc_wg_hook_scratch; WgPlan::w_hk, w_ys).  (After total: the
+                                        // debug readers of this struct take its fields in order up to total)
 };
 
 struct NlmpcDev {
@@ -54,6 +57,8 @@ struct NlmpcDev {
     const double *bnd_sign;     // [nbnd] +1: z <= val, -1: z >= val
     const double *bnd_val;      // [nbnd]
     NlmpcWsLayout ws;
+    int wg_hook_waves;          // hook models: the workspace holds the workgroup form's hook buffers for up to this many wavefronts per
+                                // instance (0, the default: it does not -- the one-wavefront form's layout)
 };
 
 struct NlmpcBatchDev {
@@ -94,6 +99,15 @@ inline int nlmpc_hook_scratch(const NlmpcDev &m)
 {
     const int rows = m.nineq + m.nue;
     return 2 * 64 * rows + kNlTrials * rows + kNlTrials * (m.ph + 1) * m.ny + 2;
+}
+
+// the workgroup form's (mpcx/nlmpc_sqp_wg.hpp, WgPlan::w_hk / w_ys) for up to `waves` wavefronts per instance: a column buffer pair per
+// lane, the line search's constraint values and output trajectories per trial point, the outputs along the trajectory (+ the rounding
+// of the plan's offsets)
+inline int nlmpc_wg_hook_scratch(const NlmpcDev &m, int waves)
+{
+    const int rows = m.nineq + m.nue, nya = m.ny > 0 ? m.ny : 1;
+    return 2 * 64 * waves * rows + kNlTrials * rows + kNlTrials * (m.ph + 1) * nya + (m.ph + 1) * nya + 4;
 }
 
 // wavefronts per workgroup of the two NLMPC kernels: a power of two, so that the blocks of a CU (160 KB of LDS) leave no slice

@@ -238,30 +238,25 @@ __device__ __forceinline__ void hook_base_outputs(const NlmpcDev &M, const doubl
     }
 }
 
-// Objective::evaluate + computeGradient (Objective.hpp:91-265) through ObjFunHandle(X, Y, U, slack)
-template <class Mdl>
-__device__ __forceinline__ void hook_cost_grad(const NlmpcDev &M, const double *z, const double *Xs, const double *Us, double *Jm,
-                                               const double *Ys, int lane, double *cost, double *grad)
+// Objective::computeGradient (Objective.hpp:107-265) through ObjFunHandle(X, Y, U, slack): the forward quotients of the state and
+// input entries, NT lanes a column each (the wavefront form: 64; the workgroup form, mpcx/nlmpc_sqp_wg.hpp: its whole workgroup).
+// put_x(k, g): state entry k = i NX + j of z; put_u(k, g): input row entry k = i NU + j (before the move blocking).  Returns the
+// slack's central quotient (every lane computes it).  f0 is the cost at the point, Y0 its outputs.
+template <class Mdl, int NT, class PX, class PU>
+__device__ __forceinline__ double hook_cost_cols(int ph, double e, const double *Xs, const double *Us, bool ho, const typename Mdl::MatY &Y0,
+                                                 const double *prm, int lane, double f0, PX &&put_x, PU &&put_u)
 {
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NY = Mdl::NY, NYA = NY > 0 ? NY : 1;
     using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
-    const int ph = M.ph, ch = M.ch, nz = M.nz;
-    const double dv = kDv, e = z[nz - 1];
-    const double *prm = M.params;
-    const bool ho = M.has_output != 0;
+    const double dv = kDv;
     auto Xa = [&](int j) { const double v = fabs(Xs[(j % (ph + 1)) * NX + j / (ph + 1)]); return v > 1.0 ? v : 1.0; };
     auto Ua = [&](int j) { const double v = fabs(Us[(j % (ph + 1)) * NU + j / (ph + 1)]); return v > 1.0 ? v : 1.0; };
     const MX X0 = MX::trajectory(Xs);
     const MU U0 = MU::trajectory(Us);
-    const MY Y0 = ho ? MY::trajectory(Ys) : MY::zeros_view();
-    const double f0 = Mdl::cost(X0, Y0, U0, e, prm);
-    if (lane == 0 && cost) *cost = f0;
-    if (!grad) return;
-    double *g = grad;
     // Every lane runs the same number of passes and makes the same calls in each (a surplus lane repeats the last column and
     // keeps the result to itself): a hook may sit behind a function pointer, and call sites inside control flow that differs
     // between lanes are where that goes wrong.
-    for (int k0 = 0; k0 < ph * NX; k0 += 64) {
+    for (int k0 = 0; k0 < ph * NX; k0 += NT) {
         const bool live = k0 + lane < ph * NX;
         const int k = live ? k0 + lane : ph * NX - 1;
         const int i = k / NX, j = k - i * NX;
@@ -271,9 +266,9 @@ __device__ __forceinline__ void hook_cost_grad(const NlmpcDev &M, const double *
         double yo1[NYA];
         if (ho) { hook_out_row<Mdl>(yo1, Xs, Us, i + 1, j, dx, -1, 0.0, prm); Yp.perturb(i + 1, -1, -1, 0.0).replace_rows(yo1, nullptr); }
         const double fp = Mdl::cost(Xp, Yp, U0, e, prm);
-        if (live) g[k] = (fp - f0) / dx;
+        if (live) put_x(k, (fp - f0) / dx);                                   // (no chain rule for the state scaling: Objective.hpp:107-144)
     }
-    for (int k0 = 0; k0 < ph * NU; k0 += 64) {
+    for (int k0 = 0; k0 < ph * NU; k0 += NT) {
         const bool live = k0 + lane < ph * NU;
         const int k = live ? k0 + lane : ph * NU - 1;
         const int i = k / NU, j = k - i * NU;
@@ -288,55 +283,63 @@ __device__ __forceinline__ void hook_cost_grad(const NlmpcDev &M, const double *
             Yp.perturb(i, pair, -1, 0.0).replace_rows(yo1, pair >= 0 ? yo2 : nullptr);
         }
         const double fp = Mdl::cost(X0, Yp, Up, e, prm);
-        if (live) Jm[k] = (fp - f0) / du;
+        if (live) put_u(k, (fp - f0) / du);
     }
+    const double de = fmax(dv, fabs(e)) * dv;
+    return (Mdl::cost(X0, Y0, U0, e + de, prm) - Mdl::cost(X0, Y0, U0, e - de, prm)) / (2 * de);
+}
+
+// Objective::evaluate + computeGradient (Objective.hpp:91-265) through ObjFunHandle(X, Y, U, slack)
+template <class Mdl>
+__device__ __forceinline__ void hook_cost_grad(const NlmpcDev &M, const double *z, const double *Xs, const double *Us, double *Jm,
+                                               const double *Ys, int lane, double *cost, double *grad)
+{
+    constexpr int NU = Mdl::NU;
+    using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
+    const int ph = M.ph, ch = M.ch, nz = M.nz;
+    const double e = z[nz - 1];
+    const double *prm = M.params;
+    const bool ho = M.has_output != 0;
+    const MX X0 = MX::trajectory(Xs);
+    const MU U0 = MU::trajectory(Us);
+    const MY Y0 = ho ? MY::trajectory(Ys) : MY::zeros_view();
+    const double f0 = Mdl::cost(X0, Y0, U0, e, prm);
+    if (lane == 0 && cost) *cost = f0;
+    if (!grad) return;
+    double *g = grad;
+    const double ge = hook_cost_cols<Mdl, 64>(ph, e, Xs, Us, ho, Y0, prm, lane, f0, [&](int k, double v) { g[k] = v; }, [&](int k, double v) { Jm[k] = v; });
     nl_wave_sync();
     for (int k = lane; k < ch * NU; k += 64) {
         const int bl = k / NU, j = k - bl * NU;
         double s = 0;
         for (int i = 0; i < ph; ++i) if (min(i, ch - 1) == bl) s += Jm[i * NU + j];
-        g[ph * NX + k] = Scale(M).by_su(s, j);                                // Iz2u' * vec(Jmv)
+        g[ph * Mdl::NX + k] = Scale(M).by_su(s, j);                          // Iz2u' * vec(Jmv)
     }
-    {
-        const double de = fmax(dv, fabs(e)) * dv;
-        const double ge = (Mdl::cost(X0, Y0, U0, e + de, prm) - Mdl::cost(X0, Y0, U0, e - de, prm)) / (2 * de);
-        if (lane == 0) g[nz - 1] = ge;
-    }
+    if (lane == 0) g[nz - 1] = ge;
     nl_wave_sync();
 }
 
-// Constraints::evaluateIneq / evaluateEq with their central-difference Jacobians (Constraints.hpp:211-442, 641-832)
-// through IConFunHandle / EConFunHandle.  A lane owns a column; the hook fills the whole vector at the point moved up
-// into one column buffer and at the point moved down into another (hk: [2][rows][64]); their difference is the column.
-template <class Mdl>
-__device__ __forceinline__ void hook_constraints(const NlmpcDev &M, const double *z, const double *Xs, const double *Us,
-                                                 const double *Ys, double *hk, int lane, double *cineq, double *jineq)
+// Constraints::computeIneqJacobian / computeEqJacobian (Constraints.hpp:641-832) through IConFunHandle / EConFunHandle: central
+// quotients, NT lanes a column each.  The hook fills the whole vector at the point moved up into one column buffer and at the point
+// moved down into the other (cA, cB: this lane's columns, element r at [r * NT]); their difference is the column.  The sink J takes them:
+//   J.x(r, k, v)       row r's entry in state column k = i NX + j of z (already times the state scaling);
+//   J.u_zero(r, q), J.u_add(r, q, v), J.u_scale(r, q, s)
+//                      row r's entry in input column q of the move-blocked z: the steps the block drives add up, then the input scaling;
+//   J.e(r, v)          row r's slack entry (called by lane 0; every lane computes it).
+template <class Mdl, int NT, class Sink>
+__device__ __forceinline__ void hook_constraint_cols(int ph, int ch, double e, const double *Xs, const double *Us, bool ho, const typename Mdl::MatY &Y0,
+                                                     const double *prm, const Scale &sc, double *cA, double *cB, int lane, Sink &J)
 {
-    constexpr int NX = Mdl::NX, NU = Mdl::NU, NY = Mdl::NY, NYA = NY > 0 ? NY : 1, NI = Mdl::NI, NE = Mdl::NE;
+    constexpr int NX = Mdl::NX, NU = Mdl::NU, NY = Mdl::NY, NYA = NY > 0 ? NY : 1, NI = Mdl::NI, NE = Mdl::NE, m = NI + NE;
     using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
     using VI = typename Mdl::VecI; using VE = typename Mdl::VecE;
-    const int ph = M.ph, ch = M.ch, nz = M.nz, m = NI + NE;
-    const double dv = kDv, e = z[nz - 1];
-    const double *prm = M.params;
-    const bool ho = M.has_output != 0;
-    const Scale sc(M);
+    const double dv = kDv;
     auto Xa = [&](int j) { const double v = fabs(Xs[(j % (ph + 1)) * NX + j / (ph + 1)]); return v > 1.0 ? v : 1.0; };
     auto Ua = [&](int j) { const double v = fabs(Us[(j % (ph + 1)) * NU + j / (ph + 1)]); return v > 1.0 ? v : 1.0; };
     const MX X0 = MX::trajectory(Xs);
     const MU U0 = MU::trajectory(Us);
-    const MY Y0 = ho ? MY::trajectory(Ys) : MY::zeros_view();
-    double *J = jineq;
-    double *cA = hk + lane, *cB = hk + (size_t)64 * m + lane;                  // element r at [r * 64]
-    // values: every lane evaluates the vectors into its own column buffer (same calls in every lane, see hook_cost_grad),
-    // lane 0 files them
-    if (cineq) {
-        if constexpr (NI > 0) { VI o = VI::output(cA, 64); Mdl::ineq_all(o, X0, Y0, U0, e, prm); }
-        if constexpr (NE > 0) { VE o = VE::output(cA + (size_t)64 * NI, 64); Mdl::eq_all(o, X0, U0, prm); }
-        if (lane == 0) for (int r = 0; r < m; ++r) cineq[r] = cA[r * 64];
-    }
-    if (!jineq) { nl_wave_sync(); return; }
     // state columns
-    for (int k0 = 0; k0 < ph * NX; k0 += 64) {
+    for (int k0 = 0; k0 < ph * NX; k0 += NT) {
         const bool live = k0 + lane < ph * NX;
         const int k = live ? k0 + lane : ph * NX - 1;
         const int i = k / NX, j = k - i * NX;
@@ -348,31 +351,31 @@ __device__ __forceinline__ void hook_constraints(const NlmpcDev &M, const double
                 MY Yp = Y0;
                 double yo1[NYA];
                 if (ho) { hook_out_row<Mdl>(yo1, Xs, Us, i + 1, j, d, -1, 0.0, prm); Yp.perturb(i + 1, -1, -1, 0.0).replace_rows(yo1, nullptr); }
-                VI o = VI::output(sgn ? cB : cA, 64);
+                VI o = VI::output(sgn ? cB : cA, NT);
                 Mdl::ineq_all(o, Xp, Yp, U0, e, prm);
             }
             // computeIneqJacobian multiplies the state columns by the state scaling (Constraints.hpp:269-284)
-            if (live) for (int r = 0; r < NI; ++r) J[(size_t)r * nz + k] = sc.by_ss((cA[r * 64] - cB[r * 64]) / (2 * dx), j);
+            if (live) for (int r = 0; r < NI; ++r) J.x(r, k, sc.by_ss((cA[r * NT] - cB[r * NT]) / (2 * dx), j));
         }
         if constexpr (NE > 0) {
             const double dx = dv * fmax(fabs(Xs[(i + 1) * NX + j]), 1.0);
             for (int sgn = 0; sgn < 2; ++sgn) {
                 MX Xp = MX::trajectory(Xs); Xp.perturb(i + 1, -1, j, sgn ? -dx : dx);
-                VE o = VE::output((sgn ? cB : cA) + (size_t)64 * NI, 64);
+                VE o = VE::output((sgn ? cB : cA) + (size_t)NT * NI, NT);
                 Mdl::eq_all(o, Xp, U0, prm);
             }
-            if (live) for (int r = NI; r < m; ++r) J[(size_t)r * nz + k] = sc.by_ss((cA[r * 64] - cB[r * 64]) / (2 * dx), j);
+            if (live) for (int r = NI; r < m; ++r) J.x(r, k, sc.by_ss((cA[r * NT] - cB[r * NT]) / (2 * dx), j));
         }
     }
     // input columns: block bl drives the steps i_first..i_last; the passes over the steps are the same for every lane (the
     // longest block), a lane whose block is shorter repeats its last step and drops the result
     const int span_max = ph - ch + 1;
-    for (int q0 = 0; q0 < ch * NU; q0 += 64) {
+    for (int q0 = 0; q0 < ch * NU; q0 += NT) {
         const bool live = q0 + lane < ch * NU;
         const int q = live ? q0 + lane : ch * NU - 1;
-        const int bl = q / NU, j = q - bl * NU, k = ph * NX + q;
+        const int bl = q / NU, j = q - bl * NU;
         const int i_first = bl, i_last = bl == ch - 1 ? ph - 1 : bl;           // the steps this block drives
-        if (live) for (int r = 0; r < m; ++r) J[(size_t)r * nz + k] = 0.0;
+        if (live) for (int r = 0; r < m; ++r) J.u_zero(r, q);
         for (int t = 0; t < span_max; ++t) {
             const bool step_live = live && i_first + t <= i_last;
             const int i = min(i_first + t, i_last);
@@ -384,36 +387,72 @@ __device__ __forceinline__ void hook_constraints(const NlmpcDev &M, const double
                     MY Yp = Y0;
                     double yo1[NYA];
                     if (ho) { hook_out_row<Mdl>(yo1, Xs, Us, i, -1, 0.0, j, d, prm); Yp.perturb(i, -1, -1, 0.0).replace_rows(yo1, nullptr); }
-                    VI o = VI::output(sgn ? cB : cA, 64);
+                    VI o = VI::output(sgn ? cB : cA, NT);
                     Mdl::ineq_all(o, X0, Yp, Up, e, prm);
                 }
-                if (step_live) for (int r = 0; r < NI; ++r) J[(size_t)r * nz + k] += (cA[r * 64] - cB[r * 64]) / (2 * du);
+                if (step_live) for (int r = 0; r < NI; ++r) J.u_add(r, q, (cA[r * NT] - cB[r * NT]) / (2 * du));
             }
             if constexpr (NE > 0) {
                 const double du = dv * fmax(fabs(Us[(ph - 1) * NU + j]), 1.0);  // row ph-1's magnitude for every step (Constraints.hpp:780,806)
                 for (int sgn = 0; sgn < 2; ++sgn) {
                     MU Up = MU::trajectory(Us); Up.perturb(i, i == ph - 1 ? ph : -1, j, sgn ? -du : du);
-                    VE o = VE::output((sgn ? cB : cA) + (size_t)64 * NI, 64);
+                    VE o = VE::output((sgn ? cB : cA) + (size_t)NT * NI, NT);
                     Mdl::eq_all(o, X0, Up, prm);
                 }
-                if (step_live) for (int r = NI; r < m; ++r) J[(size_t)r * nz + k] += (cA[r * 64] - cB[r * 64]) / (2 * du);
+                if (step_live) for (int r = NI; r < m; ++r) J.u_add(r, q, (cA[r * NT] - cB[r * NT]) / (2 * du));
             }
         }
-        if (live && sc.on) for (int r = 0; r < m; ++r) J[(size_t)r * nz + k] *= sc.su[j];      // glueJacobian: Jmanvar * Iz2u
+        if (live && sc.on) for (int r = 0; r < m; ++r) J.u_scale(r, q, sc.su[j]);      // glueJacobian: Jmanvar * Iz2u
     }
     // slack column (every lane computes it, lane 0 files it)
     {
-        const int k = nz - 1;
         const double de = fmax(dv, fabs(e)) * dv;
         if constexpr (NI > 0) {
             for (int sgn = 0; sgn < 2; ++sgn) {
-                VI o = VI::output(sgn ? cB : cA, 64);
+                VI o = VI::output(sgn ? cB : cA, NT);
                 Mdl::ineq_all(o, X0, Y0, U0, sgn ? e - de : e + de, prm);
             }
-            if (lane == 0) for (int r = 0; r < NI; ++r) J[(size_t)r * nz + k] = (cA[r * 64] - cB[r * 64]) / (2 * de);
+            if (lane == 0) for (int r = 0; r < NI; ++r) J.e(r, (cA[r * NT] - cB[r * NT]) / (2 * de));
         }
-        if (lane == 0) for (int r = NI; r < m; ++r) J[(size_t)r * nz + k] = 0.0;
+        if (lane == 0) for (int r = NI; r < m; ++r) J.e(r, 0.0);
     }
+}
+
+// Constraints::evaluateIneq / evaluateEq with their central-difference Jacobians (Constraints.hpp:211-442, 641-832)
+// through IConFunHandle / EConFunHandle, the Jacobian dense [rows x nz] (hk: the column buffers [2][rows][64]).
+template <class Mdl>
+__device__ __forceinline__ void hook_constraints(const NlmpcDev &M, const double *z, const double *Xs, const double *Us,
+                                                 const double *Ys, double *hk, int lane, double *cineq, double *jineq)
+{
+    constexpr int NI = Mdl::NI, NE = Mdl::NE;
+    using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
+    using VI = typename Mdl::VecI; using VE = typename Mdl::VecE;
+    const int ph = M.ph, ch = M.ch, nz = M.nz, m = NI + NE;
+    const double e = z[nz - 1];
+    const double *prm = M.params;
+    const bool ho = M.has_output != 0;
+    const Scale sc(M);
+    const MX X0 = MX::trajectory(Xs);
+    const MU U0 = MU::trajectory(Us);
+    const MY Y0 = ho ? MY::trajectory(Ys) : MY::zeros_view();
+    double *cA = hk + lane, *cB = hk + (size_t)64 * m + lane;                  // element r at [r * 64]
+    // values: every lane evaluates the vectors into its own column buffer (same calls in every lane, see hook_cost_cols),
+    // lane 0 files them
+    if (cineq) {
+        if constexpr (NI > 0) { VI o = VI::output(cA, 64); Mdl::ineq_all(o, X0, Y0, U0, e, prm); }
+        if constexpr (NE > 0) { VE o = VE::output(cA + (size_t)64 * NI, 64); Mdl::eq_all(o, X0, U0, prm); }
+        if (lane == 0) for (int r = 0; r < m; ++r) cineq[r] = cA[r * 64];
+    }
+    if (!jineq) { nl_wave_sync(); return; }
+    struct Dense {
+        double *J; int nz, kx;
+        __device__ void x(int r, int k, double v) { J[(size_t)r * nz + k] = v; }
+        __device__ void u_zero(int r, int q) { J[(size_t)r * nz + kx + q] = 0.0; }
+        __device__ void u_add(int r, int q, double v) { J[(size_t)r * nz + kx + q] += v; }
+        __device__ void u_scale(int r, int q, double s) { J[(size_t)r * nz + kx + q] *= s; }
+        __device__ void e(int r, double v) { J[(size_t)r * nz + nz - 1] = v; }
+    } J{jineq, nz, ph * Mdl::NX};
+    hook_constraint_cols<Mdl, 64>(ph, ch, e, Xs, Us, ho, Y0, prm, sc, cA, cB, lane, J);
     nl_wave_sync();
 }
 
@@ -2160,7 +2199,9 @@ inline void nlmpc_plan(NlmpcDev &m)
     w.r = take(m.neq); w.phi = take(m.neq * m.nzu); w.einv = take(ph * nx * nx);
     w.gr = take(m.nr); w.art = take(m.nr * mld); w.br = take(mtot);
     w.hinv = take(m.nr * m.nr); w.mu = take(mtot); w.glold = take(m.nr); w.s = take(m.nr); w.p = take(m.nr);
-    w.qn = take(KW * m.nr); w.qv = take(KW * m.nr); w.qs = take(KW * (KW + 1)); w.qs2 = take(KW * (KW + 1)); w.scal = take(16);
+    w.qn = take(KW * m.nr); w.qv = take(KW * m.nr); w.qs = take(KW * (KW + 1)); w.qs2 = take(KW * (KW + 1));
+    w.wgh = take(m.vector_hooks && m.wg_hook_waves > 0 ? nlmpc_wg_hook_scratch(m, m.wg_hook_waves) : 0);
+    w.scal = take(16);
     w.lamw = take(m.neq);
     w.hook = take(m.vector_hooks ? nlmpc_hook_scratch(m) : 0);
     w.sp = take(mtot * kNlSparse + (mtot * kNlSparse + mtot + 1) / 2);

@@ -51,13 +51,29 @@ struct HookSet {
     }
 };
 
-template <int NX_, int NU_, int NY_, int PH_, int CH_, int NI_, int NE_, class Hooks>
+// KIND / OUT: what the model knows when it is compiled -- the transcription (1: continuous, setDiscretizationSamplingTime; 0: the
+// state hook is x(k+1)) and whether an output hook exists (1 / 0).  -1 (the default): "may be", the controller's NlmpcDev::continuous /
+// has_output decide at run time -- what the one-wavefront kernel reads.  The workgroup form (mpcx/nlmpc_sqp_wg.hpp) fixes its transcription
+// at compile time: its plan (wg_plan) refuses a controller whose run-time flags contradict the model's.
+template <int NX_, int NU_, int NY_, int PH_, int CH_, int NI_, int NE_, class Hooks, int KIND = -1, int OUT = -1>
 struct HookModel {
     static constexpr bool VECTOR_HOOKS = true;
-    static constexpr bool CONTINUOUS = true;            // "may be": NlmpcDev::continuous decides at run time
-    static constexpr bool HAS_OUTPUT = true;            // "may have": NlmpcDev::has_output decides at run time
+    static constexpr bool ERASED = Hooks::kErased;      // the hooks are reached through device function pointers (ErasedHooks)
+    static constexpr bool CONTINUOUS = KIND != 0;       // (KIND < 0: "may be"; NlmpcDev::continuous decides at run time)
+    static constexpr bool HAS_OUTPUT = OUT != 0;        // (OUT < 0: "may have"; NlmpcDev::has_output decides at run time)
     static constexpr bool INEQ_USES_SLACK = true;
     static constexpr int NX = NX_, NU = NU_, NY = NY_, PH = PH_, CH = CH_, NI = NI_, NE = NE_;
+    // The members the workgroup form and its plan read, each at its conservative value: no declared structure -- every constraint row
+    // reads every state and input row (dense rows, differenced as one black box), no stage-wise cost (no Gauss-Newton start of the
+    // curvature estimate: the identity, as NLopt's SLSQP), no short-list or affine rows.  The closures travel in NlmpcDev::params, which the
+    // phases read where they are (NPARAMS = 0: nothing of them is copied into LDS).
+    static constexpr int NPARAMS = 0;
+    static constexpr bool COST_STAGEWISE = false;
+    static constexpr bool XFREE_ROWS_SPARSE = false;
+    static constexpr bool SPARSE_ROWS_ONE_ENTRY = false;
+    static constexpr bool XFREE_ROWS_AFFINE = false;
+    static constexpr bool INEQ_U_ROWS_DISJOINT = false;
+    static constexpr int CURV0_AFTER = 0;
     using MatX = mpc::mat<PH + 1, NX>;
     using MatU = mpc::mat<PH + 1, NU>;
     using MatY = mpc::mat<PH + 1, NY>;
@@ -91,9 +107,16 @@ struct HookModel {
     __device__ static double cost(const MatX &X, const MatY &Y, const MatU &U, double e, const double *prm) { return H(prm).obj(X, Y, U, e); }
     __device__ static void ineq_all(VecI &g, const MatX &X, const MatY &Y, const MatU &U, double e, const double *prm) { H(prm).ineq(g, X, Y, U, e); }
     __device__ static void eq_all(VecE &h, const MatX &X, const MatU &U, const double *prm) { H(prm).eq(h, X, U); }
-    // no declared structure: every constraint may read every state
-    __device__ static bool ineq_reads_x(int, int) { return true; }
-    __device__ static bool eq_reads_x(int, int) { return true; }
+    // no declared structure: every constraint may read every state and input row, in both directions of the question
+    __host__ __device__ static bool ineq_reads_x(int, int) { return true; }
+    __host__ __device__ static bool eq_reads_x(int, int) { return true; }
+    __host__ __device__ static bool ineq_reads_u(int, int) { return true; }
+    __host__ __device__ static bool eq_reads_u(int, int) { return true; }
+    __device__ static void ineq_rows_of_x(int, int &first, int &count) { first = 0; count = NI; }
+    __device__ static void ineq_rows_of_u(int, int &first, int &count) { first = 0; count = NI; }
+    // (never called: COST_STAGEWISE is false -- present because the workgroup form's Gauss-Newton start names them)
+    template <class XA, class UA> __device__ static double stage(int, const XA &, const UA &, int, const double *) { return 0.0; }
+    __device__ static double slack_cost(double, const double *) { return 0.0; }
 };
 
 #if !defined(__HIPCC_RTC__)

@@ -21,7 +21,9 @@
 //   * the phases (evaluate / condense / BFGS / sub-problem / step / merit / line search / update) are separate non-inlined functions
 //     whose only shared state is the LDS block: each gets its own register allocation and the loop around them carries a dozen scalars.
 //
-// Vector-valued user hooks (mpcx/nlmpc_hooks.hpp) keep going through nlmpc_sqp.
+// Vector-valued user hooks (mpcx/nlmpc_hooks.hpp, Mdl::VECTOR_HOOKS) take the same phases with the reference's whole-vector calls in place of
+// the component-wise ones: black boxes differenced as the one-wavefront form differences them (hook_cost_cols / hook_constraint_cols of
+// nlmpc_engine.hpp, a column per lane over the whole workgroup), every user row dense, the curvature estimate from the identity.
 #pragma once
 
 #include "nlmpc_engine.hpp"
@@ -60,6 +62,7 @@ struct WgPlan {
     int o_L;                                              // overlay, inside the sub-problem: the packed factor
     // workspace offsets (doubles) of one instance
     int w_scal, w_F, w_art, w_einv, w_gx, w_hinv, w_sp, w_msave, w_phi;   // (w_scal: the controller's NlmpcWsLayout::scal, 16 doubles: cost, dual steps, cycles per phase)
+    int w_hk, w_ys;             // whole-vector hooks: two column buffers [rows][NT] and the line search's trial rows and outputs; the outputs along the trajectory
     int ws_total;
 };
 
@@ -497,12 +500,17 @@ template <class Mdl, int WAVES, bool FL> struct kWgWavesPerSimdOf {
 };
 
 // ---- the kernel's phases ----------------------------------------------------------------------------------------------------------------
+// (whole-vector hooks: the workgroup form calls them inlined and in control flow that differs between lanes -- not through pointers)
+template <class Mdl, bool = Mdl::VECTOR_HOOKS> struct wg_hooks_inlined { static constexpr bool value = true; };
+template <class Mdl> struct wg_hooks_inlined<Mdl, true> { static constexpr bool value = !Mdl::ERASED; };
+
 template <class Mdl, int WAVES, bool FL>
 struct WgSqp {
     static constexpr int NX = Mdl::NX, NU = Mdl::NU, FW = NX + NU + 1, NT = 64 * WAVES;
     static constexpr bool CT = Mdl::CONTINUOUS;
     static constexpr int GW = 3 * NX + NU + 1;                 // columns of the Gauss-Jordan tableau [E | A B c | I] of one step
     using T = Team<WAVES>;
+    static_assert(wg_hooks_inlined<Mdl>::value, "the workgroup form takes hook sets whose types are known together (HookSet)");
 
     struct V {                                                 // what a phase needs of the arguments and of the LDS block (scalars throughout)
         WgArgsPtr A;
@@ -518,7 +526,25 @@ struct WgSqp {
         __device__ __forceinline__ const double *x0() const { return A->S.x0 + (size_t)b * NX; }
         __device__ __forceinline__ const double *u0() const { return A->S.u0 + (size_t)b * NU; }
         __device__ __forceinline__ Scale scale() const { return Scale(A->M.su, A->M.ss, A->M.iss, A->M.scaled != 0); }
+        // the model's parameters: their LDS copy; a hook model's closures where the controller keeps them (NlmpcDev::params)
+        __device__ __forceinline__ const double *prm() const
+        {
+            if constexpr (Mdl::VECTOR_HOOKS) return A->M.params; else return at(A->P.o_prm);
+        }
+        __device__ __forceinline__ bool hook_out() const { return Mdl::VECTOR_HOOKS && Mdl::HAS_OUTPUT && A->M.has_output != 0; }
     };
+    // Whole-vector hooks read the trajectories through views that hold generic pointers, the phases write them through LDS-typed ones:
+    // the two kinds of access to the same data are ordered by a workgroup-scope fence before the hooks read (with one wavefront per instance
+    // the phases' own barrier is a wavefront-scope one)
+    static __device__ __forceinline__ void hook_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); }
+    // the per-lane column buffers of the hooks in the workspace (element r of lane t's column at [r * NT + t]), then the line search's
+    // per-trial constraint vectors and outputs (kNlTrials each)
+    static __device__ __forceinline__ double *hook_cols(const V &v) { return v.w + v.A->P.w_hk; }
+    static __device__ __forceinline__ double *hook_trial_rows(const V &v, int grp) { return v.w + v.A->P.w_hk + (size_t)2 * NT * v.m + (size_t)grp * v.m; }
+    static __device__ __forceinline__ double *hook_trial_outputs(const V &v, int grp)
+    {
+        return v.w + v.A->P.w_hk + (size_t)2 * NT * v.m + (size_t)kNlTrials * v.m + (size_t)grp * (v.ph + 1) * (Mdl::NY > 0 ? Mdl::NY : 1);
+    }
     // the folded blocks: LDS or workspace, the pointer typed accordingly
     struct FP {
         typedef typename BlockPtr<FL>::type type;
@@ -665,6 +691,7 @@ struct WgSqp {
         const double dv = kDv;
         const double *prm = v.at(P.o_prm), *x0 = v.x0();
         const Scale sc = v.scale();
+        (void)M;
         double *z = v.at(P.o_z), *Xs = v.at(P.o_Xs), *Us = v.at(P.o_Us), *Jm = v.at(P.o_Jm), *lam = v.at(P.o_lam), *st = v.at(P.o_st),
                *gu = v.at(P.o_gu);
         gwp gxg = (gwp)(v.w + P.w_gx);
@@ -678,6 +705,40 @@ struct WgSqp {
         }
         T::sync();
         const double e = z[nz - 1];
+        if constexpr (Mdl::VECTOR_HOOKS) {
+            // whole-vector hooks: the outputs along the trajectory (the objective hook reads them), the cost, its forward quotients -- one
+            // perturbed point per lane over the workgroup (hook_cost_cols)
+            using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
+            constexpr int NY = Mdl::NY;
+            const double *hp = v.prm();
+            const bool ho = v.hook_out();
+            double *Ys = v.w + P.w_ys;
+            hook_order();
+            if (ho) {
+                for (int i0 = 0; i0 <= ph; i0 += NT) {               // (every lane makes the call: surplus lanes redo row ph)
+                    const int i = min(i0 + tid, ph);
+                    double yr[NY > 0 ? NY : 1];
+                    hook_out_row<Mdl>(yr, Xs, Us, i, -1, 0.0, -1, 0.0, hp);
+                    if (i0 + tid <= ph) for (int a = 0; a < NY; ++a) Ys[i * NY + a] = yr[a];
+                }
+                T::sync();
+            }
+            const MY Y0 = ho ? MY::trajectory(Ys) : MY::zeros_view();
+            const double f0 = Mdl::cost(MX::trajectory(Xs), Y0, MU::trajectory(Us), e, hp);
+            if (tid == 0) st[ST_COST] = f0;
+            if (!values_only) {
+                const double ge = hook_cost_cols<Mdl, NT>(ph, e, Xs, Us, ho, Y0, hp, tid, f0, [&](int k, double g) { lam[k] = g; gxg[k] = g; },
+                                                          [&](int k, double g) { Jm[k] = g; });
+                T::sync();
+                for (int k = tid; k < nzu; k += NT) {
+                    const int bl = k / NU, j = k - bl * NU;
+                    double s = 0;
+                    for (int i = 0; i < ph; ++i) if (min(i, ch - 1) == bl) s += Jm[i * NU + j];
+                    gu[k] = sc.by_su(s, j);                              // Iz2u' * vec(Jmv)
+                }
+                if (tid == 0) gu[nzu] = ge;
+            }
+        } else {
         auto Xa = [&](int j) { const double a = fabs(Xs[(j % (ph + 1)) * NX + j / (ph + 1)]); return a > 1.0 ? a : 1.0; };
         auto Ua = [&](int j) { const double a = fabs(Us[(j % (ph + 1)) * NU + j / (ph + 1)]); return a > 1.0 ? a : 1.0; };
         const Pert X0{Xs, NX, -1, -1, -1, 0.0}, U0{Us, NU, -1, -1, -1, 0.0};
@@ -727,6 +788,7 @@ struct WgSqp {
             }
             if (tid == 0) gu[nzu] = (st[ST_FP] - st[ST_FM]) / (2 * de);
         }
+        }
         T::sync();
     }
 
@@ -737,19 +799,20 @@ struct WgSqp {
         const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int ph = v.ph;
         const double dv = kDv;
-        const double *prm = v.at(P.o_prm);
+        const double *prm = v.prm();
         const Scale sc = v.scale();
         const double *Xs = v.at(P.o_Xs), *Us = v.at(P.o_Us);
         double *c = v.at(P.o_c);
         const double h = 0.5 * M.Ts;
+        if constexpr (Mdl::VECTOR_HOOKS) hook_order();
         if (values_only) {
             for (int i = tid; i < ph; i += NT) {
                 double xk[NX], xk1[NX], uk[NU], fa[NX], fb[NX];
                 for (int a = 0; a < NX; ++a) { xk[a] = Xs[i * NX + a]; xk1[a] = Xs[(i + 1) * NX + a]; }
                 for (int a = 0; a < NU; ++a) uk[a] = Us[i * NU + a];
-                Mdl::f(fa, xk, uk, prm);
+                call_f<Mdl>(fa, xk, uk, prm, i);
                 if (CT) {
-                    Mdl::f(fb, xk1, uk, prm);
+                    call_f<Mdl>(fb, xk1, uk, prm, i);
                     for (int a = 0; a < NX; ++a) c[i * NX + a] = sc.over_ss(xk[a] + (h * (fa[a] + fb[a])) - xk1[a], a);
                 } else {
                     for (int a = 0; a < NX; ++a) c[i * NX + a] = sc.over_ss(xk1[a] - fa[a], a);
@@ -771,10 +834,10 @@ struct WgSqp {
                 const double d = isv ? 0.0 : dv * fmax(fabs(base), 1.0);
                 for (int a = 0; a < NX; ++a) if (!isv && !isu && a == vv) xk[a] = base + d;
                 for (int a = 0; a < NU; ++a) if (!isv && isu && a == vv) uk[a] = base + d;
-                Mdl::f(f1, xk, uk, prm);
+                call_f<Mdl>(f1, xk, uk, prm, i);
                 for (int a = 0; a < NX; ++a) if (!isv && !isu && a == vv) xk[a] = base - d;
                 for (int a = 0; a < NU; ++a) if (!isv && isu && a == vv) uk[a] = base - d;
-                Mdl::f(f2, xk, uk, prm);
+                call_f<Mdl>(f2, xk, uk, prm, i);
                 const double i2d = isv ? 0.0 : 1.0 / (2 * d);
                 for (int a = 0; a < NX; ++a) {
                     double out;
@@ -830,14 +893,14 @@ struct WgSqp {
                         for (int a = 0; a < NX; ++a) if (pert && !isu && a == vv) xp[a] = bs + d;
 #pragma unroll
                         for (int a = 0; a < NU; ++a) if (pert && isu && a == vv) up[a] = bs + d;
-                        Mdl::f(o1, xp, up, prm);
+                        call_f<Mdl>(o1, xp, up, prm, ii);
 #pragma unroll
                         for (int a = 0; a < NX; ++a) xp[a] = xr[(n2 ? NX : 0) + a];
 #pragma unroll
                         for (int a = 0; a < NX; ++a) if (pert && !isu && a == vv) xp[a] = bs - d;
 #pragma unroll
                         for (int a = 0; a < NU; ++a) if (pert && isu && a == vv) up[a] = bs - d;
-                        Mdl::f(o2, xp, up, prm);
+                        call_f<Mdl>(o2, xp, up, prm, ii);
                         const double i2d = 1.0 / (2 * d);                 // (one division per column; the quotient's last bit is below the differences' noise)
 #pragma unroll
                         for (int a = 0; a < NX; ++a) col[a] = kind == 3 ? o1[a] + o2[a] : (o1[a] - o2[a]) * i2d;
@@ -954,6 +1017,38 @@ struct WgSqp {
         auto Xa = [&](int j) { const double a = fabs(Xs[(j % (ph + 1)) * NX + j / (ph + 1)]); return a > 1.0 ? a : 1.0; };
         auto Ua = [&](int j) { const double a = fabs(Us[(j % (ph + 1)) * NU + j / (ph + 1)]); return a > 1.0 ? a : 1.0; };
         const Pert X0{Xs, NX, -1, -1, -1, 0.0}, U0{Us, NU, -1, -1, -1, 0.0};
+        gwp spv = (gwp)(v.w + P.w_sp);
+        int *spi = reinterpret_cast<int *>(v.w + P.w_sp + (size_t)mt * kNlSparse);
+        if constexpr (Mdl::VECTOR_HOOKS) {
+            // whole-vector hooks: every lane evaluates the vectors into its own column buffer (the same calls in every lane) and files
+            // the rows it owns from there; then one column of the Jacobian per lane (hook_constraint_cols: a surplus lane redoes a column
+            // and drops it).  Every user row is dense -- it reads every state and input row: its state part goes to the (row, state
+            // row) slots jx, its input and slack part straight into its row of art (dcol: the user rows in order, each wg_row_len long)
+            using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
+            using VI = typename Mdl::VecI; using VE = typename Mdl::VecE;
+            constexpr int NI = Mdl::NI, NE = Mdl::NE;
+            const double *hp = v.prm();
+            const bool ho = v.hook_out();
+            const MY Y0 = ho ? MY::trajectory(v.w + P.w_ys) : MY::zeros_view();
+            double *cA = hook_cols(v) + tid, *cB = cA + (size_t)NT * m;
+            hook_order();
+            if constexpr (NI > 0) { VI o = VI::output(cA, NT); Mdl::ineq_all(o, MX::trajectory(Xs), Y0, MU::trajectory(Us), e, hp); }
+            if constexpr (NE > 0) { VE o = VE::output(cA + (size_t)NT * NI, NT); Mdl::eq_all(o, MX::trajectory(Xs), MU::trajectory(Us), hp); }
+            for (int k = tid; k < m; k += NT) gin[k] = cA[k * NT];
+            T::sync();
+            if (values_only) return;
+            struct Rows {
+                double *jx; typename FP::type art; const int *jxoff, *dcol, *aoff, *alen; int nzu;
+                __device__ void x(int r, int k, double val) { const int i = k / NX, j = k - i * NX; jx[(jxoff[r] + i) * NX + j] = val; }
+                __device__ void u_zero(int r, int q) { art[aoff[dcol[r]] + q] = 0.0; }
+                __device__ void u_add(int r, int q, double val) { art[aoff[dcol[r]] + q] += val; }
+                __device__ void u_scale(int r, int q, double f) { art[aoff[dcol[r]] + q] *= f; }
+                // the slack column, where the row holds one (wg_row_len: soft inequality rows; every row of a wide system): an equality's entry is zero
+                __device__ void e(int r, double val) { if ((alen[dcol[r]] & 0xffff) > nzu) art[aoff[dcol[r]] + nzu] = r < NI ? val : 0.0; }
+            } rows{jx, art, v.iat(P.o_jxoff), dcol, aoff, alen, nzu};
+            hook_constraint_cols<Mdl, NT>(ph, ch, e, Xs, Us, ho, Y0, hp, sc, cA, cB, tid, rows);
+            for (int k = tid; k < m; k += NT) { br[k] = gin[k]; s1v[k] = 0.0; s1m[k] = kSpDense; }
+        } else {
         for (int k = tid; k < mi; k += NT) gin[k] = Mdl::ineq(k, X0, U0, e, ph, prm);
         for (int k = tid; k < m - mi; k += NT) gin[mi + k] = Mdl::eq(k, X0, U0, ph, prm);
         T::sync();                                               // (an equality's value is read below by the thread that owns its row)
@@ -973,8 +1068,6 @@ struct WgSqp {
             jx[t] = sc.by_ss(val, j);                            // the state columns are multiplied by the state scaling (Constraints.hpp:269-284)
         }
         // the input part, one lane per user row: into the row's column of art (dense rows) or its (index, value) list
-        gwp spv = (gwp)(v.w + P.w_sp);
-        int *spi = reinterpret_cast<int *>(v.w + P.w_sp + (size_t)mt * kNlSparse);
         // (Mdl::XFREE_ROWS_AFFINE: a short-list row's entries are the same at every iterate -- differenced once, at the first; what central
         // differences make of a constant afterwards is that constant with nine good digits, a different ninth each time)
         const bool frozen = Mdl::XFREE_ROWS_AFFINE && st[ST_CONSET] != 0.0;
@@ -1039,6 +1132,7 @@ struct WgSqp {
             } else {
                 s1v[k] = 0.0; s1m[k] = kSpDense;
             }
+        }
         }
         // rows of the bounds lb <= z + d <= ub (NLOptimizer::setStateBounds / setInputBounds): on an input one entry, on a state a row of Phi
         for (int kb = tid; kb < mt - m; kb += NT) {
@@ -2625,8 +2719,27 @@ struct WgSqp {
         const Lin XL{v.at(P.o_Xs), v.at(P.o_dXs), NX, al}, UL{v.at(P.o_Us), v.at(P.o_dUs), NU, al};
         const double et = z[v.nz - 1] + al * p[v.nzu];
         double vio = 0.0;
-        for (int k = part; k < mi; k += stride) vio += fmax(Mdl::ineq(k, XL, UL, et, ph, prm), 0.0);
-        for (int k = part; k < m - mi; k += stride) vio += fabs(Mdl::eq(k, XL, UL, ph, prm));
+        if constexpr (Mdl::VECTOR_HOOKS) {
+            // whole-vector hooks: every lane of the trial point's group makes the calls and stores the same values to the same place (its
+            // group's row), then each adds its share of the row up
+            using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
+            using VI = typename Mdl::VecI; using VE = typename Mdl::VecE;
+            constexpr int NI = Mdl::NI, NE = Mdl::NE;
+            const int grp = threadIdx.x / stride;
+            const double *hp = v.prm();
+            const MX XV = MX::trajectory(v.at(P.o_Xs), v.at(P.o_dXs), al);
+            const MU UV = MU::trajectory(v.at(P.o_Us), v.at(P.o_dUs), al);
+            const MY YV = v.hook_out() ? MY::trajectory(hook_trial_outputs(v, grp)) : MY::zeros_view();
+            double *gl = hook_trial_rows(v, grp);
+            if constexpr (NI > 0) { VI o = VI::output(gl, 1); Mdl::ineq_all(o, XV, YV, UV, et, hp); }
+            if constexpr (NE > 0) { VE o = VE::output(gl + NI, 1); Mdl::eq_all(o, XV, UV, hp); }
+            T::sync();
+            for (int k = part; k < m; k += stride) vio += k < mi ? fmax(gl[k], 0.0) : fabs(gl[k]);
+            (void)prm; (void)XL; (void)UL;
+        } else {
+            for (int k = part; k < mi; k += stride) vio += fmax(Mdl::ineq(k, XL, UL, et, ph, prm), 0.0);
+            for (int k = part; k < m - mi; k += stride) vio += fabs(Mdl::eq(k, XL, UL, ph, prm));
+        }
         return vio;
     }
     // (this lane's share of the trial point's cost: all of it on lane 0 of the group, or -- a cost that is a sum over the horizon's rows -- the
@@ -2637,7 +2750,15 @@ struct WgSqp {
         const double *z = v.at(P.o_z), *p = v.at(P.o_p);
         const Lin XL{v.at(P.o_Xs), v.at(P.o_dXs), NX, al}, UL{v.at(P.o_Us), v.at(P.o_dUs), NU, al};
         const double et = z[v.nz - 1] + al * p[v.nzu];
-        if constexpr (Mdl::COST_STAGEWISE) {
+        if constexpr (Mdl::VECTOR_HOOKS) {
+            using MX = typename Mdl::MatX; using MU = typename Mdl::MatU; using MY = typename Mdl::MatY;
+            const MX XV = MX::trajectory(v.at(P.o_Xs), v.at(P.o_dXs), al);
+            const MU UV = MU::trajectory(v.at(P.o_Us), v.at(P.o_dUs), al);
+            const MY YV = v.hook_out() ? MY::trajectory(hook_trial_outputs(v, threadIdx.x / stride)) : MY::zeros_view();
+            const double c = Mdl::cost(XV, YV, UV, et, v.prm());      // (every lane evaluates it: no divergence around the call)
+            (void)XL; (void)UL;
+            return part == 0 ? c : 0.0;
+        } else if constexpr (Mdl::COST_STAGEWISE) {
             double s = part == 0 ? Mdl::slack_cost(et, v.at(P.o_prm)) : 0.0;
             for (int i = part; i <= v.ph; i += stride) s += Mdl::stage(i, XL, UL, v.ph, v.at(P.o_prm));
             return s;
@@ -2646,11 +2767,30 @@ struct WgSqp {
             return part == 0 ? c : 0.0;
         }
     }
+    // (whole-vector hooks) the outputs of trial point grp's rows into its buffer, the rows part, part + stride, ..: the cost and constraint
+    // hooks of the trial point read them (the caller's barrier follows)
+    static __device__ __attribute__((noinline)) void ls_hook_outputs(double al, int part, int stride)
+    {
+        const V v; const auto &P = v.A->P;
+        if (!v.hook_out()) return;
+        constexpr int NY = Mdl::NY;
+        const int ph = v.ph;
+        const Lin XL{v.at(P.o_Xs), v.at(P.o_dXs), NX, al}, UL{v.at(P.o_Us), v.at(P.o_dUs), NU, al};
+        double *yt = hook_trial_outputs(v, threadIdx.x / stride);
+        for (int i0 = 0; i0 <= ph; i0 += stride) {                  // (every lane makes the call: surplus lanes redo row ph)
+            const int i = min(i0 + part, ph);
+            double xr[NX], ur[NU], yr[NY > 0 ? NY : 1];
+            for (int a = 0; a < NX; ++a) xr[a] = XL(i, a);
+            for (int a = 0; a < NU; ++a) ur[a] = UL(i, a);
+            call_out<Mdl>(yr, xr, ur, v.prm(), i);
+            if (i0 + part <= ph) for (int a = 0; a < NY; ++a) yt[i * NY + a] = yr[a];
+        }
+    }
     static __device__ __attribute__((noinline)) double ls_defects(double al, int part, int stride)
     {
         const V v; const auto &M = v.A->M; const auto &P = v.A->P;
         const int ph = v.ph;
-        const double *prm = v.at(P.o_prm);
+        const double *prm = v.prm();
         const Scale sc = v.scale();
         const Lin XL{v.at(P.o_Xs), v.at(P.o_dXs), NX, al}, UL{v.at(P.o_Us), v.at(P.o_dUs), NU, al};
         const double h = 0.5 * M.Ts;
@@ -2659,10 +2799,10 @@ struct WgSqp {
             double xk[NX], xk1[NX], uk[NU], fa[NX], s = 0;
             for (int a = 0; a < NX; ++a) { xk[a] = XL(i, a); xk1[a] = XL(i + 1, a); }
             for (int a = 0; a < NU; ++a) uk[a] = UL(i, a);
-            Mdl::f(fa, xk, uk, prm);
+            call_f<Mdl>(fa, xk, uk, prm, i);
             if (CT) {
                 double fb[NX];
-                Mdl::f(fb, xk1, uk, prm);
+                call_f<Mdl>(fb, xk1, uk, prm, i);
                 for (int a = 0; a < NX; ++a) s += fabs(sc.over_ss(xk[a] + (h * (fa[a] + fb[a])) - xk1[a], a));
             } else {
                 for (int a = 0; a < NX; ++a) s += fabs(sc.over_ss(xk1[a] - fa[a], a));
@@ -2697,6 +2837,11 @@ struct WgSqp {
         double a_step = -1.0;
         for (int round = 0; round < 5 && a_step < 0.0; ++round) {
             const double al = ldexp(1.0, -(grp + 8 * round));
+            if constexpr (Mdl::VECTOR_HOOKS) {
+                hook_order();
+                ls_hook_outputs(al, part, GS);
+                T::sync();
+            }
             const double cst = ls_cost(al, part, GS);
             const double vio = ls_user_rows(al, part, GS) + ls_defects(al, part, GS);
             double mer = cst + nu_pen * vio;
@@ -2990,9 +3135,10 @@ struct WgSqp {
         const V v; const auto &S = v.A->S; const auto &P = v.A->P;
         const int tid = threadIdx.x;
         const int ph = v.ph, nz = v.nz, nr = v.nr, mi = v.mi, m = v.m, mt = v.mt, b = v.b;
+        const bool has_out = Mdl::VECTOR_HOOKS ? v.hook_out() : Mdl::HAS_OUTPUT;
         const double *z = v.at(P.o_z), *Xs = v.at(P.o_Xs), *Us = v.at(P.o_Us), *gin = v.at(P.o_gin), *mu = v.at(P.o_mu), *hinv = v.at(P.o_hinv),
                      *st = v.at(P.o_st);
-        const double *u0 = v.u0(), *prm = v.at(P.o_prm);
+        const double *u0 = v.u0(), *prm = v.prm();
         Red<WAVES> R(v.at(P.o_red));
         double gmax = -1e300, hmax = 0.0;
         for (int k = tid; k < m; k += NT) { if (k < mi) gmax = fmax(gmax, gin[k]); else hmax = fmax(hmax, fabs(gin[k])); }
@@ -3019,7 +3165,7 @@ struct WgSqp {
             for (int i = tid; i <= ph; i += NT) {
                 double y[Mdl::NY > 0 ? Mdl::NY : 1];
                 for (int a = 0; a < Mdl::NY; ++a) y[a] = 0.0;
-                if (Mdl::HAS_OUTPUT && !failed) Mdl::out(y, Xs + i * NX, Us + i * NU, prm);
+                if (has_out && !failed) call_out<Mdl>(y, Xs + i * NX, Us + i * NU, prm, i);
                 for (int a = 0; a < Mdl::NY; ++a) o_sy[((size_t)b * (ph + 1) + i) * Mdl::NY + a] = y[a];
             }
         // the curvature estimate stays in the workspace for a receding-horizon successor (keep_curvature)
@@ -3211,6 +3357,11 @@ inline int wg_plan(const NlmpcDev &m, int hard, int waves_wanted, int state_boun
     constexpr int NX = Mdl::NX, NU = Mdl::NU, FW = NX + NU + 1;
     const int ph = m.ph, nxs = ph * NX, nr = m.nr, nz = m.nz, mi = m.nineq, mu_ = mi + m.nue, mt = mu_ + m.nbnd;
     if (ph > 64 || ph >= 255 || mu_ >= (1 << 19) || 3 * NX + NU + 1 > 64 || m.nr >= 0xffff) return -2;
+    if constexpr (Mdl::VECTOR_HOOKS) {
+        // the transcription is compiled in (WgSqp::CT): a controller whose run-time kind or output hook contradicts the model's is not taken
+        if (!m.vector_hooks || (m.continuous != 0) != Mdl::CONTINUOUS || (m.has_output != 0 && !Mdl::HAS_OUTPUT)) return -2;
+        if (m.nineq != Mdl::NI || m.nue != Mdl::NE) return -2;
+    }
     P = WgPlan{};
     P.hard = hard ? 1 : 0;
     P.nq = hard ? m.nzu : nr;
@@ -3343,6 +3494,14 @@ inline int wg_plan(const NlmpcDev &m, int hard, int waves_wanted, int state_boun
         }
         // the carried inverse (see ws_warm): where no row's entries change between sub-problems -- bounds on inputs, user rows affine in the inputs (Mdl::XFREE_ROWS_AFFINE) --
         // and the controller's workspace has the room
+        // whole-vector hooks: a column buffer pair per lane of the workgroup, the line search's rows and outputs per trial point, the
+        // outputs along the trajectory
+        P.w_hk = P.w_ys = 0;
+        if constexpr (Mdl::VECTOR_HOOKS) {
+            const int nya = Mdl::NY > 0 ? Mdl::NY : 1;
+            P.w_hk = take(2 * 64 * P.waves * mu_ + kNlTrials * mu_ + kNlTrials * (ph + 1) * nya);
+            P.w_ys = take((ph + 1) * nya);
+        }
         const int carry_env = carry_wanted < 0 ? 1 : carry_wanted;
         P.carry_m = 0; P.w_msave = 0;
         if (carry_env && P.minv && P.nd == 0 && (mu_ == 0 || Mdl::XFREE_ROWS_AFFINE) && o + P.kw * (P.kw + 1) / 2 + 2 <= m.ws.scal) { P.carry_m = 1; P.w_msave = take(P.kw * (P.kw + 1) / 2); }
