@@ -456,7 +456,8 @@ int mpcx_lmpc_set_total_batch(mpcx_lmpc_t h, int total);
 int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream, int repeats, float *ms3);
 /* condensed arrays of the host set-up by name ("H", "Kinv", "Gr", "Gc", "Y", "lw", "uw", "rho_b", "lg0", "ug0", "rho_g", "dims",
  * "dims_maps", "MA0", "MA1", "g_refrow", "g_step", "g_kind", "g_comp", "flags" = [cost from its definition, one-workgroup form
- * available, fused mat-vec form available]); out = NULL returns the length                                                      */
+ * available, fused mat-vec form available], "fallback" = [instances the fallback kernel served in the last step that left it any (reading
+ * clears it), entries the failure queue holds, wavefronts of the fallback kernel's grid]); out = NULL returns the length                     */
 int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap);
 /* how many full set-ups (condensing + device rebuild) and how many reference-only refreshes have run on this handle */
 int mpcx_lmpc_debug_setup_counts(mpcx_lmpc_t h, int *full, int *refs);
@@ -489,7 +490,7 @@ int mpcx_nlmpc_debug_get_ws(mpcx_nlmpc_t h, int instance, double *out, int cap, 
 int mpcx_nlmpc_debug_generated_source(const mpcx_nlmpc_source *src, char *out, int cap);
 int mpcx_nlmpc_debug_compile_source(const mpcx_nlmpc_source *src);
 /* one O(n^3) array ("H", "Kinv", "Gr", "Gc", "Y", "rho_b", "rho_g"; "flags" = [cost_direct, condensed on the device]) of controller k
- * of a bank, copied to the host; out = NULL returns the length */
+ * of a bank, copied to the host; out = NULL returns the length.  "fallback": the bank's failure queue, as mpcx_lmpc_debug_get's */
 int mpcx_lmpc_hetero_debug_get(mpcx_lmpc_hetero_t f, int k, const char *name, double *out, int cap);
 
 const char *mpcx_version(void);

@@ -81,9 +81,9 @@ struct LmpcBatchDev {
     int32_t *polish_rounds, *active_count;
     const uint32_t *warm_lower, *warm_upper;      // optional previous active sets (reference row numbering)
     int warm_shift;
-    int chunked;                                  // fallback kernel: one wavefront screens a chunk of instances
+    int fq_cap;                                   // entries the failure queue's list holds
     int fused;                                    // 0: record from the workspace; 1 / 2: lmpc_solve_fused with MF0 / MF1; 3 / 4: lmpc_solve_group with MA0 / MA1
-    int32_t *done;                                // lmpc_solve_group: [B] 2 = solved there, 0 = left to the fallback kernel (null: the flag in the workspace record)
+    int *fq;                                      // failure queue (described below; lmpc_launch fills it in): the polish-first kernels list the instances they leave open, the fallback kernel serves the list.  Null when polish is switched off: the fallback then serves every instance
     int *pcounter;                                // work counter of the persistent fused kernel (null: one instance per launched wavefront)
     // heterogeneous batch (mpcx_lmpc_hetero_*): the kernels' model pointer is an array of n_models structs of identical dimensions and
     // constraint structure, instance b uses entry model_index[b] (null: entry b); 0 models = the one shared controller
@@ -94,6 +94,18 @@ struct LmpcBatchDev {
 // which entry of the model array instance b uses
 __host__ __device__ inline int lmpc_model_of(const LmpcBatchDev &Bt, int b) { return Bt.n_models <= 0 ? 0 : (Bt.model_index ? Bt.model_index[b] : b); }
 
+// The failure queue, device resident, one per handle: [count, ticket, served_last, (pad) | list[cap]] ints.  A producer (lmpc_solve_group: once per
+// workgroup; the other polish-first kernels: once per failing wavefront) takes `count` forward with one atomic and stores the indices of the instances
+// it leaves open; one that leaves none touches nothing.  The fallback kernel returns at once when count is 0; otherwise wavefront w of W serves
+// list[w], list[w + W], ..., every wavefront takes a ticket when it is through, and the last one files count under served_last and zeroes count
+// and ticket.  Invariant: count == ticket == 0 between complete steps (a producer launched without the consumer behind it: lmpc_fallback_reset).
+constexpr int kFqCount = 0, kFqTicket = 1, kFqServed = 2, kFqList = 4;
+inline size_t lmpc_fallback_queue_bytes(size_t cap) { return (kFqList + cap) * sizeof(int); }
+// wavefronts the fallback kernel launches after a polish pass (the largest count whose idle launch costs what the smallest does)
+int lmpc_fallback_waves();
+// stream-ordered zeroing of count and ticket
+int lmpc_fallback_reset(int *fq, void *stream);
+
 // LDS a workgroup of the current device may take (one CU's: gfx950 160 KB), asked of the runtime once per device -- implemented in lmpc_kernels.hip
 size_t lmpc_lds_limit();
 // implemented in lmpc_kernels.hip
@@ -103,10 +115,11 @@ int lmpc_kernel_variant(int ldz, int ldg);     // -1 if the dimensions are not c
 // assemble kernel with shared / per-instance-constant output reference.
 // pbuf / pslots: the fallback kernel's buffer for working sets of more than kMaxActive rows, pslots slots of nz x nz doubles
 // (lmpc_fallback_slots); its grid is then capped at pslots wavefronts.  Null: such sets are left to ADMM.
+// fq / fq_cap: the handle's failure queue (zeroed when allocated) and the entries its list holds, at least the batch.
 int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream,
-                int which = 7, int fast_variant = -1, double *pbuf = nullptr, int pslots = 0);
-// slots of that buffer to allocate for batches of up to `batch` instances: one per wavefront the fallback kernel launches, at most what fits in
-// a fixed budget (at least one workgroup's)
+                int which, int fast_variant, double *pbuf, int pslots, int *fq, int fq_cap);
+// slots of that buffer to allocate for batches of up to `batch` instances: one per wavefront the fallback kernel launches (lmpc_fallback_waves,
+// never more than instances), at most what fits in a fixed budget (at least one workgroup's)
 int lmpc_fallback_slots(const LmpcDev &m, int batch);
 int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len);
 // src: rows x K column-major (rows a multiple of 16, K of 4) -> out[((t G + g) 64 + lane) 4 + e] = src[(4 (4 g + e) + kq) rows + 16 t + j] with lane = 16 kq + j,

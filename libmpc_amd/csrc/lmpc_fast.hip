@@ -565,6 +565,7 @@ __device__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b
             if (lane == 0) st2(ws + ldz + ldy + 2 * ldg, c0, flag0);
         }
         if (outs && lane == 0) outs[7] = 0.0;
+        if constexpr (SRC != 2) { if (Bt.fq && lane == 0) fallback_append(Bt.fq, Bt.fq_cap, b); }      // (lmpc_solve_group files its workgroup's failures together)
         return;
     }
     const int solver_status = infeasible ? -3 : (fixed_violation ? -2 : 1);
@@ -897,7 +898,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
     constexpr int kGroupWaves = kGroupWavesOf<CPZ>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
 #if defined(MPCX_GROUP_CUT) && MPCX_GROUP_CUT == 0
-    { if (threadIdx.x < kGroupWavesOf<CPZ> && blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x < Bt.batch) Bt.done[blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x] = 2; return; }                                   // (timing experiment, tools/group_cut.sh: what a launch costs up to here)
+    { return; }                                   // (timing experiment, tools/group_cut.sh: what a launch costs up to here)
 #endif
     kernarg_touch<sizeof(LmpcDev) + sizeof(LmpcBatchDev) + sizeof(double *) + sizeof(int)>();
     const LmpcDev &M = Mv;
@@ -997,7 +998,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
     __syncthreads();
     gstamp(7);
 #if defined(MPCX_GROUP_CUT) && MPCX_GROUP_CUT == 1
-    { if (threadIdx.x < kGroupWavesOf<CPZ> && blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x < Bt.batch) Bt.done[blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x] = 2; return; }
+    { return; }
 #endif
 
     {
@@ -1059,7 +1060,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
         __syncthreads();
         gstamp(5);
 #if defined(MPCX_GROUP_CUT) && MPCX_GROUP_CUT == 2
-        { if (threadIdx.x < kGroupWavesOf<CPZ> && blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x < Bt.batch) Bt.done[blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x] = 2; return; }
+        { return; }
 #endif
 
         auto tile2 = [&]<bool PRE>(const int t) {
@@ -1155,7 +1156,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
         const int b = b0 + inst;
         gstamp(6);
 #if defined(MPCX_GROUP_CUT) && MPCX_GROUP_CUT == 3
-        { if (threadIdx.x < kGroupWavesOf<CPZ> && blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x < Bt.batch) Bt.done[blockIdx.x * kGroupWavesOf<CPZ> + threadIdx.x] = 2; return; }
+        { return; }
 #endif
         if (b < Bt.batch) solve_fast<CPZ, CPG, 2>(M, Bt, b, lane, slice_i, lwuw, glw(wsbase) + (size_t)b * M.wsld, nullptr, outs + inst * outld, eqbits);
         __syncthreads();
@@ -1165,9 +1166,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
             if (t < kGroupWaves && b0 + t < Bt.batch) {
                 const double *o = outs + t * outld;
                 const int bb = b0 + t;
-                const bool done = o[7] == 2.0;
-                glw(Bt.done)[bb] = done ? 2 : 0;
-                if (done) {
+                if (o[7] == 2.0) {
                     if (Bt.cost) glw(Bt.cost)[bb] = o[0];
                     if (Bt.status) glw(Bt.status)[bb] = (int)o[1];
                     if (Bt.solver_status) glw(Bt.solver_status)[bb] = (int)o[2];
@@ -1180,6 +1179,18 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
             for (int e = t; e < kGroupWaves * nu; e += blockDim.x) {
                 const int ti = e / nu, jj = e - ti * nu;
                 if (b0 + ti < Bt.batch && outs[ti * outld + 7] == 2.0) glw(Bt.cmd)[(size_t)(b0 + ti) * nu + jj] = outs[ti * outld + 8 + jj];
+            }
+            // the instances left open go to the failure queue: one atomic per workgroup that has any, nothing at all otherwise
+            if (Bt.fq && t < 64) {
+                const bool open = t < kGroupWaves && b0 + t < Bt.batch && outs[t * outld + 7] != 2.0;
+                const unsigned long long om = __ballot(open);
+                if (om) {
+                    int base = 0;
+                    if (t == 0) base = atomicAdd(Bt.fq + kFqCount, (int)__builtin_popcountll(om));
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    const int at = base + (int)__builtin_popcountll(om & ((1ull << t) - 1ull));
+                    if (open && at >= 0 && at < Bt.fq_cap) glw(Bt.fq)[kFqList + at] = b0 + t;
+                }
             }
         }
     }

@@ -18,7 +18,6 @@ namespace {
 #define MPCX_WAVES_PER_BLOCK 2
 #endif
 constexpr int kWavesPerBlock = MPCX_WAVES_PER_BLOCK;
-constexpr int kFallbackChunk = 64;      // instances one wavefront of the fallback kernel screens (one flag per lane)
 // a working set with all signs right grows by the rows violated by at least this fraction of the largest violation: adding
 // every violated row at once over-constrains, the surplus rows are shed one round later and the slowest instances ping-pong
 // (max rounds 18-22 over six batches of 4096 with 0, 12-14 with 0.3; 0.1 and 0.5 are worse than either)
@@ -55,6 +54,13 @@ __device__ __forceinline__ void st2(gdw p, double a, double b)
 {
     d2 v; v.x = a; v.y = b;
     *reinterpret_cast<d2 MPCX_GAS *>(p) = v;
+}
+
+// One lane files instance b in the failure queue (lmpc_device.hpp): one atomic, one store, clamped to the list's capacity
+__device__ __forceinline__ void fallback_append(int *fq, const int cap, const int b)
+{
+    const int at = atomicAdd(fq + kFqCount, 1);
+    if (at >= 0 && at < cap) glw(fq)[kFqList + at] = b;
 }
 
 __device__ __forceinline__ void wave_sync()

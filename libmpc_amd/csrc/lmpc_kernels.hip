@@ -1380,50 +1380,73 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
 }
 
 
-// Fallback for the instances the polish-only kernel left unsolved (a handful in a thousand, or
+// Fallback for the instances the polish-only kernels left unsolved (a handful in a thousand, or
 // everything when polish is switched off): ADMM iterations, then polish again.
+//
+// The kernel's arguments travel as ONE struct that is only ever read in place, in the kernel-argument segment.  A by-value struct argument whose
+// address reaches a real callee (solve_one is one: it takes the batch by reference) gets a per-lane stack copy at kernel entry -- 304 bytes a lane,
+// 1.2 MB of scratch writes per launch at the benchmark batch, and the exit test of the usual, idle launch used to wait for its round trip.
+struct AdmmArgs {
+    const LmpcDev *Mp;
+    LmpcBatchDev Bt;
+    double *wsbase, *pbuf;
+    int pslots;
+};
+
 template <int CPZ, int CPG>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_solve_admm(const LmpcDev *__restrict__ Mp, const LmpcBatchDev Bt, double *wsbase,
-                                                                        double *pbuf, const int pslots)
+__device__ __noinline__ void admm_serve(const AdmmArgs *ap, double *smem, const int nopen)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const AdmmArgs &A = *ap;
+    const LmpcBatchDev &Bt = A.Bt;
+    const LmpcDev *Mp = A.Mp;
+    const LmpcDev &M = *Mp;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wpb = blockDim.x >> 6;
-    // the usual launch finds nothing to do: with the flags in an array of their own (lmpc_solve_group's), a wavefront whose first chunk is the only one it
-    // has and is all done leaves before it has looked at the model struct at all -- one trip to memory instead of three in a row
-    if (Bt.chunked && Bt.done) {
-        const int c0 = (blockIdx.x * wpb + wave) * kFallbackChunk;
-        if (c0 + (int)(gridDim.x * wpb * kFallbackChunk) >= Bt.batch) {
-            const int bi = c0 + lane;
-            if (__ballot(lane < kFallbackChunk && bi < Bt.batch && gl(Bt.done)[bi] == 0) == 0ull) return;
-        }
-    }
-    const LmpcDev &M = *Mp;
+    const int slot = blockIdx.x * wpb + wave, nwaves = gridDim.x * wpb;
     double *stage = smem + (size_t)wave * M.lds_per_wave;
     double *nt0 = stage + M.stage_len;
     double *arena = nt0 + M.ldy;
     // this wavefront's slot for working sets of more than kMaxActive rows (the host caps the grid at pslots wavefronts)
-    const int slot = blockIdx.x * wpb + wave;
-    const gdw bigS = (pbuf && slot < pslots) ? glw(pbuf) + (size_t)slot * M.nz * M.nz : nullptr;
-    if (Bt.chunked) {
-        // after the polish-only kernel almost nothing is left: a wavefront looks at the flags of kFallbackChunk instances at
-        // once (one load each, side by side) and only enters the solver for those still open -- an eighth of the wavefronts
-        // to launch and retire
-        for (int c0 = (blockIdx.x * wpb + wave) * kFallbackChunk; c0 < Bt.batch; c0 += gridDim.x * wpb * kFallbackChunk) {
-            const int bi = c0 + lane;
-            const bool open = lane < kFallbackChunk && bi < Bt.batch &&
-                              (Bt.done ? gl(Bt.done)[bi] == 0 : glw(wsbase)[(size_t)bi * M.wsld + M.ldz + M.ldy + 2 * M.ldg + 1] != 2.0);
-            unsigned long long todo = __ballot(open);
-            while (todo) {
-                const int b = c0 + (int)__builtin_ctzll(todo);
-                todo &= todo - 1;
-                solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(wsbase) + (size_t)b * M.wsld, nullptr, bigS);
+    const gdw bigS = (A.pbuf && slot < A.pslots) ? glw(A.pbuf) + (size_t)slot * M.nz * M.nz : nullptr;
+    if (Bt.fq) {
+        // wavefront w of W serves list[w], list[w + W], ...: which wavefront serves an instance changes nothing of its arithmetic
+        const int n = nopen < Bt.fq_cap ? nopen : Bt.fq_cap;
+        for (int i = slot; i < n; i += nwaves) {
+            const int b = __builtin_amdgcn_readfirstlane(gl(Bt.fq)[kFqList + i]);
+            if (b < 0 || b >= Bt.batch) continue;
+            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(A.wsbase) + (size_t)b * M.wsld, nullptr, bigS);
+        }
+        // every wavefront of a launch that saw work takes a ticket when it is through; the last one files the count and restores count = ticket = 0
+        wave_sync();
+        if (lane == 0) {
+            __threadfence();
+            const int tk = atomicAdd(Bt.fq + kFqTicket, 1);
+            if (tk == nwaves - 1) {
+                __hip_atomic_store(Bt.fq + kFqServed, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(Bt.fq + kFqCount, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(Bt.fq + kFqTicket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     } else {
-        for (int b = blockIdx.x * wpb + wave; b < Bt.batch; b += gridDim.x * wpb)
-            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(wsbase) + (size_t)b * M.wsld, nullptr, bigS);
+        for (int b = slot; b < Bt.batch; b += nwaves)
+            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(A.wsbase) + (size_t)b * M.wsld, nullptr, bigS);
     }
+}
+
+template <int CPZ, int CPG>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_solve_admm(const AdmmArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (`args` itself is never named: naming it is what makes the compiler copy it)
+    const AdmmArgs *ap = (const AdmmArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    // the usual launch finds nothing to do: the queue's pointer out of the kernel arguments, its count, and out -- no atomic, no byte written
+    int *const fq = ap->Bt.fq;
+    int nopen = 0;
+    if (fq) {
+        nopen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(fq + kFqCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (nopen <= 0) return;
+    }
+    admm_serve<CPZ, CPG>(ap, smem, nopen);
 }
 
 
@@ -1517,9 +1540,14 @@ __global__ __launch_bounds__(256) void lmpc_cost_mfma(const LmpcDev *__restrict_
 }
 
 template <int CPZ, int CPG>
-int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, hipStream_t stream, int which, int fast,
-                   double *pbuf, int pslots)
+int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b_in, double *ws, hipStream_t stream, int which, int fast,
+                   double *pbuf, int pslots, int *fq, int fq_cap)
 {
+    // the failure queue goes with polish: without it no kernel solves anything before the fallback, which then serves the whole batch
+    LmpcBatchDev b = b_in;
+    b.fq = (m.polish && fq && fq_cap >= b.batch) ? fq : nullptr;
+    b.fq_cap = b.fq ? fq_cap : 0;
+    if (m.polish && !b.fq) return -3;
     const size_t lds = (size_t)kWavesPerBlock * m.lds_per_wave * sizeof(double);
     if (lds > lmpc_lds_limit()) return -2;
     auto k1 = lmpc_assemble_generic<CPZ, CPG>;
@@ -1568,19 +1596,18 @@ int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b
         }
     }
     if (which & 4) {
-        LmpcBatchDev b3 = b;
         int blocks3 = blocks;
-        if (m.polish) {                          // a polish pass always comes first then: few instances are left
-            b3.chunked = 1;
-            blocks3 = (b.batch + kFallbackChunk * kWavesPerBlock - 1) / (kFallbackChunk * kWavesPerBlock);
-            if (blocks3 > cap) blocks3 = cap;
+        if (m.polish) {                          // a polish pass always comes first then: the grid is a fixed number of wavefronts, never more than instances
+            blocks3 = lmpc_fallback_waves() / kWavesPerBlock;
+            if (blocks3 > blocks) blocks3 = blocks;
             if (blocks3 < 1) blocks3 = 1;
         }
-        if (pbuf && m.polish) {                  // one slot of the large-working-set buffer per wavefront (the kernel strides over the batch)
+        if (pbuf && m.polish) {                  // one slot of the large-working-set buffer per wavefront
             if (pslots < kWavesPerBlock) pbuf = nullptr;
             else if (blocks3 > pslots / kWavesPerBlock) blocks3 = pslots / kWavesPerBlock;
         }
-        hipLaunchKernelGGL(k3, dim3(blocks3), dim3(kWavesPerBlock * 64), lds, stream, m_dev, b3, ws, m.polish ? pbuf : nullptr, pslots);
+        const AdmmArgs a3{m_dev, b, ws, m.polish ? pbuf : nullptr, pslots};
+        hipLaunchKernelGGL(k3, dim3(blocks3), dim3(kWavesPerBlock * 64), lds, stream, a3);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -1630,24 +1657,45 @@ int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len)
     return st + ldy + ar;
 }
 
+int lmpc_fallback_waves()
+{
+    // DESIGN.md 4.3 (table "fallback grid"); MPCX_DBG_FALLBACK_WAVES: the measurement's knob, read once
+    static const int w = [] {
+        const char *e = getenv("MPCX_DBG_FALLBACK_WAVES");
+        int v = e ? atoi(e) : 0;
+        if (v <= 0) v = 1024;
+        if (v > 256 * 8 * kWavesPerBlock) v = 256 * 8 * kWavesPerBlock;
+        return (v + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock;
+    }();
+    return w;
+}
+
+int lmpc_fallback_reset(int *fq, void *stream)
+{
+    if (!fq) return 0;
+    return hipMemsetAsync(fq, 0, kFqServed * sizeof(int), reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -3;
+}
+
 int lmpc_fallback_slots(const LmpcDev &m, int batch)
 {
     constexpr size_t kBudget = (size_t)256 << 20;           // bytes
     const size_t per = (size_t)m.nz * m.nz * sizeof(double);
-    long long waves = ((long long)batch + kFallbackChunk * kWavesPerBlock - 1) / (kFallbackChunk * kWavesPerBlock) * kWavesPerBlock;
+    long long waves = lmpc_fallback_waves();
+    const long long inst = ((long long)batch + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock;
+    if (waves > inst) waves = inst;
     const long long fit = per ? (long long)(kBudget / per) / kWavesPerBlock * kWavesPerBlock : waves;
     if (waves > fit) waves = fit;
-    if (waves > 256 * 8 * kWavesPerBlock) waves = 256 * 8 * kWavesPerBlock;
     return (int)(waves < kWavesPerBlock ? kWavesPerBlock : waves);
 }
 
-int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, int which, int fast, double *pbuf, int pslots)
+int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, int which, int fast, double *pbuf, int pslots,
+                int *fq, int fq_cap)
 {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (lmpc_kernel_variant(m.ldz, m.ldg)) {
-    case 1: return launch_variant<1, 1>(m, m_dev, b, ws, s, which, fast, pbuf, pslots);
-    case 2: return launch_variant<2, 2>(m, m_dev, b, ws, s, which, fast, pbuf, pslots);
-    case 4: return launch_variant<4, 4>(m, m_dev, b, ws, s, which, fast, pbuf, pslots);
+    case 1: return launch_variant<1, 1>(m, m_dev, b, ws, s, which, fast, pbuf, pslots, fq, fq_cap);
+    case 2: return launch_variant<2, 2>(m, m_dev, b, ws, s, which, fast, pbuf, pslots, fq, fq_cap);
+    case 4: return launch_variant<4, 4>(m, m_dev, b, ws, s, which, fast, pbuf, pslots, fq, fq_cap);
     default: return -2;
     }
 }

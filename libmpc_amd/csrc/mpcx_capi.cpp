@@ -64,7 +64,7 @@ struct mpcx_lmpc {
     int n_full_setups = 0, n_ref_refreshes = 0;      // how often each kind of set-up ran (mpcx_lmpc_debug_setup_counts)
     double *ws = nullptr;               // per-instance workspace between assemble and solve
     int *pcounter = nullptr;            // work counters of the persistent fused kernel (eight ints of its own)
-    int32_t *done = nullptr;            // [ws_cap] lmpc_solve_group: which instances it solved (the fallback kernel screens this instead of the records)
+    int *fq = nullptr;                  // failure queue (lmpc_device.hpp): the instances the polish-first kernels leave to the fallback kernel, a list of ws_cap entries
     size_t ws_cap = 0;                  // instances
     double *pbuf = nullptr;             // the fallback kernel's slots for working sets of more than kMaxActive rows (pslots x nz x nz), sized with ws
     int pslots = 0;
@@ -76,9 +76,9 @@ struct mpcx_lmpc {
         allocs.clear();
         if (ws) (void)hipFree(ws);
         if (pcounter) (void)hipFree(pcounter);
-        if (done) (void)hipFree(done);
+        if (fq) (void)hipFree(fq);
         if (pbuf) (void)hipFree(pbuf);
-        ws = nullptr; pcounter = nullptr; done = nullptr; ws_cap = 0; pbuf = nullptr; pslots = 0;
+        ws = nullptr; pcounter = nullptr; fq = nullptr; ws_cap = 0; pbuf = nullptr; pslots = 0;
         warm_batch = 0;                 // row numbering may have changed with the model
     }
     void release_staging()
@@ -240,6 +240,7 @@ struct mpcx_lmpc_hetero {
     char *slab = nullptr, *slab_dev = nullptr;     // uploaded arrays / arrays the condensing kernel fills
     double *ws = nullptr; size_t ws_cap = 0;
     double *pbuf = nullptr; int pslots = 0;      // as mpcx_lmpc's
+    int *fq = nullptr;                           // as mpcx_lmpc's
     int active_words = 0, m_ref = 0;
     bool condensed_on_device = false;
     float setup_kernel_ms = 0, setup_total_ms = 0;   // the condensing kernel alone / the whole mpcx_lmpc_hetero_create
@@ -251,6 +252,7 @@ struct mpcx_lmpc_hetero {
         if (slab_dev) (void)hipFree(slab_dev);
         if (ws) (void)hipFree(ws);
         if (pbuf) (void)hipFree(pbuf);
+        if (fq) (void)hipFree(fq);
     }
 };
 
@@ -662,13 +664,14 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
     if ((size_t)b->batch > h->ws_cap) {
         // grows only when a larger batch than ever before arrives (not capturable in a graph)
         if (h->ws) (void)hipFree(h->ws);
-        if (h->done) (void)hipFree(h->done);
+        if (h->fq) (void)hipFree(h->fq);
         if (h->pbuf) (void)hipFree(h->pbuf);
-        h->ws = nullptr; h->done = nullptr; h->ws_cap = 0; h->pbuf = nullptr; h->pslots = 0;
+        h->ws = nullptr; h->fq = nullptr; h->ws_cap = 0; h->pbuf = nullptr; h->pslots = 0;
         const int slots = mpcx::lmpc_fallback_slots(h->dev, b->batch);
         if (hipMalloc(reinterpret_cast<void **>(&h->ws), (size_t)b->batch * h->dev.wsld * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&h->done), (size_t)b->batch * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&h->pbuf), (size_t)slots * h->dev.nz * h->dev.nz * sizeof(double)) != hipSuccess)
+            hipMalloc(reinterpret_cast<void **>(&h->fq), mpcx::lmpc_fallback_queue_bytes((size_t)b->batch)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&h->pbuf), (size_t)slots * h->dev.nz * h->dev.nz * sizeof(double)) != hipSuccess ||
+            hipMemsetAsync(h->fq, 0, mpcx::lmpc_fallback_queue_bytes(0), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
             return fail(MPCX_E_DEVICE, "workspace allocation failed");
         h->pslots = slots;
         if (!h->pcounter) {
@@ -684,9 +687,10 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
         if (b->yref_mode == MPCX_REF_SHARED) fast = 0;
         else if (b->yref_mode == MPCX_REF_PER_INSTANCE) fast = 1;
     }
-    if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; B.done = h->done; }
+    if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; }
     else if (fast >= 0 && h->dev.fused_ok && !B.dbg_cycles && h->use_fused == 1) { B.fused = fast + 1; B.pcounter = h->pcounter; }
-    int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 7, fast, h->pbuf, h->pslots);
+    int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 7, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
+    if (lr != 0) (void)mpcx::lmpc_fallback_reset(h->fq, stream);      // a step that broke off may have filed failures nobody served
     if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
     if (lr != 0) return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     return MPCX_OK;
@@ -976,10 +980,27 @@ int mpcx_lmpc_hetero_destroy(mpcx_lmpc_hetero_t f)
 }
 
 /* testing aid: one O(n^3) array ("H", "Kinv", "Gr", "Gc", "Y", "rho_b", "rho_g") of model k copied to the host; returns its length */
+// testing aid: {instances the fallback kernel served in the last step that had any since the previous read, entries the failure queue holds, wavefronts of the fallback
+// kernel's grid at a full batch}; waits for the device
+static bool fallback_state(int *fq, size_t cap, int pslots, double *out3)
+{
+    int served = 0;
+    // (the idle fallback launch writes nothing, not even a zero here: the read clears the figure, so that it speaks of the steps since the last read)
+    if (fq && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&served, fq + mpcx::kFqServed, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+               hipMemset(fq + mpcx::kFqServed, 0, sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) return false;
+    const int w = mpcx::lmpc_fallback_waves();
+    out3[0] = served; out3[1] = (double)cap; out3[2] = fq ? (pslots < w ? pslots : w) : w;
+    return true;
+}
+
 int mpcx_lmpc_hetero_debug_get(mpcx_lmpc_hetero_t f, int k, const char *name, double *out, int cap)
 {
     if (!f || k < 0 || k >= f->count || !name) return fail(MPCX_E_INVALID, "bad argument");
     if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (std::string(name) == "fallback") {
+        if (out && cap >= 3 && !fallback_state(f->fq, f->ws_cap, f->pslots, out)) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
+        return 3;
+    }
     mpcx::LmpcDev D;
     if (hipMemcpy(&D, f->models_d + k, sizeof(D), hipMemcpyDeviceToHost) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
     const std::string n(name);
@@ -1046,15 +1067,19 @@ int mpcx_lmpc_hetero_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b,
     if ((size_t)b->batch > f->ws_cap) {
         if (f->ws) (void)hipFree(f->ws);
         if (f->pbuf) (void)hipFree(f->pbuf);
-        f->ws = nullptr; f->ws_cap = 0; f->pbuf = nullptr; f->pslots = 0;
+        if (f->fq) (void)hipFree(f->fq);
+        f->ws = nullptr; f->fq = nullptr; f->ws_cap = 0; f->pbuf = nullptr; f->pslots = 0;
         const int slots = mpcx::lmpc_fallback_slots(f->dev0, b->batch);
         if (hipMalloc(reinterpret_cast<void **>(&f->ws), (size_t)b->batch * f->dev0.wsld * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&f->pbuf), (size_t)slots * f->dev0.nz * f->dev0.nz * sizeof(double)) != hipSuccess)
+            hipMalloc(reinterpret_cast<void **>(&f->pbuf), (size_t)slots * f->dev0.nz * f->dev0.nz * sizeof(double)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&f->fq), mpcx::lmpc_fallback_queue_bytes((size_t)b->batch)) != hipSuccess ||
+            hipMemsetAsync(f->fq, 0, mpcx::lmpc_fallback_queue_bytes(0), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
             return fail(MPCX_E_DEVICE, "workspace allocation failed");
         f->pslots = slots;
         f->ws_cap = (size_t)b->batch;
     }
-    const int lr = mpcx::lmpc_launch(f->dev0, f->models_d, B, f->ws, stream, 7, -1, f->pbuf, f->pslots);      // roll-out assemble, lean solve, ADMM fallback
+    const int lr = mpcx::lmpc_launch(f->dev0, f->models_d, B, f->ws, stream, 7, -1, f->pbuf, f->pslots, f->fq, (int)f->ws_cap);      // roll-out assemble, lean solve, ADMM fallback
+    if (lr != 0) (void)mpcx::lmpc_fallback_reset(f->fq, stream);
     if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
     if (lr != 0) return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     return MPCX_OK;
@@ -1095,7 +1120,7 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
         if (b->yref_mode == MPCX_REF_SHARED) fast = 0;
         else if (b->yref_mode == MPCX_REF_PER_INSTANCE) fast = 1;
     }
-    if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; B.done = h->done; }
+    if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; }
     else if (fast >= 0 && h->dev.fused_ok && !B.dbg_cycles && h->use_fused == 1) { B.fused = fast + 1; B.pcounter = h->pcounter; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipEvent_t e0, e1;
@@ -1105,9 +1130,9 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
         if (which == 2 && h->dev.cost_direct) {
             // with pending costs the solve leaves w in t0's place: every timed launch needs a freshly assembled workspace
             for (int i = 0; i < repeats; i++) {
-                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 1, fast, h->pbuf, h->pslots);
+                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 1, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
                 (void)hipEventRecord(e0, s);
-                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 2, fast, h->pbuf, h->pslots);
+                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 2, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
                 (void)hipEventRecord(e1, s);
                 (void)hipEventSynchronize(e1);
                 float one = 0;
@@ -1116,11 +1141,14 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
             }
         } else {
             (void)hipEventRecord(e0, s);
-            for (int i = 0; i < repeats; i++) mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, which, fast, h->pbuf, h->pslots);
+            for (int i = 0; i < repeats; i++) mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, which, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
             (void)hipEventRecord(e1, s);
             (void)hipEventSynchronize(e1);
             (void)hipEventElapsedTime(&ms, e0, e1);
         }
+        // the solve kernels ran without the fallback behind them: what they filed in the failure queue is dropped (outside the timed window), so that
+        // slot 2 times the idle fallback launch and the next step starts from an empty queue
+        if (which == 2) (void)mpcx::lmpc_fallback_reset(h->fq, stream);
         ms2[which == 1 ? 0 : (which == 2 ? 1 : 2)] = ms / (float)repeats;
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -1220,6 +1248,13 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "g_step") { tmp.assign(o.g_step.begin(), o.g_step.end()); v = &tmp; }
     else if (n == "g_kind") { tmp.assign(o.g_kind.begin(), o.g_kind.end()); v = &tmp; }
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }
+    else if (n == "fallback") {           // the failure queue: served in the last step that had failures, capacity, fallback wavefronts
+        tmp.assign(3, 0.0);
+        if (out && !h->host_only) {
+            if (hipSetDevice(h->device) != hipSuccess || !fallback_state(h->fq, h->ws_cap, h->pslots, tmp.data())) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
+        }
+        v = &tmp;
+    }
     else return fail(MPCX_E_INVALID, "unknown array name");
     if (!out) return (int)v->size();
     if (cap < (int)v->size()) return fail(MPCX_E_INVALID, "buffer too small");
