@@ -11,7 +11,9 @@
 // 128*c + 2*l and 128*c + 2*l + 1 for c < CP (CP = ceil(n / 128)).
 #pragma once
 
+#include <atomic>
 #include <cstdint>
+#include <initializer_list>
 
 namespace mpcx {
 
@@ -82,9 +84,9 @@ struct LmpcBatchDev {
     const uint32_t *warm_lower, *warm_upper;      // optional previous active sets (reference row numbering)
     int warm_shift;
     int fq_cap;                                   // entries the failure queue's list holds
-    int fused;                                    // 0: record from the workspace; 1 / 2: lmpc_solve_fused with MF0 / MF1; 3 / 4: lmpc_solve_group with MA0 / MA1
+    int fused;                                    // 0: record from the workspace; 1 / 2: lmpc_solve_fused with MF0 / MF1; 3 / 4: lmpc_solve_group with MA0 / MA1.  The kernels read this encoding; the host writes it in one place, LmpcPlan::fused (lmpc_launch copies it here)
     int *fq;                                      // failure queue (described below; lmpc_launch fills it in): the polish-first kernels list the instances they leave open, the fallback kernel serves the list.  Null when polish is switched off: the fallback then serves every instance
-    int *pcounter;                                // work counter of the persistent fused kernel (null: one instance per launched wavefront)
+    int *pcounter;                                // work counter of the persistent fused kernel (lmpc_launch fills it in for the fused mat-vec form; null: one instance per launched wavefront)
     // heterogeneous batch (mpcx_lmpc_hetero_*): the kernels' model pointer is an array of n_models structs of identical dimensions and
     // constraint structure, instance b uses entry model_index[b] (null: entry b); 0 models = the one shared controller
     int n_models;
@@ -110,15 +112,31 @@ int lmpc_fallback_reset(int *fq, void *stream);
 size_t lmpc_lds_limit();
 // implemented in lmpc_kernels.hip
 int lmpc_kernel_variant(int ldz, int ldg);     // -1 if the dimensions are not covered
-// which: bit 0 = assemble, bit 1 = polish-only solve, bit 2 = ADMM fallback (7 = the normal path;
-// single bits are for per-kernel timing).  fast_variant: -1 = generic assemble kernel, 0/1 = MFMA
-// assemble kernel with shared / per-instance-constant output reference.
-// pbuf / pslots: the fallback kernel's buffer for working sets of more than kMaxActive rows, pslots slots of nz x nz doubles
-// (lmpc_fallback_slots); its grid is then capped at pslots wavefronts.  Null: such sets are left to ADMM.
-// fq / fq_cap: the handle's failure queue (zeroed when allocated) and the entries its list holds, at least the batch.
-int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream,
-                int which, int fast_variant, double *pbuf, int pslots, int *fq, int fq_cap);
-// slots of that buffer to allocate for batches of up to `batch` instances: one per wavefront the fallback kernel launches (lmpc_fallback_waves,
+// One handle's scratch memory on the device, sized for batches of up to `cap` instances:
+//   ws       per-instance workspace between assemble and solve, cap records of wsld doubles
+//   fq       failure queue (above), a list of cap entries, count and ticket zeroed when allocated
+//   pbuf     the fallback kernel's slots for working sets of more than kMaxActive rows, pslots (lmpc_fallback_slots) x nz x nz doubles; the
+//            fallback's grid is capped at pslots wavefronts
+//   pcounter work counters of the persistent fused kernel, eight ints (single-controller handles only; null in a bank)
+struct LmpcScratch { double *ws; size_t cap; int *fq; double *pbuf; int pslots; int *pcounter; };
+// grow-only: allocates anew when `batch` exceeds cap (not capturable in a graph: the first, plain solve of a batch size does it); the queue's header
+// is zeroed in `stream`'s order.  with_pcounter: the counters come with the workspace, never later -- a launch under capture must not allocate.
+// 0, or -3 (cap stays 0: the next call starts over)
+int lmpc_scratch_reserve(LmpcScratch &s, const LmpcDev &m, int batch, bool with_pcounter, void *stream);
+void lmpc_scratch_release(LmpcScratch &s);
+
+// What one call launches, decided once by the caller (mpcx_capi.cpp: lmpc_plan) and only read by the launchers.
+enum class LmpcAssemble { Generic, MfmaSharedYref, MfmaInstanceYref };      // roll-out kernel, or the MFMA kernel with a shared / per-instance-constant output reference
+enum class LmpcForm { TwoKernels, FusedMatvec, Group };                     // assemble + lmpc_solve; lmpc_solve_fused / lmpc_solve_persistent; lmpc_solve_group
+struct LmpcPlan {
+    LmpcAssemble assemble;
+    LmpcForm form;
+    int fused;                                    // what LmpcBatchDev::fused is given: 0 for two kernels, 1 / 2 fused mat-vec, 3 / 4 group, the odd value for the shared reference
+};
+// which: bit 0 = assemble, bit 1 = polish-only solve, bit 2 = ADMM fallback (7 = the normal path; single bits are for per-kernel timing).
+// The scratch must hold the batch (lmpc_scratch_reserve); without large-working-set slots such sets are left to ADMM.
+int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, const LmpcScratch &scratch, void *stream, int which, const LmpcPlan &plan);
+// slots of the large-working-set buffer (LmpcScratch::pbuf) to allocate for batches of up to `batch` instances: one per wavefront the fallback kernel launches (lmpc_fallback_waves,
 // never more than instances), at most what fits in a fixed budget (at least one workgroup's)
 int lmpc_fallback_slots(const LmpcDev &m, int batch);
 int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len);
@@ -128,8 +146,13 @@ void lmpc_pack_mfma_tiles(const double *src, int rows, int K, double *out);
 inline size_t lmpc_packed_len(int rows, int K) { return (size_t)(rows / 16) * ((K + 15) / 16) * 256; }
 int lmpc_fast_slice(const LmpcDev &m);          // needs wsld, kin, nx
 size_t lmpc_group_lds_bytes(const LmpcDev &m);  // LDS block of lmpc_solve_group (0: no group form for the variant); needs fast_slice, kin, nz16, nu
-// implemented in lmpc_fast.hip: the lean polish kernel (b.fused: the fused / persistent forms) on `stream`
-int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream);
+// implemented in lmpc_fast.hip: the polish-first kernel of `form` on `stream`
+int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, LmpcForm form);
+// hipFuncAttributeMaxDynamicSharedMemorySize of `kernels` raised to `bytes` on the current device unless `cache` says it has been: one cache per
+// set of kernels that are raised together, grow-only, an atomic per device (two host threads or two handles on different GPUs can neither skip
+// nor tear the update).  0, or -3
+struct LmpcLdsCache { std::atomic<size_t> bytes[64]; };
+int lmpc_raise_dynamic_lds(LmpcLdsCache &cache, std::initializer_list<const void *> kernels, size_t bytes);
 // implemented in lmpc_hetero.hip: the O(n^3) arrays of `count` model structs (device array) computed in place, one workgroup each;
 // -2: the dimensions do not fit the kernel's LDS plan (the bank then condenses on the host)
 size_t lmpc_condense_lds(const LmpcDev &m, int *NP_out, int *NQ_out, size_t *big_out = nullptr);

@@ -10,7 +10,7 @@ namespace {
 // =====================================================================================
 // solve, lean form: the polish-only path of lmpc_solve, one instance per wavefront
 // =====================================================================================
-// Same algorithm and same outputs as solve_one<.., ADMM = false> (OSQP's polish promoted to the main iteration, a verified
+// The polish-first solve (OSQP's polish promoted to the main iteration, a verified
 // point is the exact optimum), rebuilt around what the round-2 profile showed: the kernel is bound by the number of
 // instructions a wavefront issues per round and by the rounds of the slowest instances, not by arithmetic.
 //   * repair rule: wrong-signed rows leave AND violated rows enter in the same round (drop-then-add doubled the rounds of the
@@ -225,6 +225,101 @@ __device__ __forceinline__ void fast_init_pads(double *slice, const int ldz, con
 // lwuw: the workgroup's copy of the box bounds [lw (ZP) | uw (ZP)], padded the same way
 template <int CPZ, int CPG> constexpr int fast_slice_fixed() { return 2 * 128 * CPZ + 3 * 128 * CPG + 2 + 2 * (kFastCap + 2) + (kFastCap + 2) / 2 + 1; }
 
+// =====================================================================================
+// the record of one instance without the workspace: ProblemBuilder::get as ONE mat-vec
+// =====================================================================================
+// Everything the solve needs of an instance -- f, t0 = -Hinv f, G t0, the row offsets, the feasibility rows and the cost
+// constant -- is MF * vin with vin = [x0 | lastU | yref | 1] (lmpc_model.cpp: compose_fused_maps).  The wavefront computes it
+// into its own LDS slice, in the layout of the workspace record (f | t0 | gt0 | lg | ug | c0, flag), and solve_fast reads it
+// from there: no assemble kernel, no 2.7 KB per instance written to HBM and read back.  MF streams from L2 (87 KB at N = 20).
+constexpr int kCpFused = 3;            // rows of MF per lane pair: up to 384
+// where the pieces of the record go (the lean kernels keep them in padded LDS arrays)
+struct RecPtrs { double *f, *t0, *gt0, *lg, *ug, *tail; };
+// (__forceinline__: as a real call the lean kernels' fused form faulted on its by-reference arguments)
+__device__ __forceinline__ void fused_record(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane, double *stage,
+                                             const RecPtrs &rp, const double *mf_lds)
+{
+    const int nx = M.nx, nu = M.nu, ny = M.ny, kin = M.kin;
+    const int ldz = M.ldz, ldg = M.ldg, ldy = M.ldy, rowsF = M.rowsF;
+    const int variant = Bt.fused - 1;
+    // vin: the same k -> (x0 | lastU | yref | 1) map as lmpc_assemble_mfma (kin may exceed the 64 lanes: nx + nu + ny past 60)
+    for (int k = lane; k < kin; k += 64) {
+        double v = 0.0;
+        if (k < M.nxp) { if (k < nx) v = gl(Bt.x0)[(size_t)b * nx + k]; }
+        else if (k < M.nxp + M.nup) { const int c = k - M.nxp; if (c < nu) v = gl(Bt.u0)[(size_t)b * nu + c]; }
+        else if (k < M.ione) { const int c = k - M.nxp - M.nup; if (variant && c < ny) v = gl(Bt.yref)[(size_t)b * Bt.yref_bs + c]; }
+        else if (k == M.ione) v = 1.0;
+        stage[k] = v;
+    }
+    wave_sync();
+    double acc[2 * kCpFused];
+#pragma unroll
+    for (int s = 0; s < 2 * kCpFused; ++s) acc[s] = 0.0;
+    if (mf_lds) {
+        // the composed map sits in this workgroup's LDS (lmpc_solve_persistent loaded it once): sixteen-byte reads, lanes on
+        // consecutive rows (no bank conflicts), four columns in flight
+        int off[kCpFused];
+#pragma unroll
+        for (int c = 0; c < kCpFused; ++c) { const int e = 128 * c + 2 * lane; off[c] = e < rowsF ? e : 0; }
+        for (int j = 0; j < kin; j += 4) {
+            double2 m[4][kCpFused];
+            double xj[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double *col = mf_lds + (size_t)(j + u) * rowsF;
+#pragma unroll
+                for (int c = 0; c < kCpFused; ++c) m[u][c] = *reinterpret_cast<const double2 *>(col + off[c]);
+                xj[u] = stage[j + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int c = 0; c < kCpFused; ++c) {
+                    acc[2 * c] = fma(m[u][c].x, xj[u], acc[2 * c]);
+                    acc[2 * c + 1] = fma(m[u][c].y, xj[u], acc[2 * c + 1]);
+                }
+            }
+        }
+    } else {
+        // from L2, two columns per batch: the stream is bandwidth-bound there -- every wavefront of the launch reads the same
+        // 87 KB -- and deeper batches only made the burst worse (146 us against 122 us for the launch at the benchmark batch)
+        matvec_acc<kCpFused>(gl(variant ? M.MF1 : M.MF0), rowsF, rowsF, kin, stage, acc, lane);
+    }
+    const int r_goff = ldy, r_f = r_goff + ldg, r_s = r_f + ldz, r_q = r_s + M.nsp;
+    double c0p = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < kCpFused; ++c) {
+        const int e = 128 * c + 2 * lane;          // block boundaries are even: a pair never straddles two blocks
+        if (e >= rowsF) continue;
+        const double a0 = acc[2 * c], a1 = acc[2 * c + 1];
+        if (e < ldz) {                             // t0
+            *reinterpret_cast<double2 *>(rp.t0 + e) = make_double2(a0, a1);
+        } else if (e < r_goff) {                   // gt0
+            *reinterpret_cast<double2 *>(rp.gt0 + (e - ldz)) = make_double2(a0, a1);
+        } else if (e < r_f) {                      // row offsets -> bounds of this instance
+            const int r = e - r_goff;
+            const d2 l0 = ld2(GP(lg0) + r), u0 = ld2(GP(ug0) + r);
+            *reinterpret_cast<double2 *>(rp.lg + r) = make_double2(l0.x - a0, l0.y - a1);
+            *reinterpret_cast<double2 *>(rp.ug + r) = make_double2(u0.x - a0, u0.y - a1);
+        } else if (e < r_s) {                      // linear term
+            *reinterpret_cast<double2 *>(rp.f + (e - r_f)) = make_double2(a0, a1);
+        } else if (e < r_q) {                      // rows that do not see the inputs: pure feasibility conditions on (x0, lastU)
+            const int r = e - r_s;
+            if (r < M.ns) bad |= violates(a0, GP(slo)[r], GP(shi)[r], M.eps_abs, M.eps_rel);
+            if (r + 1 < M.ns) bad |= violates(a1, GP(slo)[r + 1], GP(shi)[r + 1], M.eps_abs, M.eps_rel);
+        } else {                                   // cost constant: vin' Qc vin / 2
+            const int k = e - r_q;
+            c0p = fma(0.5 * stage[k], a0, c0p);
+            c0p = fma(0.5 * stage[k + 1], a1, c0p);
+        }
+    }
+    c0p = wave_sum(c0p);
+    const bool anybad = wave_any(bad);
+    if (lane == 0) *reinterpret_cast<double2 *>(rp.tail) = make_double2(c0p, anybad ? 1.0 : 0.0);
+    wave_sync();
+}
+
 // SRC: where the instance's record comes from -- 0 the workspace (two-kernel path), 1 computed here by fused_record (one mat-vec
 // with the composed maps), 2 already in the slice (lmpc_solve_group: the workgroup's MFMA assemble phase put it there)
 template <int CPZ, int CPG, int SRC = 0>
@@ -292,7 +387,7 @@ __device__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b
     }
     const double c0 = tail[0];
     const double flag0 = tail[1];
-    // a violated step-0 / input-independent row: see solve_one
+    // a violated step-0 / input-independent row: see admm_solve_one (lmpc_kernels.hip)
     const bool fixed_violation = flag0 == 1.0;
     const bool infeasible = fixed_violation && M.strict_infeasible;
 
@@ -341,7 +436,7 @@ __device__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b
     stamp(ts1);   // 1: loaded
 
     if (Bt.warm_lower) {
-        // warm start: the first working set is the previous solve's active set (see solve_one)
+        // warm start: the first working set is the previous solve's active set (see admm_solve_one)
         const unsigned MPCX_GAS *wl = gl(Bt.warm_lower) + (size_t)b * M.active_words;
         const unsigned MPCX_GAS *wu = gl(Bt.warm_upper) + (size_t)b * M.active_words;
         const int na = M.nx + M.nu, n1 = M.ph + 1;
@@ -590,7 +685,8 @@ __device__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b
     if (infeasible) {
         cost = 1e30;
     } else if (!M.cost_direct) {
-        // cost from the multipliers: (f'w - lambda'b_A)/2 + c0 (see solve_one)
+        // cost from the multipliers: at the verified point H w + f + N_A' lambda = 0 and N_A w = b_A, hence w'Hw/2 + f'w = (f'w - lambda'b_A)/2 -- no
+        // pass over H (the single largest read of an instance), and the products involve the bounded solution w, not the possibly huge unconstrained optimum
         double j = 0;
 #pragma unroll
         for (int s = 0; s < NZS; ++s) j = fma(f[s], w[s], j);
@@ -1201,7 +1297,7 @@ size_t lmpc_group_lds_bytes(const LmpcDev &m);
 namespace {
 
 template <int CPZ, int CPG>
-int launch_fast_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, hipStream_t stream)
+int launch_fast_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, hipStream_t stream, const LmpcForm form)
 {
     size_t ldsf = ((size_t)2 * 128 * CPZ + (size_t)kWavesPerBlock * m.fast_slice + (b.n_models > 0 ? (size_t)kWavesPerBlock * 2 * 128 * CPZ : 0)) * sizeof(double);
     static const size_t dbg_pad = [] { const char *pad = getenv("MPCX_DBG_LDS_PAD"); return pad ? (size_t)atoi(pad) : (size_t)0; }();      // (occupancy experiments; read once)
@@ -1213,46 +1309,31 @@ int launch_fast_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchD
     // the fused forms serve the one-chunk variant only (fused_record: up to 384 rows of the composed map)
     auto k4 = lmpc_solve_fused<1, 1>;
     auto k5 = lmpc_solve_persistent<1, 1>;
-    static std::atomic<size_t> configured[64];
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    devid &= 63;
-    if (ldsf > configured[devid].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k2h), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf) != hipSuccess)
-            return -3;
-        size_t prev = configured[devid].load(std::memory_order_relaxed);
-        while (prev < ldsf && !configured[devid].compare_exchange_weak(prev, ldsf, std::memory_order_release)) {}
-    }
+    static LmpcLdsCache configured;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(k2), reinterpret_cast<const void *>(k2h), reinterpret_cast<const void *>(k4)}, ldsf) != 0) return -3;
     int blocks = (b.batch + kWavesPerBlock - 1) / kWavesPerBlock;      // one wavefront per instance: the grid covers the batch
     if (blocks < 1) blocks = 1;
-    const bool fused = b.fused != 0 && CPZ == 1 && CPG == 1;
-    if constexpr (CPZ <= 2 && CPZ == CPG) {
-        if (b.fused >= 3) {
+    if (form == LmpcForm::Group) {
+        if constexpr (CPZ <= 2 && CPZ == CPG) {
             // assemble + solve in one workgroup of sixteen (two-chunk variant: eight) wavefronts, one per CU
             constexpr int NW = kGroupWavesOf<CPZ>;
             const size_t ldsg = lmpc_group_lds_bytes(m);
             if (ldsg == 0 || ldsg > lds_max) return -2;
-            static std::atomic<int> gconf[64];
-            if (!gconf[devid].load(std::memory_order_acquire)) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(lmpc_solve_group<CPZ, CPG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return -3;
-                gconf[devid].store(1, std::memory_order_release);
-            }
+            static LmpcLdsCache gconf;
+            if (lmpc_raise_dynamic_lds(gconf, {reinterpret_cast<const void *>(lmpc_solve_group<CPZ, CPG>)}, lds_max) != 0) return -3;
             const int wgs = (b.batch + NW - 1) / NW;
             hipLaunchKernelGGL((lmpc_solve_group<CPZ, CPG>), dim3(wgs), dim3(NW * 64), ldsg, stream, m, b, ws, b.fused - 3);      // (the model struct by value: see the kernel)
             return hipGetLastError() == hipSuccess ? 0 : -3;
         }
+        return -2;      // (no group form for the four-chunk variant: lmpc_group_lds_bytes is 0 there, no plan names it)
     }
+    const bool fused = form == LmpcForm::FusedMatvec;
     // persistent form: the composed map, the box bounds and kPersistWaves slices must fit one CU's LDS, and the batch must be worth
     // the prologue of every workgroup (the composed map: 87 KB at N = 20)
     const size_t ldsp = ((size_t)m.rowsF * m.kin + 2 * (size_t)128 + kPersistWaves * (size_t)m.fast_slice) * sizeof(double);
     if (fused && b.pcounter && ldsp <= lds_max && b.batch >= 1024) {
-        static std::atomic<int> pconf[64];
-        if (!pconf[devid].load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return -3;
-            pconf[devid].store(1, std::memory_order_release);
-        }
+        static LmpcLdsCache pconf;
+        if (lmpc_raise_dynamic_lds(pconf, {reinterpret_cast<const void *>(k5)}, lds_max) != 0) return -3;
         (void)hipMemsetAsync(b.pcounter, 0, 8 * sizeof(int), stream);
         int wgs = (b.batch + kPersistWaves - 1) / kPersistWaves;
         if (wgs > 256) wgs = 256;
@@ -1286,14 +1367,14 @@ size_t lmpc_group_lds_bytes(const LmpcDev &m)
     return ((size_t)2 * 128 * cp + (size_t)nw * m.fast_slice + (size_t)(m.kin / 4 + m.nz16 / 4) * 64 + (size_t)nw * 16 + 16 + (size_t)nw * (8 + ((m.nu + 1) & ~1)) + 32) * sizeof(double);
 }
 
-int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream)
+int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, LmpcForm form)
 {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (lmpc_kernel_variant(m.ldz, m.ldg)) {
-    case 1: return launch_fast_variant<1, 1>(m, m_dev, b, ws, s);
+    case 1: return launch_fast_variant<1, 1>(m, m_dev, b, ws, s, form);
 #ifndef MPCX_FAST_ONLY_CP1
-    case 2: return launch_fast_variant<2, 2>(m, m_dev, b, ws, s);
-    case 4: return launch_fast_variant<4, 4>(m, m_dev, b, ws, s);
+    case 2: return launch_fast_variant<2, 2>(m, m_dev, b, ws, s, form);
+    case 4: return launch_fast_variant<4, 4>(m, m_dev, b, ws, s, form);
 #endif
     default: return -2;
     }

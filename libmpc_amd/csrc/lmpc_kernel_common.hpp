@@ -1,5 +1,5 @@
 // Helpers shared by the LMPC kernel translation units (lmpc_kernels.hip, lmpc_fast.hip): address-space casts, wave-level
-// primitives, the batched mat-vec, the fused record.  Everything lives in an anonymous namespace: each unit gets its own copy.
+// primitives, the batched mat-vec.  Everything lives in an anonymous namespace: each unit gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,9 +34,6 @@ constexpr int kWavesPerBlock = MPCX_WAVES_PER_BLOCK;
 #endif
 #ifndef MPCX_FAST_ADD_THETA
 #define MPCX_FAST_ADD_THETA 0.2
-#endif
-#ifndef MPCX_SOLVE_WAVES
-#define MPCX_SOLVE_WAVES 2
 #endif
 
 // Pointers that come out of the model struct are generic pointers to the compiler, which
@@ -174,103 +171,6 @@ __device__ __forceinline__ bool violates(double v, double lo, double hi, double 
 #define GP(field) gl(M.field)
 
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-// =====================================================================================
-// the record of one instance without the workspace: ProblemBuilder::get as ONE mat-vec
-// =====================================================================================
-// Everything the solve needs of an instance -- f, t0 = -Hinv f, G t0, the row offsets, the feasibility rows and the cost
-// constant -- is MF * vin with vin = [x0 | lastU | yref | 1] (lmpc_model.cpp: compose_fused_maps).  The wavefront computes it
-// into its own LDS slice, in the layout of the workspace record (f | t0 | gt0 | lg | ug | c0, flag), and solve_one reads it
-// from there: no assemble kernel, no 2.7 KB per instance written to HBM and read back.  MF streams from L2 (87 KB at N = 20).
-constexpr int kCpFused = 3;            // rows of MF per lane pair: up to 384
-#ifndef MPCX_FUSED_RECORD_INLINE
-#define MPCX_FUSED_RECORD_INLINE __forceinline__      // (as a real call the lean kernels' fused form faulted on its by-reference arguments)
-#endif
-// where the pieces of the record go (the lean kernels keep them in padded LDS arrays)
-struct RecPtrs { double *f, *t0, *gt0, *lg, *ug, *tail; };
-__device__ MPCX_FUSED_RECORD_INLINE void fused_record(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane, double *stage,
-                                                      const RecPtrs &rp, const double *mf_lds)
-{
-    const int nx = M.nx, nu = M.nu, ny = M.ny, kin = M.kin;
-    const int ldz = M.ldz, ldg = M.ldg, ldy = M.ldy, rowsF = M.rowsF;
-    const int variant = Bt.fused - 1;
-    // vin: the same k -> (x0 | lastU | yref | 1) map as lmpc_assemble_mfma (kin may exceed the 64 lanes: nx + nu + ny past 60)
-    for (int k = lane; k < kin; k += 64) {
-        double v = 0.0;
-        if (k < M.nxp) { if (k < nx) v = gl(Bt.x0)[(size_t)b * nx + k]; }
-        else if (k < M.nxp + M.nup) { const int c = k - M.nxp; if (c < nu) v = gl(Bt.u0)[(size_t)b * nu + c]; }
-        else if (k < M.ione) { const int c = k - M.nxp - M.nup; if (variant && c < ny) v = gl(Bt.yref)[(size_t)b * Bt.yref_bs + c]; }
-        else if (k == M.ione) v = 1.0;
-        stage[k] = v;
-    }
-    wave_sync();
-    double acc[2 * kCpFused];
-#pragma unroll
-    for (int s = 0; s < 2 * kCpFused; ++s) acc[s] = 0.0;
-    if (mf_lds) {
-        // the composed map sits in this workgroup's LDS (lmpc_solve_persistent loaded it once): sixteen-byte reads, lanes on
-        // consecutive rows (no bank conflicts), four columns in flight
-        int off[kCpFused];
-#pragma unroll
-        for (int c = 0; c < kCpFused; ++c) { const int e = 128 * c + 2 * lane; off[c] = e < rowsF ? e : 0; }
-        for (int j = 0; j < kin; j += 4) {
-            double2 m[4][kCpFused];
-            double xj[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double *col = mf_lds + (size_t)(j + u) * rowsF;
-#pragma unroll
-                for (int c = 0; c < kCpFused; ++c) m[u][c] = *reinterpret_cast<const double2 *>(col + off[c]);
-                xj[u] = stage[j + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                for (int c = 0; c < kCpFused; ++c) {
-                    acc[2 * c] = fma(m[u][c].x, xj[u], acc[2 * c]);
-                    acc[2 * c + 1] = fma(m[u][c].y, xj[u], acc[2 * c + 1]);
-                }
-            }
-        }
-    } else {
-        // from L2, two columns per batch: the stream is bandwidth-bound there -- every wavefront of the launch reads the same
-        // 87 KB -- and deeper batches only made the burst worse (146 us against 122 us for the launch at the benchmark batch)
-        matvec_acc<kCpFused>(gl(variant ? M.MF1 : M.MF0), rowsF, rowsF, kin, stage, acc, lane);
-    }
-    const int r_goff = ldy, r_f = r_goff + ldg, r_s = r_f + ldz, r_q = r_s + M.nsp;
-    double c0p = 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int c = 0; c < kCpFused; ++c) {
-        const int e = 128 * c + 2 * lane;          // block boundaries are even: a pair never straddles two blocks
-        if (e >= rowsF) continue;
-        const double a0 = acc[2 * c], a1 = acc[2 * c + 1];
-        if (e < ldz) {                             // t0
-            *reinterpret_cast<double2 *>(rp.t0 + e) = make_double2(a0, a1);
-        } else if (e < r_goff) {                   // gt0
-            *reinterpret_cast<double2 *>(rp.gt0 + (e - ldz)) = make_double2(a0, a1);
-        } else if (e < r_f) {                      // row offsets -> bounds of this instance
-            const int r = e - r_goff;
-            const d2 l0 = ld2(GP(lg0) + r), u0 = ld2(GP(ug0) + r);
-            *reinterpret_cast<double2 *>(rp.lg + r) = make_double2(l0.x - a0, l0.y - a1);
-            *reinterpret_cast<double2 *>(rp.ug + r) = make_double2(u0.x - a0, u0.y - a1);
-        } else if (e < r_s) {                      // linear term
-            *reinterpret_cast<double2 *>(rp.f + (e - r_f)) = make_double2(a0, a1);
-        } else if (e < r_q) {                      // rows that do not see the inputs: pure feasibility conditions on (x0, lastU)
-            const int r = e - r_s;
-            if (r < M.ns) bad |= violates(a0, GP(slo)[r], GP(shi)[r], M.eps_abs, M.eps_rel);
-            if (r + 1 < M.ns) bad |= violates(a1, GP(slo)[r + 1], GP(shi)[r + 1], M.eps_abs, M.eps_rel);
-        } else {                                   // cost constant: vin' Qc vin / 2
-            const int k = e - r_q;
-            c0p = fma(0.5 * stage[k], a0, c0p);
-            c0p = fma(0.5 * stage[k + 1], a1, c0p);
-        }
-    }
-    c0p = wave_sum(c0p);
-    const bool anybad = wave_any(bad);
-    if (lane == 0) *reinterpret_cast<double2 *>(rp.tail) = make_double2(c0p, anybad ? 1.0 : 0.0);
-    wave_sync();
-}
 
 }  // namespace
 

@@ -512,11 +512,11 @@ __global__ __launch_bounds__(256) void lmpc_assemble_mfma(const LmpcDev *__restr
 }
 
 // =====================================================================================
-// solve: one instance per wavefront
+// the ADMM fallback's solve: one instance per wavefront
 // =====================================================================================
-template <int CPZ, int CPG, bool ADMM, bool FUSED = false>
-__device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
-                          double *stage, double *nt0, double *arena, gdw ws, const double *mf_lds = nullptr, gdw bigS = nullptr)
+template <int CPZ, int CPG>
+__device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
+                               double *stage, double *nt0, double *arena, gdw ws, gdw bigS)
 {
     constexpr int NZS = 2 * CPZ, NGS = 2 * CPG;
     const int nx = M.nx, nu = M.nu, ny = M.ny, ndu = M.ndu, ph = M.ph;
@@ -525,29 +525,13 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     const gdp gY = GP(Y);
 
-    long long tstamp[8];
-    // profiling aid (tools/phase_cycles.py): cycles per phase of a polish round.  Compiled in with -DMPCX_PROFILE_ROUNDS only:
-    // even switched off at run time the counters cost registers the kernel does not have (16 more spilled VGPRs).
-#ifdef MPCX_PROFILE_ROUNDS
-    long long pacc[4] = {0, 0, 0, 0}, plast = 0;
-    auto plap = [&](int k) { if (Bt.dbg_cycles) { const long long now = (long long)__builtin_readcyclecounter(); pacc[k] += now - plast; plast = now; } };
-#else
-    auto plap = [](int) {};
-#endif
+    long long tstamp[8];      // profiling aid (tools/phase_cycles.py): start, loaded, solved, unpacked
     int tsi = 0;
     auto stamp = [&]() { if (Bt.dbg_cycles && tsi < 8) tstamp[tsi++] = (long long)__builtin_readcyclecounter(); };
     stamp();
 
-    // ---- load the assembled problem: from the workspace record the assemble kernel left, or from the one this wavefront just
-    // computed into its LDS slice (same layout)
-    if constexpr (FUSED) {
-        RecPtrs rp{arena, arena + ldz, arena + 2 * ldz, arena + ldz + ldy, arena + ldz + ldy + ldg, arena + ldz + ldy + 2 * ldg};
-        fused_record(M, Bt, b, lane, stage, rp, mf_lds);
-    }
-    auto rec2 = [&](int at) -> d2 {
-        if constexpr (FUSED) { const double2 v = *reinterpret_cast<const double2 *>(arena + at); d2 r; r.x = v.x; r.y = v.y; return r; }
-        else return ld2(ws + at);
-    };
+    // ---- load the assembled problem from the workspace record (the assemble kernel left it, or the one-kernel form that gave the instance up filed it)
+    auto rec2 = [&](int at) -> d2 { return ld2(ws + at); };
     double f[NZS], lw[NZS], uw[NZS], rb[NZS], t0[NZS];
     bool eqb[NZS];
 #pragma unroll
@@ -589,8 +573,7 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
     // strict mode: INFEASIBLE.
     const bool fixed_violation = tail.y == 1.0;
     const bool infeasible0 = fixed_violation && M.strict_infeasible;
-    if (ADMM && tail.y == 2.0) return;          // already solved by the polish-only kernel
-    if constexpr (FUSED) wave_sync();           // the record has been read: its LDS is the polish arena from here on
+    if (tail.y == 2.0) return;                  // already solved by the polish-only kernel
     stage_store<CPZ>(nt0, t0, ldz, lane);
     stage_store<CPG>(nt0 + ldz, gt0, ldg, lane);
     wave_sync();
@@ -674,9 +657,6 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                                  // else most violated row in), which does not cycle in practice
         for (int rd = 0; rd < rounds; ++rd) {
             ++rounds_total;
-#ifdef MPCX_PROFILE_ROUNDS
-            if (Bt.dbg_cycles) plast = (long long)__builtin_readcyclecounter();
-#endif
             int na = 0;
             unsigned long long hsh = 0x9E3779B97F4A7C15ull;
 #pragma unroll
@@ -719,7 +699,6 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
             seen[0] = hsh;
             na_last = na;
             wave_sync();
-            plap(0);
             int dep_at = -1;
             if (na > 0) {
                 // ---- Schur complement in registers: lane i owns row i; LDL' with the pivot column
@@ -857,7 +836,6 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                 wave_sync();
                 continue;
             }
-            plap(1);
             // w = t0 - Y[:, A] lambda, all row fetches unpredicated
             int offz[CPZ], offg[CPG];
 #pragma unroll
@@ -896,7 +874,6 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                     }
                 }
             }
-            plap(2);
             const double dtol = 1e-9 * lmax + 1e-300;
             dtol_last = dtol;
             bool nanv = false, changed = false;
@@ -1022,7 +999,6 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
                     }
                 }
             }
-            plap(3);
             if (wave_any(nanv)) return false;
             if (!changed) return true;
             wave_sync();
@@ -1152,29 +1128,7 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
     bool solved = false, polished = false, infeasible = infeasible0;
     int solver_status = -10;
     if (!infeasible) {
-        if (M.polish && !ADMM) { solved = polish(M.polish_rounds0); polished = solved; }
-        if (!ADMM && !solved) {                       // left for the fallback kernel (flag stays 0 / 1)
-            if constexpr (FUSED) {
-                // the fallback reads the workspace record: file the one this wavefront computed (a handful of instances in a thousand)
-#pragma unroll
-                for (int c = 0; c < CPZ; ++c) {
-                    const int e = 128 * c + 2 * lane;
-                    if (e < ldz) { st2(ws + e, f[2 * c], f[2 * c + 1]); st2(ws + ldz + e, t0[2 * c], t0[2 * c + 1]); }
-                }
-#pragma unroll
-                for (int c = 0; c < CPG; ++c) {
-                    const int r = 128 * c + 2 * lane;
-                    if (r < ldg) {
-                        st2(ws + ldz + ldz + r, gt0[2 * c], gt0[2 * c + 1]);
-                        st2(ws + ldz + ldy + r, lg[2 * c], lg[2 * c + 1]);
-                        st2(ws + ldz + ldy + ldg + r, ug[2 * c], ug[2 * c + 1]);
-                    }
-                }
-                if (lane == 0) st2(ws + ldz + ldy + 2 * ldg, c0, tail.y);
-            }
-            return;
-        }
-        while (ADMM && !solved && iters < M.max_iter) {
+        while (!solved && iters < M.max_iter) {
             const int nblk = min(M.check_every, M.max_iter - iters);
             for (int k = 0; k < nblk; ++k) admm_iter();
             iters += nblk;
@@ -1216,7 +1170,6 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
     for (int s = 0; s < NZS; ++s) w[s] = polished ? wv[s] : x[s];
     const double qnan = __builtin_nan("");
     double cost;
-    bool cost_pending = false;
     if (infeasible) {
 #pragma unroll
         for (int s = 0; s < NZS; ++s) w[s] = qnan;
@@ -1226,28 +1179,8 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
     wave_sync();
     if (infeasible) {
         cost = 1e30;
-    } else if (!ADMM && polished && !M.cost_direct) {
-        // At the verified point H w + f + N_A' lambda = 0 and N_A w = b_A, hence w'Hw/2 + f'w = (f'w - lambda'b_A)/2: no pass
-        // over H (the single largest read of an instance: nz x nz doubles), and the products involve the bounded solution w,
-        // not the possibly huge unconstrained optimum
-        double j = 0;
-#pragma unroll
-        for (int s = 0; s < NZS; ++s) j = fma(f[s], w[s], j);
-        for (int a = lane; a < na_last; a += 64) j = fma(-lam[a], wsb[a], j);
-        cost = 0.5 * wave_sum(j) + c0;
-    } else if (!ADMM && polished && !FUSED) {
-        // cost from its definition (M.cost_direct: the identity above loses digits on an ill-conditioned Hessian), but not here:
-        // H is nz x nz doubles per instance from L2 for a mat-vec, 320 KB at N = 50.  The solution goes to the workspace in
-        // t0's place and lmpc_cost_mfma does H W for sixteen instances per pass over H on the matrix pipe.
-#pragma unroll
-        for (int c = 0; c < CPZ; ++c) {
-            const int e = 128 * c + 2 * lane;
-            if (e < ldz) st2(ws + ldz + e, w[2 * c], w[2 * c + 1]);
-        }
-        cost = 0.0;
-        cost_pending = true;
     } else {
-        // any other point (ADMM iterate, regularised Hessian): the definition
+        // from its definition: the point may be an ADMM iterate, the Hessian regularised
         double hw[NZS];
 #pragma unroll
         for (int s = 0; s < NZS; ++s) hw[s] = 0;
@@ -1263,7 +1196,7 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
         if (e < nu) glw(Bt.cmd)[(size_t)b * nu + e] = w[s];
     }
     if (lane == 0) {
-        if (Bt.cost && !cost_pending) glw(Bt.cost)[b] = cost;
+        if (Bt.cost) glw(Bt.cost)[b] = cost;
         if (Bt.solver_status) glw(Bt.solver_status)[b] = solver_status;
         if (Bt.status) {
             // LOptimizer.hpp:386-415
@@ -1369,14 +1302,9 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
         }
     }
     wave_sync();
-    if (!ADMM && lane == 0) ws[ldz + ldy + 2 * ldg + 1] = cost_pending ? 3.0 : 2.0;     // 2: done, the fallback kernel skips it; 3: lmpc_cost_mfma first
     stamp();   // 3: unpacked
     if (Bt.dbg_cycles && lane == 0)
-#ifdef MPCX_PROFILE_ROUNDS
-        for (int k = 0; k < 8; ++k) Bt.dbg_cycles[(size_t)b * 8 + k] = k < 4 ? (k < tsi ? tstamp[k] : 0) : pacc[k - 4];
-#else
         for (int k = 0; k < 8; ++k) Bt.dbg_cycles[(size_t)b * 8 + k] = k < tsi ? tstamp[k] : 0;
-#endif
 }
 
 
@@ -1384,7 +1312,7 @@ __device__ void solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b,
 // everything when polish is switched off): ADMM iterations, then polish again.
 //
 // The kernel's arguments travel as ONE struct that is only ever read in place, in the kernel-argument segment.  A by-value struct argument whose
-// address reaches a real callee (solve_one is one: it takes the batch by reference) gets a per-lane stack copy at kernel entry -- 304 bytes a lane,
+// address reaches a real callee (admm_solve_one is one: it takes the batch by reference) gets a per-lane stack copy at kernel entry -- 304 bytes a lane,
 // 1.2 MB of scratch writes per launch at the benchmark batch, and the exit test of the usual, idle launch used to wait for its round trip.
 struct AdmmArgs {
     const LmpcDev *Mp;
@@ -1414,7 +1342,7 @@ __device__ __noinline__ void admm_serve(const AdmmArgs *ap, double *smem, const 
         for (int i = slot; i < n; i += nwaves) {
             const int b = __builtin_amdgcn_readfirstlane(gl(Bt.fq)[kFqList + i]);
             if (b < 0 || b >= Bt.batch) continue;
-            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(A.wsbase) + (size_t)b * M.wsld, nullptr, bigS);
+            admm_solve_one<CPZ, CPG>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(A.wsbase) + (size_t)b * M.wsld, bigS);
         }
         // every wavefront of a launch that saw work takes a ticket when it is through; the last one files the count and restores count = ticket = 0
         wave_sync();
@@ -1429,7 +1357,7 @@ __device__ __noinline__ void admm_serve(const AdmmArgs *ap, double *smem, const 
         }
     } else {
         for (int b = slot; b < Bt.batch; b += nwaves)
-            solve_one<CPZ, CPG, true>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(A.wsbase) + (size_t)b * M.wsld, nullptr, bigS);
+            admm_solve_one<CPZ, CPG>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, nt0, arena, glw(A.wsbase) + (size_t)b * M.wsld, bigS);
     }
 }
 
@@ -1540,54 +1468,42 @@ __global__ __launch_bounds__(256) void lmpc_cost_mfma(const LmpcDev *__restrict_
 }
 
 template <int CPZ, int CPG>
-int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b_in, double *ws, hipStream_t stream, int which, int fast,
-                   double *pbuf, int pslots, int *fq, int fq_cap)
+int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b_in, const LmpcScratch &sc, hipStream_t stream, int which, const LmpcPlan &plan)
 {
     // the failure queue goes with polish: without it no kernel solves anything before the fallback, which then serves the whole batch
     LmpcBatchDev b = b_in;
-    b.fq = (m.polish && fq && fq_cap >= b.batch) ? fq : nullptr;
+    const int fq_cap = (int)sc.cap;
+    b.fq = (m.polish && sc.fq && fq_cap >= b.batch) ? sc.fq : nullptr;
     b.fq_cap = b.fq ? fq_cap : 0;
     if (m.polish && !b.fq) return -3;
+    b.fused = plan.fused;
+    b.pcounter = plan.form == LmpcForm::FusedMatvec ? sc.pcounter : nullptr;
+    double *const ws = sc.ws;
     const size_t lds = (size_t)kWavesPerBlock * m.lds_per_wave * sizeof(double);
     if (lds > lmpc_lds_limit()) return -2;
     auto k1 = lmpc_assemble_generic<CPZ, CPG>;
     auto k3 = lmpc_solve_admm<CPZ, CPG>;
-    // the attribute is per device: remember what each device was given (an atomic per device, so that two host threads or
-    // two handles on different GPUs cannot skip or tear the update)
-    static std::atomic<size_t> configured[64];
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    devid &= 63;
-    if (lds > configured[devid].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return -3;
-        size_t prev = configured[devid].load(std::memory_order_relaxed);
-        while (prev < lds && !configured[devid].compare_exchange_weak(prev, lds, std::memory_order_release)) {}
-    }
+    static LmpcLdsCache configured;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(k1), reinterpret_cast<const void *>(k3)}, lds) != 0) return -3;
     int blocks = (b.batch + kWavesPerBlock - 1) / kWavesPerBlock;
     const int cap = 256 * 8;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    // (one-kernel forms: the fused / persistent mat-vec forms serve the one-chunk variant, the in-workgroup form -- b.fused >= 3 -- the two-chunk one too)
-    const bool fused = b.fused != 0 && ((CPZ == 1 && CPG == 1) || (b.fused >= 3 && CPZ == 2 && CPG == 2));
+    // (the one-kernel forms assemble for themselves: the plan names one only where the variant has it)
+    const bool fused = plan.form != LmpcForm::TwoKernels;
     if ((which & 1) && !fused) {
-        if (fast >= 0) {
+        if (plan.assemble != LmpcAssemble::Generic) {
             const size_t lds1 = ((size_t)(m.kin / 4 + m.nz16 / 4) * 64 + 64 + 32) * sizeof(double);
             int blocks1 = (b.batch + 15) / 16;
             if (blocks1 > 4096) blocks1 = 4096;
-            hipLaunchKernelGGL(lmpc_assemble_mfma, dim3(blocks1), dim3(256), lds1, stream, m_dev, b, ws, fast);
+            hipLaunchKernelGGL(lmpc_assemble_mfma, dim3(blocks1), dim3(256), lds1, stream, m_dev, b, ws, plan.assemble == LmpcAssemble::MfmaInstanceYref ? 1 : 0);
         } else {
             hipLaunchKernelGGL(k1, dim3((b.batch + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWavesPerBlock * 64), lds, stream, m_dev, b, ws);
         }
     }
     if (which & 2) {
-        {
-            LmpcBatchDev bf = b;
-            if (!fused) bf.fused = 0;
-            const int rf = lmpc_launch_fast(m, m_dev, bf, ws, stream);      // lean kernels (lmpc_fast.hip)
-            if (rf != 0) return rf;
-        }
+        const int rf = lmpc_launch_fast(m, m_dev, b, ws, stream, plan.form);      // lean kernels (lmpc_fast.hip)
+        if (rf != 0) return rf;
         if (m.cost_direct && m.polish && !fused && b.n_models <= 0) {       // the costs lmpc_solve left pending
             const size_t ldsc = ((size_t)(m.nz16 / 4) * 64 + 64) * sizeof(double);
             int blocksq = (b.batch + 15) / 16;
@@ -1602,11 +1518,12 @@ int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b
             if (blocks3 > blocks) blocks3 = blocks;
             if (blocks3 < 1) blocks3 = 1;
         }
-        if (pbuf && m.polish) {                  // one slot of the large-working-set buffer per wavefront
-            if (pslots < kWavesPerBlock) pbuf = nullptr;
-            else if (blocks3 > pslots / kWavesPerBlock) blocks3 = pslots / kWavesPerBlock;
+        double *pbuf = m.polish ? sc.pbuf : nullptr;
+        if (pbuf) {                              // one slot of the large-working-set buffer per wavefront
+            if (sc.pslots < kWavesPerBlock) pbuf = nullptr;
+            else if (blocks3 > sc.pslots / kWavesPerBlock) blocks3 = sc.pslots / kWavesPerBlock;
         }
-        const AdmmArgs a3{m_dev, b, ws, m.polish ? pbuf : nullptr, pslots};
+        const AdmmArgs a3{m_dev, b, ws, pbuf, sc.pslots};
         hipLaunchKernelGGL(k3, dim3(blocks3), dim3(kWavesPerBlock * 64), lds, stream, a3);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -1688,14 +1605,51 @@ int lmpc_fallback_slots(const LmpcDev &m, int batch)
     return (int)(waves < kWavesPerBlock ? kWavesPerBlock : waves);
 }
 
-int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, int which, int fast, double *pbuf, int pslots,
-                int *fq, int fq_cap)
+int lmpc_scratch_reserve(LmpcScratch &s, const LmpcDev &m, int batch, bool with_pcounter, void *stream)
+{
+    if ((size_t)batch <= s.cap) return 0;
+    lmpc_scratch_release(s);
+    const int slots = lmpc_fallback_slots(m, batch);
+    if (hipMalloc(reinterpret_cast<void **>(&s.ws), (size_t)batch * m.wsld * sizeof(double)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s.fq), lmpc_fallback_queue_bytes((size_t)batch)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s.pbuf), (size_t)slots * m.nz * m.nz * sizeof(double)) != hipSuccess ||
+        hipMemsetAsync(s.fq, 0, lmpc_fallback_queue_bytes(0), reinterpret_cast<hipStream_t>(stream)) != hipSuccess ||
+        (with_pcounter && (hipMalloc(reinterpret_cast<void **>(&s.pcounter), 8 * sizeof(int)) != hipSuccess || hipMemset(s.pcounter, 0, 8 * sizeof(int)) != hipSuccess)))
+        return -3;
+    s.pslots = slots;
+    s.cap = (size_t)batch;
+    return 0;
+}
+
+void lmpc_scratch_release(LmpcScratch &s)
+{
+    if (s.ws) (void)hipFree(s.ws);
+    if (s.fq) (void)hipFree(s.fq);
+    if (s.pbuf) (void)hipFree(s.pbuf);
+    if (s.pcounter) (void)hipFree(s.pcounter);
+    s = LmpcScratch{};
+}
+
+int lmpc_raise_dynamic_lds(LmpcLdsCache &cache, std::initializer_list<const void *> kernels, size_t bytes)
+{
+    int devid = 0;
+    (void)hipGetDevice(&devid);
+    std::atomic<size_t> &have = cache.bytes[devid & 63];
+    if (bytes <= have.load(std::memory_order_acquire)) return 0;
+    for (const void *k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -3;
+    size_t prev = have.load(std::memory_order_relaxed);
+    while (prev < bytes && !have.compare_exchange_weak(prev, bytes, std::memory_order_release)) {}
+    return 0;
+}
+
+int lmpc_launch(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, const LmpcScratch &scratch, void *stream, int which, const LmpcPlan &plan)
 {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (lmpc_kernel_variant(m.ldz, m.ldg)) {
-    case 1: return launch_variant<1, 1>(m, m_dev, b, ws, s, which, fast, pbuf, pslots, fq, fq_cap);
-    case 2: return launch_variant<2, 2>(m, m_dev, b, ws, s, which, fast, pbuf, pslots, fq, fq_cap);
-    case 4: return launch_variant<4, 4>(m, m_dev, b, ws, s, which, fast, pbuf, pslots, fq, fq_cap);
+    case 1: return launch_variant<1, 1>(m, m_dev, b, scratch, s, which, plan);
+    case 2: return launch_variant<2, 2>(m, m_dev, b, scratch, s, which, plan);
+    case 4: return launch_variant<4, 4>(m, m_dev, b, scratch, s, which, plan);
     default: return -2;
     }
 }

@@ -62,23 +62,14 @@ struct mpcx_lmpc {
     size_t stage_cap = 0;               // instances
     int warm_batch = 0;                 // batch size whose active sets are in stage_act (0: none)
     int n_full_setups = 0, n_ref_refreshes = 0;      // how often each kind of set-up ran (mpcx_lmpc_debug_setup_counts)
-    double *ws = nullptr;               // per-instance workspace between assemble and solve
-    int *pcounter = nullptr;            // work counters of the persistent fused kernel (eight ints of its own)
-    int *fq = nullptr;                  // failure queue (lmpc_device.hpp): the instances the polish-first kernels leave to the fallback kernel, a list of ws_cap entries
-    size_t ws_cap = 0;                  // instances
-    double *pbuf = nullptr;             // the fallback kernel's slots for working sets of more than kMaxActive rows (pslots x nz x nz), sized with ws
-    int pslots = 0;
+    mpcx::LmpcScratch scratch{};        // workspace, failure queue, large-working-set slots, persistent kernel's counters (lmpc_device.hpp)
     explicit mpcx_lmpc(const mpcx_dims &d) : ctl(d) {}
 
     void release()
     {
         for (void *p : allocs) (void)hipFree(p);
         allocs.clear();
-        if (ws) (void)hipFree(ws);
-        if (pcounter) (void)hipFree(pcounter);
-        if (fq) (void)hipFree(fq);
-        if (pbuf) (void)hipFree(pbuf);
-        ws = nullptr; pcounter = nullptr; fq = nullptr; ws_cap = 0; pbuf = nullptr; pslots = 0;
+        mpcx::lmpc_scratch_release(scratch);
         warm_batch = 0;                 // row numbering may have changed with the model
     }
     void release_staging()
@@ -238,9 +229,7 @@ struct mpcx_lmpc_hetero {
     mpcx::LmpcDev dev0{};                        // model 0 with device pointers (dimensions, LDS plan)
     mpcx::LmpcDev *models_d = nullptr;           // [count] device structs
     char *slab = nullptr, *slab_dev = nullptr;     // uploaded arrays / arrays the condensing kernel fills
-    double *ws = nullptr; size_t ws_cap = 0;
-    double *pbuf = nullptr; int pslots = 0;      // as mpcx_lmpc's
-    int *fq = nullptr;                           // as mpcx_lmpc's
+    mpcx::LmpcScratch scratch{};                 // as mpcx_lmpc's, without the counters
     int active_words = 0, m_ref = 0;
     bool condensed_on_device = false;
     float setup_kernel_ms = 0, setup_total_ms = 0;   // the condensing kernel alone / the whole mpcx_lmpc_hetero_create
@@ -250,9 +239,7 @@ struct mpcx_lmpc_hetero {
         if (models_d) (void)hipFree(models_d);
         if (slab) (void)hipFree(slab);
         if (slab_dev) (void)hipFree(slab_dev);
-        if (ws) (void)hipFree(ws);
-        if (pbuf) (void)hipFree(pbuf);
-        if (fq) (void)hipFree(fq);
+        mpcx::lmpc_scratch_release(scratch);
     }
 };
 
@@ -618,25 +605,23 @@ int mpcx_lmpc_setup(mpcx_lmpc_t h)
     return MPCX_OK;
 }
 
-static int make_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, mpcx::LmpcBatchDev &B)
+// The caller's batch as the kernels take it.  shared[4]: where a reference in MPCX_REF_SHARED mode is read from (yref, uref, duref, dmeas) -- the
+// controller's own device arrays; null in a bank, where each controller reads its own through the model struct.
+static int make_batch(const mpcx_dims &d, const mpcx_lmpc_batch *b, const double *const shared[4], mpcx::LmpcBatchDev &B)
 {
-    const auto &d = h->ctl.d;
-    const auto &D = h->dev;
-    if (b->batch < 0) return fail(MPCX_E_INVALID, "negative batch");
-    if (b->batch > 0 && (!b->x0 || !b->u0 || !b->cmd)) return fail(MPCX_E_INVALID, "x0, u0 and cmd are required");
     B = mpcx::LmpcBatchDev{};
     B.batch = b->batch; B.x0 = b->x0; B.u0 = b->u0;
-    auto refsel = [&](const double *p, int mode, const double *shared, int n, const double *&op, long &bs, long &ks) -> bool {
-        if (mode == MPCX_REF_SHARED) { op = shared; bs = 0; ks = n; return true; }
+    auto refsel = [&](const double *p, int mode, const double *sh, int n, const double *&op, long &bs, long &ks) -> bool {
+        if (mode == MPCX_REF_SHARED) { op = sh; bs = 0; ks = n; return true; }
         if (!p) return false;
         if (mode == MPCX_REF_PER_INSTANCE) { op = p; bs = n; ks = 0; return true; }
         if (mode == MPCX_REF_PER_STEP) { op = p; bs = (long)d.ph * n; ks = n; return true; }
         return false;
     };
-    if (!refsel(b->yref, b->yref_mode, D.yref_s, d.ny, B.yref, B.yref_bs, B.yref_ks) ||
-        !refsel(b->uref, b->uref_mode, D.uref_s, d.nu, B.uref, B.uref_bs, B.uref_ks) ||
-        !refsel(b->duref, b->duref_mode, D.duref_s, d.nu, B.duref, B.duref_bs, B.duref_ks) ||
-        !refsel(b->dmeas, b->dmeas_mode, D.dmeas_s, d.ndu, B.dmeas, B.dmeas_bs, B.dmeas_ks))
+    if (!refsel(b->yref, b->yref_mode, shared[0], d.ny, B.yref, B.yref_bs, B.yref_ks) ||
+        !refsel(b->uref, b->uref_mode, shared[1], d.nu, B.uref, B.uref_bs, B.uref_ks) ||
+        !refsel(b->duref, b->duref_mode, shared[2], d.nu, B.duref, B.duref_bs, B.duref_ks) ||
+        !refsel(b->dmeas, b->dmeas_mode, shared[3], d.ndu, B.dmeas, B.dmeas_bs, B.dmeas_ks))
         return fail(MPCX_E_INVALID, "reference array missing for a non-shared mode, or unknown mode");
     B.cmd = b->cmd; B.cost = b->cost; B.status = b->status; B.solver_status = b->solver_status;
     B.is_feasible = b->is_feasible; B.iterations = b->iterations;
@@ -645,8 +630,47 @@ static int make_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, mpcx::LmpcBatchDe
     B.polish_rounds = b->polish_rounds; B.active_count = b->active_count;
     B.warm_lower = b->warm_active_lower; B.warm_upper = b->warm_active_upper; B.warm_shift = b->warm_shift;
     if ((B.warm_lower == nullptr) != (B.warm_upper == nullptr)) return fail(MPCX_E_INVALID, "warm_active_lower and warm_active_upper go together");
-    B.dbg_cycles = h->dbg_cycles;
     return MPCX_OK;
+}
+
+// ... of a single controller: its argument checks, its own shared references, its cycle buffer
+static int make_handle_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, mpcx::LmpcBatchDev &B)
+{
+    if (b->batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (b->batch > 0 && (!b->x0 || !b->u0 || !b->cmd)) return fail(MPCX_E_INVALID, "x0, u0 and cmd are required");
+    const auto &D = h->dev;
+    const double *const shared[4] = {D.yref_s, D.uref_s, D.duref_s, D.dmeas_s};
+    const int rc = make_batch(h->ctl.d, b, shared, B);
+    B.dbg_cycles = h->dbg_cycles;
+    return rc;
+}
+
+// Which kernels a call of this handle takes.  The MFMA assemble kernel serves shared or per-instance-constant output references with everything
+// else shared, any other layout goes through the generic roll-out kernel; the one-kernel forms assemble the same way, so they need the same layouts.
+// Automatic mode (use_fused < 0) takes the group form up to group_max instances -- of the whole batch where this handle solves a shard of one.
+static mpcx::LmpcPlan lmpc_plan(const mpcx_lmpc *h, const mpcx_lmpc_batch *b)
+{
+    using mpcx::LmpcAssemble; using mpcx::LmpcForm;
+    mpcx::LmpcPlan p{LmpcAssemble::Generic, LmpcForm::TwoKernels, 0};
+    if (b->uref_mode != MPCX_REF_SHARED || b->duref_mode != MPCX_REF_SHARED || b->dmeas_mode != MPCX_REF_SHARED || h->force_generic) return p;
+    if (b->yref_mode == MPCX_REF_SHARED) p.assemble = LmpcAssemble::MfmaSharedYref;
+    else if (b->yref_mode == MPCX_REF_PER_INSTANCE) p.assemble = LmpcAssemble::MfmaInstanceYref;
+    else return p;
+    const int per_instance = p.assemble == LmpcAssemble::MfmaInstanceYref ? 1 : 0;
+    const int whole = b->batch > h->total_batch ? b->batch : h->total_batch;
+    if (h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && whole <= h->group_max))) { p.form = LmpcForm::Group; p.fused = 3 + per_instance; }
+    else if (h->dev.fused_ok && !h->dbg_cycles && h->use_fused == 1) { p.form = LmpcForm::FusedMatvec; p.fused = 1 + per_instance; }
+    return p;
+}
+// the bank: roll-out assemble, lean solve, ADMM fallback
+static constexpr mpcx::LmpcPlan kHeteroPlan{mpcx::LmpcAssemble::Generic, mpcx::LmpcForm::TwoKernels, 0};
+
+// a launch that failed: a step that broke off may have filed failures nobody served
+static int launch_failed(int lr, const mpcx::LmpcScratch &sc, void *stream)
+{
+    (void)mpcx::lmpc_fallback_reset(sc.fq, stream);
+    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
+    return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
 }
 
 int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
@@ -659,41 +683,11 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
     if (b->batch == 0) return MPCX_OK;      // an empty batch is a no-op, whatever its pointers
     mpcx::LmpcBatchDev B;
-    rc = make_batch(h, b, B);
+    rc = make_handle_batch(h, b, B);
     if (rc != MPCX_OK) return rc;
-    if ((size_t)b->batch > h->ws_cap) {
-        // grows only when a larger batch than ever before arrives (not capturable in a graph)
-        if (h->ws) (void)hipFree(h->ws);
-        if (h->fq) (void)hipFree(h->fq);
-        if (h->pbuf) (void)hipFree(h->pbuf);
-        h->ws = nullptr; h->fq = nullptr; h->ws_cap = 0; h->pbuf = nullptr; h->pslots = 0;
-        const int slots = mpcx::lmpc_fallback_slots(h->dev, b->batch);
-        if (hipMalloc(reinterpret_cast<void **>(&h->ws), (size_t)b->batch * h->dev.wsld * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&h->fq), mpcx::lmpc_fallback_queue_bytes((size_t)b->batch)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&h->pbuf), (size_t)slots * h->dev.nz * h->dev.nz * sizeof(double)) != hipSuccess ||
-            hipMemsetAsync(h->fq, 0, mpcx::lmpc_fallback_queue_bytes(0), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
-            return fail(MPCX_E_DEVICE, "workspace allocation failed");
-        h->pslots = slots;
-        if (!h->pcounter) {
-            if (hipMalloc(reinterpret_cast<void **>(&h->pcounter), 8 * sizeof(int)) != hipSuccess) return fail(MPCX_E_DEVICE, "workspace allocation failed");
-            (void)hipMemset(h->pcounter, 0, 8 * sizeof(int));
-        }
-        h->ws_cap = (size_t)b->batch;
-    }
-    // the MFMA assemble kernel serves shared or per-instance-constant output references with
-    // everything else shared; any other layout goes through the generic roll-out kernel
-    int fast = -1;
-    if (b->uref_mode == MPCX_REF_SHARED && b->duref_mode == MPCX_REF_SHARED && b->dmeas_mode == MPCX_REF_SHARED && !h->force_generic) {
-        if (b->yref_mode == MPCX_REF_SHARED) fast = 0;
-        else if (b->yref_mode == MPCX_REF_PER_INSTANCE) fast = 1;
-    }
-    if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; }
-    else if (fast >= 0 && h->dev.fused_ok && !B.dbg_cycles && h->use_fused == 1) { B.fused = fast + 1; B.pcounter = h->pcounter; }
-    int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 7, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
-    if (lr != 0) (void)mpcx::lmpc_fallback_reset(h->fq, stream);      // a step that broke off may have filed failures nobody served
-    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
-    if (lr != 0) return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return MPCX_OK;
+    if (mpcx::lmpc_scratch_reserve(h->scratch, h->dev, b->batch, true, stream) != 0) return fail(MPCX_E_DEVICE, "workspace allocation failed");
+    const int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->scratch, stream, 7, lmpc_plan(h, b));
+    return lr == 0 ? MPCX_OK : launch_failed(lr, h->scratch, stream);
 }
 
 struct mpcx_lmpc_graph {
@@ -982,14 +976,15 @@ int mpcx_lmpc_hetero_destroy(mpcx_lmpc_hetero_t f)
 /* testing aid: one O(n^3) array ("H", "Kinv", "Gr", "Gc", "Y", "rho_b", "rho_g") of model k copied to the host; returns its length */
 // testing aid: {instances the fallback kernel served in the last step that had any since the previous read, entries the failure queue holds, wavefronts of the fallback
 // kernel's grid at a full batch}; waits for the device
-static bool fallback_state(int *fq, size_t cap, int pslots, double *out3)
+static bool fallback_state(const mpcx::LmpcScratch &sc, double *out3)
 {
+    int *const fq = sc.fq;
     int served = 0;
     // (the idle fallback launch writes nothing, not even a zero here: the read clears the figure, so that it speaks of the steps since the last read)
     if (fq && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&served, fq + mpcx::kFqServed, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
                hipMemset(fq + mpcx::kFqServed, 0, sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) return false;
     const int w = mpcx::lmpc_fallback_waves();
-    out3[0] = served; out3[1] = (double)cap; out3[2] = fq ? (pslots < w ? pslots : w) : w;
+    out3[0] = served; out3[1] = (double)sc.cap; out3[2] = fq ? (sc.pslots < w ? sc.pslots : w) : w;
     return true;
 }
 
@@ -998,7 +993,7 @@ int mpcx_lmpc_hetero_debug_get(mpcx_lmpc_hetero_t f, int k, const char *name, do
     if (!f || k < 0 || k >= f->count || !name) return fail(MPCX_E_INVALID, "bad argument");
     if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
     if (std::string(name) == "fallback") {
-        if (out && cap >= 3 && !fallback_state(f->fq, f->ws_cap, f->pslots, out)) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
+        if (out && cap >= 3 && !fallback_state(f->scratch, out)) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
         return 3;
     }
     mpcx::LmpcDev D;
@@ -1042,47 +1037,15 @@ int mpcx_lmpc_hetero_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b,
     if (b->batch == 0) return MPCX_OK;
     if (b->batch < 0 || !b->x0 || !b->u0 || !b->cmd) return fail(MPCX_E_INVALID, "x0, u0 and cmd are required");
     if (!model_index && b->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
-    const auto &d = f->d;
-    mpcx::LmpcBatchDev B{};
-    B.batch = b->batch; B.x0 = b->x0; B.u0 = b->u0;
     // references: per instance or per step from the caller; "shared" = each controller's own (its setReferences), read through the model
-    auto refsel = [&](const double *p, int mode, int n, const double *&op, long &bs, long &ks) -> bool {
-        if (mode == MPCX_REF_SHARED) { op = nullptr; bs = 0; ks = n; return true; }
-        if (!p) return false;
-        if (mode == MPCX_REF_PER_INSTANCE) { op = p; bs = n; ks = 0; return true; }
-        if (mode == MPCX_REF_PER_STEP) { op = p; bs = (long)d.ph * n; ks = n; return true; }
-        return false;
-    };
-    if (!refsel(b->yref, b->yref_mode, d.ny, B.yref, B.yref_bs, B.yref_ks) || !refsel(b->uref, b->uref_mode, d.nu, B.uref, B.uref_bs, B.uref_ks) ||
-        !refsel(b->duref, b->duref_mode, d.nu, B.duref, B.duref_bs, B.duref_ks) || !refsel(b->dmeas, b->dmeas_mode, d.ndu, B.dmeas, B.dmeas_bs, B.dmeas_ks))
-        return fail(MPCX_E_INVALID, "reference array missing for a non-shared mode, or unknown mode");
-    B.cmd = b->cmd; B.cost = b->cost; B.status = b->status; B.solver_status = b->solver_status;
-    B.is_feasible = b->is_feasible; B.iterations = b->iterations;
-    B.active_lower = b->active_lower; B.active_upper = b->active_upper;
-    B.seq_state = b->seq_state; B.seq_output = b->seq_output; B.seq_input = b->seq_input;
-    B.polish_rounds = b->polish_rounds; B.active_count = b->active_count;
-    B.warm_lower = b->warm_active_lower; B.warm_upper = b->warm_active_upper; B.warm_shift = b->warm_shift;
-    if ((B.warm_lower == nullptr) != (B.warm_upper == nullptr)) return fail(MPCX_E_INVALID, "warm_active_lower and warm_active_upper go together");
+    const double *const own[4] = {nullptr, nullptr, nullptr, nullptr};
+    mpcx::LmpcBatchDev B;
+    const int rc = make_batch(f->d, b, own, B);
+    if (rc != MPCX_OK) return rc;
     B.n_models = f->count; B.model_index = model_index;
-    if ((size_t)b->batch > f->ws_cap) {
-        if (f->ws) (void)hipFree(f->ws);
-        if (f->pbuf) (void)hipFree(f->pbuf);
-        if (f->fq) (void)hipFree(f->fq);
-        f->ws = nullptr; f->fq = nullptr; f->ws_cap = 0; f->pbuf = nullptr; f->pslots = 0;
-        const int slots = mpcx::lmpc_fallback_slots(f->dev0, b->batch);
-        if (hipMalloc(reinterpret_cast<void **>(&f->ws), (size_t)b->batch * f->dev0.wsld * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&f->pbuf), (size_t)slots * f->dev0.nz * f->dev0.nz * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&f->fq), mpcx::lmpc_fallback_queue_bytes((size_t)b->batch)) != hipSuccess ||
-            hipMemsetAsync(f->fq, 0, mpcx::lmpc_fallback_queue_bytes(0), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
-            return fail(MPCX_E_DEVICE, "workspace allocation failed");
-        f->pslots = slots;
-        f->ws_cap = (size_t)b->batch;
-    }
-    const int lr = mpcx::lmpc_launch(f->dev0, f->models_d, B, f->ws, stream, 7, -1, f->pbuf, f->pslots, f->fq, (int)f->ws_cap);      // roll-out assemble, lean solve, ADMM fallback
-    if (lr != 0) (void)mpcx::lmpc_fallback_reset(f->fq, stream);
-    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the kernel's LDS budget");
-    if (lr != 0) return fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return MPCX_OK;
+    if (mpcx::lmpc_scratch_reserve(f->scratch, f->dev0, b->batch, false, stream) != 0) return fail(MPCX_E_DEVICE, "workspace allocation failed");
+    const int lr = mpcx::lmpc_launch(f->dev0, f->models_d, B, f->scratch, stream, 7, kHeteroPlan);
+    return lr == 0 ? MPCX_OK : launch_failed(lr, f->scratch, stream);
 }
 
 int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream, int repeats, float *ms_mean)
@@ -1113,15 +1076,10 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
     int rc = mpcx_lmpc_solve_batch(h, b, stream);      // sizes the workspace, fills it
     if (rc != MPCX_OK) return rc;
     mpcx::LmpcBatchDev B;
-    rc = make_batch(h, b, B);
+    rc = make_handle_batch(h, b, B);
     if (rc != MPCX_OK) return rc;
-    int fast = -1;
-    if (b->uref_mode == MPCX_REF_SHARED && b->duref_mode == MPCX_REF_SHARED && b->dmeas_mode == MPCX_REF_SHARED && !h->force_generic) {
-        if (b->yref_mode == MPCX_REF_SHARED) fast = 0;
-        else if (b->yref_mode == MPCX_REF_PER_INSTANCE) fast = 1;
-    }
-    if (fast >= 0 && h->dev.group_ok && (h->use_fused == 2 || (h->use_fused < 0 && (b->batch > h->total_batch ? b->batch : h->total_batch) <= h->group_max))) { B.fused = fast + 3; }
-    else if (fast >= 0 && h->dev.fused_ok && !B.dbg_cycles && h->use_fused == 1) { B.fused = fast + 1; B.pcounter = h->pcounter; }
+    const mpcx::LmpcPlan plan = lmpc_plan(h, b);
+    auto launch = [&](int which) { return mpcx::lmpc_launch(h->dev, h->dev_d, B, h->scratch, stream, which, plan); };
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -1130,9 +1088,9 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
         if (which == 2 && h->dev.cost_direct) {
             // with pending costs the solve leaves w in t0's place: every timed launch needs a freshly assembled workspace
             for (int i = 0; i < repeats; i++) {
-                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 1, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
+                launch(1);
                 (void)hipEventRecord(e0, s);
-                mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, 2, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
+                launch(2);
                 (void)hipEventRecord(e1, s);
                 (void)hipEventSynchronize(e1);
                 float one = 0;
@@ -1141,14 +1099,14 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
             }
         } else {
             (void)hipEventRecord(e0, s);
-            for (int i = 0; i < repeats; i++) mpcx::lmpc_launch(h->dev, h->dev_d, B, h->ws, stream, which, fast, h->pbuf, h->pslots, h->fq, (int)h->ws_cap);
+            for (int i = 0; i < repeats; i++) launch(which);
             (void)hipEventRecord(e1, s);
             (void)hipEventSynchronize(e1);
             (void)hipEventElapsedTime(&ms, e0, e1);
         }
         // the solve kernels ran without the fallback behind them: what they filed in the failure queue is dropped (outside the timed window), so that
         // slot 2 times the idle fallback launch and the next step starts from an empty queue
-        if (which == 2) (void)mpcx::lmpc_fallback_reset(h->fq, stream);
+        if (which == 2) (void)mpcx::lmpc_fallback_reset(h->scratch.fq, stream);
         ms2[which == 1 ? 0 : (which == 2 ? 1 : 2)] = ms / (float)repeats;
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -1251,7 +1209,7 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "fallback") {           // the failure queue: served in the last step that had failures, capacity, fallback wavefronts
         tmp.assign(3, 0.0);
         if (out && !h->host_only) {
-            if (hipSetDevice(h->device) != hipSuccess || !fallback_state(h->fq, h->ws_cap, h->pslots, tmp.data())) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
+            if (hipSetDevice(h->device) != hipSuccess || !fallback_state(h->scratch, tmp.data())) return fail(MPCX_E_DEVICE, "hipMemcpy failed");
         }
         v = &tmp;
     }

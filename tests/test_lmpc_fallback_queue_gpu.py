@@ -165,6 +165,52 @@ def test_heterogeneous_bank_has_a_queue_of_its_own():
     assert_matches_oracle(r2, ref, ref["neq"], ref["ncon"])
 
 
+GROW = (8, 40)      # a handle's scratch sized for 8 instances, then a batch of more than one group workgroup of 16 and no multiple of 16
+
+
+@pytest.mark.parametrize("path", HANDOVER_PATHS, ids=lambda p: p[0])
+def test_scratch_grows_between_two_calls(case, path):
+    """workspace, queue and large-working-set slots are allocated anew for the larger batch: same bits as a handle that never had the small ones"""
+    sp, x0, u0, ref = case
+    name, generic, fused = path
+    small, large = GROW
+    c = _controller(sp, generic, fused)
+    _solve(c, x0[:small], u0[:small])
+    assert _fallback(c)[1] == small
+    grown = _arrays(_solve(c, x0[:large], u0[:large]))
+    assert _fallback(c)[1] == large
+    fresh = _controller(sp, generic, fused)
+    _assert_same(grown, _arrays(_solve(fresh, x0[:large], u0[:large])), "%s: grown against a fresh handle" % name)
+    assert _fallback(fresh)[1] == large
+
+
+def test_scratch_of_a_bank_grows_between_two_calls():
+    import torch
+    from libmpc_amd import LMPC
+    from libmpc_amd.bank import LMPCHetero
+    K = 8
+    small, large = GROW
+    specs = [axes_spec(3, 20, perturb=0.2, seed=1000 + k) for k in range(K)]
+    x0, u0, _ = axes_batch(specs[0], large, seed=3)
+    model = np.arange(large) % K
+
+    def bank():
+        return LMPCHetero([configure_axes(LMPC(*s["dims"], device=-1), s, SHAPES_MAXIT) for s in specs], device=0)
+
+    def solve(het, n):
+        r = het.optimizeBatch(x0[:n], u0[:n], model=model[:n], want_active=True); torch.cuda.synchronize()
+        return _arrays(r)
+
+    het = bank()
+    solve(het, small)
+    assert int(het.debug_get(0, "fallback")[1]) == small
+    grown = solve(het, large)
+    assert int(het.debug_get(0, "fallback")[1]) == large
+    fresh = bank()
+    _assert_same(grown, solve(fresh, large), "bank: grown against a fresh handle")
+    assert int(fresh.debug_get(0, "fallback")[1]) == large
+
+
 def test_the_headline_batch_leaves_the_fallback_nothing():
     from libmpc_amd.workloads import quadrotor_batch, quadrotor_lmpc
     import torch

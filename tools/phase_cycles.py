@@ -1,4 +1,6 @@
-"""Profiling aid: per-phase shader-cycle breakdown of lmpc_solve_kernel (median over instances)."""
+"""Profiling aid: per-phase shader-cycle breakdown of the LMPC solve (median over instances): the four stamps -- start, loaded, solved,
+unpacked -- that the polish-first kernel of the call's form (lmpc_solve_group / lmpc_solve) and, for the instances it serves, lmpc_solve_admm
+write into the buffer of mpcx_lmpc_debug_set_cycle_buffer."""
 import ctypes as C
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
