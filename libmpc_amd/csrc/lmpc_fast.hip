@@ -1,6 +1,7 @@
 // Lean polish kernels of the batched LMPC solve (see the comment at solve_fast); launched by lmpc_launch (lmpc_kernels.hip)
 // through lmpc_launch_fast.
 #include "lmpc_kernel_common.hpp"
+#include <cstddef>
 #include <cstdlib>
 
 namespace mpcx {
@@ -30,6 +31,13 @@ namespace {
 //     workspace record (f | t0 | gt0 | lg | ug | c0, flag) followed by a small arena, the box bounds are shared by the
 //     workgroup.  The one-chunk variant fits 128 VGPRs and 3.3 KB of LDS per wavefront: four wavefronts per SIMD, i.e. at the
 //     benchmark batch every instance is resident at once (the dispatch order no longer matters).
+//   * round 8: no register spilled inside the round loop.  The compiler used to carry 134-160 SGPRs through the rounds in lanes of two VGPRs (the model
+//     struct's fields for the unpack behind the loop, sixteen 64-bit row bases of the Schur loads, the sixteen masks lane == k and the identity's entries
+//     for every size class, formed ahead of the loop) and paid a v_writelane / v_readlane for each use: 358 of the loop's 4 124 vector instructions, a sixth
+//     of the sixteen-row class.  Now the Schur entries and the rows of Y are loaded as one scalar base plus a 32-bit byte offset, the lane-dependent masks are
+//     formed where they are used, the later rows' indices are read from LDS again, lmpc_solve_group reads its arguments through the kernel-argument
+//     pointer and once more behind the loop (fast_finish), and the pad of the Schur matrix is two moves per column under one execution mask with the
+//     pivot threshold from one more load instead of a select chain per column.  No floating-point operation changed; profiles/r08_round_isa_census.txt.
 // Working sets of more than kFastCap rows are left to the fallback kernel (none in 32768 instances of config 2, none in 8192 of
 // config 4).
 #ifndef MPCX_FAST_PF_MAXCAP
@@ -84,47 +92,62 @@ __device__ __forceinline__ double wave_max_dpp(double v)
 #define MPCX_PROF_PASS
 #endif
 
-template <int CAP, int CPZ, int CPG>
-__device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const int ldz, const int na, const int lane,
+template <int CAP, int NLO, int CPZ, int CPG>
+__device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const int ldz, const int na, const int lane_in,
                                             const int *wsidx, const double *wsb, const double *t0s, double *lam,
-                                            const int (&offz)[CPZ], const int (&offg)[CPG],
+                                            const unsigned (&offz)[CPZ], const unsigned (&offg)[CPG],
                                             double (&wv)[2 * CPZ], double (&gw)[2 * CPG], double &lmax MPCX_PROF_ARGS)
 {
+    // offz / offg: this lane's element pairs within a row of Y, in bytes -- with the row's scalar base an addressing mode of the load, no vector address arithmetic
+    // NLO <= na <= CAP: the size class (the caller's dispatch), so only the columns from NLO on can lie past the working set
     // rows of Y requested ahead of the elimination (none for the largest working sets: their elimination needs the registers, and a
     // spilled register is HBM traffic -- scratch is memory)
     constexpr int PF = CAP > MPCX_FAST_PF_MAXCAP ? 0 : (CAP < MPCX_FAST_PF ? CAP : MPCX_FAST_PF);
+    // the lane number as this round's own value: what depends on it (the masks lane == k of the elimination, the identity's entries) is then formed
+    // where it is used, one compare each, instead of ahead of the round loop for every size class at once -- more than the register files hold
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));
     const bool real = lane < na;
     const int li = real ? lane : 0;
     const int qi = wsidx[li];
     int qc[CAP];                                    // wave-uniform: SGPRs
 #pragma unroll
-    for (int c = 0; c < CAP; ++c) qc[c] = __builtin_amdgcn_readfirstlane(wsidx[c < na ? c : 0]);
+    for (int c = 0; c < CAP; ++c) qc[c] = __builtin_amdgcn_readfirstlane(wsidx[(c < NLO || c < na) ? c : 0]);
     double Sr[CAP];
-    const int rowoff = qi * ldy;
+    // one 64-bit base and a 32-bit element offset per entry (sixteen 64-bit scalar row bases were more than the SGPR file holds next to
+    // the pivot row: they were spilled to VGPR lanes and read back, two vector instructions per entry)
+    const unsigned rowoff = (unsigned)(qi * ldy) * 8u;       // in bytes: base + 32-bit offset is an addressing mode of the load
+    const char MPCX_GAS *const gYb = reinterpret_cast<const char MPCX_GAS *>(gY);
+    auto y_at = [&](unsigned off) { return *reinterpret_cast<gdp>(gYb + off); };
+    auto row_ld2 = [&](int q, unsigned off) { return *reinterpret_cast<const d2 MPCX_GAS *>(gYb + (unsigned)(q * ldy) * 8u + off); };     // the pair at `off` of row q
 #pragma unroll
-    for (int c = 0; c < CAP; ++c) Sr[c] = (gY + qc[c])[rowoff];
+    for (int c = 0; c < CAP; ++c) Sr[c] = y_at(rowoff + (unsigned)qc[c] * 8u);
+    const double dg = y_at(rowoff + (unsigned)qi * 8u);    // this lane's own diagonal, for its pivot threshold: the same element as Sr[lane]
     d2 pz[PF > 0 ? PF : 1][CPZ], pg[PF > 0 ? PF : 1][CPG];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
-        const gdp row = gY + (size_t)qc[u] * ldy;
 #pragma unroll
-        for (int c = 0; c < CPZ; ++c) pz[u][c] = ld2(row + offz[c]);
+        for (int c = 0; c < CPZ; ++c) pz[u][c] = row_ld2(qc[u], offz[c]);
 #pragma unroll
-        for (int c = 0; c < CPG; ++c) pg[u][c] = ld2(row + offg[c]);
+        for (int c = 0; c < CPG; ++c) pg[u][c] = row_ld2(qc[u], offg[c]);
     }
     double y = real ? t0s[qi < ldz ? qi : qi - ldz + 128 * CPZ] - wsb[li] : 0.0;       // [t0 | G t0] by unified index (padded arrays)
     MPCX_LAP_WAIT(1);                              // 1: working set to registers + every load of the round answered
-    // rows and columns past na: the identity (the elimination below is straight-line code over all CAP steps)
+    // rows and columns past na: the identity (the elimination below is straight-line code over all CAP steps).  The lanes past na take their
+    // whole rows under one execution mask; a column past na (wave-uniform, from NLO on only) is zero on the real lanes, which lie before it
+    if (!real) {
 #pragma unroll
-    for (int c = 0; c < CAP; ++c) Sr[c] = (real && c < na) ? Sr[c] : (lane == c ? 1.0 : 0.0);
-    double pthr = 0.0, mydinv = 1.0;               // this lane's pivot threshold (relative to its original diagonal)
+        for (int c = 0; c < CAP; ++c) Sr[c] = 0.0;
+    }
 #pragma unroll
-    for (int c = 0; c < CAP; ++c) if (lane == c) pthr = 1e-11 * Sr[c];
+    for (int c = NLO; c < CAP; ++c) if (c >= na) Sr[c] = lane == c ? 1.0 : 0.0;
+    const double pthr = 1e-11 * (real ? dg : 1.0);  // this lane's pivot threshold (relative to its original diagonal; the identity's is 1)
+    double mydinv = 1.0;
     unsigned long long dep = 0ull;
     // Gauss-Jordan on [S | y], lane i = row i; a failed pivot test is recorded and looked at once, after the loop
 #pragma unroll
     for (int k = 0; k < CAP; ++k) {
-        dep |= __ballot(lane == k && !(Sr[k] > pthr));
+        dep |= __ballot(!(Sr[k] > pthr)) & (1ull << k);       // lane k's verdict on its pivot
         const double rinv = pivot_rcp(readlane_d(Sr[k], k));
         double pj[CAP];
 #pragma unroll
@@ -165,17 +188,23 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
     }
     if constexpr (CAP > PF) {
         constexpr int RB = CAP - PF < MPCX_FAST_RB ? CAP - PF : MPCX_FAST_RB;      // rows of Y per later batch (the elimination's registers are free by now)
+        // the later rows' indices come from LDS once more: sixteen of them do not stay in SGPRs through the elimination beside its pivot row, and they
+        // were spilled to VGPR lanes.  (An offset the compiler cannot see through makes these loads of their own, not the first ones' registers kept.)
+        int again = 0;
+        asm volatile("" : "+s"(again));
+        const int *wsidx_again = wsidx + again;
 #pragma unroll
         for (int a0 = PF; a0 < CAP; a0 += RB) {
             if (a0 < na) {
                 d2 mz[RB][CPZ], mgv[RB][CPG];
 #pragma unroll
                 for (int u = 0; u < RB; ++u) {
-                    const gdp row = gY + (size_t)qc[a0 + u < CAP ? a0 + u : 0] * ldy;
+                    const int cu = a0 + u < CAP ? a0 + u : 0;
+                    const int q = __builtin_amdgcn_readfirstlane(wsidx_again[(cu < NLO || cu < na) ? cu : 0]);
 #pragma unroll
-                    for (int c = 0; c < CPZ; ++c) mz[u][c] = ld2(row + offz[c]);
+                    for (int c = 0; c < CPZ; ++c) mz[u][c] = row_ld2(q, offz[c]);
 #pragma unroll
-                    for (int c = 0; c < CPG; ++c) mgv[u][c] = ld2(row + offg[c]);
+                    for (int c = 0; c < CPG; ++c) mgv[u][c] = row_ld2(q, offg[c]);
                 }
 #pragma unroll
                 for (int u = 0; u < RB; ++u) {
@@ -320,320 +349,33 @@ __device__ __forceinline__ void fused_record(const LmpcDev &M, const LmpcBatchDe
     wave_sync();
 }
 
-// SRC: where the instance's record comes from -- 0 the workspace (two-kernel path), 1 computed here by fused_record (one mat-vec
-// with the composed maps), 2 already in the slice (lmpc_solve_group: the workgroup's MFMA assemble phase put it there)
-template <int CPZ, int CPG, int SRC = 0>
-__device__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
-                           double *slice, const double *lwuw, gdw ws, const double *mf_lds = nullptr, double *outs = nullptr, const int eqbits = 0)
+// lmpc_solve_group's kernel arguments as they lie in the kernel-argument segment.  The kernel reads them through the segment pointer, not through
+// its by-value parameters: a by-value struct has every field loaded at the kernel's entry and kept in SGPRs until its last use, and what the unpack
+// behind the round loop reads was spilled to VGPR lanes across the loop -- writelane / readlane pairs on the issue slots the rounds are bound by.
+struct GroupArgs { LmpcDev M; LmpcBatchDev Bt; double *wsbase; int variant; };
+typedef const GroupArgs __attribute__((address_space(4))) *group_args_p;
+static_assert(offsetof(GroupArgs, Bt) == sizeof(LmpcDev) && offsetof(GroupArgs, wsbase) == sizeof(LmpcDev) + sizeof(LmpcBatchDev), "GroupArgs mirrors lmpc_solve_group's parameter list");
+
+// What follows the rounds of solve_fast: the instance goes to the fallback kernel, or its solution is unpacked and written out
+// (LOptimizer.hpp:305-347).  A function of its own so that lmpc_solve_group can hand it the kernel arguments re-read behind the round loop.
+template <int CPZ, int CPG, int SRC>
+__device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane, double *slice, const double *lwuw, gdw ws, double *outs,
+                                            const bool infeasible, const bool solved, const bool fixed_violation,
+                                            const double (&wv)[2 * CPZ], const int (&actb)[2 * CPZ], const int (&actg)[2 * CPG], const int (&posb)[2 * CPZ],
+                                            const int (&posg)[2 * CPG], const double dtol_last, const int na_last, const int rounds_total,
+                                            const long long ts0, const long long ts1, const long long ts2 MPCX_PROF_ARGS)
 {
-    // eqbits (SRC = 2, lmpc_solve_group): bit s = this lane's general row s is an equality (lg0 == ug0), looked up by the caller with its other loads
-    // outs (lmpc_solve_group): the instance's scalar results and its command go to this LDS record [cost, status, solver status,
-    // feasible, iterations, rounds, active rows, done | cmd (nu)] instead of to HBM; the workgroup writes sixteen of them coalesced
     constexpr int NZS = 2 * CPZ, NGS = 2 * CPG, ZP = 128 * CPZ, GPD = 128 * CPG;
+    constexpr bool FUSED = SRC != 0;
     const int nx = M.nx, nu = M.nu, ny = M.ny, ndu = M.ndu, ph = M.ph;
     const int nz = M.nz, mg = M.mg, ldz = M.ldz, ldg = M.ldg, ldy = M.ldy;
-    const gdp gY = GP(Y);
     double *t0s = slice, *gt0s = t0s + ZP, *lgs = gt0s + GPD, *ugs = lgs + GPD, *fs = ugs + GPD, *tail = fs + ZP;
     double *lam = tail + 2, *wsb = lam + (kFastCap + 2);
-    int *wsidx = reinterpret_cast<int *>(wsb + (kFastCap + 2));
     double *scratch = wsb + (kFastCap + 2) + (kFastCap + 2) / 2 + 1;
     const double *lws = lwuw, *uws = lwuw + ZP;
-    const double INF = __builtin_huge_val();
-
-    long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0;          // profiling aid: start, loaded, solved, unpacked (Bt.dbg_cycles)
-#ifdef MPCX_PROFILE_ROUNDS
-    long long pacc[6] = {0, 0, 0, 0, 0, 0}, plast = 0;
-#endif
+    const double c0 = tail[0], flag0 = tail[1];     // (read again rather than carried through the rounds in registers)
+    long long ts3 = 0;
     auto stamp = [&](long long &t) { if (Bt.dbg_cycles) t = (long long)__builtin_readcyclecounter(); };
-    stamp(ts0);
-
-    // offsets of this lane's element pairs into the rows of Y (clamped: lanes past the end re-read pair 0, their results are never used)
-    int offz[CPZ], offg[CPG];
-#pragma unroll
-    for (int c = 0; c < CPZ; ++c) { const int e = 128 * c + 2 * lane; offz[c] = e < ldz ? e : 0; }
-#pragma unroll
-    for (int c = 0; c < CPG; ++c) { const int r = 128 * c + 2 * lane; offg[c] = ldz + (r < ldg ? r : 0); }
-
-    constexpr bool FUSED = SRC != 0;                 // the workspace holds no record of this instance
-    // ---- the assembled problem: the workspace record the assemble kernel left, copied into the slice, or computed in place
-    if constexpr (SRC != 2) fast_init_pads<CPZ, CPG>(slice, ldz, ldg, lane);
-    if constexpr (SRC == 2) {
-        // nothing to do: the record is in place
-    } else if constexpr (SRC == 1) {
-        RecPtrs rp{fs, t0s, gt0s, lgs, ugs, tail};
-        fused_record(M, Bt, b, lane, scratch, rp, mf_lds);
-    } else {
-#pragma unroll
-        for (int c = 0; c < CPZ; ++c) {
-            const int e = 128 * c + 2 * lane;
-            if (e < ldz) {
-                const d2 vf = ld2(ws + e), vt = ld2(ws + ldz + e);
-                *reinterpret_cast<double2 *>(fs + e) = make_double2(vf.x, vf.y);
-                *reinterpret_cast<double2 *>(t0s + e) = make_double2(vt.x, vt.y);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < CPG; ++c) {
-            const int r = 128 * c + 2 * lane;
-            if (r < ldg) {
-                const d2 vt = ld2(ws + 2 * ldz + r), vl = ld2(ws + ldz + ldy + r), vu = ld2(ws + ldz + ldy + ldg + r);
-                *reinterpret_cast<double2 *>(gt0s + r) = make_double2(vt.x, vt.y);
-                *reinterpret_cast<double2 *>(lgs + r) = make_double2(vl.x, vl.y);
-                *reinterpret_cast<double2 *>(ugs + r) = make_double2(vu.x, vu.y);
-            }
-        }
-        if (lane == 0) { const d2 t = ld2(ws + ldz + ldy + 2 * ldg); *reinterpret_cast<double2 *>(tail) = make_double2(t.x, t.y); }
-        wave_sync();
-    }
-    const double c0 = tail[0];
-    const double flag0 = tail[1];
-    // a violated step-0 / input-independent row: see admm_solve_one (lmpc_kernels.hip)
-    const bool fixed_violation = flag0 == 1.0;
-    const bool infeasible = fixed_violation && M.strict_infeasible;
-
-    // working-set state of this lane's rows: 0 free, -1 / +1 at the lower / upper bound, 2 equality row (always in, never shed)
-    int actb[NZS], actg[NGS];
-    const double ptol = 1e-8;
-    auto viol = [&](double v, double lo, double hi) {
-        return fmax(fmax(lo - ptol * fmax(1.0, fabs(lo)) - v, v - hi - ptol * fmax(1.0, fabs(hi))), 0.0);
-    };
-    {
-        // first working set: equalities, and the rows the unconstrained optimum violates by >= MPCX_INIT_THETA x the largest violation
-        double vb[NZS], vg[NGS], vinit = 0.0;
-        bool lowb[NZS], lowg[NGS];
-#pragma unroll
-        for (int c = 0; c < CPZ; ++c) {
-            const int e = 128 * c + 2 * lane;
-            const double2 l = *reinterpret_cast<const double2 *>(lws + e), u = *reinterpret_cast<const double2 *>(uws + e);
-            const double2 t = *reinterpret_cast<const double2 *>(t0s + e);
-            vb[2 * c] = viol(t.x, l.x, u.x); vb[2 * c + 1] = viol(t.y, l.y, u.y);
-            lowb[2 * c] = t.x < l.x; lowb[2 * c + 1] = t.y < l.y;
-            actb[2 * c] = l.x == u.x ? 2 : 0; actb[2 * c + 1] = l.y == u.y ? 2 : 0;
-            vinit = fmax(vinit, fmax(vb[2 * c], vb[2 * c + 1]));
-        }
-#pragma unroll
-        for (int c = 0; c < CPG; ++c) {
-            const int r = 128 * c + 2 * lane;
-            const double2 l = *reinterpret_cast<const double2 *>(lgs + r), u = *reinterpret_cast<const double2 *>(ugs + r);
-            const double2 t = *reinterpret_cast<const double2 *>(gt0s + r);
-            vg[2 * c] = viol(t.x, l.x, u.x); vg[2 * c + 1] = viol(t.y, l.y, u.y);
-            lowg[2 * c] = t.x < l.x; lowg[2 * c + 1] = t.y < l.y;
-            if constexpr (SRC == 2) {
-                actg[2 * c] = ((eqbits >> (2 * c)) & 1) ? 2 : 0; actg[2 * c + 1] = ((eqbits >> (2 * c + 1)) & 1) ? 2 : 0;
-            } else {
-                const d2 l0 = ld2(GP(lg0) + (offg[c] - ldz)), u0 = ld2(GP(ug0) + (offg[c] - ldz));
-                const bool ok = r < ldg;
-                actg[2 * c] = (ok && l0.x == u0.x) ? 2 : 0; actg[2 * c + 1] = (ok && l0.y == u0.y) ? 2 : 0;
-            }
-            vinit = fmax(vinit, fmax(vg[2 * c], vg[2 * c + 1]));
-        }
-        const double thr0 = MPCX_INIT_THETA * wave_max_dpp(vinit);
-#pragma unroll
-        for (int s = 0; s < NZS; ++s) actb[s] = (actb[s] == 0 && vb[s] > 0.0 && vb[s] >= thr0) ? (lowb[s] ? -1 : 1) : actb[s];
-#pragma unroll
-        for (int s = 0; s < NGS; ++s) actg[s] = (actg[s] == 0 && vg[s] > 0.0 && vg[s] >= thr0) ? (lowg[s] ? -1 : 1) : actg[s];
-    }
-    stamp(ts1);   // 1: loaded
-
-    if (Bt.warm_lower) {
-        // warm start: the first working set is the previous solve's active set (see admm_solve_one)
-        const unsigned MPCX_GAS *wl = gl(Bt.warm_lower) + (size_t)b * M.active_words;
-        const unsigned MPCX_GAS *wu = gl(Bt.warm_upper) + (size_t)b * M.active_words;
-        const int na = M.nx + M.nu, n1 = M.ph + 1;
-        const int b_box = M.neq_ref, b_out = b_box + n1 * na, b_du = b_out + n1 * M.ny, b_sc = b_du + M.ph * M.nu;
-        auto look = [&](int rr) {
-            if (!Bt.warm_shift) return rr;
-            if (rr < b_out) return rr + na < b_out ? rr + na : rr;
-            if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
-            if (rr < b_sc) return rr;
-            return rr + 1 < M.m_ref ? rr + 1 : rr;
-        };
-#pragma unroll
-        for (int s = 0; s < NZS; ++s) {
-            const int e = 128 * (s >> 1) + 2 * lane + (s & 1);
-            if (e >= nz || actb[s] == 2) continue;
-            const double lo = lws[e], hi = uws[e];
-            int side = 0;
-            for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
-                const int rr = look(GP(boxrow_ref)[p]);
-                if (((wl[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_lo)[p] == lo) side = -1;
-                if (((wu[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_hi)[p] == hi) side = 1;
-            }
-            actb[s] = side;
-        }
-#pragma unroll
-        for (int s = 0; s < NGS; ++s) {
-            const int r = 128 * (s >> 1) + 2 * lane + (s & 1);
-            if (r >= mg || actg[s] == 2) continue;
-            const int rr = look(GP(g_refrow)[r]);
-            actg[s] = ((wl[rr >> 5] >> (rr & 31)) & 1u) ? -1 : (((wu[rr >> 5] >> (rr & 31)) & 1u) ? 1 : 0);
-        }
-    }
-
-    double wv[NZS], gw[NGS];
-    int posb[NZS], posg[NGS];                        // position in the working set (kFastCap: not in it)
-    double dtol_last = 0;
-    int na_last = 0, rounds_total = 0;
-    bool solved = false;
-
-    if (!infeasible && M.polish) {
-        const int rounds = M.polish_rounds0;
-        for (int rd = 0; rd < rounds; ++rd) {
-            ++rounds_total;
-#ifdef MPCX_PROFILE_ROUNDS
-            plast = (long long)__builtin_readcyclecounter();
-#endif
-            // A launch lasts as long as its slowest instance, and the slow ones are those that need many rounds: from the fourth
-            // round on a wavefront asks the instruction arbiter for precedence over its three neighbours on the SIMD.
-            if (rd == 3) __builtin_amdgcn_s_setprio(1);
-            else if (rd == 5) __builtin_amdgcn_s_setprio(2);
-            else if (rd == 7) __builtin_amdgcn_s_setprio(3);
-            // ---- the working set, in row order, to LDS: unified index and bound value per row.  Straight-line code: a row that
-            // is not in the set writes to the spare slot kFastCap (so does a row past the capacity, which ends the solve below).
-            int na = 0;
-#pragma unroll
-            for (int c = 0; c < CPZ; ++c) {
-                const int e = 128 * c + 2 * lane;
-                const double2 l = *reinterpret_cast<const double2 *>(lws + e), u = *reinterpret_cast<const double2 *>(uws + e);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int s = 2 * c + h;
-                    const bool act = actb[s] != 0;
-                    const unsigned long long mk = __ballot(act);
-                    int pos = na + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
-                    pos = (act && pos < kFastCap) ? pos : kFastCap;
-                    posb[s] = pos;
-                    wsidx[pos] = e + h;
-                    wsb[pos] = actb[s] < 0 ? (h ? l.y : l.x) : (h ? u.y : u.x);
-                    na += __popcll(mk);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < CPG; ++c) {
-                const int r = 128 * c + 2 * lane;
-                const double2 l = *reinterpret_cast<const double2 *>(lgs + r), u = *reinterpret_cast<const double2 *>(ugs + r);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int s = 2 * c + h;
-                    const bool act = actg[s] != 0;
-                    const unsigned long long mk = __ballot(act);
-                    int pos = na + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
-                    pos = (act && pos < kFastCap) ? pos : kFastCap;
-                    posg[s] = pos;
-                    wsidx[pos] = ldz + r + h;
-                    wsb[pos] = actg[s] < 0 ? (h ? l.y : l.x) : (h ? u.y : u.x);
-                    na += __popcll(mk);
-                }
-            }
-            if (na > kFastCap) break;                // left to the fallback kernel
-            na_last = na;
-            wave_sync();
-            MPCX_LAP_WAIT(0);                        // 0: working set built and in LDS
-            int dep_at = -1;
-            double lmax = 0.0;
-            if (na == 0) {
-#pragma unroll
-                for (int c = 0; c < CPZ; ++c) { const double2 v = *reinterpret_cast<const double2 *>(t0s + 128 * c + 2 * lane); wv[2 * c] = v.x; wv[2 * c + 1] = v.y; }
-#pragma unroll
-                for (int c = 0; c < CPG; ++c) { const double2 v = *reinterpret_cast<const double2 *>(gt0s + 128 * c + 2 * lane); gw[2 * c] = v.x; gw[2 * c + 1] = v.y; }
-            } else if (na <= 4) dep_at = ws_solve_reg<4, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 6) dep_at = ws_solve_reg<6, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 8) dep_at = ws_solve_reg<8, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 10) dep_at = ws_solve_reg<10, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 12) dep_at = ws_solve_reg<12, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 14) dep_at = ws_solve_reg<14, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            else dep_at = ws_solve_reg<kFastCap, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, offz, offg, wv, gw, lmax MPCX_PROF_PASS);
-            if (dep_at >= 0) {
-                // linearly dependent working set: drop the offending row and try again
-                const int q = wsidx[dep_at];
-#pragma unroll
-                for (int s = 0; s < NZS; ++s)
-                    if (128 * (s >> 1) + 2 * lane + (s & 1) == q) actb[s] = 0;
-#pragma unroll
-                for (int s = 0; s < NGS; ++s)
-                    if (ldz + 128 * (s >> 1) + 2 * lane + (s & 1) == q) actg[s] = 0;
-                wave_sync();
-                continue;
-            }
-            wave_sync();                             // lam is in LDS
-            MPCX_LAP_WAIT(3);                        // 3: w = t0 - Y[:, A] lambda, multipliers in LDS
-            const double dtol = 1e-9 * lmax + 1e-300;
-            dtol_last = dtol;
-            // ---- how wrong is each working row's multiplier (> dtol: wrong sign), how violated each free row: straight-line code,
-            // every slot looks a multiplier up (0 in the spare slot) and measures a violation, selects decide which one counts
-            double badb[NZS], badg[NGS], vb[NZS], vg[NGS], vm = 0.0, bm = 0.0, chk = 0.0;
-            bool lowb[NZS], lowg[NGS];
-            double lmb[NZS], lmg[NGS];
-#pragma unroll
-            for (int s = 0; s < NZS; ++s) lmb[s] = lam[posb[s]];
-#pragma unroll
-            for (int s = 0; s < NGS; ++s) lmg[s] = lam[posg[s]];
-#pragma unroll
-            for (int c = 0; c < CPZ; ++c) {
-                const int e = 128 * c + 2 * lane;
-                const double2 l = *reinterpret_cast<const double2 *>(lws + e), u = *reinterpret_cast<const double2 *>(uws + e);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int s = 2 * c + h;
-                    const double lo = h ? l.y : l.x, hi = h ? u.y : u.x;
-                    chk += wv[s];
-                    lowb[s] = wv[s] < lo;
-                    const double v = viol(wv[s], lo, hi);
-                    vb[s] = actb[s] == 0 ? v : 0.0;
-                    badb[s] = actb[s] == -1 ? lmb[s] : (actb[s] == 1 ? -lmb[s] : 0.0);
-                    vm = fmax(vm, vb[s]); bm = fmax(bm, badb[s]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < CPG; ++c) {
-                const int r = 128 * c + 2 * lane;
-                const double2 l = *reinterpret_cast<const double2 *>(lgs + r), u = *reinterpret_cast<const double2 *>(ugs + r);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int s = 2 * c + h;
-                    const double lo = h ? l.y : l.x, hi = h ? u.y : u.x;
-                    chk += gw[s];
-                    lowg[s] = gw[s] < lo;
-                    const double v = viol(gw[s], lo, hi);
-                    vg[s] = actg[s] == 0 ? v : 0.0;
-                    badg[s] = actg[s] == -1 ? lmg[s] : (actg[s] == 1 ? -lmg[s] : 0.0);
-                    vm = fmax(vm, vg[s]); bm = fmax(bm, badg[s]);
-                }
-            }
-            if (wave_any(!(chk - chk == 0.0))) break;       // a NaN or an infinity in the point: left to the fallback kernel
-            MPCX_LAP(4);                             // 4: multipliers and violations
-            const bool any_bad = wave_any(bm > dtol), any_viol = wave_any(vm > 0.0);
-            if (!any_bad && !any_viol) { solved = true; break; }
-            if (rd < MPCX_FAST_SAFE_AFTER) {
-                // every wrong-signed row leaves, and the rows violated by at least MPCX_FAST_ADD_THETA x the largest violation enter
-                const double thr = any_viol ? (rd < 3 ? MPCX_FAST_ADD_THETA : MPCX_FAST_ADD_THETA_LATE) * wave_max_dpp(vm) : INF;
-#pragma unroll
-                for (int s = 0; s < NZS; ++s) actb[s] = badb[s] > dtol ? 0 : ((vb[s] > 0.0 && vb[s] >= thr) ? (lowb[s] ? -1 : 1) : actb[s]);
-#pragma unroll
-                for (int s = 0; s < NGS; ++s) actg[s] = badg[s] > dtol ? 0 : ((vg[s] > 0.0 && vg[s] >= thr) ? (lowg[s] ? -1 : 1) : actg[s]);
-            } else {
-                // an instance that is still here (none in 40 000 of the benchmark workloads: the rule above may cycle in principle) goes
-                // on with one exchange per round: the most wrong multiplier leaves, else the most violated row enters
-                const double mx = wave_max_dpp(any_bad ? bm : vm);
-                int slot = -1;
-#pragma unroll
-                for (int s = 0; s < NZS; ++s) if (slot < 0 && (any_bad ? badb[s] : vb[s]) == mx) slot = s;
-#pragma unroll
-                for (int s = 0; s < NGS; ++s) if (slot < 0 && (any_bad ? badg[s] : vg[s]) == mx) slot = NZS + s;
-                const unsigned long long mk = __ballot(slot >= 0);
-                if (slot >= 0 && lane == (int)__builtin_ctzll(mk)) {
-#pragma unroll
-                    for (int s = 0; s < NZS; ++s) if (slot == s) actb[s] = any_bad ? 0 : (lowb[s] ? -1 : 1);
-#pragma unroll
-                    for (int s = 0; s < NGS; ++s) if (slot == NZS + s) actg[s] = any_bad ? 0 : (lowg[s] ? -1 : 1);
-                }
-            }
-            wave_sync();
-            MPCX_LAP(5);                             // 5: repair
-        }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    stamp(ts2);   // 2: solved
 
     if (!infeasible && !solved) {
         // left for the fallback kernel (flag stays 0 / 1), which reads the workspace record
@@ -821,6 +563,336 @@ __device__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b
     }
 }
 
+// SRC: where the instance's record comes from -- 0 the workspace (two-kernel path), 1 computed here by fused_record (one mat-vec
+// with the composed maps), 2 already in the slice (lmpc_solve_group: the workgroup's MFMA assemble phase put it there)
+template <int CPZ, int CPG, int SRC = 0>
+__device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
+                           double *slice, const double *lwuw, gdw ws, const double *mf_lds = nullptr, double *outs = nullptr, const int eqbits = 0)
+{
+    // eqbits (SRC = 2, lmpc_solve_group): bit s = this lane's general row s is an equality (lg0 == ug0), looked up by the caller with its other loads
+    // outs (lmpc_solve_group): the instance's scalar results and its command go to this LDS record [cost, status, solver status,
+    // feasible, iterations, rounds, active rows, done | cmd (nu)] instead of to HBM; the workgroup writes sixteen of them coalesced
+    constexpr int NZS = 2 * CPZ, NGS = 2 * CPG, ZP = 128 * CPZ, GPD = 128 * CPG;
+    const int nz = M.nz, mg = M.mg, ldz = M.ldz, ldg = M.ldg, ldy = M.ldy;
+    const gdp gY = GP(Y);
+    double *t0s = slice, *gt0s = t0s + ZP, *lgs = gt0s + GPD, *ugs = lgs + GPD, *fs = ugs + GPD, *tail = fs + ZP;
+    double *lam = tail + 2, *wsb = lam + (kFastCap + 2);
+    int *wsidx = reinterpret_cast<int *>(wsb + (kFastCap + 2));
+    double *scratch = wsb + (kFastCap + 2) + (kFastCap + 2) / 2 + 1;
+    const double *lws = lwuw, *uws = lwuw + ZP;
+    const double INF = __builtin_huge_val();
+
+    long long ts0 = 0, ts1 = 0, ts2 = 0;                   // profiling aid: start, loaded, solved (Bt.dbg_cycles; fast_finish stamps the unpack)
+#ifdef MPCX_PROFILE_ROUNDS
+    long long pacc[6] = {0, 0, 0, 0, 0, 0}, plast = 0;
+#endif
+    auto stamp = [&](long long &t) { if (Bt.dbg_cycles) t = (long long)__builtin_readcyclecounter(); };
+    stamp(ts0);
+
+    // offsets of this lane's element pairs into the rows of Y (clamped: lanes past the end re-read pair 0, their results are never used)
+    int offz[CPZ], offg[CPG];
+#pragma unroll
+    for (int c = 0; c < CPZ; ++c) { const int e = 128 * c + 2 * lane; offz[c] = e < ldz ? e : 0; }
+#pragma unroll
+    for (int c = 0; c < CPG; ++c) { const int r = 128 * c + 2 * lane; offg[c] = ldz + (r < ldg ? r : 0); }
+    unsigned boffz[CPZ], boffg[CPG];                 // the same in bytes, as ws_solve_reg takes them
+#pragma unroll
+    for (int c = 0; c < CPZ; ++c) boffz[c] = (unsigned)offz[c] * 8u;
+#pragma unroll
+    for (int c = 0; c < CPG; ++c) boffg[c] = (unsigned)offg[c] * 8u;
+
+    // ---- the assembled problem: the workspace record the assemble kernel left, copied into the slice, or computed in place
+    if constexpr (SRC != 2) fast_init_pads<CPZ, CPG>(slice, ldz, ldg, lane);
+    if constexpr (SRC == 2) {
+        // nothing to do: the record is in place
+    } else if constexpr (SRC == 1) {
+        RecPtrs rp{fs, t0s, gt0s, lgs, ugs, tail};
+        fused_record(M, Bt, b, lane, scratch, rp, mf_lds);
+    } else {
+#pragma unroll
+        for (int c = 0; c < CPZ; ++c) {
+            const int e = 128 * c + 2 * lane;
+            if (e < ldz) {
+                const d2 vf = ld2(ws + e), vt = ld2(ws + ldz + e);
+                *reinterpret_cast<double2 *>(fs + e) = make_double2(vf.x, vf.y);
+                *reinterpret_cast<double2 *>(t0s + e) = make_double2(vt.x, vt.y);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CPG; ++c) {
+            const int r = 128 * c + 2 * lane;
+            if (r < ldg) {
+                const d2 vt = ld2(ws + 2 * ldz + r), vl = ld2(ws + ldz + ldy + r), vu = ld2(ws + ldz + ldy + ldg + r);
+                *reinterpret_cast<double2 *>(gt0s + r) = make_double2(vt.x, vt.y);
+                *reinterpret_cast<double2 *>(lgs + r) = make_double2(vl.x, vl.y);
+                *reinterpret_cast<double2 *>(ugs + r) = make_double2(vu.x, vu.y);
+            }
+        }
+        if (lane == 0) { const d2 t = ld2(ws + ldz + ldy + 2 * ldg); *reinterpret_cast<double2 *>(tail) = make_double2(t.x, t.y); }
+        wave_sync();
+    }
+    const double flag0 = tail[1];
+    // a violated step-0 / input-independent row: see admm_solve_one (lmpc_kernels.hip)
+    const bool fixed_violation = flag0 == 1.0;
+    const bool infeasible = fixed_violation && M.strict_infeasible;
+
+    // working-set state of this lane's rows: 0 free, -1 / +1 at the lower / upper bound, 2 equality row (always in, never shed)
+    int actb[NZS], actg[NGS];
+    const double ptol = 1e-8;
+    auto viol = [&](double v, double lo, double hi) {
+        return fmax(fmax(lo - ptol * fmax(1.0, fabs(lo)) - v, v - hi - ptol * fmax(1.0, fabs(hi))), 0.0);
+    };
+    {
+        // first working set: equalities, and the rows the unconstrained optimum violates by >= MPCX_INIT_THETA x the largest violation
+        double vb[NZS], vg[NGS], vinit = 0.0;
+        bool lowb[NZS], lowg[NGS];
+#pragma unroll
+        for (int c = 0; c < CPZ; ++c) {
+            const int e = 128 * c + 2 * lane;
+            const double2 l = *reinterpret_cast<const double2 *>(lws + e), u = *reinterpret_cast<const double2 *>(uws + e);
+            const double2 t = *reinterpret_cast<const double2 *>(t0s + e);
+            vb[2 * c] = viol(t.x, l.x, u.x); vb[2 * c + 1] = viol(t.y, l.y, u.y);
+            lowb[2 * c] = t.x < l.x; lowb[2 * c + 1] = t.y < l.y;
+            actb[2 * c] = l.x == u.x ? 2 : 0; actb[2 * c + 1] = l.y == u.y ? 2 : 0;
+            vinit = fmax(vinit, fmax(vb[2 * c], vb[2 * c + 1]));
+        }
+#pragma unroll
+        for (int c = 0; c < CPG; ++c) {
+            const int r = 128 * c + 2 * lane;
+            const double2 l = *reinterpret_cast<const double2 *>(lgs + r), u = *reinterpret_cast<const double2 *>(ugs + r);
+            const double2 t = *reinterpret_cast<const double2 *>(gt0s + r);
+            vg[2 * c] = viol(t.x, l.x, u.x); vg[2 * c + 1] = viol(t.y, l.y, u.y);
+            lowg[2 * c] = t.x < l.x; lowg[2 * c + 1] = t.y < l.y;
+            if constexpr (SRC == 2) {
+                actg[2 * c] = ((eqbits >> (2 * c)) & 1) ? 2 : 0; actg[2 * c + 1] = ((eqbits >> (2 * c + 1)) & 1) ? 2 : 0;
+            } else {
+                const d2 l0 = ld2(GP(lg0) + (offg[c] - ldz)), u0 = ld2(GP(ug0) + (offg[c] - ldz));
+                const bool ok = r < ldg;
+                actg[2 * c] = (ok && l0.x == u0.x) ? 2 : 0; actg[2 * c + 1] = (ok && l0.y == u0.y) ? 2 : 0;
+            }
+            vinit = fmax(vinit, fmax(vg[2 * c], vg[2 * c + 1]));
+        }
+        const double thr0 = MPCX_INIT_THETA * wave_max_dpp(vinit);
+#pragma unroll
+        for (int s = 0; s < NZS; ++s) actb[s] = (actb[s] == 0 && vb[s] > 0.0 && vb[s] >= thr0) ? (lowb[s] ? -1 : 1) : actb[s];
+#pragma unroll
+        for (int s = 0; s < NGS; ++s) actg[s] = (actg[s] == 0 && vg[s] > 0.0 && vg[s] >= thr0) ? (lowg[s] ? -1 : 1) : actg[s];
+    }
+    stamp(ts1);   // 1: loaded
+
+    if (Bt.warm_lower) {
+        // warm start: the first working set is the previous solve's active set (see admm_solve_one)
+        const unsigned MPCX_GAS *wl = gl(Bt.warm_lower) + (size_t)b * M.active_words;
+        const unsigned MPCX_GAS *wu = gl(Bt.warm_upper) + (size_t)b * M.active_words;
+        const int na = M.nx + M.nu, n1 = M.ph + 1;
+        const int b_box = M.neq_ref, b_out = b_box + n1 * na, b_du = b_out + n1 * M.ny, b_sc = b_du + M.ph * M.nu;
+        auto look = [&](int rr) {
+            if (!Bt.warm_shift) return rr;
+            if (rr < b_out) return rr + na < b_out ? rr + na : rr;
+            if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
+            if (rr < b_sc) return rr;
+            return rr + 1 < M.m_ref ? rr + 1 : rr;
+        };
+#pragma unroll
+        for (int s = 0; s < NZS; ++s) {
+            const int e = 128 * (s >> 1) + 2 * lane + (s & 1);
+            if (e >= nz || actb[s] == 2) continue;
+            const double lo = lws[e], hi = uws[e];
+            int side = 0;
+            for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
+                const int rr = look(GP(boxrow_ref)[p]);
+                if (((wl[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_lo)[p] == lo) side = -1;
+                if (((wu[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_hi)[p] == hi) side = 1;
+            }
+            actb[s] = side;
+        }
+#pragma unroll
+        for (int s = 0; s < NGS; ++s) {
+            const int r = 128 * (s >> 1) + 2 * lane + (s & 1);
+            if (r >= mg || actg[s] == 2) continue;
+            const int rr = look(GP(g_refrow)[r]);
+            actg[s] = ((wl[rr >> 5] >> (rr & 31)) & 1u) ? -1 : (((wu[rr >> 5] >> (rr & 31)) & 1u) ? 1 : 0);
+        }
+    }
+
+    double wv[NZS], gw[NGS];
+    int posb[NZS], posg[NGS];                        // position in the working set (kFastCap: not in it)
+    double dtol_last = 0;
+    int na_last = 0, rounds_total = 0;
+    bool solved = false;
+
+    if (!infeasible && M.polish) {
+        const int rounds = M.polish_rounds0;
+        for (int rd = 0; rd < rounds; ++rd) {
+            ++rounds_total;
+#ifdef MPCX_PROFILE_ROUNDS
+            plast = (long long)__builtin_readcyclecounter();
+#endif
+            // A launch lasts as long as its slowest instance, and the slow ones are those that need many rounds: from the fourth
+            // round on a wavefront asks the instruction arbiter for precedence over its three neighbours on the SIMD.
+            if (rd == 3) __builtin_amdgcn_s_setprio(1);
+            else if (rd == 5) __builtin_amdgcn_s_setprio(2);
+            else if (rd == 7) __builtin_amdgcn_s_setprio(3);
+            // ---- the working set, in row order, to LDS: unified index and bound value per row.  Straight-line code: a row that
+            // is not in the set writes to the spare slot kFastCap (so does a row past the capacity, which ends the solve below).
+            int na = 0;
+#pragma unroll
+            for (int c = 0; c < CPZ; ++c) {
+                const int e = 128 * c + 2 * lane;
+                const double2 l = *reinterpret_cast<const double2 *>(lws + e), u = *reinterpret_cast<const double2 *>(uws + e);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int s = 2 * c + h;
+                    const bool act = actb[s] != 0;
+                    const unsigned long long mk = __ballot(act);
+                    int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, (unsigned)na));      // (na as the count's addend)
+                    pos = (act && pos < kFastCap) ? pos : kFastCap;
+                    posb[s] = pos;
+                    wsidx[pos] = e + h;
+                    wsb[pos] = actb[s] < 0 ? (h ? l.y : l.x) : (h ? u.y : u.x);
+                    na += __popcll(mk);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CPG; ++c) {
+                const int r = 128 * c + 2 * lane;
+                const double2 l = *reinterpret_cast<const double2 *>(lgs + r), u = *reinterpret_cast<const double2 *>(ugs + r);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int s = 2 * c + h;
+                    const bool act = actg[s] != 0;
+                    const unsigned long long mk = __ballot(act);
+                    int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, (unsigned)na));      // (na as the count's addend)
+                    pos = (act && pos < kFastCap) ? pos : kFastCap;
+                    posg[s] = pos;
+                    wsidx[pos] = ldz + r + h;
+                    wsb[pos] = actg[s] < 0 ? (h ? l.y : l.x) : (h ? u.y : u.x);
+                    na += __popcll(mk);
+                }
+            }
+            if (na > kFastCap) break;                // left to the fallback kernel
+            na_last = na;
+            wave_sync();
+            MPCX_LAP_WAIT(0);                        // 0: working set built and in LDS
+            int dep_at = -1;
+            double lmax = 0.0;
+            if (na == 0) {
+#pragma unroll
+                for (int c = 0; c < CPZ; ++c) { const double2 v = *reinterpret_cast<const double2 *>(t0s + 128 * c + 2 * lane); wv[2 * c] = v.x; wv[2 * c + 1] = v.y; }
+#pragma unroll
+                for (int c = 0; c < CPG; ++c) { const double2 v = *reinterpret_cast<const double2 *>(gt0s + 128 * c + 2 * lane); gw[2 * c] = v.x; gw[2 * c + 1] = v.y; }
+            } else if (na <= 4) dep_at = ws_solve_reg<4, 1, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 6) dep_at = ws_solve_reg<6, 5, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 8) dep_at = ws_solve_reg<8, 7, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 10) dep_at = ws_solve_reg<10, 9, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 12) dep_at = ws_solve_reg<12, 11, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 14) dep_at = ws_solve_reg<14, 13, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else dep_at = ws_solve_reg<kFastCap, 15, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            if (dep_at >= 0) {
+                // linearly dependent working set: drop the offending row and try again
+                const int q = wsidx[dep_at];
+#pragma unroll
+                for (int s = 0; s < NZS; ++s)
+                    if (128 * (s >> 1) + 2 * lane + (s & 1) == q) actb[s] = 0;
+#pragma unroll
+                for (int s = 0; s < NGS; ++s)
+                    if (ldz + 128 * (s >> 1) + 2 * lane + (s & 1) == q) actg[s] = 0;
+                wave_sync();
+                continue;
+            }
+            wave_sync();                             // lam is in LDS
+            MPCX_LAP_WAIT(3);                        // 3: w = t0 - Y[:, A] lambda, multipliers in LDS
+            const double dtol = 1e-9 * lmax + 1e-300;
+            dtol_last = dtol;
+            // ---- how wrong is each working row's multiplier (> dtol: wrong sign), how violated each free row: straight-line code,
+            // every slot looks a multiplier up (0 in the spare slot) and measures a violation, selects decide which one counts
+            double badb[NZS], badg[NGS], vb[NZS], vg[NGS], vm = 0.0, bm = 0.0, chk = 0.0;
+            bool lowb[NZS], lowg[NGS];
+            double lmb[NZS], lmg[NGS];
+#pragma unroll
+            for (int s = 0; s < NZS; ++s) lmb[s] = lam[posb[s]];
+#pragma unroll
+            for (int s = 0; s < NGS; ++s) lmg[s] = lam[posg[s]];
+#pragma unroll
+            for (int c = 0; c < CPZ; ++c) {
+                const int e = 128 * c + 2 * lane;
+                const double2 l = *reinterpret_cast<const double2 *>(lws + e), u = *reinterpret_cast<const double2 *>(uws + e);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int s = 2 * c + h;
+                    const double lo = h ? l.y : l.x, hi = h ? u.y : u.x;
+                    chk += wv[s];
+                    lowb[s] = wv[s] < lo;
+                    const double v = viol(wv[s], lo, hi);
+                    vb[s] = actb[s] == 0 ? v : 0.0;
+                    badb[s] = actb[s] == -1 ? lmb[s] : (actb[s] == 1 ? -lmb[s] : 0.0);
+                    vm = fmax(vm, vb[s]); bm = fmax(bm, badb[s]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CPG; ++c) {
+                const int r = 128 * c + 2 * lane;
+                const double2 l = *reinterpret_cast<const double2 *>(lgs + r), u = *reinterpret_cast<const double2 *>(ugs + r);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int s = 2 * c + h;
+                    const double lo = h ? l.y : l.x, hi = h ? u.y : u.x;
+                    chk += gw[s];
+                    lowg[s] = gw[s] < lo;
+                    const double v = viol(gw[s], lo, hi);
+                    vg[s] = actg[s] == 0 ? v : 0.0;
+                    badg[s] = actg[s] == -1 ? lmg[s] : (actg[s] == 1 ? -lmg[s] : 0.0);
+                    vm = fmax(vm, vg[s]); bm = fmax(bm, badg[s]);
+                }
+            }
+            if (wave_any(!(chk - chk == 0.0))) break;       // a NaN or an infinity in the point: left to the fallback kernel
+            MPCX_LAP(4);                             // 4: multipliers and violations
+            const bool any_bad = wave_any(bm > dtol), any_viol = wave_any(vm > 0.0);
+            if (!any_bad && !any_viol) { solved = true; break; }
+            if (rd < MPCX_FAST_SAFE_AFTER) {
+                // every wrong-signed row leaves, and the rows violated by at least MPCX_FAST_ADD_THETA x the largest violation enter
+                const double thr = any_viol ? (rd < 3 ? MPCX_FAST_ADD_THETA : MPCX_FAST_ADD_THETA_LATE) * wave_max_dpp(vm) : INF;
+#pragma unroll
+                for (int s = 0; s < NZS; ++s) actb[s] = badb[s] > dtol ? 0 : ((vb[s] > 0.0 && vb[s] >= thr) ? (lowb[s] ? -1 : 1) : actb[s]);
+#pragma unroll
+                for (int s = 0; s < NGS; ++s) actg[s] = badg[s] > dtol ? 0 : ((vg[s] > 0.0 && vg[s] >= thr) ? (lowg[s] ? -1 : 1) : actg[s]);
+            } else {
+                // an instance that is still here (none in 40 000 of the benchmark workloads: the rule above may cycle in principle) goes
+                // on with one exchange per round: the most wrong multiplier leaves, else the most violated row enters
+                const double mx = wave_max_dpp(any_bad ? bm : vm);
+                int slot = -1;
+#pragma unroll
+                for (int s = 0; s < NZS; ++s) if (slot < 0 && (any_bad ? badb[s] : vb[s]) == mx) slot = s;
+#pragma unroll
+                for (int s = 0; s < NGS; ++s) if (slot < 0 && (any_bad ? badg[s] : vg[s]) == mx) slot = NZS + s;
+                const unsigned long long mk = __ballot(slot >= 0);
+                if (slot >= 0 && lane == (int)__builtin_ctzll(mk)) {
+#pragma unroll
+                    for (int s = 0; s < NZS; ++s) if (slot == s) actb[s] = any_bad ? 0 : (lowb[s] ? -1 : 1);
+#pragma unroll
+                    for (int s = 0; s < NGS; ++s) if (slot == NZS + s) actg[s] = any_bad ? 0 : (lowg[s] ? -1 : 1);
+                }
+            }
+            wave_sync();
+            MPCX_LAP(5);                             // 5: repair
+        }
+    }
+    __builtin_amdgcn_s_setprio(0);
+    stamp(ts2);   // 2: solved
+
+    // lmpc_solve_group re-reads its kernel arguments here (see GroupArgs): the empty asm keeps the compiler from loading a field the finish needs
+    // ahead of the rounds and carrying it through them
+    if constexpr (SRC == 2) {
+        group_args_p ka = (group_args_p)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        fast_finish<CPZ, CPG, SRC>((const LmpcDev &)ka->M, (const LmpcBatchDev &)ka->Bt, b, lane, slice, lwuw, ws, outs, infeasible, solved, fixed_violation,
+                                   wv, actb, actg, posb, posg, dtol_last, na_last, rounds_total, ts0, ts1, ts2 MPCX_PROF_PASS);
+    } else {
+        fast_finish<CPZ, CPG, SRC>(M, Bt, b, lane, slice, lwuw, ws, outs, infeasible, solved, fixed_violation,
+                                   wv, actb, actg, posb, posg, dtol_last, na_last, rounds_total, ts0, ts1, ts2 MPCX_PROF_PASS);
+    }
+}
+
 // waves per SIMD the lean kernels are compiled for: the one-chunk variant fits 128 VGPRs
 #ifndef MPCX_FAST_WAVES1
 #define MPCX_FAST_WAVES1 4
@@ -989,7 +1061,7 @@ constexpr int kGroupG1 = 2;               // ... of the first product (kin = 32:
 // Measured by cutting the kernel short (tools/group_cut.py; quadrotor N = 20, 4096 instances, us per step with the idle fallback launch): empty
 // 6.9, inputs staged 7.6, first product 10.6, second product 15.3, whole 49.0 before the packed copies.
 template <int CPZ, int CPG>
-__global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(const LmpcDev Mv, const LmpcBatchDev Bt, double *wsbase, const int variant)
+__global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(const LmpcDev Mv, const LmpcBatchDev Btv, double *wsbasev, const int variantv)
 {
     constexpr int kGroupWaves = kGroupWavesOf<CPZ>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -997,7 +1069,11 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
     { return; }                                   // (timing experiment, tools/group_cut.sh: what a launch costs up to here)
 #endif
     kernarg_touch<sizeof(LmpcDev) + sizeof(LmpcBatchDev) + sizeof(double *) + sizeof(int)>();
-    const LmpcDev &M = Mv;
+    const group_args_p ka = (group_args_p)__builtin_amdgcn_kernarg_segment_ptr();      // (see GroupArgs)
+    const LmpcDev &M = (const LmpcDev &)ka->M;
+    const LmpcBatchDev &Bt = (const LmpcBatchDev &)ka->Bt;
+    double *const wsbase = ka->wsbase;
+    const int variant = ka->variant;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, kq = lane >> 4;
     const int nx = M.nx, nu = M.nu, ny = M.ny;
