@@ -22,11 +22,12 @@ namespace {
 //     no forward / backward substitution, no transposition through LDS, no predication -- 3 instructions per eliminated entry
 //     (two v_readlane, one fma) instead of 5 plus two substitutions.  On the Schur complements of config 2 / config 4 its error
 //     is that of the Cholesky factorisation (6e-15 relative).
-//   * the rows of Y the update w = t0 - Y[:, A] lambda needs are requested together with the Schur entries, before the
-//     elimination: one trip to L2 per round instead of three; the multipliers reach the update by v_readlane, not through LDS;
-//     the working-set indices are wave-uniform and live in SGPRs (scalar row addresses).
-//   * wave-wide maxima by DPP row operations and four v_readlane pairs (the ds_bpermute butterfly of __shfl_xor is a chain of
-//     six LDS round trips);
+//   * rows of Y the update w = t0 - Y[:, A] lambda needs are requested together with the Schur entries, before the elimination -- all of
+//     them for working sets of up to six rows (one trip to L2 per round), the first four for up to twelve, none beyond; the rest follows
+//     the elimination, pipelined (round 9, below).  The multipliers reach the update by v_readlane, not through LDS; the working-set
+//     indices are wave-uniform and live in SGPRs (scalar row addresses).
+//   * wave-wide maxima by DPP operations -- four within the rows of sixteen lanes, two across them -- and one v_readlane pair (the
+//     ds_bpermute butterfly of __shfl_xor is a chain of six LDS round trips);
 //   * what a round only reads -- t0, G t0, the linear term and the bounds -- stays in LDS: the wave's slice has the layout of the
 //     workspace record (f | t0 | gt0 | lg | ug | c0, flag) followed by a small arena, the box bounds are shared by the
 //     workgroup.  The one-chunk variant fits 128 VGPRs and 3.3 KB of LDS per wavefront: four wavefronts per SIMD, i.e. at the
@@ -38,8 +39,20 @@ namespace {
 //     formed where they are used, the later rows' indices are read from LDS again, lmpc_solve_group reads its arguments through the kernel-argument
 //     pointer and once more behind the loop (fast_finish), and the pad of the Schur matrix is two moves per column under one execution mask with the
 //     pivot threshold from one more load instead of a select chain per column.  No floating-point operation changed; profiles/r08_round_isa_census.txt.
+//   * round 9: fewer exposed trips and a leaner verify phase.  The six-row class requests all its rows ahead of the elimination.  Behind the
+//     elimination the remaining rows come in batches of two with three batches in flight, each batch requested before the one ahead of it is waited
+//     for: one fresh trip in the 8- and 10-row classes, two in the 12-row class, three in the 14- and 16-row classes (they were 1, 2, 2, 4, 4; the
+//     eight rows in flight that would make it one or two everywhere do not fit 128 VGPRs without scratch), and no branch in the update any more.
+//     The verify phase's multiplier signs are bit arithmetic instead of four exec-mask ladders, the wave maximum's DPP moves no longer copy their source,
+//     and viol()'s contractions are written out.  What is still not straight-line code there: the NaN screen, the "solved" test and the choice between
+//     the two repair rules are wave-uniform branches.  No floating-point operation changed; profiles/r09_round_isa_census.txt.
 // Working sets of more than kFastCap rows are left to the fallback kernel (none in 32768 instances of config 2, none in 8192 of
 // config 4).
+// How deep a round reaches into memory ahead of its arithmetic (ws_solve_reg).  Rows of Y requested with the Schur entries, ahead of the elimination:
+// every row in the size classes up to MPCX_FAST_PF_ALL rows, MPCX_FAST_PF rows in the classes up to MPCX_FAST_PF_MAXCAP, none beyond (their elimination
+// needs the registers).  The rows behind them come in batches after the elimination: MPCX_FAST_RB_DEEP rows per batch and MPCX_FAST_NBUF batches in flight
+// where a row is cheap in registers (a lane holds at most MPCX_FAST_DEEP_CHUNKS pairs of a row: the one- and two-chunk variants), one batch of
+// MPCX_FAST_RB rows at a time and no deeper first trip in the four-chunk variant, where a row is 32 VGPRs.
 #ifndef MPCX_FAST_PF_MAXCAP
 #define MPCX_FAST_PF_MAXCAP 12
 #endif
@@ -48,6 +61,22 @@ namespace {
 #endif
 #ifndef MPCX_FAST_PF
 #define MPCX_FAST_PF 4
+#endif
+#ifndef MPCX_FAST_PF_ALL
+#define MPCX_FAST_PF_ALL 6
+#endif
+#ifndef MPCX_FAST_NBUF
+#define MPCX_FAST_NBUF 3
+#endif
+#ifndef MPCX_FAST_RB_DEEP
+#define MPCX_FAST_RB_DEEP 2
+#endif
+#ifndef MPCX_FAST_DEEP_CHUNKS
+#define MPCX_FAST_DEEP_CHUNKS 4
+#endif
+// between the stages of the pipelined update: the instruction scheduler moves nothing across (a batch's loads stay ahead of the wait for the batch before it)
+#ifndef MPCX_FAST_STAGE
+#define MPCX_FAST_STAGE() __builtin_amdgcn_sched_barrier(0)
 #endif
 constexpr int kFastCap = 16;
 #ifndef MPCX_FAST_ADD_THETA_LATE
@@ -60,9 +89,10 @@ constexpr int kFastCap = 16;
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov_d(double v)
 {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
+    // a move whose `old` operand is not its source (there is none: a lane without a source reads 0): the destination is a fresh register, so no copy
+    // of the source has to be made in front of the move to keep the source alive
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
     return __hiloint2double(hi, lo);
 }
 // maximum over the wavefront of non-NaN values, the same in every lane
@@ -72,7 +102,11 @@ __device__ __forceinline__ double wave_max_dpp(double v)
     v = fmax(v, dpp_mov_d<0x4E>(v));     // quad_perm [2,3,0,1]
     v = fmax(v, dpp_mov_d<0x141>(v));    // row_half_mirror
     v = fmax(v, dpp_mov_d<0x140>(v));    // row_mirror: every row of 16 lanes is uniform now
-    return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
+    // across the rows towards lane 63: row r takes in the last lane of row r - 1, then rows 2 and 3 the last lane of row 1.  Rows without a source
+    // take in a 0 and hold values nobody reads; lane 63 holds the maximum of all four rows and is read back -- one pair of v_readlane instead of four
+    v = fmax(v, dpp_mov_d<0x142>(v));    // row_bcast:15
+    v = fmax(v, dpp_mov_d<0x143>(v));    // row_bcast:31
+    return readlane_d(v, 63);
 }
 
 // One solve of the working-set system and the update of the primal point, working set of at most CAP (<= 16) rows.
@@ -102,7 +136,11 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
     // NLO <= na <= CAP: the size class (the caller's dispatch), so only the columns from NLO on can lie past the working set
     // rows of Y requested ahead of the elimination (none for the largest working sets: their elimination needs the registers, and a
     // spilled register is HBM traffic -- scratch is memory)
-    constexpr int PF = CAP > MPCX_FAST_PF_MAXCAP ? 0 : (CAP < MPCX_FAST_PF ? CAP : MPCX_FAST_PF);
+    // (round 9: the six-row class, where the mean working set falls, takes ALL its rows ahead -- no trip after the elimination; the same for the eight-row
+    // class spills 104 B per lane, six rows ahead in the 8- to 12-row classes 60 B, so from there on four rows go ahead and the rest is pipelined below.
+    // DEEP: see the macros above)
+    constexpr bool DEEP = CPZ + CPG <= MPCX_FAST_DEEP_CHUNKS;
+    constexpr int PF = CAP > MPCX_FAST_PF_MAXCAP ? 0 : (CAP <= (DEEP ? MPCX_FAST_PF_ALL : MPCX_FAST_PF) ? CAP : MPCX_FAST_PF);
     // the lane number as this round's own value: what depends on it (the masks lane == k of the elimination, the identity's entries) is then formed
     // where it is used, one compare each, instead of ahead of the round loop for every size class at once -- more than the register files hold
     int lane = lane_in;
@@ -177,47 +215,55 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
         gw[2 * c] = v.x; gw[2 * c + 1] = v.y;
     }
     double lm = 0.0;
-#pragma unroll
-    for (int a = 0; a < PF; ++a) {
-        const double la = readlane_d(y, a);        // rows past na: copies of row 0 with multiplier 0
+    // one row of Y applied: rows in ascending working-set position, whichever batch brought them (a row past na is a copy of row 0 with multiplier 0)
+    auto apply_row = [&](const int a, const d2 (&rz)[CPZ], const d2 (&rg)[CPG]) {
+        const double la = readlane_d(y, a);
         lm = fmax(lm, fabs(la));
 #pragma unroll
-        for (int c = 0; c < CPZ; ++c) { wv[2 * c] = fma(-la, pz[a][c].x, wv[2 * c]); wv[2 * c + 1] = fma(-la, pz[a][c].y, wv[2 * c + 1]); }
+        for (int c = 0; c < CPZ; ++c) { wv[2 * c] = fma(-la, rz[c].x, wv[2 * c]); wv[2 * c + 1] = fma(-la, rz[c].y, wv[2 * c + 1]); }
 #pragma unroll
-        for (int c = 0; c < CPG; ++c) { gw[2 * c] = fma(-la, pg[a][c].x, gw[2 * c]); gw[2 * c + 1] = fma(-la, pg[a][c].y, gw[2 * c + 1]); }
-    }
-    if constexpr (CAP > PF) {
-        constexpr int RB = CAP - PF < MPCX_FAST_RB ? CAP - PF : MPCX_FAST_RB;      // rows of Y per later batch (the elimination's registers are free by now)
+        for (int c = 0; c < CPG; ++c) { gw[2 * c] = fma(-la, rg[c].x, gw[2 * c]); gw[2 * c + 1] = fma(-la, rg[c].y, gw[2 * c + 1]); }
+    };
+    if constexpr (CAP == PF) {
+#pragma unroll
+        for (int a = 0; a < PF; ++a) apply_row(a, pz[a], pg[a]);
+    } else {
+        // round 9: the rows behind the first PF in batches of RB, software-pipelined over NBUF buffers -- the first NBUF batches are requested together,
+        // batch k + NBUF as soon as batch k's FMAs are issued (its registers are free then), i.e. always ahead of the wait for batch k + 1.  The requests
+        // follow the FMAs of the rows that came ahead of the elimination, whose registers they take over (requested before them, the two sets are live
+        // together and the kernels spill).  Every batch starts before the class's smallest working set ends (a0 < NLO: the size classes are two rows
+        // wide), so nothing here is under a branch.  Rows are still applied in ascending working-set position.
+        constexpr int RB0 = DEEP ? MPCX_FAST_RB_DEEP : MPCX_FAST_RB, RB = CAP - PF < RB0 ? CAP - PF : RB0;      // rows of Y per later batch
+        constexpr int NB = (CAP - PF + RB - 1) / RB, NBUF = DEEP ? MPCX_FAST_NBUF : 1;
+        static_assert(PF + (NB - 1) * RB < NLO, "a later batch would start past the class's smallest working set");
         // the later rows' indices come from LDS once more: sixteen of them do not stay in SGPRs through the elimination beside its pivot row, and they
         // were spilled to VGPR lanes.  (An offset the compiler cannot see through makes these loads of their own, not the first ones' registers kept.)
         int again = 0;
         asm volatile("" : "+s"(again));
         const int *wsidx_again = wsidx + again;
+        d2 mz[NBUF][RB][CPZ], mgv[NBUF][RB][CPG];
+        auto request = [&](const int k, d2 (&bz)[RB][CPZ], d2 (&bg)[RB][CPG]) {
 #pragma unroll
-        for (int a0 = PF; a0 < CAP; a0 += RB) {
-            if (a0 < na) {
-                d2 mz[RB][CPZ], mgv[RB][CPG];
+            for (int u = 0; u < RB; ++u) {
+                const int cu = PF + k * RB + u < CAP ? PF + k * RB + u : 0;
+                const int q = __builtin_amdgcn_readfirstlane(wsidx_again[(cu < NLO || cu < na) ? cu : 0]);
 #pragma unroll
-                for (int u = 0; u < RB; ++u) {
-                    const int cu = a0 + u < CAP ? a0 + u : 0;
-                    const int q = __builtin_amdgcn_readfirstlane(wsidx_again[(cu < NLO || cu < na) ? cu : 0]);
+                for (int c = 0; c < CPZ; ++c) bz[u][c] = row_ld2(q, offz[c]);
 #pragma unroll
-                    for (int c = 0; c < CPZ; ++c) mz[u][c] = row_ld2(q, offz[c]);
-#pragma unroll
-                    for (int c = 0; c < CPG; ++c) mgv[u][c] = row_ld2(q, offg[c]);
-                }
-#pragma unroll
-                for (int u = 0; u < RB; ++u) {
-                    if (a0 + u < CAP) {
-                        const double la = readlane_d(y, a0 + u < CAP ? a0 + u : 0);
-                        lm = fmax(lm, fabs(la));
-#pragma unroll
-                        for (int c = 0; c < CPZ; ++c) { wv[2 * c] = fma(-la, mz[u][c].x, wv[2 * c]); wv[2 * c + 1] = fma(-la, mz[u][c].y, wv[2 * c + 1]); }
-#pragma unroll
-                        for (int c = 0; c < CPG; ++c) { gw[2 * c] = fma(-la, mgv[u][c].x, gw[2 * c]); gw[2 * c + 1] = fma(-la, mgv[u][c].y, gw[2 * c + 1]); }
-                    }
-                }
+                for (int c = 0; c < CPG; ++c) bg[u][c] = row_ld2(q, offg[c]);
             }
+        };
+#pragma unroll
+        for (int a = 0; a < PF; ++a) apply_row(a, pz[a], pg[a]);
+#pragma unroll
+        for (int k = 0; k < NBUF && k < NB; ++k) request(k, mz[k], mgv[k]);
+        MPCX_FAST_STAGE();
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+#pragma unroll
+            for (int u = 0; u < RB; ++u)
+                if (PF + k * RB + u < CAP) apply_row(PF + k * RB + u, mz[k % NBUF][u], mgv[k % NBUF][u]);
+            if (k + NBUF < NB) { request(k + NBUF, mz[k % NBUF], mgv[k % NBUF]); MPCX_FAST_STAGE(); }
         }
     }
     lmax = lm;
@@ -639,8 +685,19 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
     // working-set state of this lane's rows: 0 free, -1 / +1 at the lower / upper bound, 2 equality row (always in, never shed)
     int actb[NZS], actg[NGS];
     const double ptol = 1e-8;
+    // by how much v lies outside [lo, hi] widened by ptol max(1, |bound|), with the contractions written out: the low side's bound is widened first and v
+    // subtracted from it, the high side subtracts first and widens the difference (what the compiler made of lo - ptol m - v and v - hi - ptol m)
     auto viol = [&](double v, double lo, double hi) {
-        return fmax(fmax(lo - ptol * fmax(1.0, fabs(lo)) - v, v - hi - ptol * fmax(1.0, fabs(hi))), 0.0);
+        const double lo_wide = fma(-ptol, fmax(1.0, fabs(lo)), lo), hi_scale = fmax(1.0, fabs(hi));
+        return fmax(fmax(lo_wide - v, fma(-ptol, hi_scale, v - hi)), 0.0);
+    };
+    // a working row's multiplier as "how wrong": lm at the lower bound (act = -1), -lm at the upper (act = 1), 0 for a free or an equality row (0, 2).
+    // Bit arithmetic on the high word, no select and no branch: (act + 1) << 30 is the sign bit for act = 1 and nothing for act = -1, bit 0 of act
+    // says whether the row counts at all.  -lm is the exact negation (the sign bit flipped), the 0 is +0.
+    auto wrong_signed = [](double lm, int act) {
+        const int in = -(act & 1);
+        const int hi = (__double2hiint(lm) ^ (int)((unsigned)(act + 1) << 30)) & in;
+        return __hiloint2double(hi, __double2loint(lm) & in);
     };
     {
         // first working set: equalities, and the rows the unconstrained optimum violates by >= MPCX_INIT_THETA x the largest violation
@@ -805,7 +862,7 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
             const double dtol = 1e-9 * lmax + 1e-300;
             dtol_last = dtol;
             // ---- how wrong is each working row's multiplier (> dtol: wrong sign), how violated each free row: straight-line code,
-            // every slot looks a multiplier up (0 in the spare slot) and measures a violation, selects decide which one counts
+            // every slot looks a multiplier up (0 in the spare slot) and measures a violation; a select (violation) and the state's bits (multiplier) decide which one counts
             double badb[NZS], badg[NGS], vb[NZS], vg[NGS], vm = 0.0, bm = 0.0, chk = 0.0;
             bool lowb[NZS], lowg[NGS];
             double lmb[NZS], lmg[NGS];
@@ -825,7 +882,7 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
                     lowb[s] = wv[s] < lo;
                     const double v = viol(wv[s], lo, hi);
                     vb[s] = actb[s] == 0 ? v : 0.0;
-                    badb[s] = actb[s] == -1 ? lmb[s] : (actb[s] == 1 ? -lmb[s] : 0.0);
+                    badb[s] = wrong_signed(lmb[s], actb[s]);
                     vm = fmax(vm, vb[s]); bm = fmax(bm, badb[s]);
                 }
             }
@@ -841,7 +898,7 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
                     lowg[s] = gw[s] < lo;
                     const double v = viol(gw[s], lo, hi);
                     vg[s] = actg[s] == 0 ? v : 0.0;
-                    badg[s] = actg[s] == -1 ? lmg[s] : (actg[s] == 1 ? -lmg[s] : 0.0);
+                    badg[s] = wrong_signed(lmg[s], actg[s]);
                     vm = fmax(vm, vg[s]); bm = fmax(bm, badg[s]);
                 }
             }
@@ -922,7 +979,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, fast_waves<CPZ>()) void lmpc_s
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const LmpcDev &M = *Mp;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and known to be: the instance number and what is addressed with it stay scalar)
     constexpr int ZP = 128 * CPZ;
     const int wpb = blockDim.x >> 6;
     double *rec = smem + 2 * ZP + (size_t)wave * M.fast_slice;
@@ -940,7 +997,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, fast_waves<CPZ>()) void lmpc_s
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const LmpcDev &M = *Mp;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and known to be: the instance number and what is addressed with it stay scalar)
     constexpr int ZP = 128 * CPZ;
     const int wpb = blockDim.x >> 6;
     double *rec = smem + 2 * ZP + (size_t)wave * M.fast_slice;
@@ -969,7 +1026,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, fast_waves<CPZ>()) void lmpc_s
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const LmpcDev &M = *Mp;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and known to be: the instance number and what is addressed with it stay scalar)
     fast_load_box<CPZ>(M, smem);
     double *rec = smem + 2 * 128 * CPZ + (size_t)wave * M.fast_slice;
     const int wpb = blockDim.x >> 6;
@@ -988,7 +1045,7 @@ __global__ __launch_bounds__(kPersistWaves * 64) void lmpc_solve_persistent(cons
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const LmpcDev &M = *Mp;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and known to be: the instance number and what is addressed with it stay scalar)
     const int nmf = M.rowsF * M.kin;                  // even
     {
         const gdp src = gl(Bt.fused == 2 ? M.MF1 : M.MF0);
