@@ -3,6 +3,7 @@
 #include "lmpc_kernel_common.hpp"
 #include <cstddef>
 #include <cstdlib>
+#include <utility>
 
 namespace mpcx {
 
@@ -24,7 +25,7 @@ namespace {
 //     is that of the Cholesky factorisation (6e-15 relative).
 //   * rows of Y the update w = t0 - Y[:, A] lambda needs are requested together with the Schur entries, before the elimination -- all of
 //     them for working sets of up to six rows (one trip to L2 per round), the first four for up to twelve, none beyond; the rest follows
-//     the elimination, pipelined (round 9, below).  The multipliers reach the update by v_readlane, not through LDS; the working-set
+//     the elimination, pipelined (round 9, below).  The multipliers reach the update by v_readlane or, in the classes where that wins, from LDS (round 10); the working-set
 //     indices are wave-uniform and live in SGPRs (scalar row addresses).
 //   * wave-wide maxima by DPP operations -- four within the rows of sixteen lanes, two across them -- and one v_readlane pair (the
 //     ds_bpermute butterfly of __shfl_xor is a chain of six LDS round trips);
@@ -46,6 +47,17 @@ namespace {
 //     The verify phase's multiplier signs are bit arithmetic instead of four exec-mask ladders, the wave maximum's DPP moves no longer copy their source,
 //     and viol()'s contractions are written out.  What is still not straight-line code there: the NaN screen, the "solved" test and the choice between
 //     the two repair rules are wave-uniform branches.  No floating-point operation changed; profiles/r09_round_isa_census.txt.
+//   * round 10: the broadcasts of ws_solve_reg off the vector pipe, behind two switches per size class (MPCX_FAST_XBAR_CLASSES, MPCX_FAST_LDSMULT_CLASSES below),
+//     each kept where it wins on the GPU.  (1) The update's multipliers read back from lam[] in LDS at wave-uniform addresses, two per 16-byte read, each read
+//     travelling with the rows of Y it multiplies, instead of a v_readlane pair per row: on in the 8- and 10-row classes.  Whole step, parent -> this:
+//     0.03414 -> 0.03359 ms, 0.03280 -> 0.03220 ms at --steps 2000.  In the 4- and 6-row classes it is within the noise of the scalar reads; in the 12- to
+//     16-row classes the pairs in flight beside three batches of rows do not fit 128 VGPRs (12 B of scratch) and the step is 0.7 us SLOWER.  (2) The
+//     elimination's pivot row and right-hand side through the LDS crossbar (ds_swizzle_b32, broadcast mode): built, measured, and OFF in every class.  A step's
+//     FMAs wait for the crossbar, whose result the next step's pivot row depends on -- sixteen LDS round trips on the dependent chain where v_readlane's are a
+//     few cycles each: the elimination phase goes from 790 to 1030 cycles per round in the 4-row class and from 2077 to 3038 in the 16-row class, the step
+//     from 0.0346 to 0.0386 ms with every class on it (fewer vector instructions, but it is the slowest chain that ends the launch, and that chain is latency).
+//     The elimination's steps are instances of one lambda over the step number either way (the crossbar's lane is an immediate).  No floating-point operation
+//     changed; profiles/r10_round_ab.txt, r10_round_isa_census.txt.
 // Working sets of more than kFastCap rows are left to the fallback kernel (none in 32768 instances of config 2, none in 8192 of
 // config 4).
 // How deep a round reaches into memory ahead of its arithmetic (ws_solve_reg).  Rows of Y requested with the Schur entries, ahead of the elimination:
@@ -74,6 +86,26 @@ namespace {
 #ifndef MPCX_FAST_DEEP_CHUNKS
 #define MPCX_FAST_DEEP_CHUNKS 4
 #endif
+// Which size classes of ws_solve_reg take their broadcasts off the vector pipe (round 10 in the comment above), two switches per class, each decided by
+// measurement (profiles/r10_round_ab.txt), never by round number at run time.  Bit CAP / 2 stands for the class of at most CAP rows (4, 6, ..., 16: bits 2
+// to 8).  MPCX_FAST_XBAR_CLASSES: the elimination's pivot row and right-hand side through the LDS crossbar (its parameter XB).  MPCX_FAST_LDSMULT_CLASSES:
+// the update's multipliers read back from LDS (XL).  Both only in the variants whose lane holds at most MPCX_FAST_XBAR_CHUNKS pairs of a row, and not in
+// the kernels that compute the record themselves (lmpc_solve_fused, lmpc_solve_persistent: they sit at their register budgets, see solve_fast).
+#ifndef MPCX_FAST_XBAR_CLASSES
+#define MPCX_FAST_XBAR_CLASSES 0
+#endif
+#ifndef MPCX_FAST_LDSMULT_CLASSES
+#define MPCX_FAST_LDSMULT_CLASSES 0x30
+#endif
+#ifndef MPCX_FAST_XBAR_CHUNKS
+#define MPCX_FAST_XBAR_CHUNKS 4
+#endif
+// entries of a step's pivot row per chunk (two chunks are in flight), one hexadecimal digit per size class: digit CAP / 2, as the bits above
+#ifndef MPCX_FAST_XBAR_CHUNK
+#define MPCX_FAST_XBAR_CHUNK 0x333442400ull
+#endif
+constexpr int fast_xbar_chunk(int cap) { return (int)((MPCX_FAST_XBAR_CHUNK >> (4 * (cap / 2))) & 15) > 0 ? (int)((MPCX_FAST_XBAR_CHUNK >> (4 * (cap / 2))) & 15) : 1; }
+constexpr bool fast_class_bit(unsigned mask, int cap, int chunks) { return chunks <= MPCX_FAST_XBAR_CHUNKS && ((mask >> (cap / 2)) & 1u) != 0; }
 // between the stages of the pipelined update: the instruction scheduler moves nothing across (a batch's loads stay ahead of the wait for the batch before it)
 #ifndef MPCX_FAST_STAGE
 #define MPCX_FAST_STAGE() __builtin_amdgcn_sched_barrier(0)
@@ -126,7 +158,7 @@ __device__ __forceinline__ double wave_max_dpp(double v)
 #define MPCX_PROF_PASS
 #endif
 
-template <int CAP, int NLO, int CPZ, int CPG>
+template <int CAP, int NLO, int CPZ, int CPG, bool XB = false, bool XL = false>
 __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const int ldz, const int na, const int lane_in,
                                             const int *wsidx, const double *wsb, const double *t0s, double *lam,
                                             const unsigned (&offz)[CPZ], const unsigned (&offg)[CPG],
@@ -183,26 +215,80 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
     double mydinv = 1.0;
     unsigned long long dep = 0ull;
     // Gauss-Jordan on [S | y], lane i = row i; a failed pivot test is recorded and looked at once, after the loop
+    // (the step number is a template argument: the crossbar's lane is an immediate of the instruction)
+    auto gj_step = [&]<int K>() {
+        dep |= __ballot(!(Sr[K] > pthr)) & (1ull << K);       // lane K's verdict on its pivot
+        // the pivot itself stays a scalar read in both forms: its reciprocal chain starts at once and runs while the crossbar answers
+        const double rinv = pivot_rcp(readlane_d(Sr[K], K));
+        if constexpr (XB) {
+            // Round 10: the pivot row and the right-hand side through the crossbar.  The step's entries -- columns K + 1 .. CAP - 1, then y -- are consumed
+            // in chunks of XCH, chunk c + 1 requested before chunk c's FMAs: a broadcast value is a pair of VGPRs where v_readlane's was a pair of SGPRs,
+            // and a whole row in flight beside the rows of Y requested ahead spills (MPCX_FAST_XBAR_CHUNK).  The requests run with every lane active --
+            // lane K is the source, and an inactive lane reads as 0 -- so each chunk's FMAs are masked on their own (two scalar instructions per chunk).
+            // The crossbar broadcasts within 32 lanes.  The rows live in lanes 0..15, which receive lane K's values as v_readlane delivered them.  Lanes
+            // 32..63 receive lane 32 + K's instead: a row of the padding, all zero and never a pivot row, so their own m is 0 x rinv and their rows stay
+            // zero (or turn NaN where a pivot is not a positive finite number, as the padding in lanes 16..31 does and did: the dep test ends that solve).
+            // Nothing reads those lanes: the ballot keeps bit K < 16 only, lam[] is written by the lanes below CAP, and the update takes no lane's y.
+            constexpr int NE = CAP - K, XCH = fast_xbar_chunk(CAP), NC = (NE + XCH - 1) / XCH;
+            double pv[2][XCH];
+            auto request = [&](const int c) {
 #pragma unroll
-    for (int k = 0; k < CAP; ++k) {
-        dep |= __ballot(!(Sr[k] > pthr)) & (1ull << k);       // lane k's verdict on its pivot
-        const double rinv = pivot_rcp(readlane_d(Sr[k], k));
-        double pj[CAP];
+                for (int u = 0; u < XCH; ++u) {
+                    const int j = K + 1 + c * XCH + u;
+                    if (j <= CAP) pv[c & 1][u] = swizzle_bcast_d<K>(j < CAP ? Sr[j < CAP ? j : 0] : y);
+                }
+            };
+            request(0);
+            if (lane == K) mydinv = rinv;
+            asm volatile("" : "+v"(mydinv));       // taken here: sunk to the loop's end, the selects keep every step's mask lane == K alive (spilled SGPRs)
+            const double m = Sr[K] * rinv;         // (lane K's is not used)
 #pragma unroll
-        for (int j = k + 1; j < CAP; ++j) pj[j] = readlane_d(Sr[j], k);
-        const double py = readlane_d(y, k);
-        if (lane == k) mydinv = rinv;
-        else {
-            const double m = Sr[k] * rinv;
+            for (int c = 0; c < NC; ++c) {
+                if (c + 1 < NC) request(c + 1);
+                if (lane != K) {
 #pragma unroll
-            for (int j = k + 1; j < CAP; ++j) Sr[j] = fma(-m, pj[j], Sr[j]);
-            y = fma(-m, py, y);
+                    for (int u = 0; u < XCH; ++u) {
+                        const int j = K + 1 + c * XCH + u;
+                        if (j < CAP) Sr[j] = fma(-m, pv[c & 1][u], Sr[j]);
+                        else if (j == CAP) y = fma(-m, pv[c & 1][u], y);
+                    }
+                }
+            }
+        } else {
+            double pj[CAP];
+#pragma unroll
+            for (int j = K + 1; j < CAP; ++j) pj[j] = readlane_d(Sr[j], K);
+            const double py = readlane_d(y, K);
+            if (lane == K) mydinv = rinv;
+            else {
+                const double m = Sr[K] * rinv;
+#pragma unroll
+                for (int j = K + 1; j < CAP; ++j) Sr[j] = fma(-m, pj[j], Sr[j]);
+                y = fma(-m, py, y);
+            }
         }
-    }
+    };
+    [&]<int... Ks>(std::integer_sequence<int, Ks...>) { (gj_step.template operator()<Ks>(), ...); }(std::make_integer_sequence<int, CAP>{});
     MPCX_LAP(2);                                   // 2: elimination
     if (dep != 0ull) return (int)__builtin_ctzll(dep);
     y *= mydinv;                                   // lanes >= na: 0
-    if (real) lam[lane] = y;
+    // XL: the update reads the multipliers back from here, a pair per read, so the positions from na up to CAP hold their lanes' exact +0 too (the verify
+    // phase looks up positions below na or the spare slot, as before)
+    if (XL ? lane < CAP : real) lam[lane] = y;
+    // wave-uniform addresses, two multipliers per 16-byte read.  The reads travel with the rows of Y they multiply: the first PF rows' here, next to t0, a later
+    // batch's with the batch's loads (all CAP of them at once, live beside three batches of rows, spill: profiles/r10_resource_usage_lmpc.txt)
+    auto lam_pair = [&](const int a, double (&l2)[2]) {
+        const double2 v = *reinterpret_cast<const double2 *>(lam + a);
+        l2[0] = v.x; l2[1] = v.y;
+    };
+    constexpr int NLP = XL && PF > 0 ? PF / 2 : 1;
+    double lamp[NLP][2];
+    if constexpr (XL) {
+        static_assert(CAP % 2 == 0 && PF % 2 == 0 && kFastCap % 2 == 0, "multipliers are read back in pairs");
+        wave_sync();                               // the multipliers are written by other lanes
+#pragma unroll
+        for (int p = 0; p < PF / 2; ++p) lam_pair(2 * p, lamp[p]);
+    }
     // w = t0 - Y[:, A] lambda
 #pragma unroll
     for (int c = 0; c < CPZ; ++c) {
@@ -216,8 +302,9 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
     }
     double lm = 0.0;
     // one row of Y applied: rows in ascending working-set position, whichever batch brought them (a row past na is a copy of row 0 with multiplier 0)
-    auto apply_row = [&](const int a, const d2 (&rz)[CPZ], const d2 (&rg)[CPG]) {
-        const double la = readlane_d(y, a);
+    // (lds: the multiplier as read back from lam[a].  The update runs on all 64 lanes, so a 32-lane crossbar broadcast does not serve here)
+    auto apply_row = [&](const int a, const double lds, const d2 (&rz)[CPZ], const d2 (&rg)[CPG]) {
+        const double la = XL ? lds : readlane_d(y, a);
         lm = fmax(lm, fabs(la));
 #pragma unroll
         for (int c = 0; c < CPZ; ++c) { wv[2 * c] = fma(-la, rz[c].x, wv[2 * c]); wv[2 * c + 1] = fma(-la, rz[c].y, wv[2 * c + 1]); }
@@ -226,7 +313,7 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
     };
     if constexpr (CAP == PF) {
 #pragma unroll
-        for (int a = 0; a < PF; ++a) apply_row(a, pz[a], pg[a]);
+        for (int a = 0; a < PF; ++a) apply_row(a, lamp[XL ? a / 2 : 0][a % 2], pz[a], pg[a]);
     } else {
         // round 9: the rows behind the first PF in batches of RB, software-pipelined over NBUF buffers -- the first NBUF batches are requested together,
         // batch k + NBUF as soon as batch k's FMAs are issued (its registers are free then), i.e. always ahead of the wait for batch k + 1.  The requests
@@ -241,8 +328,15 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
         int again = 0;
         asm volatile("" : "+s"(again));
         const int *wsidx_again = wsidx + again;
+        static_assert(!XL || RB % 2 == 0, "multipliers are read back in pairs");
         d2 mz[NBUF][RB][CPZ], mgv[NBUF][RB][CPG];
-        auto request = [&](const int k, d2 (&bz)[RB][CPZ], d2 (&bg)[RB][CPG]) {
+        double ml[NBUF][XL ? RB / 2 : 1][2];
+        auto request = [&](const int k, d2 (&bz)[RB][CPZ], d2 (&bg)[RB][CPG], double (&bl)[XL ? RB / 2 : 1][2]) {
+            if constexpr (XL) {
+#pragma unroll
+                for (int u = 0; u < RB; u += 2)
+                    if (PF + k * RB + u < CAP) lam_pair(PF + k * RB + u, bl[u / 2]);
+            }
 #pragma unroll
             for (int u = 0; u < RB; ++u) {
                 const int cu = PF + k * RB + u < CAP ? PF + k * RB + u : 0;
@@ -254,16 +348,16 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
             }
         };
 #pragma unroll
-        for (int a = 0; a < PF; ++a) apply_row(a, pz[a], pg[a]);
+        for (int a = 0; a < PF; ++a) apply_row(a, lamp[XL ? a / 2 : 0][a % 2], pz[a], pg[a]);
 #pragma unroll
-        for (int k = 0; k < NBUF && k < NB; ++k) request(k, mz[k], mgv[k]);
+        for (int k = 0; k < NBUF && k < NB; ++k) request(k, mz[k], mgv[k], ml[k]);
         MPCX_FAST_STAGE();
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
 #pragma unroll
             for (int u = 0; u < RB; ++u)
-                if (PF + k * RB + u < CAP) apply_row(PF + k * RB + u, mz[k % NBUF][u], mgv[k % NBUF][u]);
-            if (k + NBUF < NB) { request(k + NBUF, mz[k % NBUF], mgv[k % NBUF]); MPCX_FAST_STAGE(); }
+                if (PF + k * RB + u < CAP) apply_row(PF + k * RB + u, ml[k % NBUF][XL ? u / 2 : 0][u % 2], mz[k % NBUF][u], mgv[k % NBUF][u]);
+            if (k + NBUF < NB) { request(k + NBUF, mz[k % NBUF], mgv[k % NBUF], ml[k % NBUF]); MPCX_FAST_STAGE(); }
         }
     }
     lmax = lm;
@@ -833,18 +927,21 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
             MPCX_LAP_WAIT(0);                        // 0: working set built and in LDS
             int dep_at = -1;
             double lmax = 0.0;
+            // (SRC = 1, the kernels that compute the record themselves, keep the scalar reads: at 128 and 168 VGPRs every broadcast value kept in a VGPR spills there)
+            constexpr auto xb = [](int cap) { return SRC != 1 && fast_class_bit(MPCX_FAST_XBAR_CLASSES, cap, CPZ + CPG); };
+            constexpr auto xl = [](int cap) { return SRC != 1 && fast_class_bit(MPCX_FAST_LDSMULT_CLASSES, cap, CPZ + CPG); };
             if (na == 0) {
 #pragma unroll
                 for (int c = 0; c < CPZ; ++c) { const double2 v = *reinterpret_cast<const double2 *>(t0s + 128 * c + 2 * lane); wv[2 * c] = v.x; wv[2 * c + 1] = v.y; }
 #pragma unroll
                 for (int c = 0; c < CPG; ++c) { const double2 v = *reinterpret_cast<const double2 *>(gt0s + 128 * c + 2 * lane); gw[2 * c] = v.x; gw[2 * c + 1] = v.y; }
-            } else if (na <= 4) dep_at = ws_solve_reg<4, 1, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 6) dep_at = ws_solve_reg<6, 5, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 8) dep_at = ws_solve_reg<8, 7, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 10) dep_at = ws_solve_reg<10, 9, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 12) dep_at = ws_solve_reg<12, 11, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 14) dep_at = ws_solve_reg<14, 13, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else dep_at = ws_solve_reg<kFastCap, 15, CPZ, CPG>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            } else if (na <= 4) dep_at = ws_solve_reg<4, 1, CPZ, CPG, xb(4), xl(4)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 6) dep_at = ws_solve_reg<6, 5, CPZ, CPG, xb(6), xl(6)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 8) dep_at = ws_solve_reg<8, 7, CPZ, CPG, xb(8), xl(8)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 10) dep_at = ws_solve_reg<10, 9, CPZ, CPG, xb(10), xl(10)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 12) dep_at = ws_solve_reg<12, 11, CPZ, CPG, xb(12), xl(12)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 14) dep_at = ws_solve_reg<14, 13, CPZ, CPG, xb(14), xl(14)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else dep_at = ws_solve_reg<kFastCap, 15, CPZ, CPG, xb(kFastCap), xl(kFastCap)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
             if (dep_at >= 0) {
                 // linearly dependent working set: drop the offending row and try again
                 const int q = wsidx[dep_at];
