@@ -198,6 +198,41 @@ int mpcx_lmpc_graph_create(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream
 int mpcx_lmpc_graph_launch(mpcx_lmpc_graph_t g, void *stream);
 int mpcx_lmpc_graph_destroy(mpcx_lmpc_graph_t g);
 
+/* The closed loop on the device (no reference counterpart: there the loop is the caller's `for`, examples/quadrotor_ex.cpp).  `ticks`
+ * receding-horizon steps of `batch` instances of one controller -- closed-loop Monte-Carlo runs, or a fleet in lock step: tick k is the batched
+ * solve of mpcx_lmpc_solve_batch (same kernels, same choice of them) on the loop's own current state and last input, followed by one kernel that
+ * steps the plant, x <- A_p x + B_p cmd + Bd_p d_k + w_k (d_k: step 0 of the tick's exogenous input, what the controller's own prediction uses
+ * for its first transition), makes cmd the next tick's last input (as it is, unclipped), logs the tick and prepares the next one.  Both are
+ * captured in a HIP graph; between ticks the host only enqueues graph launches.
+ * References: the modes of mpcx_lmpc_batch mean the same thing at every tick; MPCX_REF_PREVIEW is an array [B x (ticks + ph) x n] of which tick k
+ * sees rows k .. k + ph - 1 as its MPCX_REF_PER_STEP matrix (and the plant row k of dmeas).
+ * Trajectories are tick-major: traj_x [(ticks + 1) x B x nx] (row 0 = x0), traj_u [ticks x B x nu], the optional ones [ticks x B].
+ * A loop uses its handle's one workspace: the concurrency rule of mpcx_lmpc_solve_batch holds unchanged, a run counts as a launch in flight until
+ * the stream has been synchronised.  A setter on the controller invalidates the loop (mpcx_lmpc_loop_run returns MPCX_E_STATE): create a new one. */
+#define MPCX_REF_PREVIEW       3  /* loops only: [B x (ticks + ph) x n], a window of ph rows per tick */
+typedef struct mpcx_lmpc_loop_desc {
+    int batch, ticks;
+    const double *plant_A, *plant_B, *plant_Bd;   /* HOST, column-major [nx x nx], [nx x nu], [nx x ndu]; NULL = the controller's own */
+    const double *x0, *u0;                        /* device, [B x nx], [B x nu]: initial state and last input, read again by every run */
+    const double *yref;  int yref_mode;           /* device, as in mpcx_lmpc_batch, or MPCX_REF_PREVIEW */
+    const double *uref;  int uref_mode;
+    const double *duref; int duref_mode;
+    const double *dmeas; int dmeas_mode;
+    const double *noise;                          /* device, [ticks x B x nx] additive process disturbance w_k, or NULL */
+    int carry_working_set;                        /* 1: tick k's active sets warm-start tick k + 1 (warm_shift = 1); tick 0 is cold */
+    double *traj_x, *traj_u;                      /* device, required */
+    double *traj_cost;                            /* device, optional from here on */
+    int32_t *traj_status, *traj_solver_status, *traj_iterations, *traj_polish_rounds, *traj_active_count;
+} mpcx_lmpc_loop_desc;
+typedef struct mpcx_lmpc_loop *mpcx_lmpc_loop_t;
+/* `stream`: any non-default stream (warm-up solves and the capture, as for mpcx_lmpc_graph_create).  The descriptor's device pointers are baked
+ * into the graph; what they point to may change between runs. */
+int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out);
+/* asynchronous: resets the tick counter, reads x0 / u0 again, enqueues the ticks; the trajectories are valid once `stream` has been synchronised */
+int mpcx_lmpc_loop_run(mpcx_lmpc_loop_t l, void *stream);
+int mpcx_lmpc_loop_destroy(mpcx_lmpc_loop_t l);
+int mpcx_lmpc_loop_desc_size(void);               /* sizeof(mpcx_lmpc_loop_desc), for bindings that mirror the struct */
+
 /* Convenience for callers whose data lives in host memory (the reference's optimize(x0, lastU) is
  * such a caller): stages the inputs to HBM, runs mpcx_lmpc_solve_batch on the default stream, copies
  * the results back and synchronises.  References use the matrices given to the host setters.  Any
@@ -472,6 +507,10 @@ int mpcx_lmpc_debug_force_generic(mpcx_lmpc_t h, int on);
 int mpcx_lmpc_debug_set_rounds(mpcx_lmpc_t h, int rounds0, int check_every);
 /* device buffer [B x 8] of int64 receiving per-instance cycle stamps of the solve kernel (NULL: off) */
 int mpcx_lmpc_debug_set_cycle_buffer(mpcx_lmpc_t h, void *dev_ptr);
+/* one more replay of a loop's tick graph behind a finished run, without the reset: the tick counter stands at `ticks`, so the replay writes no
+ * trajectory, state or counter / the tick counter as it stands on the device, after synchronising the device */
+int mpcx_lmpc_loop_debug_replay(mpcx_lmpc_loop_t l, void *stream);
+int mpcx_lmpc_loop_debug_tick(mpcx_lmpc_loop_t l, int *tick);
 /* the SQP kernel's own convergence test: step length relative to max(1, |z|) and largest constraint defect */
 int mpcx_nlmpc_debug_set_tolerances(mpcx_nlmpc_t h, double tol_step, double tol_con);
 /* which kernel the last solve of a built-in system went through: 0 = nlmpc_sqp (one wavefront per instance, the reduced problem in a

@@ -12,6 +12,7 @@ OK = 0
 E_INVALID, E_UNSUPPORTED, E_DEVICE, E_NUMERIC, E_STATE = -1, -2, -3, -4, -5
 STATUS_SUCCESS, STATUS_MAX_ITERATION, STATUS_INFEASIBLE, STATUS_ERROR, STATUS_UNKNOWN = range(5)
 REF_SHARED, REF_PER_INSTANCE, REF_PER_STEP = 0, 1, 2
+REF_PREVIEW = 3          # loops only: [B x (ticks + ph) x n], a window of ph rows per tick
 
 
 class Dims(C.Structure):
@@ -42,6 +43,21 @@ class Batch(C.Structure):
                 ("warm_active_lower", C.c_void_p), ("warm_active_upper", C.c_void_p), ("warm_shift", C.c_int)]
 
 
+class LoopDesc(C.Structure):
+    """mpcx_lmpc_loop_desc: a closed-loop run on the device (plant_* are host pointers, everything else device pointers)"""
+    _fields_ = [("batch", C.c_int), ("ticks", C.c_int),
+                ("plant_A", C.c_void_p), ("plant_B", C.c_void_p), ("plant_Bd", C.c_void_p),
+                ("x0", C.c_void_p), ("u0", C.c_void_p),
+                ("yref", C.c_void_p), ("yref_mode", C.c_int),
+                ("uref", C.c_void_p), ("uref_mode", C.c_int),
+                ("duref", C.c_void_p), ("duref_mode", C.c_int),
+                ("dmeas", C.c_void_p), ("dmeas_mode", C.c_int),
+                ("noise", C.c_void_p), ("carry_working_set", C.c_int),
+                ("traj_x", C.c_void_p), ("traj_u", C.c_void_p), ("traj_cost", C.c_void_p),
+                ("traj_status", C.c_void_p), ("traj_solver_status", C.c_void_p), ("traj_iterations", C.c_void_p),
+                ("traj_polish_rounds", C.c_void_p), ("traj_active_count", C.c_void_p)]
+
+
 class Info(C.Structure):
     _fields_ = [("n_ref", C.c_int), ("m_ref", C.c_int), ("neq_ref", C.c_int), ("nz", C.c_int), ("mg", C.c_int),
                 ("active_words", C.c_int), ("kernel_variant", C.c_int),
@@ -62,6 +78,7 @@ EXPORTS = [
     "mpcx_lmpc_set_optimizer_parameters", "mpcx_lmpc_set_strict_infeasibility", "mpcx_lmpc_setup", "mpcx_lmpc_solve_batch",
     "mpcx_lmpc_time_solve_batch", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
     "mpcx_lmpc_graph_create", "mpcx_lmpc_graph_launch", "mpcx_lmpc_graph_destroy",
+    "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
     "mpcx_nlmpc_create", "mpcx_nlmpc_destroy", "mpcx_nlmpc_get_dims", "mpcx_nlmpc_evaluate_batch",
     "mpcx_nlparams_default", "mpcx_nlmpc_set_optimizer_parameters", "mpcx_nlmpc_solve_batch", "mpcx_nlmpc_time_solve_batch", "mpcx_discretize_batch",
     "mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice", "mpcx_nlmpc_solve_host",
@@ -72,6 +89,7 @@ EXPORTS = [
     # profiling and testing aids (declared in include/mpcx.h under that heading)
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
     "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer",
+    "mpcx_lmpc_loop_debug_replay", "mpcx_lmpc_loop_debug_tick",
     "mpcx_nlmpc_debug_set_tolerances", "mpcx_nlmpc_debug_last_form", "mpcx_nlmpc_last_form", "mpcx_nlmpc_debug_get_ws", "mpcx_nlmpc_debug_generated_source", "mpcx_nlmpc_debug_compile_source",
 ]
 
@@ -131,6 +149,11 @@ def lib():
         _lib.mpcx_lmpc_graph_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_destroy.argtypes = [C.c_void_p]
+        _lib.mpcx_lmpc_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.mpcx_lmpc_loop_run.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_lmpc_loop_destroy.argtypes = [C.c_void_p]
+        _lib.mpcx_lmpc_loop_debug_replay.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_lmpc_loop_debug_tick.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_get_dims.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_evaluate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
         _lib.mpcx_nlparams_default.restype = None

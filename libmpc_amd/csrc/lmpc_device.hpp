@@ -158,4 +158,31 @@ int lmpc_raise_dynamic_lds(LmpcLdsCache &cache, std::initializer_list<const void
 size_t lmpc_condense_lds(const LmpcDev &m, int *NP_out, int *NQ_out, size_t *big_out = nullptr);
 int lmpc_condense_launch(LmpcDev *models_d, const LmpcDev &m0, int count, void *stream);
 
+// The closed loop around the solve (lmpc_loop.hip): everything the advance kernel touches.  All device pointers; the same struct at every tick.
+struct LmpcLoopDev {
+    int batch, ticks, nx, nu, ndu, ph, aw;        // aw: active-set words per instance
+    int sx, su, sd;                               // LDS row strides of the state, command and exogenous-input tiles (lmpc_loop_plan_lds)
+    const double *plant;                          // [A_p (nx x nx) | B_p (nx x nu) | Bd_p (nx x ndu)], each row-major: read by scalar loads
+    const double *x0, *u0;                        // the caller's initial state and last input (read by lmpc_loop_begin)
+    double *x, *u;                                // the loop's current state and last input: what the solve reads as x0 / u0
+    const double *dmeas; long d_bs, d_tick;       // d_k of instance b, component a: dmeas[b * d_bs + k * d_tick + a]
+    const double *noise;                          // [ticks x B x nx] or null
+    // the solve's results of the tick ...
+    const double *cmd, *cost;
+    const int32_t *status, *solver_status, *iterations, *polish_rounds, *active_count;
+    const uint32_t *active_lower, *active_upper;
+    uint32_t *warm_lower, *warm_upper;            // ... its active sets copied here for the next solve (null: no carry)
+    // ... logged tick-major; traj_x [(ticks + 1) x B x nx], traj_u [ticks x B x nu], the others [ticks x B] or null
+    double *traj_x, *traj_u, *traj_cost;
+    int32_t *traj_status, *traj_solver_status, *traj_iterations, *traj_polish_rounds, *traj_active_count;
+    // preview references (yref, uref, duref, dmeas): source [B x (ticks + ph) x n], staging [B x ph x n]; null source: not a preview array
+    const double *pv_src[4]; double *pv_dst[4]; int pv_n[4];
+    int *state;                                   // [tick, blocks of the running advance kernel that are through]
+};
+void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd
+size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L);
+int lmpc_loop_prepare(const LmpcLoopDev &L);      // once per loop, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
+int lmpc_loop_begin(const LmpcLoopDev &L, void *stream);
+int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
+
 }  // namespace mpcx

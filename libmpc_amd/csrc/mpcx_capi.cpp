@@ -744,6 +744,208 @@ int mpcx_lmpc_graph_destroy(mpcx_lmpc_graph_t g)
     return MPCX_OK;
 }
 
+// ---- the closed loop on the device ------------------------------------------------------------------------------------------------
+// A tick is the handle's ordinary step (mpcx_lmpc_solve_batch on the loop's own x / u buffers) followed by lmpc_loop_advance; both are captured
+// once, as a linear chain on one stream, and a run is "begin kernel, then the tick graph `ticks` times".  Tick 0 solves cold and the later ticks
+// with the carried working sets: the two differ in the descriptor's warm pointers, which a captured launch cannot change, so they are two graphs.
+struct mpcx_lmpc_loop {
+    mpcx_lmpc_t owner = nullptr;
+    int device = 0, ticks = 0;
+    int setups = 0;                              // the owner's count of full set-ups when the loop was made: a later one freed what the graphs point to
+    mpcx::LmpcLoopDev L{};
+    hipGraphExec_t first = nullptr, next = nullptr;   // tick 0; every later tick (null: the same graph serves all)
+    char *slab = nullptr;                        // every private buffer of the loop, one allocation
+    ~mpcx_lmpc_loop()
+    {
+        if (first) (void)hipGraphExecDestroy(first);
+        if (next) (void)hipGraphExecDestroy(next);
+        if (slab) (void)hipFree(slab);
+    }
+};
+
+int mpcx_lmpc_loop_desc_size(void) { return (int)sizeof(mpcx_lmpc_loop_desc); }
+
+// one tick -- the step of descriptor `b`, then the advance kernel -- captured on `s`
+static int capture_tick(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, const mpcx::LmpcLoopDev &L, hipStream_t s, hipGraphExec_t *exec)
+{
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return fail(MPCX_E_DEVICE, "hipStreamBeginCapture failed");
+    int rc = mpcx_lmpc_solve_batch(h, b, s);
+    const int la = rc == MPCX_OK ? mpcx::lmpc_loop_advance(L, s) : 0;
+    hipGraph_t graph = nullptr;
+    const hipError_t ec = hipStreamEndCapture(s, &graph);
+    if (rc == MPCX_OK && la != 0) rc = fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
+    if (rc == MPCX_OK && (ec != hipSuccess || !graph)) rc = fail(MPCX_E_DEVICE, "hipStreamEndCapture failed");
+    if (rc == MPCX_OK && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) != hipSuccess) rc = fail(MPCX_E_DEVICE, "hipGraphInstantiate failed");
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc;
+}
+
+int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
+{
+    CHECK_H(h);
+    if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
+    if (d->batch <= 0) return fail(MPCX_E_INVALID, "a loop needs batch >= 1");
+    if (d->ticks <= 0) return fail(MPCX_E_INVALID, "a loop needs ticks >= 1");
+    if (!d->x0 || !d->u0) return fail(MPCX_E_INVALID, "x0 and u0 are required");
+    if (!d->traj_x || !d->traj_u) return fail(MPCX_E_INVALID, "traj_x and traj_u are required");
+    const mpcx_dims &dm = h->ctl.d;
+    const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
+    const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode};
+    const int ref_n[4] = {dm.ny, dm.nu, dm.nu, dm.ndu};
+    static const char *const ref_name[4] = {"yref", "uref", "duref", "dmeas"};
+    for (int a = 0; a < 4; ++a) {
+        if (ref_m[a] < MPCX_REF_SHARED || ref_m[a] > MPCX_REF_PREVIEW) return fail(MPCX_E_INVALID, std::string(ref_name[a]) + ": unknown reference mode");
+        if (ref_m[a] != MPCX_REF_SHARED && !ref_p[a]) return fail(MPCX_E_INVALID, std::string(ref_name[a]) + ": array missing for a non-shared mode");
+    }
+    if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
+    if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
+    if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
+    int rc = mpcx_lmpc_setup(h);
+    if (rc != MPCX_OK) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+
+    std::unique_ptr<mpcx_lmpc_loop> l(new mpcx_lmpc_loop);
+    l->owner = h; l->device = h->device; l->ticks = d->ticks; l->setups = h->n_full_setups;
+    mpcx::LmpcLoopDev &L = l->L;
+    const size_t B = (size_t)d->batch, aw = (size_t)h->dev.active_words;
+    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw;
+    mpcx::lmpc_loop_plan_lds(L);
+
+    // the slab: offsets first, pointers once it is allocated
+    size_t total = 0;
+    auto take = [&](size_t bytes) { const size_t at = total; total = (total + bytes + 255) / 256 * 256; return at; };
+    const size_t plant_len = (size_t)dm.nx * (dm.nx + dm.nu + dm.ndu);
+    const size_t o_plant = take(plant_len * sizeof(double)), o_x = take(B * dm.nx * sizeof(double)), o_u = take(B * dm.nu * sizeof(double));
+    const size_t o_cmd = take(B * dm.nu * sizeof(double)), o_cost = take(B * sizeof(double)), o_int = take(6 * B * sizeof(int32_t));
+    const size_t o_act = take(4 * B * aw * sizeof(uint32_t)), o_state = take(2 * sizeof(int));
+    size_t o_pv[4] = {0, 0, 0, 0};
+    for (int a = 0; a < 4; ++a)
+        if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
+    if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
+    if (hipMemset(l->slab, 0, total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
+    char *base = l->slab;
+    auto dp = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+
+    {   // the plant, row-major per matrix (the setters' and the descriptor's matrices are column-major)
+        const auto &c = h->ctl;
+        const double *Ah = d->plant_A ? d->plant_A : c.A.a.data(), *Bh = d->plant_B ? d->plant_B : c.B.a.data();
+        const double *Dh = d->plant_Bd ? d->plant_Bd : c.Bd.a.data();
+        std::vector<double> P(plant_len ? plant_len : 1);
+        double *pa = P.data(), *pb = pa + (size_t)dm.nx * dm.nx, *pd = pb + (size_t)dm.nx * dm.nu;
+        for (int i = 0; i < dm.nx; ++i) {
+            for (int j = 0; j < dm.nx; ++j) pa[(size_t)i * dm.nx + j] = Ah[(size_t)j * dm.nx + i];
+            for (int j = 0; j < dm.nu; ++j) pb[(size_t)i * dm.nu + j] = Bh[(size_t)j * dm.nx + i];
+            for (int j = 0; j < dm.ndu; ++j) pd[(size_t)i * dm.ndu + j] = Dh[(size_t)j * dm.nx + i];
+        }
+        if (hipMemcpy(base + o_plant, P.data(), plant_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the plant failed");
+    }
+    L.plant = dp(o_plant); L.x0 = d->x0; L.u0 = d->u0; L.x = dp(o_x); L.u = dp(o_u);
+    L.noise = d->noise;
+    int32_t *ib = reinterpret_cast<int32_t *>(base + o_int);
+    uint32_t *ab = reinterpret_cast<uint32_t *>(base + o_act);
+    L.cmd = dp(o_cmd); L.cost = dp(o_cost);
+    L.status = ib; L.solver_status = ib + B; L.iterations = ib + 3 * B; L.polish_rounds = ib + 4 * B; L.active_count = ib + 5 * B;
+    L.active_lower = ab; L.active_upper = ab + B * aw;
+    if (d->carry_working_set) { L.warm_lower = ab + 2 * B * aw; L.warm_upper = ab + 3 * B * aw; }
+    L.traj_x = d->traj_x; L.traj_u = d->traj_u; L.traj_cost = d->traj_cost;
+    L.traj_status = d->traj_status; L.traj_solver_status = d->traj_solver_status; L.traj_iterations = d->traj_iterations;
+    L.traj_polish_rounds = d->traj_polish_rounds; L.traj_active_count = d->traj_active_count;
+    L.state = reinterpret_cast<int *>(base + o_state);
+
+    // the step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step
+    mpcx_lmpc_batch cold{};
+    cold.batch = d->batch; cold.x0 = L.x; cold.u0 = L.u;
+    const double *sp[4]; int sm[4];
+    for (int a = 0; a < 4; ++a) {
+        sp[a] = ref_p[a]; sm[a] = ref_m[a];
+        if (ref_m[a] != MPCX_REF_PREVIEW) continue;
+        if (ref_n[a] == 0) { sp[a] = nullptr; sm[a] = MPCX_REF_SHARED; continue; }      // (no exogenous inputs: nothing to preview)
+        L.pv_src[a] = ref_p[a]; L.pv_dst[a] = dp(o_pv[a]); L.pv_n[a] = ref_n[a];
+        sp[a] = L.pv_dst[a]; sm[a] = MPCX_REF_PER_STEP;
+    }
+    cold.yref = sp[0]; cold.yref_mode = sm[0]; cold.uref = sp[1]; cold.uref_mode = sm[1];
+    cold.duref = sp[2]; cold.duref_mode = sm[2]; cold.dmeas = sp[3]; cold.dmeas_mode = sm[3];
+    cold.cmd = dp(o_cmd); cold.cost = dp(o_cost);
+    cold.status = ib; cold.solver_status = ib + B; cold.is_feasible = ib + 2 * B; cold.iterations = ib + 3 * B;
+    cold.polish_rounds = ib + 4 * B; cold.active_count = ib + 5 * B;
+    if (d->carry_working_set) { cold.active_lower = ab; cold.active_upper = ab + B * aw; }
+    mpcx_lmpc_batch warm = cold;
+    warm.warm_active_lower = L.warm_lower; warm.warm_active_upper = L.warm_upper; warm.warm_shift = 1;
+    const bool two = d->carry_working_set && d->ticks > 1;
+
+    // d_k, the sample that drives the plant: step 0 of the tick's exogenous input in whichever layout it has
+    if (dm.ndu > 0) {
+        switch (d->dmeas_mode) {
+        case MPCX_REF_SHARED: L.dmeas = h->dev.dmeas_s; break;
+        case MPCX_REF_PER_INSTANCE: L.dmeas = d->dmeas; L.d_bs = dm.ndu; break;
+        case MPCX_REF_PER_STEP: L.dmeas = d->dmeas; L.d_bs = (long)dm.ph * dm.ndu; break;
+        default: L.dmeas = d->dmeas; L.d_bs = (long)(d->ticks + dm.ph) * dm.ndu; L.d_tick = dm.ndu; break;
+        }
+    }
+
+    const int pr = mpcx::lmpc_loop_prepare(L);
+    if (pr != 0) return pr == -2 ? fail(MPCX_E_UNSUPPORTED, "the advance kernel's tiles exceed a compute unit's LDS") : fail(MPCX_E_DEVICE, "hipFuncSetAttribute failed");
+    // one plain pass first, as mpcx_lmpc_graph_create does: it sizes the workspace and configures the kernels, none of which can be captured
+    if (mpcx::lmpc_loop_begin(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    rc = mpcx_lmpc_solve_batch(h, &cold, s);
+    if (rc == MPCX_OK && mpcx::lmpc_loop_advance(L, s) != 0) rc = fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
+    if (rc == MPCX_OK && two) rc = mpcx_lmpc_solve_batch(h, &warm, s);
+    if (rc != MPCX_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(MPCX_E_DEVICE, "the warm-up ticks failed");
+    rc = capture_tick(h, &cold, L, s, &l->first);
+    if (rc == MPCX_OK && two) rc = capture_tick(h, &warm, L, s, &l->next);
+    if (rc != MPCX_OK) return rc;
+    *out = l.release();
+    return MPCX_OK;
+}
+
+static int loop_usable(mpcx_lmpc_loop_t l)
+{
+    if (!l || !l->first) return fail(MPCX_E_INVALID, "null loop");
+    const mpcx_lmpc_t h = l->owner;
+    if (h->dirty || h->refs_dirty || h->n_full_setups != l->setups)
+        return fail(MPCX_E_STATE, "the controller changed since the loop was created: create a new loop");
+    if (hipSetDevice(l->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_loop_run(mpcx_lmpc_loop_t l, void *stream)
+{
+    int rc = loop_usable(l);
+    if (rc != MPCX_OK) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (mpcx::lmpc_loop_begin(l->L, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    for (int k = 0; k < l->ticks; ++k)
+        if (hipGraphLaunch(k > 0 && l->next ? l->next : l->first, s) != hipSuccess) return fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_loop_debug_replay(mpcx_lmpc_loop_t l, void *stream)
+{
+    int rc = loop_usable(l);
+    if (rc != MPCX_OK) return rc;
+    if (hipGraphLaunch(l->next ? l->next : l->first, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_loop_debug_tick(mpcx_lmpc_loop_t l, int *tick)
+{
+    if (!l || !tick) return fail(MPCX_E_INVALID, "null argument");
+    if (hipSetDevice(l->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(tick, l->L.state, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(MPCX_E_DEVICE, "reading the tick counter failed");
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_loop_destroy(mpcx_lmpc_loop_t l)
+{
+    if (!l) return MPCX_OK;
+    (void)hipSetDevice(l->device);
+    delete l;
+    return MPCX_OK;
+}
+
 int mpcx_lmpc_solve_host(mpcx_lmpc_t h, int batch, const double *x0, const double *u0,
                          double *cmd, double *cost, int32_t *status, int32_t *solver_status, int32_t *is_feasible,
                          double *seq_state, double *seq_output, double *seq_input)

@@ -119,6 +119,29 @@ class BatchResult:
     active_count: "object" = None
 
 
+@dataclass
+class ClosedLoopResult:
+    """A closed-loop run on the device (LMPC.simulate), tick-major device tensors: x [ticks+1, B, nx] (row 0 = the initial
+    state), u [ticks, B, nu], the others [ticks, B]."""
+    x: "object"
+    u: "object"
+    cost: "object"
+    status: "object"
+    solver_status: "object"
+    iterations: "object"
+    polish_rounds: "object"
+    active_count: "object"
+
+
+@dataclass
+class Loop:
+    """a loop made by LMPC.make_loop: the native handle, the result whose tensors every run fills, and the tensors the graph points at"""
+    handle: "object"
+    result: ClosedLoopResult
+    ticks: int
+    keep: tuple = ()
+
+
 def _cm(a, rows, cols):
     """column-major float64 host copy with a shape check"""
     a = np.asarray(a, dtype=np.float64)
@@ -425,6 +448,107 @@ class LMPC:
 
     def destroy_graph(self, graph):
         check(self._lib.mpcx_lmpc_graph_destroy(graph))
+
+    # -- the closed loop on the device (mpcx_lmpc_loop_*) ----------------------------------------------------------------
+    def _loop_ref(self, torch, dev, a, B, n, ticks, preview):
+        """a loop's reference: None -> shared; [B,n] -> per instance; [B,ph,n] -> per step, the same at every tick; with
+        preview=True a 3-D array is [B, ticks+ph, n] and tick k sees rows k .. k+ph-1"""
+        if a is None:
+            return None, _capi.REF_SHARED
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(t.shape) == (B, n):
+            return t, _capi.REF_PER_INSTANCE
+        if preview and tuple(t.shape) == (B, ticks + self.ph, n):
+            return t, _capi.REF_PREVIEW
+        if not preview and tuple(t.shape) == (B, self.ph, n):
+            return t, _capi.REF_PER_STEP
+        want = f"[B,{ticks + self.ph},{n}] (preview)" if preview else f"[B,{self.ph},{n}]"
+        raise ValueError(f"reference must be [B,{n}] or {want}, got {tuple(t.shape)}")
+
+    def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
+                  noise=None, warm=True, stream=None) -> Loop:
+        """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by
+        the plant step x <- A_p x + B_p cmd + Bd_p d_k + w_k on the device, with no host work in between.
+
+        plant: None (the controller's own A, B, Bd) or (A_p, B_p) / (A_p, B_p, Bd_p), None entries meaning the controller's;
+        noise: [ticks, B, nx] additive process disturbance the controller does not know about; warm: carry each tick's
+        working set into the next tick's solve (tick 0 is cold); preview: 3-D references are [B, ticks+ph, n] windows.
+        x0 / lastU are read again by every run_loop: tensors given here can be refilled in place (Loop.keep[0], [1])."""
+        torch, dev = self._torch()
+        ticks = int(ticks)
+        x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
+        B = int(x0t.shape[0])
+        x0 = self._dev(torch, dev, x0, (B, self.nx))
+        u0 = self._dev(torch, dev, lastU, (B, self.nu))
+        refs = [self._loop_ref(torch, dev, a, B, n, ticks, preview)
+                for a, n in ((yref, self.ny), (uref, self.nu), (duref, self.nu), (dmeas, self.ndu))]
+        w = self._dev(torch, dev, noise, (ticks, B, self.nx))
+        f64, i32 = torch.float64, torch.int32
+        T = max(ticks, 0)
+        res = ClosedLoopResult(
+            x=torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev), u=torch.zeros((T, B, self.nu), dtype=f64, device=dev),
+            cost=torch.zeros((T, B), dtype=f64, device=dev), status=torch.zeros((T, B), dtype=i32, device=dev),
+            solver_status=torch.zeros((T, B), dtype=i32, device=dev), iterations=torch.zeros((T, B), dtype=i32, device=dev),
+            polish_rounds=torch.zeros((T, B), dtype=i32, device=dev), active_count=torch.zeros((T, B), dtype=i32, device=dev))
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        d = _capi.LoopDesc()
+        d.batch, d.ticks = B, ticks
+        mats = []
+        if plant is not None:
+            plant = tuple(plant) + (None,) * (3 - len(plant))
+            for name, m, cols in zip(("plant_A", "plant_B", "plant_Bd"), plant, (self.nx, self.nu, self.ndu)):
+                if m is not None and cols > 0:
+                    mats.append(_cm(m, self.nx, cols))
+                    setattr(d, name, mats[-1].ctypes.data)
+        d.x0, d.u0 = ptr(x0), ptr(u0)
+        (yr, d.yref_mode), (ur, d.uref_mode), (dr, d.duref_mode), (de, d.dmeas_mode) = refs
+        d.yref, d.uref, d.duref, d.dmeas = ptr(yr), ptr(ur), ptr(dr), ptr(de)
+        d.noise = ptr(w)
+        d.carry_working_set = int(bool(warm))
+        d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
+        d.traj_status, d.traj_solver_status, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.iterations)
+        d.traj_polish_rounds, d.traj_active_count = ptr(res.polish_rounds), ptr(res.active_count)
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else torch.cuda.Stream(device=dev)
+        if s.cuda_stream == 0:
+            raise ValueError("a loop is captured on a non-default stream")
+        s.wait_stream(cur)                      # the tensors above were filled on the current stream
+        h = C.c_void_p()
+        check(self._lib.mpcx_lmpc_loop_create(self._h, C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        cur.wait_stream(s)
+        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s))
+
+    def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
+        """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
+        uses the controller's one workspace, like `launch`: one launch or run of a controller in flight at a time."""
+        torch, _ = self._torch()
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+        check(self._lib.mpcx_lmpc_loop_run(loop.handle, C.c_void_p(s.cuda_stream)))
+        return loop.result
+
+    def destroy_loop(self, loop: Loop):
+        if loop.handle:
+            check(self._lib.mpcx_lmpc_loop_destroy(loop.handle))
+            loop.handle = None
+
+    def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
+                 noise=None, warm=True, stream=None) -> ClosedLoopResult:
+        """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
+        torch, _ = self._torch()
+        loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm)
+        try:
+            self.run_loop(loop, stream)
+            (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+        finally:
+            self.destroy_loop(loop)
+        return loop.result
 
     def time_launches(self, batch, repeats, stream=None):
         """Mean kernel time (ms) over `repeats` launches, HIP events on the launch stream."""

@@ -1,6 +1,8 @@
 """Receding-horizon loop on the device: B quadrotor controllers, each tick = one batched solve +
 one plant step x+ = A x + B u (the closed loop of examples/quadrotor_ex.cpp run for a batch), with and without the
-warm start that carries the working set from tick to tick.  Usage: python tools/closed_loop.py [batch] [ticks]"""
+warm start that carries the working set from tick to tick.  Three legs: the loop driven from the host (optimizeBatch and two
+torch matmuls per tick) and the device loop (LMPC.make_loop / run_loop: the plant step is a kernel, a tick is a graph replay),
+run alternately; each line gives both legs' ms per tick (median, min, max), polish rounds and solved fraction.  Usage: python tools/closed_loop.py [batch] [ticks] [repeats]"""
 import json
 import sys
 import time
@@ -33,9 +35,45 @@ def run(B, ticks, warm):
                 mean_rounds=float(rounds) / ticks, solved=float((r.status == 0).float().mean()))
 
 
+def make_device(B, ticks, warm):
+    """the device loop of the same run, ready to be timed: (controller, loop)"""
+    c = quadrotor_lmpc(20, device=0)
+    x0, u0, yref = quadrotor_batch(B)
+    return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm)
+
+
+def run_device(c, loop):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = c.run_loop(loop)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    B, ticks = res.u.shape[1], loop.ticks
+    return dict(device_loop=True, batch=B, ticks=ticks, solves_per_s=B * ticks / dt, ms_per_tick=dt / ticks * 1e3,
+                mean_rounds=float(res.polish_rounds.float().mean()), solved=float((res.status[-1] == 0).float().mean()))
+
+
+def median_spread(v):
+    v = sorted(v)
+    return v[len(v) // 2], v[0], v[-1]
+
+
 if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 100
+    repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
     run(B, 5, True)
     for w in (False, True):
-        print(json.dumps(run(B, ticks, w)))
+        c, loop = make_device(B, ticks, w)
+        run_device(c, loop)                                   # warm-up of both legs (the host leg builds its controller anew each time)
+        run(B, ticks, w)
+        host, dev = [], []
+        for _ in range(repeats):                              # alternating, so that whatever else the machine does hits both alike
+            host.append(run(B, ticks, w)); dev.append(run_device(c, loop))
+        hm, hlo, hhi = median_spread([r["ms_per_tick"] for r in host])
+        dm, dlo, dhi = median_spread([r["ms_per_tick"] for r in dev])
+        print(json.dumps(dict(warm=w, batch=B, ticks=ticks, repeats=repeats,
+                              host_ms_per_tick=dict(median=hm, min=hlo, max=hhi), device_ms_per_tick=dict(median=dm, min=dlo, max=dhi),
+                              host_mean_rounds=host[-1]["mean_rounds"], device_mean_rounds=dev[-1]["mean_rounds"],
+                              host_solved=host[-1]["solved"], device_solved=dev[-1]["solved"])))
+        c.destroy_loop(loop)
