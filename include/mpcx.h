@@ -208,7 +208,10 @@ int mpcx_lmpc_graph_destroy(mpcx_lmpc_graph_t g);
  * sees rows k .. k + ph - 1 as its MPCX_REF_PER_STEP matrix (and the plant row k of dmeas).
  * Trajectories are tick-major: traj_x [(ticks + 1) x B x nx] (row 0 = x0), traj_u [ticks x B x nu], the optional ones [ticks x B].
  * A loop uses its handle's one workspace: the concurrency rule of mpcx_lmpc_solve_batch holds unchanged, a run counts as a launch in flight until
- * the stream has been synchronised.  A setter on the controller invalidates the loop (mpcx_lmpc_loop_run returns MPCX_E_STATE): create a new one. */
+ * the stream has been synchronised.  A setter on the controller invalidates the loop (mpcx_lmpc_loop_run returns MPCX_E_STATE): create a new one.
+ * The plant: the controller's own model, one other plant for the whole batch (plant_A / _B / _Bd), or a plant per instance (plant_batch, a
+ * Monte-Carlo run over B plants); the last goes through a second advance kernel whose lanes are (instance, state row) pairs and which agrees bit
+ * for bit with the first on equal plants.  plant_batch is a device array read at the head of every run, like x0 / u0: refill it in place. */
 #define MPCX_REF_PREVIEW       3  /* loops only: [B x (ticks + ph) x n], a window of ph rows per tick */
 typedef struct mpcx_lmpc_loop_desc {
     int batch, ticks;
@@ -223,6 +226,8 @@ typedef struct mpcx_lmpc_loop_desc {
     double *traj_x, *traj_u;                      /* device, required */
     double *traj_cost;                            /* device, optional from here on */
     int32_t *traj_status, *traj_solver_status, *traj_iterations, *traj_polish_rounds, *traj_active_count;
+    const double *plant_batch;                    /* device, [B x nx (nx + nu + ndu)]: A_b | B_b | Bd_b per instance, each column-major, read again by
+                                                     every run; NULL = one plant for the batch.  Excludes plant_A / plant_B / plant_Bd */
 } mpcx_lmpc_loop_desc;
 typedef struct mpcx_lmpc_loop *mpcx_lmpc_loop_t;
 /* `stream`: any non-default stream (warm-up solves and the capture, as for mpcx_lmpc_graph_create).  The descriptor's device pointers are baked
@@ -477,6 +482,15 @@ int mpcx_lmpc_hetero_get_info(mpcx_lmpc_hetero_t f, int *count, int *active_word
 int mpcx_lmpc_hetero_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream);
 int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream,
                                       int repeats, float *ms_mean);
+/* The closed loop of a bank: a tick is mpcx_lmpc_hetero_solve_batch on the loop's own buffers followed by the advance kernel, captured as for a
+ * controller (two graphs with carry_working_set).  The loop is the type mpcx_lmpc_loop_create returns: mpcx_lmpc_loop_run, _destroy, _debug_replay
+ * and _debug_tick serve both.  The descriptor's rules are mpcx_lmpc_loop_create's; without a model_index the batch must be the bank.  model_index
+ * (device, [B] or NULL) is baked into the graph like the descriptor's pointers.  The plant: plant_batch if given; else plant_A, plant_B and
+ * plant_Bd (all of them: a bank has no one model to complete a partial plant with), one plant for all; else each instance's own controller --
+ * its A, B, Bd as the bank holds them -- through the per-instance advance kernel.  dmeas in MPCX_REF_SHARED mode drives each instance's plant
+ * with step 0 of its own controller's exogenous input.  A bank has no setters, so nothing invalidates its loops; destroy a loop BEFORE its bank
+ * (the graphs point into the bank's memory). */
+int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out);
 
 /* Sharding: this handle solves contiguous shards of a batch of `total` instances -- the kernel form is chosen for
  * the whole batch's size, so that a shard's results are bit for bit the rows of the unsharded solve (0 = every call is a whole batch). */

@@ -44,7 +44,7 @@ class Batch(C.Structure):
 
 
 class LoopDesc(C.Structure):
-    """mpcx_lmpc_loop_desc: a closed-loop run on the device (plant_* are host pointers, everything else device pointers)"""
+    """mpcx_lmpc_loop_desc: a closed-loop run on the device (plant_A / _B / _Bd are host pointers, everything else device pointers)"""
     _fields_ = [("batch", C.c_int), ("ticks", C.c_int),
                 ("plant_A", C.c_void_p), ("plant_B", C.c_void_p), ("plant_Bd", C.c_void_p),
                 ("x0", C.c_void_p), ("u0", C.c_void_p),
@@ -55,7 +55,8 @@ class LoopDesc(C.Structure):
                 ("noise", C.c_void_p), ("carry_working_set", C.c_int),
                 ("traj_x", C.c_void_p), ("traj_u", C.c_void_p), ("traj_cost", C.c_void_p),
                 ("traj_status", C.c_void_p), ("traj_solver_status", C.c_void_p), ("traj_iterations", C.c_void_p),
-                ("traj_polish_rounds", C.c_void_p), ("traj_active_count", C.c_void_p)]
+                ("traj_polish_rounds", C.c_void_p), ("traj_active_count", C.c_void_p),
+                ("plant_batch", C.c_void_p)]
 
 
 class Info(C.Structure):
@@ -85,7 +86,7 @@ EXPORTS = [
     "mpcx_nlmpc_create_custom", "mpcx_nlmpc_create_from_source", "mpcx_nlmpc_set_input_scale", "mpcx_nlmpc_set_state_scale",
     "mpcx_comm_get_unique_id", "mpcx_comm_create", "mpcx_comm_destroy", "mpcx_comm_rank", "mpcx_comm_world", "mpcx_allgather_u",
     "mpcx_lmpc_hetero_create", "mpcx_lmpc_hetero_destroy", "mpcx_lmpc_hetero_get_info", "mpcx_lmpc_hetero_solve_batch",
-    "mpcx_lmpc_hetero_time_solve_batch", "mpcx_lmpc_hetero_create_ex", "mpcx_lmpc_hetero_debug_get",
+    "mpcx_lmpc_hetero_time_solve_batch", "mpcx_lmpc_hetero_create_ex", "mpcx_lmpc_hetero_debug_get", "mpcx_lmpc_hetero_loop_create",
     # profiling and testing aids (declared in include/mpcx.h under that heading)
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
     "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer",
@@ -150,6 +151,7 @@ def lib():
         _lib.mpcx_lmpc_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.mpcx_lmpc_hetero_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_loop_run.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_loop_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_loop_debug_replay.argtypes = [C.c_void_p, C.c_void_p]

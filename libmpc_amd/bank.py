@@ -19,7 +19,7 @@ import ctypes as C
 
 from . import _capi
 from ._capi import check
-from .lmpc import LMPC, BatchResult
+from .lmpc import LMPC, BatchResult, ClosedLoopResult, Loop
 
 
 def group_by_model(model, n_models: int):
@@ -113,6 +113,7 @@ class LMPCHetero:
         check(self._lib.mpcx_lmpc_hetero_get_info(self._h, C.byref(n), C.byref(aw), C.byref(mref), C.byref(bpm)))
         self.count, self.active_words, self.m_ref, self.bytes_per_model = n.value, aw.value, mref.value, bpm.value
         self._template = c0
+        self._models = [(c._A, c._B, c._Bd) for c in controllers]        # as given to the setters: what plants=(A, None, None) completes
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -154,11 +155,61 @@ class LMPCHetero:
         return ms.value
 
     def optimizeBatch(self, x0, lastU, model=None, yref=None, uref=None, duref=None, dmeas=None, want_active=False, want_sequence=False,
-                      stream=None) -> BatchResult:
+                      stream=None, warm=None, warm_shift=False) -> BatchResult:
         """x0 [B, nx], lastU [B, nu]; model [B] controller index per instance (None: instance b = controller b); references None
-        (each controller's own) | [B, n] | [B, ph, n]"""
+        (each controller's own) | [B, n] | [B, ph, n]; warm / warm_shift: a previous result's active sets as the first working sets, as
+        LMPC.optimizeBatch takes them"""
         b, res, keep, mi = self.make_batch(x0, lastU, model, yref=yref, uref=uref, duref=duref, dmeas=dmeas, want_active=want_active,
-                                           want_sequence=want_sequence)
+                                           want_sequence=want_sequence, warm=warm, warm_shift=warm_shift)
         self.launch(b, mi, stream)
         res._inputs = keep
         return res
+
+    # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create; the loop itself is LMPC's) -------------------------------
+    _loop_ref, _check_plants, _make_loop, pack_plants = LMPC._loop_ref, LMPC._check_plants, LMPC._make_loop, staticmethod(LMPC.pack_plants)
+    run_loop, destroy_loop = LMPC.run_loop, LMPC.destroy_loop
+
+    def _own_plant(self, B, model=None):
+        """A, B, Bd of each instance's own controller, [B, nx, .] numpy"""
+        idx = np.arange(B) if model is None else np.asarray(model.cpu() if torch.is_tensor(model) else model, dtype=np.int64).reshape(-1)
+        if any(m[0] is None for m in self._models):
+            raise _capi.MpcxError(_capi.E_STATE, "state-space model not set")
+        return tuple(np.stack([m[j] for m in self._models])[idx] for j in range(3))
+
+    def make_loop(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
+                  noise=None, warm=True, stream=None) -> Loop:
+        """LMPC.make_loop for a bank: every tick is the bank's batched solve (instance b by controller model[b]; None: controller b)
+        followed by the plant step.  plant: one plant for all, (A_p, B_p, Bd_p); plants: a plant per instance, (A [B,nx,nx],
+        B [B,nx,nu] | None, Bd | None); a None entry of either, and no plant at all, mean each instance's own controller.  References:
+        None is each controller's own, also for the exogenous input that drives the plant.  Destroy the loop before the bank."""
+        x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
+        B = int(x0t.shape[0])
+        plants = self._check_plants(B, plant, plants)
+        mi = None
+        if model is not None:
+            mi = torch.as_tensor(model).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
+            if mi.numel() != B or (mi.numel() and (int(mi.min()) < 0 or int(mi.max()) >= self.count)):
+                raise ValueError("model: one controller index in [0, %d) per instance" % self.count)
+        if plant is not None:
+            plant = tuple(plant) + (None,) * (3 - len(plant))
+            if any(m is None and cols > 0 for m, cols in zip(plant, (self.nx, self.nu, self.ndu))):
+                # a bank has no one model to complete a partial plant with: the given matrices for every instance, the rest each instance's own
+                plants = tuple(None if m is None else np.broadcast_to(np.asarray(m, dtype=np.float64), (B,) + np.shape(m)) for m in plant)
+                plant = None
+
+        def create(d, s, out):
+            return self._lib.mpcx_lmpc_hetero_loop_create(self._h, d, None if mi is None else C.c_void_p(mi.data_ptr()), s, out)
+        loop = self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi)
+        loop.keep += (mi,)
+        return loop
+
+    def simulate(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
+                 noise=None, warm=True, stream=None) -> ClosedLoopResult:
+        """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
+        loop = self.make_loop(x0, lastU, ticks, model, plant, plants, yref, uref, duref, dmeas, preview, noise, warm)
+        try:
+            self.run_loop(loop, stream)
+            (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+        finally:
+            self.destroy_loop(loop)
+        return loop.result

@@ -163,6 +163,13 @@ struct LmpcLoopDev {
     int batch, ticks, nx, nu, ndu, ph, aw;        // aw: active-set words per instance
     int sx, su, sd;                               // LDS row strides of the state, command and exogenous-input tiles (lmpc_loop_plan_lds)
     const double *plant;                          // [A_p (nx x nx) | B_p (nx x nu) | Bd_p (nx x ndu)], each row-major: read by scalar loads
+    // per-instance plants (pk null: the one plant above)
+    int ipw, sv;                                  // instances per wavefront of the per-instance advance kernel, LDS stride of an instance's [x | cmd | d] (lmpc_loop_plan_lds)
+    double *pk;                                   // lmpc_loop_packed_len doubles, written by lmpc_loop_pack_plants in the order lmpc_loop.hip describes
+    const double *pk_src;                         // the caller's [B x nx (nx + nu + ndu)], A_b | B_b | Bd_b column-major; null: each instance's controller
+    const LmpcDev *models;                        // a bank's model structs and its instance -> controller map (null map: instance b = controller b)
+    const int32_t *model_index;
+    double *d_own;                                // [B x ndu]: step 0 of each controller's own exogenous input (a bank's "shared" mode), or null
     const double *x0, *u0;                        // the caller's initial state and last input (read by lmpc_loop_begin)
     double *x, *u;                                // the loop's current state and last input: what the solve reads as x0 / u0
     const double *dmeas; long d_bs, d_tick;       // d_k of instance b, component a: dmeas[b * d_bs + k * d_tick + a]
@@ -179,10 +186,12 @@ struct LmpcLoopDev {
     const double *pv_src[4]; double *pv_dst[4]; int pv_n[4];
     int *state;                                   // [tick, blocks of the running advance kernel that are through]
 };
-void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd
+void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv
+size_t lmpc_loop_packed_len(const LmpcLoopDev &L);   // doubles of pk (whole tiles)
 size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L);
 int lmpc_loop_prepare(const LmpcLoopDev &L);      // once per loop, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
 int lmpc_loop_begin(const LmpcLoopDev &L, void *stream);
+int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of every run, next to lmpc_loop_begin: fills pk and d_own (no launch when both are null)
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
 
 }  // namespace mpcx

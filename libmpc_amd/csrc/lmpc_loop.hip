@@ -11,6 +11,14 @@
 // address space, i.e. by scalar loads into SGPRs, and feeds the FMAs as a scalar operand.  No register arrays (the dimensions are run-time
 // values), hence no scratch.  The tick number is device state: the kernel's arguments are the same at every tick, so a captured graph of one
 // tick replays unchanged; a replay with the counter at `ticks` returns before its first store.
+//
+// Per-instance plants (a Monte-Carlo run over B plants, a bank whose every controller is its own plant) cannot be scalar operands:
+//   lmpc_loop_pack_plants     head of every run: the plants, from the caller's array or from the bank's model structs, into the order below; a
+//                             bank's "shared" exogenous input (each controller's own) into a [B x ndu] array
+//   lmpc_loop_advance_plants  the same tick with lane <-> (instance, state row): a wavefront holds 64 / nx instances, its lanes accumulate their
+//                             rows' nx + nu + ndu terms in the uniform kernel's order (the two agree bit for bit on equal plants); term j of a
+//                             tile is one contiguous run of the packed array, read by consecutive lanes, the loads of a group of terms in flight
+//                             together; the lane's sum is an element of the tile's run of x and goes straight out
 #include <hip/hip_runtime.h>
 
 #include "lmpc_device.hpp"
@@ -60,17 +68,25 @@ __global__ __launch_bounds__(kTile) void lmpc_loop_begin_kernel(const LmpcLoopDe
     if (blockIdx.x == 0 && tid == 0) { gout(L.state)[0] = 0; gout(L.state)[1] = 0; }
 }
 
-__global__ __launch_bounds__(kTile) void lmpc_loop_advance_kernel(const LmpcLoopDev L)
+// kPlants: a plant per instance.  The tile is then the ipw = 64 / nx instances whose rows fill the wavefront's lanes (from nx = 33 on one instance,
+// a lane taking rows lane, lane + 64, ...; lanes past ipw * nx idle), and the packed coefficients are read as: tile t, term j (the nx columns of
+// A_b, then the nu of B_b, then the ndu of Bd_b), instance q of the tile, row i at ((t * nterms + j) * ipw + q) * nx + i -- a term is one run of
+// ipw * nx doubles of which lane (q, i) reads element q * nx + i, and the terms of a row are one loop.  Sum order per row in both forms: acc = 0,
+// fma over A by ascending column, then B, then Bd, the noise added at the store.
+template <bool kPlants>
+__device__ __forceinline__ void advance_tick(const LmpcLoopDev &L, double *lds)
 {
-    extern __shared__ double lds[];
     const int tid = threadIdx.x;
     const int k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(L.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     if (k >= L.ticks) return;                     // a replay past the run's end: nothing is written
     const int nx = L.nx, nu = L.nu, ndu = L.ndu, B = L.batch;
-    const int sx = L.sx, su = L.su, sd = L.sd;
-    const int b0 = blockIdx.x * kTile;
-    const int nvalid = min(kTile, B - b0);
-    double *xin = lds, *cin = xin + kTile * sx, *din = cin + kTile * su, *xout = din + kTile * sd;
+    // LDS rows: the uniform form keeps a tile of x, of cmd and of d apart; the per-instance form keeps an instance's [x | cmd | d] side by side, the
+    // operands of its terms in the terms' order
+    const int sx = kPlants ? L.sv : L.sx, su = kPlants ? L.sv : L.su, sd = kPlants ? L.sv : L.sd;
+    const int nt = kPlants ? L.ipw : kTile;       // instances of the block's tile
+    const int b0 = blockIdx.x * nt;
+    const int nvalid = min(nt, B - b0);
+    double *xin = lds, *cin = kPlants ? xin + nx : xin + nt * sx, *din = kPlants ? cin + nu : cin + nt * su, *xout = din + nt * sd;
     const size_t xo = (size_t)b0 * nx, uo = (size_t)b0 * nu;
 
     // in: the tile's states, commands and exogenous-input samples, one contiguous run each
@@ -95,34 +111,70 @@ __global__ __launch_bounds__(kTile) void lmpc_loop_advance_kernel(const LmpcLoop
     }
     __syncthreads();
 
-    // the plant step of the lane's instance, row by row of [A_p | B_p | Bd_p] (row-major, the rows of the three side by side per matrix)
-    if (tid < nvalid) {
-        const double LOOP_CAS *Ap = (const double LOOP_CAS *)L.plant;
-        const double LOOP_CAS *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
-        const double *xr = xin + tid * sx, *ur = cin + tid * su, *dr = din + tid * sd;
-        for (int i = 0; i < nx; ++i) {
-            double acc = 0.0;
-#pragma unroll 8
-            for (int j = 0; j < nx; ++j) acc = fma(Ap[i * nx + j], xr[j], acc);
-#pragma unroll 4
-            for (int j = 0; j < nu; ++j) acc = fma(Bp[i * nu + j], ur[j], acc);
-#pragma unroll 2
-            for (int j = 0; j < ndu; ++j) acc = fma(Dp[i * ndu + j], dr[j], acc);
-            xout[tid * sx + i] = acc;
+    if constexpr (kPlants) {
+        // the plant step of the lane's (instance, row): every term one coalesced request of the wavefront, eight of them (then four) in flight
+        // together; the sum is element q * nx + i of the tile's run of x (every read of which the barrier above put ahead of these stores)
+        const int lpi = min(nx, kTile);           // lanes per instance
+        const int q = tid / lpi;
+        if (q < nvalid) {
+            const int nterms = nx + nu + ndu;
+            const size_t width = (size_t)nt * nx;
+            const double LOOP_GAS *P = gin(L.pk) + (size_t)blockIdx.x * nterms * width + q * nx;
+            const double *v = xin + q * sx;
+            double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
+            const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
+            for (int i = tid - q * lpi; i < nx; i += lpi) {
+                const double LOOP_GAS *Pi = P + i;
+                double acc = 0.0;
+                int j = 0;
+#pragma unroll 1
+                for (; j + 8 <= nterms; j += 8) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc = fma(Pi[(j + e) * width], v[j + e], acc);
+                }
+#pragma unroll 1
+                for (; j + 4 <= nterms; j += 4) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = fma(Pi[(j + e) * width], v[j + e], acc);
+                }
+#pragma unroll 1
+                for (; j < nterms; ++j) acc = fma(Pi[j * width], v[j], acc);
+                const size_t at = xo + q * nx + i;
+                if (w) acc += w[at];
+                gout(L.x)[at] = acc;
+                tx[at] = acc;
+            }
         }
-    }
-    __syncthreads();
+    } else {
+        // the plant step of the lane's instance, row by row of [A_p | B_p | Bd_p] (row-major, the rows of the three side by side per matrix)
+        if (tid < nvalid) {
+            const double LOOP_CAS *Ap = (const double LOOP_CAS *)L.plant;
+            const double LOOP_CAS *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
+            const double *xr = xin + tid * sx, *ur = cin + tid * su, *dr = din + tid * sd;
+            for (int i = 0; i < nx; ++i) {
+                double acc = 0.0;
+#pragma unroll 8
+                for (int j = 0; j < nx; ++j) acc = fma(Ap[i * nx + j], xr[j], acc);
+#pragma unroll 4
+                for (int j = 0; j < nu; ++j) acc = fma(Bp[i * nu + j], ur[j], acc);
+#pragma unroll 2
+                for (int j = 0; j < ndu; ++j) acc = fma(Dp[i * ndu + j], dr[j], acc);
+                xout[tid * sx + i] = acc;
+            }
+        }
+        __syncthreads();
 
-    // out: the new state (plus the process disturbance the controller knows nothing about) to the loop's x and to row k + 1 of traj_x
-    {
-        double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
-        const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
-        for (int idx = tid; idx < nvalid * nx; idx += kTile) {
-            const int r = idx / nx, c = idx - r * nx;
-            double v = xout[r * sx + c];
-            if (w) v += w[xo + idx];
-            gout(L.x)[xo + idx] = v;
-            tx[xo + idx] = v;
+        // out: the new state (plus the process disturbance the controller knows nothing about) to the loop's x and to row k + 1 of traj_x
+        {
+            double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
+            const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
+            for (int idx = tid; idx < nvalid * nx; idx += kTile) {
+                const int r = idx / nx, c = idx - r * nx;
+                double v = xout[r * sx + c];
+                if (w) v += w[xo + idx];
+                gout(L.x)[xo + idx] = v;
+                tx[xo + idx] = v;
+            }
         }
     }
     // the tick's row of the per-instance logs
@@ -157,6 +209,56 @@ __global__ __launch_bounds__(kTile) void lmpc_loop_advance_kernel(const LmpcLoop
     }
 }
 
+__global__ __launch_bounds__(kTile) void lmpc_loop_advance_kernel(const LmpcLoopDev L)
+{
+    extern __shared__ double lds[];
+    advance_tick<false>(L, lds);
+}
+
+// (a block is one wavefront and a compute unit sees a few of them: registers are better spent on a group of terms in flight than on occupancy)
+__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) void lmpc_loop_advance_plants_kernel(const LmpcLoopDev L)
+{
+    extern __shared__ double lds[];
+    advance_tick<true>(L, lds);
+}
+
+constexpr int kPackThreads = 256;
+
+// Head of a run: the plants in the advance kernel's order, from the caller's array ([B x nx (nx + nu + ndu)], A_b | B_b | Bd_b column-major: term j
+// of instance b is the run of nx doubles at (b nterms + j) nx) or from the model struct of each instance's controller; the padding of the last
+// tile is zero.  And each controller's own exogenous input, step 0, as the [B x ndu] array the advance kernel addresses per instance.
+__global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_plants_kernel(const LmpcLoopDev L)
+{
+    const int nx = L.nx, nu = L.nu, ndu = L.ndu, B = L.batch, ipw = L.ipw;
+    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
+    if (L.pk) {
+        const size_t nterms = (size_t)(nx + nu + ndu), width = (size_t)ipw * nx, per_tile = nterms * width;
+        const size_t total = (size_t)((B + ipw - 1) / ipw) * per_tile;
+        for (size_t idx = first; idx < total; idx += step) {
+            const size_t t = idx / per_tile, rem = idx - t * per_tile;
+            const int j = (int)(rem / width), qi = (int)(rem - j * width);
+            const int q = qi / nx, i = qi - q * nx;
+            const size_t b = t * ipw + q;
+            double v = 0.0;
+            if (b < (size_t)B) {
+                if (L.pk_src) v = gin(L.pk_src)[(b * nterms + j) * nx + i];
+                else {
+                    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
+                    v = j < nx ? M.A[j * nx + i] : j < nx + nu ? M.B[(j - nx) * nx + i] : M.Bd[(j - nx - nu) * nx + i];
+                }
+            }
+            gout(L.pk)[idx] = v;
+        }
+    }
+    if (L.d_own) {
+        for (size_t idx = first; idx < (size_t)B * ndu; idx += step) {
+            const size_t b = idx / ndu;
+            const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
+            gout(L.d_own)[idx] = M.dmeas_s[idx - b * ndu];
+        }
+    }
+}
+
 inline int odd(int n) { return n | 1; }
 
 }  // namespace
@@ -164,12 +266,16 @@ inline int odd(int n) { return n | 1; }
 void lmpc_loop_plan_lds(LmpcLoopDev &L)
 {
     L.sx = odd(L.nx); L.su = odd(L.nu); L.sd = L.ndu > 0 ? odd(L.ndu) : 0;
+    L.ipw = L.nx < kTile ? kTile / L.nx : 1; L.sv = odd(L.nx + L.nu + L.ndu);
 }
+
+size_t lmpc_loop_packed_len(const LmpcLoopDev &L) { return (size_t)((L.batch + L.ipw - 1) / L.ipw) * (L.nx + L.nu + L.ndu) * L.ipw * L.nx; }
 
 size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L) { return (size_t)kTile * (2 * L.sx + L.su + L.sd) * sizeof(double); }
 
 int lmpc_loop_prepare(const LmpcLoopDev &L)
 {
+    if (L.pk) return 0;                           // the per-instance kernel's tile: [x | cmd | d] of at most 64 instances of 1 state ... one of many
     const size_t bytes = lmpc_loop_lds_bytes(L);
     if (bytes > lmpc_lds_limit()) return -2;
     if (bytes > 48 * 1024 &&
@@ -185,8 +291,25 @@ int lmpc_loop_begin(const LmpcLoopDev &L, void *stream)
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream)
+{
+    if (!L.pk && !L.d_own) return 0;
+    const size_t n = L.pk ? lmpc_loop_packed_len(L) : (size_t)L.batch * L.ndu;
+    size_t blocks = (n + kPackThreads - 1) / kPackThreads;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(lmpc_loop_pack_plants_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream)
 {
+    if (L.pk) {
+        const int tiles = (L.batch + L.ipw - 1) / L.ipw;
+        const size_t lds = (size_t)L.ipw * L.sv * sizeof(double);
+        hipLaunchKernelGGL(lmpc_loop_advance_plants_kernel, dim3(tiles), dim3(kTile), lds, reinterpret_cast<hipStream_t>(stream), L);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     const int blocks = (L.batch + kTile - 1) / kTile;
     hipLaunchKernelGGL(lmpc_loop_advance_kernel, dim3(blocks), dim3(kTile), lmpc_loop_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -745,11 +745,14 @@ int mpcx_lmpc_graph_destroy(mpcx_lmpc_graph_t g)
 }
 
 // ---- the closed loop on the device ------------------------------------------------------------------------------------------------
-// A tick is the handle's ordinary step (mpcx_lmpc_solve_batch on the loop's own x / u buffers) followed by lmpc_loop_advance; both are captured
-// once, as a linear chain on one stream, and a run is "begin kernel, then the tick graph `ticks` times".  Tick 0 solves cold and the later ticks
-// with the carried working sets: the two differ in the descriptor's warm pointers, which a captured launch cannot change, so they are two graphs.
+// A tick is the owner's ordinary step (mpcx_lmpc_solve_batch, or mpcx_lmpc_hetero_solve_batch for a bank, on the loop's own x / u buffers) followed
+// by lmpc_loop_advance; both are captured once, as a linear chain on one stream, and a run is "begin and pack kernels, then the tick graph `ticks`
+// times".  Tick 0 solves cold and the later ticks with the carried working sets: the two differ in the descriptor's warm pointers, which a captured
+// launch cannot change, so they are two graphs.
 struct mpcx_lmpc_loop {
-    mpcx_lmpc_t owner = nullptr;
+    mpcx_lmpc_t owner = nullptr;                 // a controller's loop ...
+    mpcx_lmpc_hetero_t bank = nullptr;           // ... or a bank's, with the caller's instance -> controller map (device array or null)
+    const int32_t *model_index = nullptr;
     int device = 0, ticks = 0;
     int setups = 0;                              // the owner's count of full set-ups when the loop was made: a later one freed what the graphs point to
     mpcx::LmpcLoopDev L{};
@@ -761,16 +764,17 @@ struct mpcx_lmpc_loop {
         if (next) (void)hipGraphExecDestroy(next);
         if (slab) (void)hipFree(slab);
     }
+    int solve(const mpcx_lmpc_batch *b, void *s) const { return owner ? mpcx_lmpc_solve_batch(owner, b, s) : mpcx_lmpc_hetero_solve_batch(bank, b, model_index, s); }
 };
 
 int mpcx_lmpc_loop_desc_size(void) { return (int)sizeof(mpcx_lmpc_loop_desc); }
 
 // one tick -- the step of descriptor `b`, then the advance kernel -- captured on `s`
-static int capture_tick(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, const mpcx::LmpcLoopDev &L, hipStream_t s, hipGraphExec_t *exec)
+static int capture_tick(const mpcx_lmpc_loop &l, const mpcx_lmpc_batch *b, hipStream_t s, hipGraphExec_t *exec)
 {
     if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return fail(MPCX_E_DEVICE, "hipStreamBeginCapture failed");
-    int rc = mpcx_lmpc_solve_batch(h, b, s);
-    const int la = rc == MPCX_OK ? mpcx::lmpc_loop_advance(L, s) : 0;
+    int rc = l.solve(b, s);
+    const int la = rc == MPCX_OK ? mpcx::lmpc_loop_advance(l.L, s) : 0;
     hipGraph_t graph = nullptr;
     const hipError_t ec = hipStreamEndCapture(s, &graph);
     if (rc == MPCX_OK && la != 0) rc = fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
@@ -780,37 +784,44 @@ static int capture_tick(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, const mpcx::Lmp
     return rc;
 }
 
-int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
+// what a descriptor must satisfy whatever it is given to: the checks that need no look at a controller's or a bank's state
+static int check_loop_desc(const mpcx_lmpc_loop_desc *d)
 {
-    CHECK_H(h);
-    if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
     if (d->batch <= 0) return fail(MPCX_E_INVALID, "a loop needs batch >= 1");
     if (d->ticks <= 0) return fail(MPCX_E_INVALID, "a loop needs ticks >= 1");
     if (!d->x0 || !d->u0) return fail(MPCX_E_INVALID, "x0 and u0 are required");
     if (!d->traj_x || !d->traj_u) return fail(MPCX_E_INVALID, "traj_x and traj_u are required");
-    const mpcx_dims &dm = h->ctl.d;
     const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
     const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode};
-    const int ref_n[4] = {dm.ny, dm.nu, dm.nu, dm.ndu};
     static const char *const ref_name[4] = {"yref", "uref", "duref", "dmeas"};
     for (int a = 0; a < 4; ++a) {
         if (ref_m[a] < MPCX_REF_SHARED || ref_m[a] > MPCX_REF_PREVIEW) return fail(MPCX_E_INVALID, std::string(ref_name[a]) + ": unknown reference mode");
         if (ref_m[a] != MPCX_REF_SHARED && !ref_p[a]) return fail(MPCX_E_INVALID, std::string(ref_name[a]) + ": array missing for a non-shared mode");
     }
-    if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
-    if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
-    if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
-    int rc = mpcx_lmpc_setup(h);
-    if (rc != MPCX_OK) return rc;
-    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (d->plant_batch && (d->plant_A || d->plant_B || d->plant_Bd))
+        return fail(MPCX_E_INVALID, "plant_batch (a plant per instance) and plant_A / plant_B / plant_Bd (one plant for the batch) exclude each other");
+    return MPCX_OK;
+}
 
+// The loop of a controller (h) or of a bank (f, model_index), once the descriptor and the owner's state have been checked and the owner is set
+// up on the current device.  dm, active_words: the owner's.
+static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words,
+                      const mpcx_lmpc_loop_desc *d, hipStream_t s, mpcx_lmpc_loop_t *out)
+{
+    const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
+    const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode};
+    const int ref_n[4] = {dm.ny, dm.nu, dm.nu, dm.ndu};
     std::unique_ptr<mpcx_lmpc_loop> l(new mpcx_lmpc_loop);
-    l->owner = h; l->device = h->device; l->ticks = d->ticks; l->setups = h->n_full_setups;
+    l->owner = h; l->bank = f; l->model_index = model_index; l->ticks = d->ticks;
+    if (h) { l->device = h->device; l->setups = h->n_full_setups; } else l->device = f->device;
     mpcx::LmpcLoopDev &L = l->L;
-    const size_t B = (size_t)d->batch, aw = (size_t)h->dev.active_words;
+    const size_t B = (size_t)d->batch, aw = (size_t)active_words;
     L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw;
     mpcx::lmpc_loop_plan_lds(L);
+    // which plant: one per instance (the caller's array; in a bank also the default, each instance's own controller), or one for the batch
+    const bool uniform = d->plant_A || d->plant_B || d->plant_Bd;
+    const bool packed = d->plant_batch || (f && !uniform);
+    const bool own_d = f && dm.ndu > 0 && d->dmeas_mode == MPCX_REF_SHARED;      // a bank's "shared" exogenous input: each controller's own
 
     // the slab: offsets first, pointers once it is allocated
     size_t total = 0;
@@ -822,15 +833,23 @@ int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *str
     size_t o_pv[4] = {0, 0, 0, 0};
     for (int a = 0; a < 4; ++a)
         if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
+    const size_t o_pk = packed ? take(mpcx::lmpc_loop_packed_len(L) * sizeof(double)) : 0;
+    const size_t o_down = own_d ? take(B * dm.ndu * sizeof(double)) : 0;
     if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
     if (hipMemset(l->slab, 0, total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
     char *base = l->slab;
     auto dp = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
 
-    {   // the plant, row-major per matrix (the setters' and the descriptor's matrices are column-major)
-        const auto &c = h->ctl;
-        const double *Ah = d->plant_A ? d->plant_A : c.A.a.data(), *Bh = d->plant_B ? d->plant_B : c.B.a.data();
-        const double *Dh = d->plant_Bd ? d->plant_Bd : c.Bd.a.data();
+    if (packed) {
+        L.pk = dp(o_pk); L.pk_src = d->plant_batch;
+    } else {   // the one plant, row-major per matrix (the setters' and the descriptor's matrices are column-major)
+        const double *Ah = d->plant_A, *Bh = d->plant_B, *Dh = d->plant_Bd;
+        if (h) {
+            const auto &c = h->ctl;
+            if (!Ah) Ah = c.A.a.data();
+            if (!Bh) Bh = c.B.a.data();
+            if (!Dh) Dh = c.Bd.a.data();
+        }
         std::vector<double> P(plant_len ? plant_len : 1);
         double *pa = P.data(), *pb = pa + (size_t)dm.nx * dm.nx, *pd = pb + (size_t)dm.nx * dm.nu;
         for (int i = 0; i < dm.nx; ++i) {
@@ -840,6 +859,7 @@ int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *str
         }
         if (hipMemcpy(base + o_plant, P.data(), plant_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the plant failed");
     }
+    if (f) { L.models = f->models_d; L.model_index = model_index; }
     L.plant = dp(o_plant); L.x0 = d->x0; L.u0 = d->u0; L.x = dp(o_x); L.u = dp(o_u);
     L.noise = d->noise;
     int32_t *ib = reinterpret_cast<int32_t *>(base + o_int);
@@ -877,7 +897,10 @@ int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *str
     // d_k, the sample that drives the plant: step 0 of the tick's exogenous input in whichever layout it has
     if (dm.ndu > 0) {
         switch (d->dmeas_mode) {
-        case MPCX_REF_SHARED: L.dmeas = h->dev.dmeas_s; break;
+        case MPCX_REF_SHARED:
+            if (own_d) { L.d_own = dp(o_down); L.dmeas = L.d_own; L.d_bs = dm.ndu; }
+            else L.dmeas = h->dev.dmeas_s;
+            break;
         case MPCX_REF_PER_INSTANCE: L.dmeas = d->dmeas; L.d_bs = dm.ndu; break;
         case MPCX_REF_PER_STEP: L.dmeas = d->dmeas; L.d_bs = (long)dm.ph * dm.ndu; break;
         default: L.dmeas = d->dmeas; L.d_bs = (long)(d->ticks + dm.ph) * dm.ndu; L.d_tick = dm.ndu; break;
@@ -888,23 +911,53 @@ int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *str
     if (pr != 0) return pr == -2 ? fail(MPCX_E_UNSUPPORTED, "the advance kernel's tiles exceed a compute unit's LDS") : fail(MPCX_E_DEVICE, "hipFuncSetAttribute failed");
     // one plain pass first, as mpcx_lmpc_graph_create does: it sizes the workspace and configures the kernels, none of which can be captured
     if (mpcx::lmpc_loop_begin(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
-    rc = mpcx_lmpc_solve_batch(h, &cold, s);
+    if (mpcx::lmpc_loop_pack_plants(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
+    int rc = l->solve(&cold, s);
     if (rc == MPCX_OK && mpcx::lmpc_loop_advance(L, s) != 0) rc = fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
-    if (rc == MPCX_OK && two) rc = mpcx_lmpc_solve_batch(h, &warm, s);
+    if (rc == MPCX_OK && two) rc = l->solve(&warm, s);
     if (rc != MPCX_OK) return rc;
     if (hipStreamSynchronize(s) != hipSuccess) return fail(MPCX_E_DEVICE, "the warm-up ticks failed");
-    rc = capture_tick(h, &cold, L, s, &l->first);
-    if (rc == MPCX_OK && two) rc = capture_tick(h, &warm, L, s, &l->next);
+    rc = capture_tick(*l, &cold, s, &l->first);
+    if (rc == MPCX_OK && two) rc = capture_tick(*l, &warm, s, &l->next);
     if (rc != MPCX_OK) return rc;
     *out = l.release();
     return MPCX_OK;
 }
 
+int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
+{
+    CHECK_H(h);
+    if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
+    int rc = check_loop_desc(d);
+    if (rc != MPCX_OK) return rc;
+    if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
+    if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
+    if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
+    rc = mpcx_lmpc_setup(h);
+    if (rc != MPCX_OK) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, reinterpret_cast<hipStream_t>(stream), out);
+}
+
+int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
+{
+    if (!f || !d || !out) return fail(MPCX_E_INVALID, "null argument");
+    int rc = check_loop_desc(d);
+    if (rc != MPCX_OK) return rc;
+    if (!model_index && d->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
+    // a bank keeps no host copy of its controllers' models: there is no "the controller's own" to complete a one-for-all plant with
+    if ((d->plant_A || d->plant_B || d->plant_Bd) && (!d->plant_A || !d->plant_B || (f->d.ndu > 0 && !d->plant_Bd)))
+        return fail(MPCX_E_INVALID, "a bank's loop takes plant_A, plant_B and plant_Bd together (or plant_batch, or none: each instance's own controller)");
+    if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, reinterpret_cast<hipStream_t>(stream), out);
+}
+
 static int loop_usable(mpcx_lmpc_loop_t l)
 {
     if (!l || !l->first) return fail(MPCX_E_INVALID, "null loop");
-    const mpcx_lmpc_t h = l->owner;
-    if (h->dirty || h->refs_dirty || h->n_full_setups != l->setups)
+    const mpcx_lmpc_t h = l->owner;              // (a bank has no setters: nothing can have changed)
+    if (h && (h->dirty || h->refs_dirty || h->n_full_setups != l->setups))
         return fail(MPCX_E_STATE, "the controller changed since the loop was created: create a new loop");
     if (hipSetDevice(l->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
     return MPCX_OK;
@@ -916,6 +969,7 @@ int mpcx_lmpc_loop_run(mpcx_lmpc_loop_t l, void *stream)
     if (rc != MPCX_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (mpcx::lmpc_loop_begin(l->L, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    if (mpcx::lmpc_loop_pack_plants(l->L, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
     for (int k = 0; k < l->ticks; ++k)
         if (hipGraphLaunch(k > 0 && l->next ? l->next : l->first, s) != hipSuccess) return fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
     return MPCX_OK;

@@ -135,11 +135,13 @@ class ClosedLoopResult:
 
 @dataclass
 class Loop:
-    """a loop made by LMPC.make_loop: the native handle, the result whose tensors every run fills, and the tensors the graph points at"""
+    """a loop made by LMPC.make_loop / LMPCHetero.make_loop: the native handle, the result whose tensors every run fills, the tensors the graph
+    points at, and (plants=) the per-instance plants as every run reads them, [B, nx (nx+nu+ndu)] in LMPC.pack_plants' layout"""
     handle: "object"
     result: ClosedLoopResult
     ticks: int
     keep: tuple = ()
+    plants: "object" = None
 
 
 def _cm(a, rows, cols):
@@ -178,6 +180,8 @@ class LMPC:
         d = _capi.Dims(self.nx, self.nu, self.ndu, self.ny, self.ph, self.ch)
         self._h = C.c_void_p()
         check(self._lib.mpcx_lmpc_create(C.byref(d), self.device, C.byref(self._h)))
+        self._A = self._B = None                                 # the model as given, for loops whose plants default to it
+        self._Bd = np.zeros((self.nx, self.ndu))
         self._last = Result(cmd=np.zeros(self.nu))
         self._stats = SolutionStats()
         self._last_u0 = np.zeros(self.nu)
@@ -227,11 +231,17 @@ class LMPC:
 
     def setStateSpaceModel(self, A, B, Cm):
         A, B, Cm = _cm(A, self.nx, self.nx), _cm(B, self.nx, self.nu), _cm(Cm, self.ny, self.nx)
-        return self._ok(self._lib.mpcx_lmpc_set_state_space_model(self._h, _p(A), _p(B), _p(Cm)))
+        ok = self._ok(self._lib.mpcx_lmpc_set_state_space_model(self._h, _p(A), _p(B), _p(Cm)))
+        if ok:
+            self._A, self._B = A.copy(), B.copy()
+        return ok
 
     def setDisturbances(self, Bd, Dd):
         Bd, Dd = _cm(Bd, self.nx, self.ndu), _cm(Dd, self.ny, self.ndu)
-        return self._ok(self._lib.mpcx_lmpc_set_disturbances(self._h, _p(Bd), _p(Dd)))
+        ok = self._ok(self._lib.mpcx_lmpc_set_disturbances(self._h, _p(Bd), _p(Dd)))
+        if ok:
+            self._Bd = Bd.copy()
+        return ok
 
     def setObjectiveWeights(self, OWeight, UWeight, DeltaUWeight, slice=None):
         ow = np.asarray(OWeight, dtype=np.float64)
@@ -466,19 +476,42 @@ class LMPC:
         want = f"[B,{ticks + self.ph},{n}] (preview)" if preview else f"[B,{self.ph},{n}]"
         raise ValueError(f"reference must be [B,{n}] or {want}, got {tuple(t.shape)}")
 
-    def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                  noise=None, warm=True, stream=None) -> Loop:
-        """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by
-        the plant step x <- A_p x + B_p cmd + Bd_p d_k + w_k on the device, with no host work in between.
+    def _check_plants(self, B, plant, plants):
+        """plants= as a triple (A [B,nx,nx], B [B,nx,nu] | None, Bd [B,nx,ndu] | None), its shapes checked -- on the host, ahead of any device call"""
+        if plant is not None and plants is not None:
+            raise ValueError("plant= (one plant for the batch) and plants= (a plant per instance) exclude each other")
+        if plants is None:
+            return None
+        plants = tuple(plants)
+        if not 1 <= len(plants) <= 3:
+            raise ValueError("plants is (A, B, Bd), the trailing entries optional")
+        plants += (None,) * (3 - len(plants))
+        for name, m, cols in zip(("A", "B", "Bd"), plants, (self.nx, self.nu, self.ndu)):
+            if m is not None and tuple((m if hasattr(m, "shape") else np.asarray(m)).shape) != (B, self.nx, cols):
+                raise ValueError(f"plants: {name} must be [{B},{self.nx},{cols}], got {tuple(np.shape(m))}")
+        return plants
 
-        plant: None (the controller's own A, B, Bd) or (A_p, B_p) / (A_p, B_p, Bd_p), None entries meaning the controller's;
-        noise: [ticks, B, nx] additive process disturbance the controller does not know about; warm: carry each tick's
-        working set into the next tick's solve (tick 0 is cold); preview: 3-D references are [B, ticks+ph, n] windows.
-        x0 / lastU are read again by every run_loop: tensors given here can be refilled in place (Loop.keep[0], [1])."""
-        torch, dev = self._torch()
+    def _own_plant(self, B, model=None):
+        """the controller's own A, B, Bd for B instances (numpy, broadcast)"""
+        if self._A is None:
+            raise MpcxError(_capi.E_STATE, "state-space model not set")
+        return tuple(np.broadcast_to(m, (B,) + m.shape) for m in (self._A, self._B, self._Bd))
+
+    @staticmethod
+    def pack_plants(A, B, Bd):
+        """[B, nx (nx+nu+ndu)]: per instance A_b | B_b | Bd_b, each column-major -- mpcx_lmpc_loop_desc.plant_batch; torch tensors in, a tensor out
+        (what to copy_ into Loop.plants for the next run)"""
+        import torch
+        n = A.shape[0]
+        return torch.cat([m.transpose(1, 2).reshape(n, m.shape[1] * m.shape[2]) for m in (A, B, Bd)], dim=1).contiguous()
+
+    def _make_loop(self, create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None):
+        """the descriptor of a loop, its result tensors and the create call: shared by LMPC and LMPCHetero (whose `create` takes the model index)"""
         ticks = int(ticks)
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
+        plants = self._check_plants(B, plant, plants)
+        torch, dev = self._torch()
         x0 = self._dev(torch, dev, x0, (B, self.nx))
         u0 = self._dev(torch, dev, lastU, (B, self.nu))
         refs = [self._loop_ref(torch, dev, a, B, n, ticks, preview)
@@ -497,13 +530,19 @@ class LMPC:
 
         d = _capi.LoopDesc()
         d.batch, d.ticks = B, ticks
-        mats = []
+        mats, pb = [], None
         if plant is not None:
             plant = tuple(plant) + (None,) * (3 - len(plant))
             for name, m, cols in zip(("plant_A", "plant_B", "plant_Bd"), plant, (self.nx, self.nu, self.ndu)):
                 if m is not None and cols > 0:
                     mats.append(_cm(m, self.nx, cols))
                     setattr(d, name, mats[-1].ctypes.data)
+        if plants is not None:
+            own = self._own_plant(B, model) if any(m is None for m in plants) else (None,) * 3
+            full = [self._dev(torch, dev, m if isinstance(m, torch.Tensor) else np.array(o if m is None else m, dtype=np.float64), (B, self.nx, cols))
+                    for m, o, cols in zip(plants, own, (self.nx, self.nu, self.ndu))]
+            pb = self.pack_plants(*full)
+            d.plant_batch = ptr(pb)
         d.x0, d.u0 = ptr(x0), ptr(u0)
         (yr, d.yref_mode), (ur, d.uref_mode), (dr, d.duref_mode), (de, d.dmeas_mode) = refs
         d.yref, d.uref, d.duref, d.dmeas = ptr(yr), ptr(ur), ptr(dr), ptr(de)
@@ -518,9 +557,24 @@ class LMPC:
             raise ValueError("a loop is captured on a non-default stream")
         s.wait_stream(cur)                      # the tensors above were filled on the current stream
         h = C.c_void_p()
-        check(self._lib.mpcx_lmpc_loop_create(self._h, C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
         cur.wait_stream(s)
-        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s))
+        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb), pb)
+
+    def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
+                  noise=None, warm=True, stream=None, plants=None) -> Loop:
+        """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by
+        the plant step x <- A_p x + B_p cmd + Bd_p d_k + w_k on the device, with no host work in between.
+
+        plant: None (the controller's own A, B, Bd) or (A_p, B_p) / (A_p, B_p, Bd_p), None entries meaning the controller's;
+        plants: a plant per instance instead, (A [B,nx,nx], B [B,nx,nu] | None, Bd [B,nx,ndu] | None), None entries again the
+        controller's -- packed into Loop.plants, which every run reads again (refill it in place: LMPC.pack_plants);
+        noise: [ticks, B, nx] additive process disturbance the controller does not know about; warm: carry each tick's
+        working set into the next tick's solve (tick 0 is cold); preview: 3-D references are [B, ticks+ph, n] windows.
+        x0 / lastU are read again by every run_loop: tensors given here can be refilled in place (Loop.keep[0], [1])."""
+        def create(d, s, out):
+            return self._lib.mpcx_lmpc_loop_create(self._h, d, s, out)
+        return self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream)
 
     def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
         """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
@@ -539,10 +593,10 @@ class LMPC:
             loop.handle = None
 
     def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                 noise=None, warm=True, stream=None) -> ClosedLoopResult:
+                 noise=None, warm=True, stream=None, plants=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
+        loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm, plants=plants)
         torch, _ = self._torch()
-        loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm)
         try:
             self.run_loop(loop, stream)
             (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()

@@ -2,11 +2,16 @@
 one plant step x+ = A x + B u (the closed loop of examples/quadrotor_ex.cpp run for a batch), with and without the
 warm start that carries the working set from tick to tick.  Three legs: the loop driven from the host (optimizeBatch and two
 torch matmuls per tick) and the device loop (LMPC.make_loop / run_loop: the plant step is a kernel, a tick is a graph replay),
-run alternately; each line gives both legs' ms per tick (median, min, max), polish rounds and solved fraction.  Usage: python tools/closed_loop.py [batch] [ticks] [repeats]"""
+run alternately; each line gives both legs' ms per tick (median, min, max), polish rounds and solved fraction.
+The bank leg (lines with "bank": true) is the same comparison for B different controllers (quadrotor_variant(k), the lmpc-hetero workload of
+bench.py): the host-driven loop is LMPCHetero.optimizeBatch plus a batched torch bmm plant step per tick, the device loop is
+LMPCHetero.make_loop / run_loop, every instance stepped by its own controller's model.
+Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|all]"""
 import json
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
@@ -53,6 +58,39 @@ def run_device(c, loop):
                 mean_rounds=float(res.polish_rounds.float().mean()), solved=float((res.status[-1] == 0).float().mean()))
 
 
+def make_bank(B, ph=20):
+    """B quadrotor variants behind one bank, their inputs on the device and their plants as bmm operands"""
+    from libmpc_amd import LMPCHetero
+    from libmpc_amd.workloads import quadrotor_variant
+    ctrls = [quadrotor_variant(k, ph, device=-1) for k in range(B)]
+    het = LMPCHetero(ctrls, device=0)
+    x0, u0, yref = quadrotor_batch(B)
+    dev = dict(x=torch.as_tensor(x0).cuda(), u=torch.as_tensor(u0).cuda(), yr=torch.as_tensor(yref).cuda(),
+               At=torch.as_tensor(np.stack([c._A.T for c in ctrls])).cuda().contiguous(),
+               Bt=torch.as_tensor(np.stack([c._B.T for c in ctrls])).cuda().contiguous())
+    return het, (x0, u0, yref), dev
+
+
+def run_bank(het, dev, ticks, warm):
+    """the host-driven loop of a bank: one batched solve and x <- A_b x + B_b u as two bmm per tick"""
+    x, u, yr = dev["x"], dev["u"], dev["yr"]
+    prev = None
+    rounds = 0.0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(ticks):
+        r = het.optimizeBatch(x, u, yref=yr, want_active=warm, warm=prev if warm else None, warm_shift=True)
+        x = (torch.bmm(x.unsqueeze(1), dev["At"]) + torch.bmm(r.cmd.unsqueeze(1), dev["Bt"])).squeeze(1)
+        u = r.cmd
+        prev = r
+        rounds += r.polish_rounds.float().mean()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    B = x.shape[0]
+    return dict(warm=warm, batch=B, ticks=ticks, solves_per_s=B * ticks / dt, ms_per_tick=dt / ticks * 1e3,
+                mean_rounds=float(rounds) / ticks, solved=float((r.status == 0).float().mean()))
+
+
 def median_spread(v):
     v = sorted(v)
     return v[len(v) // 2], v[0], v[-1]
@@ -62,8 +100,10 @@ if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
-    run(B, 5, True)
-    for w in (False, True):
+    legs = sys.argv[4] if len(sys.argv) > 4 else "all"
+    if legs in ("single", "all"):
+        run(B, 5, True)
+    for w in (False, True) if legs in ("single", "all") else ():
         c, loop = make_device(B, ticks, w)
         run_device(c, loop)                                   # warm-up of both legs (the host leg builds its controller anew each time)
         run(B, ticks, w)
@@ -77,3 +117,20 @@ if __name__ == "__main__":
                               host_mean_rounds=host[-1]["mean_rounds"], device_mean_rounds=dev[-1]["mean_rounds"],
                               host_solved=host[-1]["solved"], device_solved=dev[-1]["solved"])))
         c.destroy_loop(loop)
+    if legs in ("bank", "all"):
+        het, (x0, u0, yref), dev = make_bank(B)
+        run_bank(het, dev, 5, True)
+        for w in (False, True):
+            loop = het.make_loop(x0, u0, ticks, yref=yref, warm=w)
+            run_device(het, loop)                             # warm-up of both legs
+            run_bank(het, dev, ticks, w)
+            host, devl = [], []
+            for _ in range(repeats):                          # alternating, as above
+                host.append(run_bank(het, dev, ticks, w)); devl.append(run_device(het, loop))
+            hm, hlo, hhi = median_spread([r["ms_per_tick"] for r in host])
+            dm, dlo, dhi = median_spread([r["ms_per_tick"] for r in devl])
+            print(json.dumps(dict(bank=True, warm=w, batch=B, ticks=ticks, repeats=repeats,
+                                  host_ms_per_tick=dict(median=hm, min=hlo, max=hhi), device_ms_per_tick=dict(median=dm, min=dlo, max=dhi),
+                                  host_mean_rounds=host[-1]["mean_rounds"], device_mean_rounds=devl[-1]["mean_rounds"],
+                                  host_solved=host[-1]["solved"], device_solved=devl[-1]["solved"])))
+            het.destroy_loop(loop)
