@@ -431,6 +431,49 @@ int mpcx_nlmpc_solve_host(mpcx_nlmpc_t h, int batch, const double *x0, const dou
 /* `repeats` back-to-back launches bracketed by HIP events on `stream`; mean milliseconds. */
 int mpcx_nlmpc_time_solve_batch(mpcx_nlmpc_t h, const mpcx_nlmpc_batch *b, void *stream, int repeats, float *ms_mean);
 
+/* ---- NLMPC closed loop on the device ------------------------------------------------------------------------------------
+ * The caller's loop of the reference examples (examples/vanderpol_ex.cpp:76-85, ugv_ex.cpp: `for (;;) { res = optimize(x, lastU);
+ * lastU = res.cmd; x = plant(x, res.cmd); }`) for a batch, with no host work between two solves: a tick is mpcx_nlmpc_solve_batch on
+ * the loop's own x / u / z buffers followed by an advance kernel that steps the plant, hands the command over as the next lastU and
+ * files the tick's row of every trajectory.  A tick is captured once as a HIP graph (a linear chain on one stream) and a run replays it
+ * `ticks` times; the tick number lives on the device.  Built-in systems only: a hook model (mpcx_nlmpc_create_custom,
+ * mpcx_nlmpc_create_from_source) gets MPCX_E_UNSUPPORTED from mpcx_nlmpc_loop_create and mpcx_nlmpc_plant_step_batch -- loops for
+ * hook models come later.
+ * The plant is the controller's own state function: x <- f(x, cmd, p) for a discrete model (UGV, ugv_ex.cpp), `substeps` forward-Euler
+ * steps x <- x + (Ts / substeps) f(x, cmd, p) for a continuous one (substeps = 1 is vanderpol_ex.cpp:79-80), then x += w_k where a noise
+ * array is given.  p is the instance's row of plant_params, else its row of params, else the controller's parameters.  States and
+ * commands are in physical units (the Mapping scalings act inside the solve only).  On a failed solve cmd is already u0 (see
+ * mpcx_nlmpc_batch), which the plant then holds. */
+typedef struct mpcx_nlmpc_loop *mpcx_nlmpc_loop_t;
+typedef struct mpcx_nlmpc_loop_desc {
+    int batch, ticks;
+    const double *x0, *u0;          /* device [B x nx], [B x nu]; read again by every run */
+    const double *params;           /* device [B x n_params] or NULL: per-instance controller parameters (as mpcx_nlmpc_batch.params) */
+    const double *plant_params;     /* device [B x n_params] or NULL: the plant's parameters where they differ from the controller's */
+    const double *noise;            /* device [ticks x B x nx] or NULL */
+    int substeps;                   /* Euler sub-steps of a continuous plant per tick, >= 1 (1 = the reference example); ignored for discrete models */
+    int warm;                       /* 1: ticks >= 1 start from the shifted previous solution with the carried curvature estimate; tick 0 is cold */
+    double *traj_x, *traj_u;        /* device, required: [(ticks+1) x B x nx], [ticks x B x nu], tick-major */
+    double *traj_cost; int32_t *traj_status, *traj_solver_status, *traj_is_feasible, *traj_iterations;   /* optional */
+} mpcx_nlmpc_loop_desc;
+/* The loop of examples/vanderpol_ex.cpp:76-85 / ugv_ex.cpp, prepared: allocates the loop's buffers, runs one plain tick on `stream` (a
+ * non-default stream; that sizes the SQP workspace and uploads pending bounds), synchronises it and captures tick 0 (cold) and, with
+ * warm and ticks > 1, every later tick as a second graph.  The graphs hold the controller's workspace, bounds, scalings, optimizer
+ * parameters and tolerances as they were: after any setter of the controller, or a plain solve of a larger batch (it re-allocates the
+ * workspace), mpcx_nlmpc_loop_run returns MPCX_E_STATE -- create a new loop.  Destroy a loop before its controller. */
+int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *stream, mpcx_nlmpc_loop_t *out);
+/* One run of that loop (examples/vanderpol_ex.cpp:76-85 / ugv_ex.cpp), asynchronous: x <- x0, u <- u0, then `ticks` graph launches on
+ * `stream`.  The trajectories are complete once the stream has been synchronised.  One launch or run of a controller in flight at a time
+ * (they share its workspace); a plain solve after a run takes no curvature estimate over from it. */
+int mpcx_nlmpc_loop_run(mpcx_nlmpc_loop_t l, void *stream);
+int mpcx_nlmpc_loop_destroy(mpcx_nlmpc_loop_t l);
+int mpcx_nlmpc_loop_desc_size(void);            /* sizeof(mpcx_nlmpc_loop_desc) as the library was built: for bindings that mirror it */
+/* The plant step of that loop alone (the `x = plant(x, res.cmd)` line of examples/vanderpol_ex.cpp:79-80 / ugv_ex.cpp) for callers who
+ * drive the loop themselves: x_next [B x nx] from x, u [B x nu], per-instance params [B x n_params] or NULL (the controller's) and
+ * noise [B x nx] or NULL; x_next may be x.  The same device function as the loop's advance kernel: the two agree bit for bit. */
+int mpcx_nlmpc_plant_step_batch(mpcx_nlmpc_t h, int batch, const double *x, const double *u, const double *params,
+                                const double *noise /* [B x nx] or NULL */, int substeps, double *x_next, void *stream);
+
 /* ---- set-up utility -------------------------------------------------------- */
 /* mpc::discretization<nx, nu>(A, B, Ts, Ad, Bd) (Utils.hpp:23-47) for a batch of continuous-time models on the
  * device: [Ad Bd; 0 I] = exp([[A B]; [0 0]] Ts).  Device pointers, column-major matrices per instance
@@ -525,6 +568,11 @@ int mpcx_lmpc_debug_set_cycle_buffer(mpcx_lmpc_t h, void *dev_ptr);
  * trajectory, state or counter / the tick counter as it stands on the device, after synchronising the device */
 int mpcx_lmpc_loop_debug_replay(mpcx_lmpc_loop_t l, void *stream);
 int mpcx_lmpc_loop_debug_tick(mpcx_lmpc_loop_t l, int *tick);
+/* the same two for an NLMPC loop (the caller's loop of examples/vanderpol_ex.cpp:76-85 / ugv_ex.cpp on the device): one more replay of the
+ * later ticks' graph behind a finished run -- the counter stands at `ticks`, the advance kernel returns before its first store -- and the
+ * tick counter as it stands on the device, after synchronising the device */
+int mpcx_nlmpc_loop_debug_replay(mpcx_nlmpc_loop_t l, void *stream);
+int mpcx_nlmpc_loop_debug_tick(mpcx_nlmpc_loop_t l, int *tick);
 /* the SQP kernel's own convergence test: step length relative to max(1, |z|) and largest constraint defect */
 int mpcx_nlmpc_debug_set_tolerances(mpcx_nlmpc_t h, double tol_step, double tol_con);
 /* which kernel the last solve of a built-in system went through: 0 = nlmpc_sqp (one wavefront per instance, the reduced problem in a

@@ -6,10 +6,10 @@ reference's front-ends (ctypes; PyTorch only provides device memory and streams)
 There is no CPU fallback: a missing libmpcx.so or GPU raises.
 """
 from .lmpc import (LMPC, HorizonSlice, LParameters, Result, OptSequence, BatchResult, ClosedLoopResult, ResultStatus, SolutionStats, inf)
-from .nlmpc import NLMPC, NLMPCEvaluator, NLParameters
+from .nlmpc import NLMPC, NLMPCEvaluator, NLParameters, NLClosedLoopResult
 from ._capi import MpcxError
 from .bank import LMPCBank, LMPCHetero, group_by_model
 
 __all__ = ["LMPC", "NLMPC", "NLMPCEvaluator", "HorizonSlice", "LParameters", "NLParameters", "Result", "OptSequence",
-           "BatchResult", "ClosedLoopResult", "ResultStatus", "MpcxError", "SolutionStats", "inf", "LMPCBank", "LMPCHetero", "group_by_model"]
+           "BatchResult", "ClosedLoopResult", "NLClosedLoopResult", "ResultStatus", "MpcxError", "SolutionStats", "inf", "LMPCBank", "LMPCHetero", "group_by_model"]
 __version__ = "0.1.0"

@@ -84,13 +84,14 @@ EXPORTS = [
     "mpcx_nlparams_default", "mpcx_nlmpc_set_optimizer_parameters", "mpcx_nlmpc_solve_batch", "mpcx_nlmpc_time_solve_batch", "mpcx_discretize_batch",
     "mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice", "mpcx_nlmpc_solve_host",
     "mpcx_nlmpc_create_custom", "mpcx_nlmpc_create_from_source", "mpcx_nlmpc_set_input_scale", "mpcx_nlmpc_set_state_scale",
+    "mpcx_nlmpc_loop_create", "mpcx_nlmpc_loop_run", "mpcx_nlmpc_loop_destroy", "mpcx_nlmpc_loop_desc_size", "mpcx_nlmpc_plant_step_batch",
     "mpcx_comm_get_unique_id", "mpcx_comm_create", "mpcx_comm_destroy", "mpcx_comm_rank", "mpcx_comm_world", "mpcx_allgather_u",
     "mpcx_lmpc_hetero_create", "mpcx_lmpc_hetero_destroy", "mpcx_lmpc_hetero_get_info", "mpcx_lmpc_hetero_solve_batch",
     "mpcx_lmpc_hetero_time_solve_batch", "mpcx_lmpc_hetero_create_ex", "mpcx_lmpc_hetero_debug_get", "mpcx_lmpc_hetero_loop_create",
     # profiling and testing aids (declared in include/mpcx.h under that heading)
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
     "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer",
-    "mpcx_lmpc_loop_debug_replay", "mpcx_lmpc_loop_debug_tick",
+    "mpcx_lmpc_loop_debug_replay", "mpcx_lmpc_loop_debug_tick", "mpcx_nlmpc_loop_debug_replay", "mpcx_nlmpc_loop_debug_tick",
     "mpcx_nlmpc_debug_set_tolerances", "mpcx_nlmpc_debug_last_form", "mpcx_nlmpc_last_form", "mpcx_nlmpc_debug_get_ws", "mpcx_nlmpc_debug_generated_source", "mpcx_nlmpc_debug_compile_source",
 ]
 
@@ -107,6 +108,16 @@ class NlmpcBatch(C.Structure):
                 ("cost", C.c_void_p), ("status", C.c_void_p), ("solver_status", C.c_void_p), ("is_feasible", C.c_void_p),
                 ("iterations", C.c_void_p), ("z", C.c_void_p), ("seq_state", C.c_void_p), ("seq_input", C.c_void_p),
                 ("seq_output", C.c_void_p), ("warm_curvature", C.c_int), ("multipliers", C.c_void_p), ("params", C.c_void_p)]
+
+
+class NlmpcLoopDesc(C.Structure):
+    """mpcx_nlmpc_loop_desc: an NLMPC closed-loop run on the device (device pointers throughout)"""
+    _fields_ = [("batch", C.c_int), ("ticks", C.c_int), ("x0", C.c_void_p), ("u0", C.c_void_p),
+                ("params", C.c_void_p), ("plant_params", C.c_void_p), ("noise", C.c_void_p),
+                ("substeps", C.c_int), ("warm", C.c_int),
+                ("traj_x", C.c_void_p), ("traj_u", C.c_void_p), ("traj_cost", C.c_void_p),
+                ("traj_status", C.c_void_p), ("traj_solver_status", C.c_void_p), ("traj_is_feasible", C.c_void_p),
+                ("traj_iterations", C.c_void_p)]
 
 
 class NlmpcDims(C.Structure):
@@ -168,6 +179,12 @@ def lib():
         _lib.mpcx_nlmpc_create_from_source.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p]
         _lib.mpcx_nlmpc_set_input_scale.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_set_state_scale.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_nlmpc_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.mpcx_nlmpc_loop_run.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_nlmpc_loop_destroy.argtypes = [C.c_void_p]
+        _lib.mpcx_nlmpc_loop_debug_replay.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_nlmpc_loop_debug_tick.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_nlmpc_plant_step_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
         _lib.mpcx_comm_get_unique_id.argtypes = [C.c_void_p]
         _lib.mpcx_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.mpcx_comm_destroy.argtypes = [C.c_void_p]

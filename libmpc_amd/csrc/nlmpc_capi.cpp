@@ -2,11 +2,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/mpcx.h"
 #include "mpcx/nlmpc_device.hpp"
+#include "mpcx/nlmpc_loop.hpp"
 
 namespace mpcx {
 int capi_fail(int code, const std::string &msg);
@@ -24,6 +26,11 @@ void nlmpc_zoo_next_layout(void *z, const NlmpcDev *m, int hard, int batch, Nlmp
 void nlmpc_zoo_last_layout(void *z, NlmpcCurvLayout *out);
 // run-time compiled hooks (nlmpc_jit.cpp)
 void nlmpc_jit_release(void *jit);
+// the closed loop's kernels for the built-in systems (nlmpc_loop.hip)
+int nlmpc_loop_begin(const NlmpcDev *m, const NlmpcLoopDev *L, void *stream);
+int nlmpc_loop_advance(const NlmpcDev *m, const NlmpcLoopDev *L, void *stream);
+int nlmpc_plant_step(const NlmpcDev *m, int batch, const double *x, const double *u, const double *params, int nparams, const double *noise,
+                     int substeps, double *x_next, void *stream);
 }
 
 struct mpcx_nlmpc {
@@ -45,6 +52,8 @@ struct mpcx_nlmpc {
     double *ws = nullptr;
     size_t ws_cap = 0;          // instances
     int solved_batch = 0;       // batch size of the last solve whose state is still in the workspace (0: none)
+    unsigned long setup_gen = 0; // moved on by every setter and by every re-allocation of the workspace or the bounds block: what a loop's
+                                 // captured graphs hold (mpcx_nlmpc_loop_create) is what the handle has while this stands still
     mpcx_nlparams prm{};
     double tol_step = 1e-6, tol_con = 1e-8;      // own convergence test (mpcx_nlmpc_debug_set_tolerances: experiment knob)
     // NLOptimizer::lb / ub (NLOptimizer.hpp:346-404): bounds on the decision vector, host copy + device tables
@@ -76,6 +85,7 @@ struct mpcx_nlmpc {
         const int nb = (int)idx.size();
         if (bnd_block) (void)hipFree(bnd_block);
         bnd_block = nullptr;
+        ++setup_gen;
         const size_t bytes = sizeof(double) * (2 * (size_t)nz + 2 * (size_t)nb + 2) + sizeof(int) * ((size_t)nb + 2);
         if (hipMalloc(&bnd_block, bytes) != hipSuccess) return MPCX_E_DEVICE;
         double *d = static_cast<double *>(bnd_block);
@@ -236,6 +246,7 @@ int mpcx_nlmpc_set_optimizer_parameters(mpcx_nlmpc_t h, const mpcx_nlparams *p)
     if (!h || !p) return mpcx::capi_fail(MPCX_E_INVALID, "null argument");
     if (p->maximum_iteration < 0) return mpcx::capi_fail(MPCX_E_INVALID, "maximum_iteration must be >= 0");
     h->prm = *p;
+    ++h->setup_gen;
     return MPCX_OK;
 }
 
@@ -253,6 +264,7 @@ static int set_bounds(mpcx_nlmpc_t h, const double *lo, const double *hi, int st
     for (int i = a; i < b; ++i)
         for (int j = 0; j < n; ++j) { h->lb[base + i * n + j] = lo[j]; h->ub[base + i * n + j] = hi[j]; }
     h->bounds_dirty = true;
+    ++h->setup_gen;
     return MPCX_OK;
 }
 
@@ -273,6 +285,7 @@ static int set_scale(mpcx_nlmpc_t h, const double *s, bool state)
     std::vector<double> &dst = state ? h->ss : h->su;
     for (size_t j = 0; j < dst.size(); ++j) if (!(s[j] != 0.0) || !std::isfinite(s[j])) return capi_fail(MPCX_E_INVALID, "scaling factors must be finite and non-zero");
     dst.assign(s, s + dst.size());
+    ++h->setup_gen;
     if (hipSetDevice(h->device) != hipSuccess || h->sync_scale() != MPCX_OK) return capi_fail(MPCX_E_DEVICE, "could not upload the scalings");
     h->solved_batch = 0;
     return MPCX_OK;
@@ -318,6 +331,7 @@ static int prepare_solve(mpcx_nlmpc_t h, const mpcx_nlmpc_batch *b, mpcx::NlmpcS
     if ((size_t)b->batch > h->ws_cap) {
         if (h->ws) (void)hipFree(h->ws);
         h->ws = nullptr; h->ws_cap = 0; h->solved_batch = 0;
+        ++h->setup_gen;
         if (hipMalloc(reinterpret_cast<void **>(&h->ws), (size_t)b->batch * h->dev.ws.total * sizeof(double)) != hipSuccess)
             return capi_fail(MPCX_E_DEVICE, "could not allocate the SQP workspace");
         h->ws_cap = b->batch;
@@ -431,6 +445,178 @@ int mpcx_nlmpc_time_solve_batch(mpcx_nlmpc_t h, const mpcx_nlmpc_batch *b, void 
     return MPCX_OK;
 }
 
+// ---- the closed loop on the device --------------------------------------------------------------------------------------------------
+// A tick is the owner's ordinary step (mpcx_nlmpc_solve_batch on the loop's own x / u / z buffers) followed by nlmpc_loop_advance; both are
+// captured once, as a linear chain on one stream, and a run is "begin kernel, then the tick graph `ticks` times".  Tick 0 solves cold and, with
+// `warm`, the later ticks from the shifted previous solution (z and z_warm are one buffer) with the carried curvature estimate: the two differ
+// in the descriptor's z_warm and in keep_curvature, which a captured launch cannot change, so they are two graphs.
+struct mpcx_nlmpc_loop {
+    mpcx_nlmpc_t owner = nullptr;
+    int device = 0, ticks = 0;
+    unsigned long gen = 0;                       // the owner's set-up generation when the graphs were captured
+    mpcx::NlmpcLoopDev L{};
+    hipGraphExec_t first = nullptr, next = nullptr;   // tick 0; every later tick (null: the same graph serves all)
+    char *slab = nullptr;                        // every private buffer of the loop, one allocation
+    ~mpcx_nlmpc_loop()
+    {
+        if (first) (void)hipGraphExecDestroy(first);
+        if (next) (void)hipGraphExecDestroy(next);
+        if (slab) (void)hipFree(slab);
+    }
+};
+
+int mpcx_nlmpc_loop_desc_size(void) { return (int)sizeof(mpcx_nlmpc_loop_desc); }
+
+static bool nl_is_hook_model(const mpcx_nlmpc *h) { return h->launch_solve != mpcx::nlmpc_launch_solve || h->dev.model_id == 0; }
+
+// one tick -- the step of descriptor `b`, then the advance kernel -- captured on `s`
+static int nl_capture_tick(const mpcx_nlmpc_loop &l, const mpcx_nlmpc_batch *b, hipStream_t s, hipGraphExec_t *exec)
+{
+    using mpcx::capi_fail;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipStreamBeginCapture failed");
+    int rc = mpcx_nlmpc_solve_batch(l.owner, b, s);
+    const int la = rc == MPCX_OK ? mpcx::nlmpc_loop_advance(&l.owner->dev, &l.L, s) : 0;
+    hipGraph_t graph = nullptr;
+    const hipError_t ec = hipStreamEndCapture(s, &graph);
+    if (rc == MPCX_OK && la != 0) rc = capi_fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
+    if (rc == MPCX_OK && (ec != hipSuccess || !graph)) rc = capi_fail(MPCX_E_DEVICE, "hipStreamEndCapture failed");
+    if (rc == MPCX_OK && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) != hipSuccess) rc = capi_fail(MPCX_E_DEVICE, "hipGraphInstantiate failed");
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc;
+}
+
+int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *stream, mpcx_nlmpc_loop_t *out)
+{
+    using mpcx::capi_fail;
+    if (!h || !d || !out) return capi_fail(MPCX_E_INVALID, "null argument");
+    if (d->batch <= 0) return capi_fail(MPCX_E_INVALID, "a loop needs batch >= 1");
+    if (d->ticks <= 0) return capi_fail(MPCX_E_INVALID, "a loop needs ticks >= 1");
+    if (d->substeps <= 0) return capi_fail(MPCX_E_INVALID, "a loop needs substeps >= 1");
+    if (!d->x0 || !d->u0) return capi_fail(MPCX_E_INVALID, "x0 and u0 are required");
+    if (!d->traj_x || !d->traj_u) return capi_fail(MPCX_E_INVALID, "traj_x and traj_u are required");
+    if (!stream) return capi_fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
+    if (nl_is_hook_model(h)) return capi_fail(MPCX_E_UNSUPPORTED, "loops run the built-in systems only: hook models come later");
+    if ((d->params || d->plant_params) && h->n_params <= 0) return capi_fail(MPCX_E_INVALID, "this model has no parameters to give per instance");
+    if (hipSetDevice(h->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const mpcx::NlmpcDev &m = h->dev;
+
+    std::unique_ptr<mpcx_nlmpc_loop> l(new mpcx_nlmpc_loop);
+    l->owner = h; l->device = h->device; l->ticks = d->ticks;
+    const size_t B = (size_t)d->batch;
+    // the slab: offsets first, pointers once it is allocated
+    size_t total = 0;
+    auto take = [&](size_t bytes) { const size_t at = total; total = (total + bytes + 255) / 256 * 256; return at; };
+    const size_t o_x = take(B * m.nx * sizeof(double)), o_u = take(B * m.nu * sizeof(double)), o_cmd = take(B * m.nu * sizeof(double));
+    const size_t o_cost = take(B * sizeof(double)), o_int = take(4 * B * sizeof(int32_t)), o_z = take(B * m.nz * sizeof(double)), o_state = take(2 * sizeof(int));
+    if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return capi_fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
+    if (hipMemset(l->slab, 0, total) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipMemset failed");
+    char *base = l->slab;
+    auto dp = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+    int32_t *ib = reinterpret_cast<int32_t *>(base + o_int);
+
+    mpcx::NlmpcLoopDev &L = l->L;
+    L.batch = d->batch; L.ticks = d->ticks; L.substeps = d->substeps; L.nparams = h->n_params;
+    L.x0 = d->x0; L.u0 = d->u0; L.params = d->params; L.plant_params = d->plant_params; L.noise = d->noise;
+    L.x = dp(o_x); L.u = dp(o_u); L.cmd = dp(o_cmd); L.cost = dp(o_cost);
+    L.status = ib; L.solver_status = ib + B; L.is_feasible = ib + 2 * B; L.iterations = ib + 3 * B;
+    L.traj_x = d->traj_x; L.traj_u = d->traj_u; L.traj_cost = d->traj_cost;
+    L.traj_status = d->traj_status; L.traj_solver_status = d->traj_solver_status; L.traj_is_feasible = d->traj_is_feasible; L.traj_iterations = d->traj_iterations;
+    L.state = reinterpret_cast<int *>(base + o_state);
+
+    // the step's descriptor: the loop's own state, input and result buffers; z and z_warm one buffer (the solve shifts its start itself)
+    mpcx_nlmpc_batch cold{};
+    cold.batch = d->batch; cold.x0 = L.x; cold.u0 = L.u; cold.cmd = dp(o_cmd); cold.cost = dp(o_cost);
+    cold.status = ib; cold.solver_status = ib + B; cold.is_feasible = ib + 2 * B; cold.iterations = ib + 3 * B;
+    cold.z = dp(o_z); cold.params = d->params;
+    mpcx_nlmpc_batch warm = cold;
+    warm.z_warm = dp(o_z); warm.warm_curvature = 1;
+    const bool two = d->warm && d->ticks > 1;
+
+    // one plain pass first: it uploads pending bounds and sizes the workspace, neither of which can be captured, and leaves the handle in the state
+    // in which the warm descriptor is given the carried curvature estimate (prepare_solve: a solve of the same batch before it)
+    if (mpcx::nlmpc_loop_begin(&m, &L, s) != 0) return capi_fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    int rc = mpcx_nlmpc_solve_batch(h, &cold, s);
+    if (rc == MPCX_OK && mpcx::nlmpc_loop_advance(&m, &L, s) != 0) rc = capi_fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
+    if (rc == MPCX_OK && two) rc = mpcx_nlmpc_solve_batch(h, &warm, s);
+    if (rc != MPCX_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) { h->solved_batch = 0; return capi_fail(MPCX_E_DEVICE, "the warm-up ticks failed"); }
+    rc = nl_capture_tick(*l, &cold, s, &l->first);
+    if (rc == MPCX_OK && two) rc = nl_capture_tick(*l, &warm, s, &l->next);
+    h->solved_batch = 0;                         // (what the workspace holds is the loop's: a later plain call takes no curvature over from it)
+    if (rc != MPCX_OK) return rc;
+    l->gen = h->setup_gen;
+    *out = l.release();
+    return MPCX_OK;
+}
+
+static int nl_loop_usable(mpcx_nlmpc_loop_t l)
+{
+    using mpcx::capi_fail;
+    if (!l || !l->first) return capi_fail(MPCX_E_INVALID, "null loop");
+    if (l->owner->setup_gen != l->gen)
+        return capi_fail(MPCX_E_STATE, "the controller changed since the loop was created (a setter, or a solve that re-allocated the workspace): create a new loop");
+    if (hipSetDevice(l->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    return MPCX_OK;
+}
+
+int mpcx_nlmpc_loop_run(mpcx_nlmpc_loop_t l, void *stream)
+{
+    using mpcx::capi_fail;
+    int rc = nl_loop_usable(l);
+    if (rc != MPCX_OK) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    l->owner->solved_batch = 0;
+    if (mpcx::nlmpc_loop_begin(&l->owner->dev, &l->L, stream) != 0) return capi_fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    for (int k = 0; k < l->ticks; ++k)
+        if (hipGraphLaunch(k > 0 && l->next ? l->next : l->first, s) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
+    return MPCX_OK;
+}
+
+int mpcx_nlmpc_loop_debug_replay(mpcx_nlmpc_loop_t l, void *stream)
+{
+    int rc = nl_loop_usable(l);
+    if (rc != MPCX_OK) return rc;
+    l->owner->solved_batch = 0;
+    if (hipGraphLaunch(l->next ? l->next : l->first, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return mpcx::capi_fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
+    return MPCX_OK;
+}
+
+int mpcx_nlmpc_loop_debug_tick(mpcx_nlmpc_loop_t l, int *tick)
+{
+    using mpcx::capi_fail;
+    if (!l || !tick) return capi_fail(MPCX_E_INVALID, "null argument");
+    if (hipSetDevice(l->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(tick, l->L.state, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return capi_fail(MPCX_E_DEVICE, "reading the tick counter failed");
+    return MPCX_OK;
+}
+
+int mpcx_nlmpc_loop_destroy(mpcx_nlmpc_loop_t l)
+{
+    if (!l) return MPCX_OK;
+    (void)hipSetDevice(l->device);
+    delete l;
+    return MPCX_OK;
+}
+
+int mpcx_nlmpc_plant_step_batch(mpcx_nlmpc_t h, int batch, const double *x, const double *u, const double *params, const double *noise, int substeps,
+                                double *x_next, void *stream)
+{
+    using mpcx::capi_fail;
+    if (!h) return capi_fail(MPCX_E_INVALID, "null handle");
+    if (batch < 0) return capi_fail(MPCX_E_INVALID, "negative batch");
+    if (substeps <= 0) return capi_fail(MPCX_E_INVALID, "a plant step needs substeps >= 1");
+    if (nl_is_hook_model(h)) return capi_fail(MPCX_E_UNSUPPORTED, "the plant step runs the built-in systems only: hook models come later");
+    if (batch == 0) return MPCX_OK;
+    if (!x || !u || !x_next) return capi_fail(MPCX_E_INVALID, "x, u and x_next are required");
+    if (params && h->n_params <= 0) return capi_fail(MPCX_E_INVALID, "this model has no parameters to give per instance");
+    if (hipSetDevice(h->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (mpcx::nlmpc_plant_step(&h->dev, batch, x, u, params, h->n_params, noise, substeps, x_next, stream) != 0)
+        return capi_fail(MPCX_E_DEVICE, "launch of the plant-step kernel failed");
+    return MPCX_OK;
+}
+
 }  // extern "C"
 
 namespace mpcx {
@@ -463,6 +649,7 @@ extern "C" int mpcx_nlmpc_debug_set_tolerances(mpcx_nlmpc_t h, double tol_step, 
 {
     if (!h || !(tol_step > 0) || !(tol_con > 0)) return mpcx::capi_fail(MPCX_E_INVALID, "bad tolerances");
     h->tol_step = tol_step; h->tol_con = tol_con;
+    ++h->setup_gen;
     return MPCX_OK;
 }
 

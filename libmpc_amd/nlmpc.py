@@ -16,6 +16,7 @@ No CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -23,6 +24,29 @@ from . import _capi
 from ._capi import check
 
 VANDERPOL, UGV, OSCILLATORS6, OSCILLATORS8, VANDERPOL_TERMINAL, VANDERPOL_RATE = 1, 2, 3, 4, 5, 6
+
+
+@dataclass
+class NLClosedLoopResult:
+    """A closed-loop run on the device (NLMPC.simulate), tick-major device tensors: x [ticks+1, B, nx] (row 0 = the initial
+    state), u [ticks, B, nu], the others [ticks, B]."""
+    x: "object"
+    u: "object"
+    cost: "object"
+    status: "object"
+    solver_status: "object"
+    is_feasible: "object"
+    iterations: "object"
+
+
+@dataclass
+class NLLoop:
+    """a loop made by NLMPC.make_loop: the native handle, the result whose tensors every run fills, and the tensors the graphs point at
+    (keep[0], keep[1]: x0 and lastU as every run reads them -- refill them in place for another start)"""
+    handle: "object"
+    result: NLClosedLoopResult
+    ticks: int
+    keep: tuple = ()
 
 
 def NLParameters(**kw) -> _capi.NLParams:
@@ -199,6 +223,102 @@ class NLMPC(NLMPCEvaluator):
         s = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream if stream is None else stream
         check(self._lib.mpcx_nlmpc_solve_batch(self._h, C.byref(b), s))
         return out
+
+    # -- the closed loop on the device (mpcx_nlmpc_loop_*, mpcx_nlmpc_plant_step_batch) -----------------------------------------
+    def _rows(self, torch, dev, a, shape, what):
+        """a float64 device tensor of the given shape (None passes through)"""
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must be %s, got %s" % (what, list(shape), list(t.shape)))
+        return t
+
+    def plant_step(self, x, u, params=None, noise=None, substeps=1, stream=None, out=None):
+        """The plant step of the reference examples' closed loops (examples/vanderpol_ex.cpp:79-80, ugv_ex.cpp) for a batch, on the device:
+        x_next [B, nx] from x [B, nx] and u [B, nu] -- the controller's own state function, `substeps` forward-Euler steps of Ts / substeps
+        for a continuous model, one evaluation for a discrete one, plus `noise` [B, nx].  `params` [B, n_params]: per-instance model
+        parameters (default: the controller's).  `out`: a [B, nx] float64 device tensor to write to instead of a new one; it may be x.
+        The device function of the loop's advance kernel: the two agree bit for bit."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B = int(x.shape[0])
+        x = self._rows(torch, dev, x, (B, self.nx), "x"); u = self._rows(torch, dev, u, (B, self.nu), "u")
+        pb = self._rows(torch, dev, params, (B, self.n_params), "params"); w = self._rows(torch, dev, noise, (B, self.nx), "noise")
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (isinstance(out, torch.Tensor) and out.is_contiguous() and out.dtype == torch.float64 and out.device == x.device and tuple(out.shape) == (B, self.nx)):
+            raise ValueError("out must be a contiguous float64 tensor [%d, %d] on the controller's device" % (B, self.nx))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(self._lib.mpcx_nlmpc_plant_step_batch(self._h, B, x.data_ptr(), u.data_ptr(), ptr(pb), ptr(w), int(substeps), out.data_ptr(), s))
+        return out
+
+    def make_loop(self, x0, u0, ticks, *, params=None, plant_params=None, noise=None, warm=True, substeps=1, stream=None) -> NLLoop:
+        """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by the
+        plant step (`plant_step`) on the device, with no host work in between.
+
+        params [B, n_params]: per-instance parameters of the built-in system, for controller and plant; plant_params [B, n_params]: the
+        plant's where they differ from the controller's (model mismatch); noise [ticks, B, nx]: additive process disturbance the
+        controller does not know about; warm: ticks >= 1 start from the shifted previous solution with the carried curvature estimate
+        (tick 0 is cold); substeps: Euler sub-steps of a continuous plant per tick.
+        x0 / u0 are read again by every run_loop: refill NLLoop.keep[0], keep[1] in place for another start."""
+        import torch
+        ticks = int(ticks)
+        dev = torch.device("cuda", self.device)
+        B = int((x0 if hasattr(x0, "shape") else np.asarray(x0)).shape[0])
+        x0 = self._rows(torch, dev, x0, (B, self.nx), "x0"); u0 = self._rows(torch, dev, u0, (B, self.nu), "u0")
+        pb = self._rows(torch, dev, params, (B, self.n_params), "params")
+        pp = self._rows(torch, dev, plant_params, (B, self.n_params), "plant_params")
+        w = self._rows(torch, dev, noise, (ticks, B, self.nx), "noise")
+        f64, i32 = torch.float64, torch.int32
+        T = max(ticks, 0)
+        zi = lambda: torch.zeros((T, B), dtype=i32, device=dev)
+        res = NLClosedLoopResult(x=torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev), u=torch.zeros((T, B, self.nu), dtype=f64, device=dev),
+                                 cost=torch.zeros((T, B), dtype=f64, device=dev), status=zi(), solver_status=zi(), is_feasible=zi(), iterations=zi())
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        d = _capi.NlmpcLoopDesc()
+        d.batch, d.ticks, d.substeps, d.warm = B, ticks, int(substeps), int(bool(warm))
+        d.x0, d.u0, d.params, d.plant_params, d.noise = ptr(x0), ptr(u0), ptr(pb), ptr(pp), ptr(w)
+        d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
+        d.traj_status, d.traj_solver_status, d.traj_is_feasible, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.is_feasible), ptr(res.iterations)
+        cur = torch.cuda.current_stream(dev)
+        s = stream if stream is not None else torch.cuda.Stream(device=dev)
+        if s.cuda_stream == 0:
+            raise ValueError("a loop is captured on a non-default stream")
+        s.wait_stream(cur)                      # the tensors above were filled on the current stream
+        h = C.c_void_p()
+        check(self._lib.mpcx_nlmpc_loop_create(self._h, C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        cur.wait_stream(s)
+        return NLLoop(h, res, ticks, (x0, u0, pb, pp, w, s))
+
+    def run_loop(self, loop: NLLoop, stream=None) -> NLClosedLoopResult:
+        """One asynchronous run of a loop from its x0 / u0 tensors: `loop.result` is filled once the stream has been synchronised.  A loop
+        uses the controller's one workspace: one solve or run of a controller in flight at a time."""
+        import torch
+        cur = torch.cuda.current_stream(torch.device("cuda", self.device))
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+        check(self._lib.mpcx_nlmpc_loop_run(loop.handle, C.c_void_p(s.cuda_stream)))
+        return loop.result
+
+    def destroy_loop(self, loop: NLLoop):
+        if loop.handle:
+            check(self._lib.mpcx_nlmpc_loop_destroy(loop.handle))
+            loop.handle = None
+
+    def simulate(self, x0, u0, ticks, *, params=None, plant_params=None, noise=None, warm=True, substeps=1, stream=None) -> NLClosedLoopResult:
+        """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
+        import torch
+        loop = self.make_loop(x0, u0, ticks, params=params, plant_params=plant_params, noise=noise, warm=warm, substeps=substeps)
+        try:
+            self.run_loop(loop, stream)
+            (stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))).synchronize()
+        finally:
+            self.destroy_loop(loop)
+        return loop.result
 
     def time_launches(self, b, repeats, stream=None):
         import torch

@@ -1,6 +1,10 @@
 """Receding-horizon NLMPC loop on the device: B UGV controllers, each tick = one batched solve + one
 plant step (the closed loop of examples/ugv_ex.cpp for a batch), cold starts against the shifted warm start of
-NLOptimizer::run (NLOptimizer.hpp:460-510).  Usage: python tools/nlmpc_closed_loop.py [batch] [ticks]"""
+NLOptimizer::run (NLOptimizer.hpp:460-510) with the carried curvature estimate.  Two legs, run alternately: the loop driven from
+the host (optimizeBatch and NLMPC.plant_step per tick) and the device loop (NLMPC.make_loop / run_loop: a tick is a graph replay);
+each line gives both legs' ms per tick (median, min, max), mean iterations and the fraction that did not fail.  A last line is the
+host-driven loop with the shifted start alone (no carried curvature), which the device loop has no counterpart of.
+Usage: python tools/nlmpc_closed_loop.py [batch] [ticks] [repeats]"""
 import json
 import sys
 import time
@@ -11,10 +15,10 @@ sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(_
 from tools.nlmpc_bench import make  # noqa: E402
 
 
-def run(B, ticks, warm, curvature=False):
-    c, x0, u0 = make("ugv", B)
-    Ts = 0.1
-    x = x0.cuda(); u = u0.cuda()
+def run(c, x0, u0, ticks, warm, curvature=False):
+    """the host-driven loop: one batched solve and one plant-step kernel per tick"""
+    B = x0.shape[0]
+    x = x0.clone(); u = u0.clone()
     z = None
     its = 0.0
     torch.cuda.synchronize()
@@ -22,8 +26,7 @@ def run(B, ticks, warm, curvature=False):
     for _ in range(ticks):
         r = c.optimizeBatch(x, u, z_warm=z if warm else None, warm_curvature=curvature)
         u = r["cmd"]
-        x = torch.stack([x[:, 0] + Ts * x[:, 2] + 0.5 * Ts * Ts * u[:, 0], x[:, 1] + Ts * x[:, 3] + 0.5 * Ts * Ts * u[:, 1],
-                         x[:, 2] + Ts * u[:, 0], x[:, 3] + Ts * u[:, 1]], dim=1)
+        x = c.plant_step(x, u)
         z = r["z"]
         its += r["iterations"].float().mean()
     torch.cuda.synchronize()
@@ -33,8 +36,39 @@ def run(B, ticks, warm, curvature=False):
                 mean_iterations=float(its) / ticks, not_failed=ok)
 
 
+def run_device(c, loop):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = c.run_loop(loop)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    B, ticks = res.u.shape[1], loop.ticks
+    return dict(device_loop=True, batch=B, ticks=ticks, solves_per_s=B * ticks / dt, ms_per_tick=dt / ticks * 1e3,
+                mean_iterations=float(res.iterations.float().mean()), not_failed=float((res.status[-1] != 3).float().mean()))
+
+
+def median_spread(v):
+    v = sorted(v)
+    return v[len(v) // 2], v[0], v[-1]
+
+
 if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-    for w, k in ((False, False), (True, False), (True, True)):
-        print(json.dumps(run(B, ticks, w, k)))
+    repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    c, x0, u0 = make("ugv", B)
+    x0 = x0.cuda(); u0 = u0.cuda()
+    for w in (False, True):
+        loop = c.make_loop(x0, u0, ticks, warm=w)
+        run_device(c, loop); run(c, x0, u0, ticks, w, w)          # warm-up of both legs
+        host, dev = [], []
+        for _ in range(repeats):                                  # alternating, so that whatever else the machine does hits both alike
+            host.append(run(c, x0, u0, ticks, w, w)); dev.append(run_device(c, loop))
+        hm, hlo, hhi = median_spread([r["ms_per_tick"] for r in host])
+        dm, dlo, dhi = median_spread([r["ms_per_tick"] for r in dev])
+        print(json.dumps(dict(warm=w, keep_curvature=w, batch=B, ticks=ticks, repeats=repeats,
+                              host_ms_per_tick=dict(median=hm, min=hlo, max=hhi), device_ms_per_tick=dict(median=dm, min=dlo, max=dhi),
+                              host_mean_iterations=host[-1]["mean_iterations"], device_mean_iterations=dev[-1]["mean_iterations"],
+                              host_not_failed=host[-1]["not_failed"], device_not_failed=dev[-1]["not_failed"])), flush=True)
+        c.destroy_loop(loop)
+    print(json.dumps(run(c, x0, u0, ticks, True, False)), flush=True)
