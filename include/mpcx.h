@@ -238,6 +238,38 @@ int mpcx_lmpc_loop_run(mpcx_lmpc_loop_t l, void *stream);
 int mpcx_lmpc_loop_destroy(mpcx_lmpc_loop_t l);
 int mpcx_lmpc_loop_desc_size(void);               /* sizeof(mpcx_lmpc_loop_desc), for bindings that mirror the struct */
 
+/* Output feedback for that loop (no reference counterpart: the reference has neither the loop nor an observer; its examples hand optimize() the
+ * plant's state).  An observed loop carries the true state x and an estimate xhat per instance; the solve of tick k reads xhat_k and u_{k-1}, and
+ * the advance kernel computes, everything from tick-k data (predictor form, so every reference and dmeas mode works unchanged):
+ *     y_k     = C x_k + Dd d_k + v_k            the measurement, v_k the optional sensor noise
+ *     e_k     = y_k - (C xhat_k + Dd d_k)
+ *     x_k+1   = A_p x_k + B_p cmd_k + Bd_p d_k + w_k          as in an unobserved loop
+ *     xhat_k+1 = A xhat_k + B cmd_k + Bd d_k + L e_k
+ * with A, B, Bd, C, Dd the controller's own model and the plant whatever the loop descriptor says.  Every row is summed from 0 with fused
+ * multiply-adds by ascending column -- y over C, then Dd, then + v_k; xhat over A, B, Bd, then L -- so that e_k is an exact 0 where xhat_k equals
+ * x_k bitwise and there is no sensor noise, and an observed loop on the controller's own plant without noise reproduces the unobserved loop.
+ * xhat_0 is xhat0, or x0.  The loop is an mpcx_lmpc_loop_t: _run, _destroy, _debug_replay and _debug_tick serve it, invalidation is unchanged.
+ * gain is copied at creation; gain_batch, xhat0 and meas_noise are device arrays read by every run: refill them in place. */
+typedef struct mpcx_lmpc_observer_desc {
+    const double *gain;                           /* HOST, column-major [nx x ny]: one gain for the batch, or NULL */
+    const double *gain_batch;                     /* device, [B x nx*ny], per instance, column-major, read at the head of every run; excludes gain */
+    const double *xhat0;                          /* device [B x nx] or NULL (= x0), read again by every run */
+    const double *meas_noise;                     /* device [ticks x B x ny] or NULL */
+    double *traj_xhat;                            /* device [(ticks+1) x B x nx], optional */
+    double *traj_y;                               /* device [ticks x B x ny], optional */
+} mpcx_lmpc_observer_desc;
+/* mpcx_lmpc_loop_create with an observer (no reference counterpart).  MPCX_E_INVALID, ahead of any look at the handle's state, for a null observer
+ * and for neither or both of gain / gain_batch. */
+int mpcx_lmpc_loop_create_observed(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out);
+int mpcx_lmpc_observer_desc_size(void);           /* sizeof(mpcx_lmpc_observer_desc), for bindings that mirror the struct */
+/* The steady-state Kalman predictor gain of the controller's own (A, C) (no reference counterpart), on the host in doubles; works on a host-only
+ * handle.  L = A P C' (C P C' + Rv)^-1 with P the fixed point of P <- A P A' - A P C' (C P C' + Rv)^-1 C P A' + Qw, iterated from P = Qw and
+ * symmetrised every time, until the largest change of an entry is <= 1e-14 times the largest entry.  Qw [nx x nx], Rv [ny x ny], gain_out
+ * [nx x ny], P_out [nx x nx] or NULL, all column-major; iterations (or NULL) receives the count.  MPCX_E_STATE without a model, MPCX_E_INVALID
+ * for a Qw or Rv that is not symmetric or an Rv that is not positive definite, MPCX_E_NUMERIC when 100000 iterations have not converged (an
+ * (A, C) that is not detectable, for instance). */
+int mpcx_lmpc_kalman_gain(mpcx_lmpc_t h, const double *Qw, const double *Rv, double *gain_out, double *P_out, int *iterations);
+
 /* Convenience for callers whose data lives in host memory (the reference's optimize(x0, lastU) is
  * such a caller): stages the inputs to HBM, runs mpcx_lmpc_solve_batch on the default stream, copies
  * the results back and synchronises.  References use the matrices given to the host setters.  Any
@@ -534,6 +566,10 @@ int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batc
  * with step 0 of its own controller's exogenous input.  A bank has no setters, so nothing invalidates its loops; destroy a loop BEFORE its bank
  * (the graphs point into the bank's memory). */
 int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out);
+/* The same with an observer (no reference counterpart): instance b is estimated with the model of its controller model_index[b], as the bank holds
+ * it.  The controllers of a bank differ, so one gain for all is refused: gain_batch is required (MPCX_E_INVALID for gain). */
+int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
+                                          void *stream, mpcx_lmpc_loop_t *out);
 
 /* Sharding: this handle solves contiguous shards of a batch of `total` instances -- the kernel form is chosen for
  * the whole batch's size, so that a shard's results are bit for bit the rows of the unsharded solve (0 = every call is a whole batch). */

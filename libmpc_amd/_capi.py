@@ -59,6 +59,12 @@ class LoopDesc(C.Structure):
                 ("plant_batch", C.c_void_p)]
 
 
+class ObserverDesc(C.Structure):
+    """mpcx_lmpc_observer_desc: the observer of an observed loop (gain is a host pointer, everything else device pointers)"""
+    _fields_ = [("gain", C.c_void_p), ("gain_batch", C.c_void_p), ("xhat0", C.c_void_p), ("meas_noise", C.c_void_p),
+                ("traj_xhat", C.c_void_p), ("traj_y", C.c_void_p)]
+
+
 class Info(C.Structure):
     _fields_ = [("n_ref", C.c_int), ("m_ref", C.c_int), ("neq_ref", C.c_int), ("nz", C.c_int), ("mg", C.c_int),
                 ("active_words", C.c_int), ("kernel_variant", C.c_int),
@@ -80,6 +86,7 @@ EXPORTS = [
     "mpcx_lmpc_time_solve_batch", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
     "mpcx_lmpc_graph_create", "mpcx_lmpc_graph_launch", "mpcx_lmpc_graph_destroy",
     "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
+    "mpcx_lmpc_loop_create_observed", "mpcx_lmpc_hetero_loop_create_observed", "mpcx_lmpc_observer_desc_size", "mpcx_lmpc_kalman_gain",
     "mpcx_nlmpc_create", "mpcx_nlmpc_destroy", "mpcx_nlmpc_get_dims", "mpcx_nlmpc_evaluate_batch",
     "mpcx_nlparams_default", "mpcx_nlmpc_set_optimizer_parameters", "mpcx_nlmpc_solve_batch", "mpcx_nlmpc_time_solve_batch", "mpcx_discretize_batch",
     "mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice", "mpcx_nlmpc_solve_host",
@@ -163,6 +170,9 @@ def lib():
         _lib.mpcx_lmpc_graph_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_hetero_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.mpcx_lmpc_loop_create_observed.argtypes = [C.c_void_p] * 5
+        _lib.mpcx_lmpc_hetero_loop_create_observed.argtypes = [C.c_void_p] * 6
+        _lib.mpcx_lmpc_kalman_gain.argtypes = [C.c_void_p] * 6
         _lib.mpcx_lmpc_loop_run.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_loop_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_loop_debug_replay.argtypes = [C.c_void_p, C.c_void_p]

@@ -167,6 +167,7 @@ class LMPCHetero:
 
     # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create; the loop itself is LMPC's) -------------------------------
     _loop_ref, _check_plants, _make_loop, pack_plants = LMPC._loop_ref, LMPC._check_plants, LMPC._make_loop, staticmethod(LMPC.pack_plants)
+    _check_observer, pack_gains = LMPC._check_observer, staticmethod(LMPC.pack_gains)
     run_loop, destroy_loop = LMPC.run_loop, LMPC.destroy_loop
 
     def _own_plant(self, B, model=None):
@@ -177,14 +178,17 @@ class LMPCHetero:
         return tuple(np.stack([m[j] for m in self._models])[idx] for j in range(3))
 
     def make_loop(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                  noise=None, warm=True, stream=None) -> Loop:
+                  noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None) -> Loop:
         """LMPC.make_loop for a bank: every tick is the bank's batched solve (instance b by controller model[b]; None: controller b)
         followed by the plant step.  plant: one plant for all, (A_p, B_p, Bd_p); plants: a plant per instance, (A [B,nx,nx],
         B [B,nx,nu] | None, Bd | None); a None entry of either, and no plant at all, mean each instance's own controller.  References:
-        None is each controller's own, also for the exogenous input that drives the plant.  Destroy the loop before the bank."""
+        None is each controller's own, also for the exogenous input that drives the plant.  observer, xhat0, meas_noise: output feedback as
+        in LMPC.make_loop, instance b estimated with its own controller's model; the gain is per instance, [B, nx, ny] (the controllers
+        differ: one gain for all raises ValueError).  Destroy the loop before the bank."""
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
         plants = self._check_plants(B, plant, plants)
+        self._check_observer(B, int(ticks), observer, xhat0, meas_noise, bank=True)
         mi = None
         if model is not None:
             mi = torch.as_tensor(model).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
@@ -197,16 +201,21 @@ class LMPCHetero:
                 plants = tuple(None if m is None else np.broadcast_to(np.asarray(m, dtype=np.float64), (B,) + np.shape(m)) for m in plant)
                 plant = None
 
-        def create(d, s, out):
-            return self._lib.mpcx_lmpc_hetero_loop_create(self._h, d, None if mi is None else C.c_void_p(mi.data_ptr()), s, out)
-        loop = self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi)
+        def create(d, s, out, od):
+            mp = None if mi is None else C.c_void_p(mi.data_ptr())
+            if od is None:
+                return self._lib.mpcx_lmpc_hetero_loop_create(self._h, d, mp, s, out)
+            return self._lib.mpcx_lmpc_hetero_loop_create_observed(self._h, d, od, mp, s, out)
+        loop = self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi,
+                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, bank=True)
         loop.keep += (mi,)
         return loop
 
     def simulate(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                 noise=None, warm=True, stream=None) -> ClosedLoopResult:
+                 noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
-        loop = self.make_loop(x0, lastU, ticks, model, plant, plants, yref, uref, duref, dmeas, preview, noise, warm)
+        loop = self.make_loop(x0, lastU, ticks, model, plant, plants, yref, uref, duref, dmeas, preview, noise, warm,
+                              observer=observer, xhat0=xhat0, meas_noise=meas_noise)
         try:
             self.run_loop(loop, stream)
             (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()

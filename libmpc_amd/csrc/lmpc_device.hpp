@@ -185,13 +185,28 @@ struct LmpcLoopDev {
     // preview references (yref, uref, duref, dmeas): source [B x (ticks + ph) x n], staging [B x ph x n]; null source: not a preview array
     const double *pv_src[4]; double *pv_dst[4]; int pv_n[4];
     int *state;                                   // [tick, blocks of the running advance kernel that are through]
+    // observed loops (ek null: none): x above is then the estimate -- what the solve reads -- and xt the plant's true state.  The three packed blocks
+    // are written by lmpc_loop_pack_observer in the order lmpc_loop.hip describes; a tile stride of 0: one tile, read by every block
+    int ny, so;                                   // outputs; LDS stride of an instance's [x | xhat | cmd | d | e] (lmpc_loop_plan_lds)
+    double *xt;
+    double *ok; long ok_ts;                       // the plant [A_p | B_p | Bd_p]: pk (a plant per instance), or one tile packed from `plant`
+    double *ek; long ek_ts;                       // the estimator [A | B | Bd | L] of the instance's controller
+    double *mk; long mk_ts;                       // the measurement [C | Dd] of the instance's controller
+    const double *mA, *mB, *mBd, *mC, *mDd;       // a handle's model on the device, column-major (null in a bank: models / model_index)
+    const double *gain, *gain_batch;              // [nx x ny] one gain for the batch, or [B x nx ny] a gain per instance; column-major
+    const double *xhat0;                          // [B x nx] or null (= x0), read by lmpc_loop_begin
+    const double *meas_noise;                     // [ticks x B x ny] or null
+    double *traj_xhat, *traj_y;                   // [(ticks + 1) x B x nx], [ticks x B x ny], or null
 };
-void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv
+void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv, so (ny before the call)
 size_t lmpc_loop_packed_len(const LmpcLoopDev &L);   // doubles of pk (whole tiles)
+// doubles of an observed loop's blocks with `tiles` tiles each: 0 the plant, 1 the estimator, 2 the measurement
+size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles);
 size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L);
 int lmpc_loop_prepare(const LmpcLoopDev &L);      // once per loop, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
 int lmpc_loop_begin(const LmpcLoopDev &L, void *stream);
 int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of every run, next to lmpc_loop_begin: fills pk and d_own (no launch when both are null)
+int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills ok (unless it is pk), ek and mk
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
 
 }  // namespace mpcx

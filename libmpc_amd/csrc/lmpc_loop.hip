@@ -19,6 +19,15 @@
 //                             rows' nx + nu + ndu terms in the uniform kernel's order (the two agree bit for bit on equal plants); term j of a
 //                             tile is one contiguous run of the packed array, read by consecutive lanes, the loads of a group of terms in flight
 //                             together; the lane's sum is an element of the tile's run of x and goes straight out
+//
+// Output feedback (an observed loop, mpcx_lmpc_loop_create_observed): the solve reads an estimate xhat instead of the true state x, and the tick
+// also measures and estimates, everything from tick-k data (predictor form):
+//   y = C x + Dd d_k + v_k,  e = y - (C xhat + Dd d_k),  x <- A_p x + B_p cmd + Bd_p d_k + w_k,  xhat <- A xhat + B cmd + Bd d_k + L e
+//   lmpc_loop_pack_observer     head of every run: the estimator [A | B | Bd | L] and the measurement [C | Dd] of each instance's controller in the
+//                               per-tile order of the plants; a block that is the same for every instance is one tile, read at tile stride 0
+//   lmpc_loop_advance_observed  the per-instance kernel's shape for every plant: an instance's [x | xhat | cmd | d | e] side by side in LDS; first
+//                               the lanes of an instance take its output rows (y and yhat share a coefficient load, e to LDS, y to its log), then,
+//                               a barrier later, its state rows: the plant's sum and the estimator's, both straight out
 #include <hip/hip_runtime.h>
 
 #include "lmpc_device.hpp"
@@ -58,14 +67,60 @@ __global__ __launch_bounds__(kTile) void lmpc_loop_begin_kernel(const LmpcLoopDe
     const int b0 = blockIdx.x * kTile;
     const int nvalid = min(kTile, L.batch - b0);
     const size_t xo = (size_t)b0 * L.nx, uo = (size_t)b0 * L.nu;
+    double *const xtrue = L.ek ? L.xt : L.x;      // an observed loop keeps the true state apart: x is the estimate, xhat0 or x0
     for (int idx = tid; idx < nvalid * L.nx; idx += kTile) {
         const double v = gin(L.x0)[xo + idx];
-        gout(L.x)[xo + idx] = v;
+        gout(xtrue)[xo + idx] = v;
         gout(L.traj_x)[xo + idx] = v;
+    }
+    if (L.ek) {
+        const double *const h0 = L.xhat0 ? L.xhat0 : L.x0;
+        for (int idx = tid; idx < nvalid * L.nx; idx += kTile) {
+            const double v = gin(h0)[xo + idx];
+            gout(L.x)[xo + idx] = v;
+            if (L.traj_xhat) gout(L.traj_xhat)[xo + idx] = v;
+        }
     }
     for (int idx = tid; idx < nvalid * L.nu; idx += kTile) gout(L.u)[uo + idx] = gin(L.u0)[uo + idx];
     gather_windows(L, b0, nvalid, 0, tid);
     if (blockIdx.x == 0 && tid == 0) { gout(L.state)[0] = 0; gout(L.state)[1] = 0; }
+}
+
+// What every advance kernel ends a tick with: the tick's row of the per-instance logs, the active sets handed to the next solve, the preview windows
+// of tick k + 1, and the ticket that moves the counter.
+__device__ __forceinline__ void finish_tick(const LmpcLoopDev &L, const int b0, const int nvalid, const int k, const int tid)
+{
+    const int B = L.batch;
+    // the tick's row of the per-instance logs
+    if (tid < nvalid) {
+        const int b = b0 + tid;
+        const size_t at = (size_t)k * B + b;
+        if (L.traj_cost) gout(L.traj_cost)[at] = gin(L.cost)[b];
+        if (L.traj_status) gout(L.traj_status)[at] = gin(L.status)[b];
+        if (L.traj_solver_status) gout(L.traj_solver_status)[at] = gin(L.solver_status)[b];
+        if (L.traj_iterations) gout(L.traj_iterations)[at] = gin(L.iterations)[b];
+        if (L.traj_polish_rounds) gout(L.traj_polish_rounds)[at] = gin(L.polish_rounds)[b];
+        if (L.traj_active_count) gout(L.traj_active_count)[at] = gin(L.active_count)[b];
+    }
+    // this tick's active sets become the next solve's first working sets
+    if (L.warm_lower) {
+        const size_t ao = (size_t)b0 * L.aw;
+        for (int idx = tid; idx < nvalid * L.aw; idx += kTile) {
+            gout(L.warm_lower)[ao + idx] = gin(L.active_lower)[ao + idx];
+            gout(L.warm_upper)[ao + idx] = gin(L.active_upper)[ao + idx];
+        }
+    }
+    if (k + 1 < L.ticks) gather_windows(L, b0, nvalid, k + 1, tid);
+
+    // the counter moves when the last block is through: a block that starts late still reads tick k
+    __threadfence();
+    if (tid == 0) {
+        const int done = atomicAdd(L.state + 1, 1);
+        if (done == (int)gridDim.x - 1) {
+            __hip_atomic_store(L.state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(L.state, k + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // kPlants: a plant per instance.  The tile is then the ipw = 64 / nx instances whose rows fill the wavefront's lanes (from nx = 33 on one instance,
@@ -177,36 +232,133 @@ __device__ __forceinline__ void advance_tick(const LmpcLoopDev &L, double *lds)
             }
         }
     }
-    // the tick's row of the per-instance logs
-    if (tid < nvalid) {
-        const int b = b0 + tid;
-        const size_t at = (size_t)k * B + b;
-        if (L.traj_cost) gout(L.traj_cost)[at] = gin(L.cost)[b];
-        if (L.traj_status) gout(L.traj_status)[at] = gin(L.status)[b];
-        if (L.traj_solver_status) gout(L.traj_solver_status)[at] = gin(L.solver_status)[b];
-        if (L.traj_iterations) gout(L.traj_iterations)[at] = gin(L.iterations)[b];
-        if (L.traj_polish_rounds) gout(L.traj_polish_rounds)[at] = gin(L.polish_rounds)[b];
-        if (L.traj_active_count) gout(L.traj_active_count)[at] = gin(L.active_count)[b];
-    }
-    // this tick's active sets become the next solve's first working sets
-    if (L.warm_lower) {
-        const size_t ao = (size_t)b0 * L.aw;
-        for (int idx = tid; idx < nvalid * L.aw; idx += kTile) {
-            gout(L.warm_lower)[ao + idx] = gin(L.active_lower)[ao + idx];
-            gout(L.warm_upper)[ao + idx] = gin(L.active_upper)[ao + idx];
-        }
-    }
-    if (k + 1 < L.ticks) gather_windows(L, b0, nvalid, k + 1, tid);
+    finish_tick(L, b0, nvalid, k, tid);
+}
 
-    // the counter moves when the last block is through: a block that starts late still reads tick k
-    __threadfence();
-    if (tid == 0) {
-        const int done = atomicAdd(L.state + 1, 1);
-        if (done == (int)gridDim.x - 1) {
-            __hip_atomic_store(L.state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(L.state, k + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+// n terms behind acc in ascending order: term j is P[j * width] -- one coalesced request of the wavefront -- times v[j] from LDS, the loads of eight
+// terms (then four) in flight together
+__device__ __forceinline__ double row_terms(const double LOOP_GAS *P, const size_t width, const double *v, const int n, double acc)
+{
+    int j = 0;
+#pragma unroll 1
+    for (; j + 8 <= n; j += 8) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc = fma(P[(j + e) * width], v[j + e], acc);
+    }
+#pragma unroll 1
+    for (; j + 4 <= n; j += 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = fma(P[(j + e) * width], v[j + e], acc);
+    }
+#pragma unroll 1
+    for (; j < n; ++j) acc = fma(P[j * width], v[j], acc);
+    return acc;
+}
+
+// the same for the two output sums, which share their coefficients: y over the true state's operands, yh over the estimate's
+__device__ __forceinline__ void output_terms(const double LOOP_GAS *M, const size_t width, const double *vx, const double *vh, const int n, double &y, double &yh)
+{
+    int j = 0;
+#pragma unroll 1
+    for (; j + 4 <= n; j += 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double c = M[(j + e) * width];
+            y = fma(c, vx[j + e], y);
+            yh = fma(c, vh[j + e], yh);
         }
     }
+#pragma unroll 1
+    for (; j < n; ++j) {
+        const double c = M[j * width];
+        y = fma(c, vx[j], y);
+        yh = fma(c, vh[j], yh);
+    }
+}
+
+// The tick of an observed loop.  Tiles, lanes and the packed order are the per-instance kernel's (above); the estimator block has nx + nu + ndu + ny
+// terms of nx rows, the measurement block nx + ndu terms of ny rows (lane (q, i) reads element q * ny + i of a term's run of ipw * ny), each block
+// at its own tile stride.  Sum order, every row from acc = 0 by ascending column: y over C, then Dd, then + v_k; yhat the same without v_k; x as
+// above; xhat over A, B, Bd -- the plant's order -- then L, nothing added at the store.  Hence e = 0 exactly where xhat = x bitwise and v_k is
+// absent, and xhat <- x's own bits where the plant is the controller's model and no w_k comes on top.
+__device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *lds)
+{
+    const int tid = threadIdx.x;
+    const int k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(L.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    if (k >= L.ticks) return;                     // a replay past the run's end: nothing is written
+    const int nx = L.nx, nu = L.nu, ndu = L.ndu, ny = L.ny, B = L.batch, so = L.so;
+    const int nt = L.ipw;
+    const int b0 = blockIdx.x * nt;
+    const int nvalid = min(nt, B - b0);
+    double *xin = lds, *hin = xin + nx, *cin = hin + nx, *din = cin + nu, *ein = din + ndu;   // an instance's row: the estimator's operands are hin ... in its terms' order
+    const size_t xo = (size_t)b0 * nx, uo = (size_t)b0 * nu;
+
+    // in: the tile's true states, estimates, commands and exogenous-input samples, one contiguous run each
+    for (int idx = tid; idx < nvalid * nx; idx += kTile) {
+        const int r = idx / nx, c = idx - r * nx;
+        xin[r * so + c] = gin(L.xt)[xo + idx];
+        hin[r * so + c] = gin(L.x)[xo + idx];
+    }
+    double LOOP_GAS *tu = gout(L.traj_u) + (size_t)k * B * nu;
+    for (int idx = tid; idx < nvalid * nu; idx += kTile) {
+        const int r = idx / nu, c = idx - r * nu;
+        const double v = gin(L.cmd)[uo + idx];
+        cin[r * so + c] = v;
+        gout(L.u)[uo + idx] = v;                  // lastU of the next tick: the command as it is
+        tu[uo + idx] = v;
+    }
+    if (ndu > 0) {
+        const double LOOP_GAS *dk = gin(L.dmeas) + (size_t)k * L.d_tick;
+        for (int idx = tid; idx < nvalid * ndu; idx += kTile) {
+            const int r = idx / ndu, c = idx - r * ndu;
+            din[r * so + c] = dk[(size_t)(b0 + r) * L.d_bs + c];
+        }
+    }
+    __syncthreads();
+
+    const int lpi = min(nx, kTile);               // lanes per instance
+    const int q = tid / lpi;
+    const bool mine = q < nvalid;
+    // the measurement and the innovation of the lane's (instance, output row)
+    if (mine) {
+        const size_t width = (size_t)nt * ny;
+        const double LOOP_GAS *M = gin(L.mk) + (size_t)blockIdx.x * L.mk_ts + q * ny;
+        const double *xr = xin + q * so, *hr = hin + q * so, *dr = din + q * so;
+        const size_t yo = ((size_t)k * B + b0 + q) * ny;
+        const double LOOP_GAS *vn = L.meas_noise ? gin(L.meas_noise) + yo : nullptr;
+        for (int i = tid - q * lpi; i < ny; i += lpi) {
+            double y = 0.0, yh = 0.0;
+            output_terms(M + i, width, xr, hr, nx, y, yh);
+            output_terms(M + i + nx * width, width, dr, dr, ndu, y, yh);
+            if (vn) y += vn[i];
+            ein[q * so + i] = y - yh;
+            if (L.traj_y) gout(L.traj_y)[yo + i] = y;
+        }
+    }
+    __syncthreads();
+
+    // the plant step and the estimator step of the lane's (instance, state row); every read of x and xhat is ahead of the first barrier
+    if (mine) {
+        const size_t width = (size_t)nt * nx;
+        const double LOOP_GAS *P = gin(L.ok) + (size_t)blockIdx.x * L.ok_ts + q * nx;
+        const double LOOP_GAS *E = gin(L.ek) + (size_t)blockIdx.x * L.ek_ts + q * nx;
+        const double *xr = xin + q * so, *hr = hin + q * so, *cr = cin + q * so;
+        double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
+        double LOOP_GAS *th = L.traj_xhat ? gout(L.traj_xhat) + (size_t)(k + 1) * B * nx : nullptr;
+        const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
+        for (int i = tid - q * lpi; i < nx; i += lpi) {
+            double acc = row_terms(P + i, width, xr, nx, 0.0);
+            acc = row_terms(P + i + nx * width, width, cr, nu + ndu, acc);
+            const double est = row_terms(E + i, width, hr, nx + nu + ndu + ny, 0.0);
+            const size_t at = xo + q * nx + i;
+            if (w) acc += w[at];
+            gout(L.xt)[at] = acc;
+            tx[at] = acc;
+            gout(L.x)[at] = est;
+            if (th) th[at] = est;
+        }
+    }
+    finish_tick(L, b0, nvalid, k, tid);
 }
 
 __global__ __launch_bounds__(kTile) void lmpc_loop_advance_kernel(const LmpcLoopDev L)
@@ -220,6 +372,12 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) v
 {
     extern __shared__ double lds[];
     advance_tick<true>(L, lds);
+}
+
+__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) void lmpc_loop_advance_observed_kernel(const LmpcLoopDev L)
+{
+    extern __shared__ double lds[];
+    advance_observed(L, lds);
 }
 
 constexpr int kPackThreads = 256;
@@ -259,6 +417,65 @@ __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_plants_kernel(con
     }
 }
 
+// Head of a run of an observed loop: its blocks in the advance kernel's order.  The plant where it is one for the batch (from the row-major
+// `plant`: one tile, every instance of it the same), the estimator [A | B | Bd | L] and the measurement [C | Dd] from the handle's model or from
+// the model struct of each instance's controller, the gain from the one for the batch or from the caller's per-instance array.  A block with tile
+// stride 0 is one tile.
+__global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(const LmpcLoopDev L)
+{
+    const int nx = L.nx, nu = L.nu, ndu = L.ndu, ny = L.ny, B = L.batch, ipw = L.ipw;
+    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
+    const size_t tiles = (size_t)((B + ipw - 1) / ipw);
+    const int npl = nx + nu + ndu;
+    if (L.ok != L.pk) {
+        const size_t width = (size_t)ipw * nx, total = (size_t)npl * width;
+        const double *Ap = L.plant, *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
+        for (size_t idx = first; idx < total; idx += step) {
+            const int j = (int)(idx / width), i = (int)((idx - j * width) % nx);
+            gout(L.ok)[idx] = j < nx ? Ap[i * nx + j] : j < nx + nu ? Bp[i * nu + (j - nx)] : Dp[i * ndu + (j - nx - nu)];
+        }
+    }
+    {
+        const size_t width = (size_t)ipw * nx, per_tile = (size_t)(npl + ny) * width;
+        const size_t total = (L.ek_ts ? tiles : 1) * per_tile;
+        for (size_t idx = first; idx < total; idx += step) {
+            const size_t t = idx / per_tile, rem = idx - t * per_tile;
+            const int j = (int)(rem / width), qi = (int)(rem - j * width);
+            const int q = qi / nx, i = qi - q * nx;
+            const size_t b = L.ek_ts ? t * ipw + q : 0;
+            double v = 0.0;
+            if (b < (size_t)B) {
+                if (j >= npl) v = L.gain_batch ? gin(L.gain_batch)[(b * ny + (j - npl)) * nx + i] : L.gain[(j - npl) * nx + i];
+                else if (L.mA) v = j < nx ? L.mA[j * nx + i] : j < nx + nu ? L.mB[(j - nx) * nx + i] : L.mBd[(j - nx - nu) * nx + i];
+                else {
+                    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
+                    v = j < nx ? M.A[j * nx + i] : j < nx + nu ? M.B[(j - nx) * nx + i] : M.Bd[(j - nx - nu) * nx + i];
+                }
+            }
+            gout(L.ek)[idx] = v;
+        }
+    }
+    {
+        const size_t width = (size_t)ipw * ny, per_tile = (size_t)(nx + ndu) * width;
+        const size_t total = (L.mk_ts ? tiles : 1) * per_tile;
+        for (size_t idx = first; idx < total; idx += step) {
+            const size_t t = idx / per_tile, rem = idx - t * per_tile;
+            const int j = (int)(rem / width), qi = (int)(rem - j * width);
+            const int q = qi / ny, i = qi - q * ny;
+            const size_t b = L.mk_ts ? t * ipw + q : 0;
+            double v = 0.0;
+            if (b < (size_t)B) {
+                if (L.mC) v = j < nx ? L.mC[j * ny + i] : L.mDd[(j - nx) * ny + i];
+                else {
+                    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
+                    v = j < nx ? M.C[j * ny + i] : M.Dd[(j - nx) * ny + i];
+                }
+            }
+            gout(L.mk)[idx] = v;
+        }
+    }
+}
+
 inline int odd(int n) { return n | 1; }
 
 }  // namespace
@@ -267,14 +484,31 @@ void lmpc_loop_plan_lds(LmpcLoopDev &L)
 {
     L.sx = odd(L.nx); L.su = odd(L.nu); L.sd = L.ndu > 0 ? odd(L.ndu) : 0;
     L.ipw = L.nx < kTile ? kTile / L.nx : 1; L.sv = odd(L.nx + L.nu + L.ndu);
+    L.so = odd(2 * L.nx + L.nu + L.ndu + L.ny);
 }
 
 size_t lmpc_loop_packed_len(const LmpcLoopDev &L) { return (size_t)((L.batch + L.ipw - 1) / L.ipw) * (L.nx + L.nu + L.ndu) * L.ipw * L.nx; }
+
+size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles)
+{
+    const size_t terms = which == 0 ? L.nx + L.nu + L.ndu : which == 1 ? L.nx + L.nu + L.ndu + L.ny : L.nx + L.ndu;
+    return tiles * terms * L.ipw * (which == 2 ? L.ny : L.nx);
+}
+
+static size_t observed_lds_bytes(const LmpcLoopDev &L) { return (size_t)L.ipw * L.so * sizeof(double); }
 
 size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L) { return (size_t)kTile * (2 * L.sx + L.su + L.sd) * sizeof(double); }
 
 int lmpc_loop_prepare(const LmpcLoopDev &L)
 {
+    if (L.ek) {                                   // the observed kernel's tile: a few KB unless one instance has thousands of states
+        const size_t bytes = observed_lds_bytes(L);
+        if (bytes > lmpc_lds_limit()) return -2;
+        if (bytes > 48 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(lmpc_loop_advance_observed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+            return -3;
+        return 0;
+    }
     if (L.pk) return 0;                           // the per-instance kernel's tile: [x | cmd | d] of at most 64 instances of 1 state ... one of many
     const size_t bytes = lmpc_loop_lds_bytes(L);
     if (bytes > lmpc_lds_limit()) return -2;
@@ -302,8 +536,26 @@ int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream)
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream)
+{
+    if (!L.ek) return 0;
+    const size_t tiles = (size_t)((L.batch + L.ipw - 1) / L.ipw);
+    size_t n = lmpc_loop_block_len(L, 1, L.ek_ts ? tiles : 1);
+    if (lmpc_loop_block_len(L, 2, L.mk_ts ? tiles : 1) > n) n = lmpc_loop_block_len(L, 2, L.mk_ts ? tiles : 1);
+    size_t blocks = (n + kPackThreads - 1) / kPackThreads;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(lmpc_loop_pack_observer_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream)
 {
+    if (L.ek) {
+        const int tiles = (L.batch + L.ipw - 1) / L.ipw;
+        hipLaunchKernelGGL(lmpc_loop_advance_observed_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     if (L.pk) {
         const int tiles = (L.batch + L.ipw - 1) / L.ipw;
         const size_t lds = (size_t)L.ipw * L.sv * sizeof(double);

@@ -4,6 +4,8 @@
 // path here: without a usable HIP device every solve call fails with MPCX_E_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -768,6 +770,7 @@ struct mpcx_lmpc_loop {
 };
 
 int mpcx_lmpc_loop_desc_size(void) { return (int)sizeof(mpcx_lmpc_loop_desc); }
+int mpcx_lmpc_observer_desc_size(void) { return (int)sizeof(mpcx_lmpc_observer_desc); }
 
 // one tick -- the step of descriptor `b`, then the advance kernel -- captured on `s`
 static int capture_tick(const mpcx_lmpc_loop &l, const mpcx_lmpc_batch *b, hipStream_t s, hipGraphExec_t *exec)
@@ -803,10 +806,20 @@ static int check_loop_desc(const mpcx_lmpc_loop_desc *d)
     return MPCX_OK;
 }
 
+// what an observer must satisfy, likewise without a look at the owner's state; bank: its controllers differ, one gain cannot serve them all
+static int check_observer_desc(const mpcx_lmpc_observer_desc *o, bool bank)
+{
+    if (!o) return fail(MPCX_E_INVALID, "null observer: an observed loop needs an mpcx_lmpc_observer_desc");
+    if (o->gain && o->gain_batch) return fail(MPCX_E_INVALID, "gain (one gain for the batch) and gain_batch (a gain per instance) exclude each other");
+    if (bank && o->gain) return fail(MPCX_E_INVALID, "a bank's controllers differ: its observed loop takes gain_batch, not gain");
+    if (!o->gain && !o->gain_batch) return fail(MPCX_E_INVALID, "an observer needs gain or gain_batch");
+    return MPCX_OK;
+}
+
 // The loop of a controller (h) or of a bank (f, model_index), once the descriptor and the owner's state have been checked and the owner is set
-// up on the current device.  dm, active_words: the owner's.
+// up on the current device.  dm, active_words: the owner's.  o: the observer of an observed loop (checked), or null.
 static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words,
-                      const mpcx_lmpc_loop_desc *d, hipStream_t s, mpcx_lmpc_loop_t *out)
+                      const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, hipStream_t s, mpcx_lmpc_loop_t *out)
 {
     const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
     const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode};
@@ -816,7 +829,7 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     if (h) { l->device = h->device; l->setups = h->n_full_setups; } else l->device = f->device;
     mpcx::LmpcLoopDev &L = l->L;
     const size_t B = (size_t)d->batch, aw = (size_t)active_words;
-    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw;
+    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw; L.ny = dm.ny;
     mpcx::lmpc_loop_plan_lds(L);
     // which plant: one per instance (the caller's array; in a bank also the default, each instance's own controller), or one for the batch
     const bool uniform = d->plant_A || d->plant_B || d->plant_Bd;
@@ -835,6 +848,18 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
         if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
     const size_t o_pk = packed ? take(mpcx::lmpc_loop_packed_len(L) * sizeof(double)) : 0;
     const size_t o_down = own_d ? take(B * dm.ndu * sizeof(double)) : 0;
+    // an observed loop: the true state, and the packed blocks -- one tile where a block is the same for every instance (one plant for the batch; a
+    // controller's own model, with one gain; a controller's own outputs), else a tile per ipw instances
+    const size_t tiles = (B + L.ipw - 1) / L.ipw;
+    const bool est_shared = o && h && o->gain, meas_shared = o && h;
+    size_t o_xt = 0, o_ok = 0, o_ek = 0, o_mk = 0, o_gain = 0;
+    if (o) {
+        o_xt = take(B * dm.nx * sizeof(double));
+        if (!packed) o_ok = take(mpcx::lmpc_loop_block_len(L, 0, 1) * sizeof(double));
+        o_ek = take(mpcx::lmpc_loop_block_len(L, 1, est_shared ? 1 : tiles) * sizeof(double));
+        o_mk = take(mpcx::lmpc_loop_block_len(L, 2, meas_shared ? 1 : tiles) * sizeof(double));
+        if (o->gain) o_gain = take((size_t)dm.nx * dm.ny * sizeof(double));
+    }
     if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
     if (hipMemset(l->slab, 0, total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
     char *base = l->slab;
@@ -872,6 +897,18 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     L.traj_status = d->traj_status; L.traj_solver_status = d->traj_solver_status; L.traj_iterations = d->traj_iterations;
     L.traj_polish_rounds = d->traj_polish_rounds; L.traj_active_count = d->traj_active_count;
     L.state = reinterpret_cast<int *>(base + o_state);
+    if (o) {
+        L.xt = dp(o_xt);
+        if (packed) { L.ok = L.pk; L.ok_ts = (long)mpcx::lmpc_loop_block_len(L, 0, 1); } else L.ok = dp(o_ok);
+        L.ek = dp(o_ek); L.ek_ts = est_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 1, 1);
+        L.mk = dp(o_mk); L.mk_ts = meas_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 2, 1);
+        if (h) { L.mA = h->dev.A; L.mB = h->dev.B; L.mBd = h->dev.Bd; L.mC = h->dev.C; L.mDd = h->dev.Dd; }
+        if (o->gain) {
+            if (hipMemcpy(base + o_gain, o->gain, (size_t)dm.nx * dm.ny * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the observer gain failed");
+            L.gain = dp(o_gain);
+        }
+        L.gain_batch = o->gain_batch; L.xhat0 = o->xhat0; L.meas_noise = o->meas_noise; L.traj_xhat = o->traj_xhat; L.traj_y = o->traj_y;
+    }
 
     // the step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step
     mpcx_lmpc_batch cold{};
@@ -911,7 +948,7 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     if (pr != 0) return pr == -2 ? fail(MPCX_E_UNSUPPORTED, "the advance kernel's tiles exceed a compute unit's LDS") : fail(MPCX_E_DEVICE, "hipFuncSetAttribute failed");
     // one plain pass first, as mpcx_lmpc_graph_create does: it sizes the workspace and configures the kernels, none of which can be captured
     if (mpcx::lmpc_loop_begin(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
-    if (mpcx::lmpc_loop_pack_plants(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
+    if (mpcx::lmpc_loop_pack_plants(L, s) != 0 || mpcx::lmpc_loop_pack_observer(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
     int rc = l->solve(&cold, s);
     if (rc == MPCX_OK && mpcx::lmpc_loop_advance(L, s) != 0) rc = fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
     if (rc == MPCX_OK && two) rc = l->solve(&warm, s);
@@ -924,11 +961,13 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     return MPCX_OK;
 }
 
-int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
+// mpcx_lmpc_loop_create (observed false: o is not looked at) and mpcx_lmpc_loop_create_observed
+static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, bool observed, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
 {
     CHECK_H(h);
     if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
     int rc = check_loop_desc(d);
+    if (rc == MPCX_OK && observed) rc = check_observer_desc(o, false);
     if (rc != MPCX_OK) return rc;
     if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
     if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
@@ -936,13 +975,25 @@ int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *str
     rc = mpcx_lmpc_setup(h);
     if (rc != MPCX_OK) return rc;
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, observed ? o : nullptr, reinterpret_cast<hipStream_t>(stream), out);
 }
 
-int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
+int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return lmpc_loop_create(h, d, false, nullptr, stream, out);
+}
+
+int mpcx_lmpc_loop_create_observed(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return lmpc_loop_create(h, d, true, o, stream, out);
+}
+
+static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, bool observed, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
+                              void *stream, mpcx_lmpc_loop_t *out)
 {
     if (!f || !d || !out) return fail(MPCX_E_INVALID, "null argument");
     int rc = check_loop_desc(d);
+    if (rc == MPCX_OK && observed) rc = check_observer_desc(o, true);
     if (rc != MPCX_OK) return rc;
     if (!model_index && d->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
     // a bank keeps no host copy of its controllers' models: there is no "the controller's own" to complete a one-for-all plant with
@@ -950,7 +1001,90 @@ int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc
         return fail(MPCX_E_INVALID, "a bank's loop takes plant_A, plant_B and plant_Bd together (or plant_batch, or none: each instance's own controller)");
     if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
     if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, observed ? o : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+}
+
+int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return hetero_loop_create(f, d, false, nullptr, model_index, stream, out);
+}
+
+int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
+                                          void *stream, mpcx_lmpc_loop_t *out)
+{
+    return hetero_loop_create(f, d, true, o, model_index, stream, out);
+}
+
+// The steady-state Kalman predictor gain of the controller's own (A, C) by Riccati iteration (include/mpcx.h), host doubles throughout.
+int mpcx_lmpc_kalman_gain(mpcx_lmpc_t h, const double *Qw, const double *Rv, double *gain_out, double *P_out, int *iterations)
+{
+    CHECK_H(h);
+    if (!Qw || !Rv || !gain_out) return fail(MPCX_E_INVALID, "Qw, Rv and gain_out are required");
+    if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
+    using mpcx::Mat;
+    const int nx = h->ctl.d.nx, ny = h->ctl.d.ny;
+    const Mat &A = h->ctl.A, &Cm = h->ctl.C;
+    Mat Q(nx, nx), R(ny, ny);
+    std::memcpy(Q.a.data(), Qw, Q.a.size() * sizeof(double));
+    std::memcpy(R.a.data(), Rv, R.a.size() * sizeof(double));
+    auto symmetric = [](const Mat &M) {
+        double big = 0.0, skew = 0.0;
+        for (int j = 0; j < M.c; ++j)
+            for (int i = 0; i < M.r; ++i) { big = std::max(big, std::fabs(M(i, j))); skew = std::max(skew, std::fabs(M(i, j) - M(j, i))); }
+        return std::isfinite(big) && skew <= 1e-12 * big;
+    };
+    if (!symmetric(Q)) return fail(MPCX_E_INVALID, "Qw is not symmetric");
+    if (!symmetric(R)) return fail(MPCX_E_INVALID, "Rv is not symmetric");
+    { Mat Rc = R; if (!(mpcx::cholesky_lower(Rc) > 0.0)) return fail(MPCX_E_INVALID, "Rv is not positive definite"); }
+    const Mat At = mpcx::transpose(A), Ct = mpcx::transpose(Cm);
+    // K = A P C', S = C P C' + Rv, gain = K S^-1 (S symmetric positive definite: by its Cholesky factor, row by row of K)
+    auto gain_of = [&](const Mat &P, Mat &K, Mat &G) {
+        const Mat PCt = mpcx::matmul(P, Ct);
+        K = mpcx::matmul(A, PCt);
+        Mat S = mpcx::matmul(Cm, PCt);
+        for (int j = 0; j < ny; ++j)
+            for (int i = 0; i < ny; ++i) S(i, j) = 0.5 * (S(i, j) + S(j, i)) + R(i, j);
+        for (int j = 0; j < ny; ++j)
+            for (int i = 0; i < j; ++i) S(i, j) = S(j, i);
+        if (!(mpcx::cholesky_lower(S) > 0.0)) return false;
+        G = Mat(nx, ny);
+        std::vector<double> z(ny);
+        for (int r = 0; r < nx; ++r) {           // S g = k for row r of K: forward with the factor, back with its transpose
+            for (int i = 0; i < ny; ++i) { double v = K(r, i); for (int j = 0; j < i; ++j) v -= S(i, j) * z[j]; z[i] = v / S(i, i); }
+            for (int i = ny - 1; i >= 0; --i) { double v = z[i]; for (int j = i + 1; j < ny; ++j) v -= S(j, i) * z[j]; z[i] = v / S(i, i); }
+            for (int i = 0; i < ny; ++i) G(r, i) = z[i];
+        }
+        return true;
+    };
+    constexpr int kMaxRiccati = 100000;
+    Mat P = Q, K, G;
+    int it = 0;
+    bool converged = false;
+    for (; it < kMaxRiccati && !converged; ++it) {
+        if (!gain_of(P, K, G)) return fail(MPCX_E_NUMERIC, "C P C' + Rv does not factor");
+        Mat Pn = mpcx::matmul(mpcx::matmul(A, P), At);
+        const Mat GKt = mpcx::matmul(G, mpcx::transpose(K));
+        for (size_t e = 0; e < Pn.a.size(); ++e) Pn.a[e] += Q.a[e] - GKt.a[e];
+        double big = 0.0, change = 0.0;
+        bool finite = true;
+        for (int j = 0; j < nx; ++j)
+            for (int i = 0; i <= j; ++i) {
+                const double v = 0.5 * (Pn(i, j) + Pn(j, i));
+                Pn(i, j) = v; Pn(j, i) = v;
+                finite = finite && std::isfinite(v);
+                big = std::max(big, std::fabs(v));
+                change = std::max(change, std::fabs(v - P(i, j)));
+            }
+        if (!finite) return fail(MPCX_E_NUMERIC, "the Riccati iteration diverged: is (A, C) detectable?");
+        converged = change <= 1e-14 * big;
+        P = Pn;
+    }
+    if (iterations) *iterations = it;
+    if (!converged) return fail(MPCX_E_NUMERIC, "the Riccati iteration has not converged after 100000 steps: is (A, C) detectable?");
+    if (!gain_of(P, K, G)) return fail(MPCX_E_NUMERIC, "C P C' + Rv does not factor");
+    std::memcpy(gain_out, G.a.data(), G.a.size() * sizeof(double));
+    if (P_out) std::memcpy(P_out, P.a.data(), P.a.size() * sizeof(double));
+    return MPCX_OK;
 }
 
 static int loop_usable(mpcx_lmpc_loop_t l)
@@ -969,7 +1103,7 @@ int mpcx_lmpc_loop_run(mpcx_lmpc_loop_t l, void *stream)
     if (rc != MPCX_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (mpcx::lmpc_loop_begin(l->L, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
-    if (mpcx::lmpc_loop_pack_plants(l->L, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
+    if (mpcx::lmpc_loop_pack_plants(l->L, stream) != 0 || mpcx::lmpc_loop_pack_observer(l->L, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
     for (int k = 0; k < l->ticks; ++k)
         if (hipGraphLaunch(k > 0 && l->next ? l->next : l->first, s) != hipSuccess) return fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
     return MPCX_OK;

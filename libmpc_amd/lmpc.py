@@ -122,7 +122,8 @@ class BatchResult:
 @dataclass
 class ClosedLoopResult:
     """A closed-loop run on the device (LMPC.simulate), tick-major device tensors: x [ticks+1, B, nx] (row 0 = the initial
-    state), u [ticks, B, nu], the others [ticks, B]."""
+    state), u [ticks, B, nu], the others [ticks, B].  An observed loop (observer=) also fills xhat [ticks+1, B, nx], the estimates
+    the solves read (row 0 = xhat0), and y [ticks, B, ny], the measurements; x is then the plant's true state."""
     x: "object"
     u: "object"
     cost: "object"
@@ -131,17 +132,23 @@ class ClosedLoopResult:
     iterations: "object"
     polish_rounds: "object"
     active_count: "object"
+    xhat: "object" = None
+    y: "object" = None
 
 
 @dataclass
 class Loop:
     """a loop made by LMPC.make_loop / LMPCHetero.make_loop: the native handle, the result whose tensors every run fills, the tensors the graph
-    points at, and (plants=) the per-instance plants as every run reads them, [B, nx (nx+nu+ndu)] in LMPC.pack_plants' layout"""
+    points at, and (plants=) the per-instance plants as every run reads them, [B, nx (nx+nu+ndu)] in LMPC.pack_plants' layout.  An observed
+    loop: gains (per-instance observer=) [B, nx ny] in LMPC.pack_gains' layout, xhat0 and meas_noise as every run reads them (refill in place)"""
     handle: "object"
     result: ClosedLoopResult
     ticks: int
     keep: tuple = ()
     plants: "object" = None
+    gains: "object" = None
+    xhat0: "object" = None
+    meas_noise: "object" = None
 
 
 def _cm(a, rows, cols):
@@ -182,6 +189,7 @@ class LMPC:
         check(self._lib.mpcx_lmpc_create(C.byref(d), self.device, C.byref(self._h)))
         self._A = self._B = None                                 # the model as given, for loops whose plants default to it
         self._Bd = np.zeros((self.nx, self.ndu))
+        self._C, self._Dd = None, np.zeros((self.ny, self.ndu))               # the outputs as given: what an observed loop measures with
         self._last = Result(cmd=np.zeros(self.nu))
         self._stats = SolutionStats()
         self._last_u0 = np.zeros(self.nu)
@@ -233,14 +241,14 @@ class LMPC:
         A, B, Cm = _cm(A, self.nx, self.nx), _cm(B, self.nx, self.nu), _cm(Cm, self.ny, self.nx)
         ok = self._ok(self._lib.mpcx_lmpc_set_state_space_model(self._h, _p(A), _p(B), _p(Cm)))
         if ok:
-            self._A, self._B = A.copy(), B.copy()
+            self._A, self._B, self._C = A.copy(), B.copy(), Cm.copy()
         return ok
 
     def setDisturbances(self, Bd, Dd):
         Bd, Dd = _cm(Bd, self.nx, self.ndu), _cm(Dd, self.ny, self.ndu)
         ok = self._ok(self._lib.mpcx_lmpc_set_disturbances(self._h, _p(Bd), _p(Dd)))
         if ok:
-            self._Bd = Bd.copy()
+            self._Bd, self._Dd = Bd.copy(), Dd.copy()
         return ok
 
     def setObjectiveWeights(self, OWeight, UWeight, DeltaUWeight, slice=None):
@@ -491,6 +499,42 @@ class LMPC:
                 raise ValueError(f"plants: {name} must be [{B},{self.nx},{cols}], got {tuple(np.shape(m))}")
         return plants
 
+    def _check_observer(self, B, ticks, observer, xhat0, meas_noise, bank=False):
+        """observer= ([nx, ny] one gain, [B, nx, ny] a gain per instance), xhat0= and meas_noise=, their shapes checked -- on the host, ahead of
+        any device call; True for a gain per instance"""
+        def shape(a):
+            return tuple((a if hasattr(a, "shape") else np.asarray(a)).shape)
+        if observer is None:
+            if xhat0 is not None or meas_noise is not None:
+                raise ValueError("xhat0= and meas_noise= belong to an observed loop: give observer=")
+            return False
+        sh = shape(observer)
+        if sh not in ((self.nx, self.ny), (B, self.nx, self.ny)):
+            raise ValueError(f"observer must be [{self.nx},{self.ny}] or [{B},{self.nx},{self.ny}], got {sh}")
+        if bank and len(sh) == 2:
+            raise ValueError(f"a bank's controllers differ: observer must be a gain per instance, [{B},{self.nx},{self.ny}]")
+        if xhat0 is not None and shape(xhat0) != (B, self.nx):
+            raise ValueError(f"xhat0 must be [{B},{self.nx}], got {shape(xhat0)}")
+        if meas_noise is not None and shape(meas_noise) != (ticks, B, self.ny):
+            raise ValueError(f"meas_noise must be [{ticks},{B},{self.ny}], got {shape(meas_noise)}")
+        return len(sh) == 3
+
+    @staticmethod
+    def pack_gains(L):
+        """[B, nx ny]: per instance L_b column-major -- mpcx_lmpc_observer_desc.gain_batch; a torch tensor [B, nx, ny] in, a tensor out
+        (what to copy_ into Loop.gains for the next run)"""
+        return L.transpose(1, 2).reshape(L.shape[0], L.shape[1] * L.shape[2]).contiguous()
+
+    def kalman_gain(self, Qw, Rv, want_P=False):
+        """The steady-state Kalman predictor gain L [nx, ny] of the controller's own (A, C) for process-noise covariance Qw [nx, nx] and
+        sensor-noise covariance Rv [ny, ny] (mpcx_lmpc_kalman_gain: Riccati iteration on the host; works on a host-only handle).
+        want_P: (L, P, iterations) instead."""
+        Q, R = _cm(Qw, self.nx, self.nx), _cm(Rv, self.ny, self.ny)
+        L, P = np.zeros((self.nx, self.ny), order="F"), np.zeros((self.nx, self.nx), order="F")
+        it = C.c_int(0)
+        check(self._lib.mpcx_lmpc_kalman_gain(self._h, _p(Q), _p(R), _p(L), _p(P), C.byref(it)))
+        return (L, P, it.value) if want_P else L
+
     def _own_plant(self, B, model=None):
         """the controller's own A, B, Bd for B instances (numpy, broadcast)"""
         if self._A is None:
@@ -505,12 +549,15 @@ class LMPC:
         n = A.shape[0]
         return torch.cat([m.transpose(1, 2).reshape(n, m.shape[1] * m.shape[2]) for m in (A, B, Bd)], dim=1).contiguous()
 
-    def _make_loop(self, create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None):
-        """the descriptor of a loop, its result tensors and the create call: shared by LMPC and LMPCHetero (whose `create` takes the model index)"""
+    def _make_loop(self, create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None,
+                   observer=None, xhat0=None, meas_noise=None, bank=False):
+        """the descriptor of a loop, its result tensors and the create call: shared by LMPC and LMPCHetero (whose `create` takes the model index);
+        `create` is given the observer's descriptor, or None for an unobserved loop"""
         ticks = int(ticks)
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
         plants = self._check_plants(B, plant, plants)
+        per_instance_gain = self._check_observer(B, ticks, observer, xhat0, meas_noise, bank)
         torch, dev = self._torch()
         x0 = self._dev(torch, dev, x0, (B, self.nx))
         u0 = self._dev(torch, dev, lastU, (B, self.nu))
@@ -551,18 +598,32 @@ class LMPC:
         d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
         d.traj_status, d.traj_solver_status, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.iterations)
         d.traj_polish_rounds, d.traj_active_count = ptr(res.polish_rounds), ptr(res.active_count)
+        od, gains, gain_h, xh, v = None, None, None, None, None
+        if observer is not None:
+            od = _capi.ObserverDesc()
+            if per_instance_gain:
+                gains = self.pack_gains(self._dev(torch, dev, observer, (B, self.nx, self.ny)))
+                od.gain_batch = ptr(gains)
+            else:
+                gain_h = _cm(observer.cpu().numpy() if isinstance(observer, torch.Tensor) else observer, self.nx, self.ny)
+                od.gain = gain_h.ctypes.data
+            xh = self._dev(torch, dev, xhat0, (B, self.nx))
+            v = self._dev(torch, dev, meas_noise, (ticks, B, self.ny))
+            res.xhat = torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev)
+            res.y = torch.zeros((T, B, self.ny), dtype=f64, device=dev)
+            od.xhat0, od.meas_noise, od.traj_xhat, od.traj_y = ptr(xh), ptr(v), ptr(res.xhat), ptr(res.y)
         cur = torch.cuda.current_stream(self.device)
         s = stream if stream is not None else torch.cuda.Stream(device=dev)
         if s.cuda_stream == 0:
             raise ValueError("a loop is captured on a non-default stream")
         s.wait_stream(cur)                      # the tensors above were filled on the current stream
         h = C.c_void_p()
-        check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h), None if od is None else C.byref(od)))
         cur.wait_stream(s)
-        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb), pb)
+        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v), pb, gains, xh, v)
 
     def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                  noise=None, warm=True, stream=None, plants=None) -> Loop:
+                  noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None) -> Loop:
         """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by
         the plant step x <- A_p x + B_p cmd + Bd_p d_k + w_k on the device, with no host work in between.
 
@@ -571,10 +632,18 @@ class LMPC:
         controller's -- packed into Loop.plants, which every run reads again (refill it in place: LMPC.pack_plants);
         noise: [ticks, B, nx] additive process disturbance the controller does not know about; warm: carry each tick's
         working set into the next tick's solve (tick 0 is cold); preview: 3-D references are [B, ticks+ph, n] windows.
-        x0 / lastU are read again by every run_loop: tensors given here can be refilled in place (Loop.keep[0], [1])."""
-        def create(d, s, out):
-            return self._lib.mpcx_lmpc_loop_create(self._h, d, s, out)
-        return self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream)
+        x0 / lastU are read again by every run_loop: tensors given here can be refilled in place (Loop.keep[0], [1]).
+
+        observer: output feedback.  The solves then read an estimate xhat instead of the state: each tick measures y = C x + Dd d_k + v_k and
+        updates xhat <- A xhat + B cmd + Bd d_k + L (y - C xhat - Dd d_k) with the controller's own model.  observer is the gain L, [nx, ny]
+        for the batch (LMPC.kalman_gain) or [B, nx, ny] per instance (Loop.gains, refill with LMPC.pack_gains); xhat0: [B, nx], the first
+        estimate (None: x0); meas_noise: [ticks, B, ny] sensor noise v_k.  The result's xhat and y are then filled, and x is the true state."""
+        def create(d, s, out, od):
+            if od is None:
+                return self._lib.mpcx_lmpc_loop_create(self._h, d, s, out)
+            return self._lib.mpcx_lmpc_loop_create_observed(self._h, d, od, s, out)
+        return self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream,
+                               observer=observer, xhat0=xhat0, meas_noise=meas_noise)
 
     def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
         """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
@@ -593,9 +662,10 @@ class LMPC:
             loop.handle = None
 
     def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                 noise=None, warm=True, stream=None, plants=None) -> ClosedLoopResult:
+                 noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
-        loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm, plants=plants)
+        loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm, plants=plants,
+                              observer=observer, xhat0=xhat0, meas_noise=meas_noise)
         torch, _ = self._torch()
         try:
             self.run_loop(loop, stream)

@@ -6,7 +6,9 @@ run alternately; each line gives both legs' ms per tick (median, min, max), poli
 The bank leg (lines with "bank": true) is the same comparison for B different controllers (quadrotor_variant(k), the lmpc-hetero workload of
 bench.py): the host-driven loop is LMPCHetero.optimizeBatch plus a batched torch bmm plant step per tick, the device loop is
 LMPCHetero.make_loop / run_loop, every instance stepped by its own controller's model.
-Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|all]"""
+The observed leg (lines with "observed": true; not part of "all") is the device loop with output feedback beside the device loop without, the same
+build and the same inputs, run alternately: the observer's gain is LMPC.kalman_gain(0.01 I, 0.04 I), the sensor noise has standard deviation 0.2.
+Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|observed|all]"""
 import json
 import sys
 import time
@@ -45,6 +47,15 @@ def make_device(B, ticks, warm):
     c = quadrotor_lmpc(20, device=0)
     x0, u0, yref = quadrotor_batch(B)
     return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm)
+
+
+def make_observed(B, ticks, warm):
+    """the device loop of the same run with a Kalman predictor between plant and controller: (controller, loop)"""
+    c = quadrotor_lmpc(20, device=0)
+    x0, u0, yref = quadrotor_batch(B)
+    L = c.kalman_gain(0.01 * np.eye(c.nx), 0.04 * np.eye(c.ny))
+    v = 0.2 * np.random.default_rng(1).normal(size=(ticks, B, c.ny))
+    return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm, observer=L, meas_noise=v)
 
 
 def run_device(c, loop):
@@ -117,6 +128,20 @@ if __name__ == "__main__":
                               host_mean_rounds=host[-1]["mean_rounds"], device_mean_rounds=dev[-1]["mean_rounds"],
                               host_solved=host[-1]["solved"], device_solved=dev[-1]["solved"])))
         c.destroy_loop(loop)
+    for w in (False, True) if legs == "observed" else ():
+        c, loop = make_device(B, ticks, w)
+        co, loopo = make_observed(B, ticks, w)
+        run_device(c, loop); run_device(co, loopo)            # warm-up of both legs
+        plain, obs = [], []
+        for _ in range(repeats):                              # alternating, as above
+            plain.append(run_device(c, loop)); obs.append(run_device(co, loopo))
+        pm, plo, phi = median_spread([r["ms_per_tick"] for r in plain])
+        om, olo, ohi = median_spread([r["ms_per_tick"] for r in obs])
+        print(json.dumps(dict(observed=True, warm=w, batch=B, ticks=ticks, repeats=repeats,
+                              unobserved_ms_per_tick=dict(median=pm, min=plo, max=phi), observed_ms_per_tick=dict(median=om, min=olo, max=ohi),
+                              unobserved_mean_rounds=plain[-1]["mean_rounds"], observed_mean_rounds=obs[-1]["mean_rounds"],
+                              unobserved_solved=plain[-1]["solved"], observed_solved=obs[-1]["solved"])))
+        c.destroy_loop(loop); co.destroy_loop(loopo)
     if legs in ("bank", "all"):
         het, (x0, u0, yref), dev = make_bank(B)
         run_bank(het, dev, 5, True)
