@@ -506,6 +506,48 @@ int mpcx_nlmpc_loop_desc_size(void);            /* sizeof(mpcx_nlmpc_loop_desc) 
 int mpcx_nlmpc_plant_step_batch(mpcx_nlmpc_t h, int batch, const double *x, const double *u, const double *params,
                                 const double *noise /* [B x nx] or NULL */, int substeps, double *x_next, void *stream);
 
+/* ---- NLMPC closed loop with output feedback: an extended Kalman filter in the advance step ---------------------------------
+ * An observed loop carries the truth x, the estimate xhat and its covariance P [nx x nx] per instance.  The estimate is the loop's
+ * state buffer: the solve of tick k reads xhat_k, and the descriptors of the solve are untouched.  With Phi the noise-free plant
+ * step above, the advance kernel of tick k computes, all from tick-k data,
+ *   x_{k+1}    = Phi(x_k, cmd_k, p_plant) + w_k             as in the unobserved loop (plant_params, else params, else the controller's)
+ *   y_{k+1}    = Cm x_{k+1} + v_k                           v: meas_noise
+ *   xhat-      = Phi(xhat_k, cmd_k, p_ctrl)                 p_ctrl: the instance's row of params, else the controller's -- never plant_params
+ *   F[:, j]    = (Phi(xhat_k + h_j e_j) - Phi(xhat_k - h_j e_j)) / (x+_j - x-_j),  h_j = 2^-17 max(1, |xhat_k,j|); the divisor is the
+ *                difference of the two perturbed values as stored, not 2 h_j
+ *   P-         = F P_k F' + Q;   S = Cm P- Cm' + R;   K = P- Cm' S^-1 (Cholesky of S)
+ *   xhat_{k+1} = xhat- + K (y_{k+1} - Cm xhat-)
+ *   P_{k+1}    = sym((I - K Cm) P- (I - K Cm)' + K R K')    Joseph form, then (P + P') / 2
+ * States are in physical units.  If a pivot of S is not > 0 or not finite (tested before the square root and any division), the
+ * update of that tick is skipped: xhat_{k+1} = xhat-, P_{k+1} = sym(P-), and bit 0 of the instance's ekf_flags word is set; every
+ * run clears the flags first.  No NaN is written on that account and the loop goes on.
+ * Cm, Q, R, P0 are HOST arrays, column-major, one for the batch, copied at creation; Cm = NULL is the identity with ny = nx.  Built-in
+ * systems only (hook models: MPCX_E_UNSUPPORTED); the measurement is linear; per-instance Q / R / P0 and unscented or iterated filters
+ * are not provided. */
+typedef struct mpcx_nlmpc_ekf_desc {
+    int ny;                         /* measurements per instance, 1 .. nx */
+    const double *Cm;               /* host [ny x nx] or NULL (identity, ny = nx) */
+    const double *Q, *R, *P0;       /* host [nx x nx], [ny x ny], [nx x nx] */
+    const double *xhat0;            /* device [B x nx] or NULL (x0); read again by every run */
+    const double *meas_noise;       /* device [ticks x B x ny] or NULL; read again by every run */
+    double *traj_xhat, *traj_y;     /* device, required: [(ticks+1) x B x nx] (row 0 = xhat0), [ticks x B x ny] (row k = y_{k+1}) */
+    double *traj_P;                 /* device [(ticks+1) x B x nx nx] or NULL */
+    int32_t *ekf_flags;             /* device [B] or NULL */
+} mpcx_nlmpc_ekf_desc;
+/* mpcx_nlmpc_loop_create with the filter `e` in the advance step.  `d` means what it means there (traj_x is the truth); the loop is
+ * the same type: mpcx_nlmpc_loop_run, _destroy and the debug calls serve it, `warm` and the invalidation by a setter are unchanged. */
+int mpcx_nlmpc_loop_create_observed(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, const mpcx_nlmpc_ekf_desc *e, void *stream,
+                                    mpcx_nlmpc_loop_t *out);
+int mpcx_nlmpc_ekf_desc_size(void);             /* sizeof(mpcx_nlmpc_ekf_desc) as the library was built */
+/* The filter step of that loop alone, the sibling of mpcx_nlmpc_plant_step_batch for callers who drive the loop themselves: from device
+ * xhat [B x nx], P [B x nx nx], u [B x nu] and the measurement y [B x ny] of the new state to device xhat_next, P_next and flags [B]
+ * (0, or 1 where the update was skipped); xhat_next may be xhat and P_next may be P.  params: device [B x n_params] or NULL (the
+ * controller's); Cm (or NULL), Q, R: host, as above.  The same device function as the observed loop's advance kernel: the two agree bit
+ * for bit.  The matrices are staged through a buffer of the controller: one call of a controller in flight at a time. */
+int mpcx_nlmpc_ekf_step_batch(mpcx_nlmpc_t h, int batch, const double *xhat, const double *P, const double *u, const double *y,
+                              const double *params, const double *Cm, const double *Q, const double *R, int ny, int substeps,
+                              double *xhat_next, double *P_next, int32_t *flags, void *stream);
+
 /* ---- set-up utility -------------------------------------------------------- */
 /* mpc::discretization<nx, nu>(A, B, Ts, Ad, Bd) (Utils.hpp:23-47) for a batch of continuous-time models on the
  * device: [Ad Bd; 0 I] = exp([[A B]; [0 0]] Ts).  Device pointers, column-major matrices per instance

@@ -2,6 +2,7 @@
 // run -- the caller's loop of the reference examples (examples/vanderpol_ex.cpp:76-85, ugv_ex.cpp) -- on the device, so that a tick is
 // "solve, advance" with no host work in between.
 //
+//   loop_plant_reg<Mdl>     the noise-free step from registers to registers (shared with mpcx/nlmpc_ekf.hpp)
 //   loop_plant_lane<Mdl>    the plant step of one instance in registers: x <- f(x, cmd, p) for a discrete model, `substeps` forward-Euler
 //                           steps x <- x + (Ts / substeps) f(x, cmd, p) for a continuous one, then x += w
 //   loop_advance_tile<Mdl>  tick k of a tile of 64 instances, lane <-> instance: the plant step, u <- cmd, row k + 1 of traj_x, row k of
@@ -47,19 +48,15 @@ template <class T> __device__ __forceinline__ T __attribute__((address_space(1))
     return (T __attribute__((address_space(1))) *)p;
 }
 
-// x [NX] <- the plant's next state from xin [NX], u [NU] <- uin [NU]; w: the instance's process disturbance [NX] or null.  One function
-// for the loop and for the stand-alone step: the two agree bit for bit (the Euler update is spelled as the fused multiply-add the
-// compiler would make of it, so that no instantiation rounds differently from another)
+// x [NX] <- the noise-free step of the plant from x, with the command u [NU], both in registers: f for a discrete model, `substeps`
+// forward-Euler steps for a continuous one (the Euler update is spelled as the fused multiply-add the compiler would make of it, so
+// that no instantiation rounds differently from another).  Shared by the lane <-> instance kernels below and by the extended Kalman
+// filter of mpcx/nlmpc_ekf.hpp, whose lanes each evaluate it at a point of their own
 template <class Mdl>
-__device__ __forceinline__ void loop_plant_lane(const NlmpcDev &M, const double *xin, const double *uin, const double *p, const double *w,
-                                                const int substeps, double (&x)[Mdl::NX], double (&u)[Mdl::NU])
+__device__ __forceinline__ void loop_plant_reg(const NlmpcDev &M, const double *p, const int substeps, double (&x)[Mdl::NX], const double (&u)[Mdl::NU])
 {
-    constexpr int NX = Mdl::NX, NU = Mdl::NU;
+    constexpr int NX = Mdl::NX;
     double dx[NX];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) x[j] = loop_gin(xin)[j];
-#pragma unroll
-    for (int j = 0; j < NU; ++j) u[j] = loop_gin(uin)[j];
     if (is_ct<Mdl>(M)) {
         const double h = M.Ts / (double)substeps;
         for (int s = 0; s < substeps; ++s) {
@@ -72,6 +69,20 @@ __device__ __forceinline__ void loop_plant_lane(const NlmpcDev &M, const double 
 #pragma unroll
         for (int j = 0; j < NX; ++j) x[j] = dx[j];
     }
+}
+
+// x [NX] <- the plant's next state from xin [NX], u [NU] <- uin [NU]; w: the instance's process disturbance [NX] or null.  One function
+// for the loop and for the stand-alone step: the two agree bit for bit
+template <class Mdl>
+__device__ __forceinline__ void loop_plant_lane(const NlmpcDev &M, const double *xin, const double *uin, const double *p, const double *w,
+                                                const int substeps, double (&x)[Mdl::NX], double (&u)[Mdl::NU])
+{
+    constexpr int NX = Mdl::NX, NU = Mdl::NU;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) x[j] = loop_gin(xin)[j];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) u[j] = loop_gin(uin)[j];
+    loop_plant_reg<Mdl>(M, p, substeps, x, u);
     if (w) {
 #pragma unroll
         for (int j = 0; j < NX; ++j) x[j] += loop_gin(w)[j];

@@ -92,6 +92,7 @@ EXPORTS = [
     "mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice", "mpcx_nlmpc_solve_host",
     "mpcx_nlmpc_create_custom", "mpcx_nlmpc_create_from_source", "mpcx_nlmpc_set_input_scale", "mpcx_nlmpc_set_state_scale",
     "mpcx_nlmpc_loop_create", "mpcx_nlmpc_loop_run", "mpcx_nlmpc_loop_destroy", "mpcx_nlmpc_loop_desc_size", "mpcx_nlmpc_plant_step_batch",
+    "mpcx_nlmpc_loop_create_observed", "mpcx_nlmpc_ekf_desc_size", "mpcx_nlmpc_ekf_step_batch",
     "mpcx_comm_get_unique_id", "mpcx_comm_create", "mpcx_comm_destroy", "mpcx_comm_rank", "mpcx_comm_world", "mpcx_allgather_u",
     "mpcx_lmpc_hetero_create", "mpcx_lmpc_hetero_destroy", "mpcx_lmpc_hetero_get_info", "mpcx_lmpc_hetero_solve_batch",
     "mpcx_lmpc_hetero_time_solve_batch", "mpcx_lmpc_hetero_create_ex", "mpcx_lmpc_hetero_debug_get", "mpcx_lmpc_hetero_loop_create",
@@ -125,6 +126,13 @@ class NlmpcLoopDesc(C.Structure):
                 ("traj_x", C.c_void_p), ("traj_u", C.c_void_p), ("traj_cost", C.c_void_p),
                 ("traj_status", C.c_void_p), ("traj_solver_status", C.c_void_p), ("traj_is_feasible", C.c_void_p),
                 ("traj_iterations", C.c_void_p)]
+
+
+class NlmpcEkfDesc(C.Structure):
+    """mpcx_nlmpc_ekf_desc: the extended Kalman filter of an observed NLMPC loop (Cm, Q, R, P0 are host pointers, everything else device pointers)"""
+    _fields_ = [("ny", C.c_int), ("Cm", C.c_void_p), ("Q", C.c_void_p), ("R", C.c_void_p), ("P0", C.c_void_p),
+                ("xhat0", C.c_void_p), ("meas_noise", C.c_void_p), ("traj_xhat", C.c_void_p), ("traj_y", C.c_void_p),
+                ("traj_P", C.c_void_p), ("ekf_flags", C.c_void_p)]
 
 
 class NlmpcDims(C.Structure):
@@ -195,6 +203,8 @@ def lib():
         _lib.mpcx_nlmpc_loop_debug_replay.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_loop_debug_tick.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_plant_step_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+        _lib.mpcx_nlmpc_loop_create_observed.argtypes = [C.c_void_p] * 5
+        _lib.mpcx_nlmpc_ekf_step_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         _lib.mpcx_comm_get_unique_id.argtypes = [C.c_void_p]
         _lib.mpcx_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.mpcx_comm_destroy.argtypes = [C.c_void_p]

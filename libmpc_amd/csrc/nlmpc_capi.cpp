@@ -8,6 +8,7 @@
 
 #include "../../include/mpcx.h"
 #include "mpcx/nlmpc_device.hpp"
+#include "mpcx/nlmpc_ekf.hpp"
 #include "mpcx/nlmpc_loop.hpp"
 
 namespace mpcx {
@@ -31,6 +32,10 @@ int nlmpc_loop_begin(const NlmpcDev *m, const NlmpcLoopDev *L, void *stream);
 int nlmpc_loop_advance(const NlmpcDev *m, const NlmpcLoopDev *L, void *stream);
 int nlmpc_plant_step(const NlmpcDev *m, int batch, const double *x, const double *u, const double *params, int nparams, const double *noise,
                      int substeps, double *x_next, void *stream);
+int nlmpc_ekf_begin(const NlmpcDev *m, const NlmpcLoopDev *L, const NlmpcEkfDev *E, void *stream);
+int nlmpc_ekf_advance(const NlmpcDev *m, const NlmpcLoopDev *L, const NlmpcEkfDev *E, void *stream);
+int nlmpc_ekf_step(const NlmpcDev *m, int batch, const double *xhat, const double *P, const double *u, const double *y, const double *params, int nparams,
+                   const double *cb, int ny, int substeps, double *xhat_next, double *P_next, int *flags, void *stream);
 }
 
 struct mpcx_nlmpc {
@@ -60,6 +65,8 @@ struct mpcx_nlmpc {
     std::vector<double> lb, ub;
     bool bounds_dirty = true;
     void *bnd_block = nullptr;  // one allocation: zlb | zub | bnd_val | bnd_sign | bnd_idx
+    double *ekf_cb = nullptr;   // mpcx_nlmpc_ekf_step_batch: where the call's Cm | Q | R are staged (at most 3 nx nx doubles) ...
+    std::vector<double> ekf_cb_host;    // ... and the host array they are copied from, which outlives the call
 
     int sync_scale()
     {
@@ -227,6 +234,7 @@ int mpcx_nlmpc_destroy(mpcx_nlmpc_t h)
     if (h->zoo) mpcx::nlmpc_zoo_free(h->zoo);
     if (h->ws) (void)hipFree(h->ws);
     if (h->bnd_block) (void)hipFree(h->bnd_block);
+    if (h->ekf_cb) (void)hipFree(h->ekf_cb);
     delete h;
     return MPCX_OK;
 }
@@ -455,6 +463,10 @@ struct mpcx_nlmpc_loop {
     int device = 0, ticks = 0;
     unsigned long gen = 0;                       // the owner's set-up generation when the graphs were captured
     mpcx::NlmpcLoopDev L{};
+    bool observed = false;                       // an extended Kalman filter in the advance step (mpcx_nlmpc_loop_create_observed): E is in use
+    mpcx::NlmpcEkfDev E{};
+    int begin(void *s) const { return observed ? mpcx::nlmpc_ekf_begin(&owner->dev, &L, &E, s) : mpcx::nlmpc_loop_begin(&owner->dev, &L, s); }
+    int advance(void *s) const { return observed ? mpcx::nlmpc_ekf_advance(&owner->dev, &L, &E, s) : mpcx::nlmpc_loop_advance(&owner->dev, &L, s); }
     hipGraphExec_t first = nullptr, next = nullptr;   // tick 0; every later tick (null: the same graph serves all)
     char *slab = nullptr;                        // every private buffer of the loop, one allocation
     ~mpcx_nlmpc_loop()
@@ -466,6 +478,7 @@ struct mpcx_nlmpc_loop {
 };
 
 int mpcx_nlmpc_loop_desc_size(void) { return (int)sizeof(mpcx_nlmpc_loop_desc); }
+int mpcx_nlmpc_ekf_desc_size(void) { return (int)sizeof(mpcx_nlmpc_ekf_desc); }
 
 static bool nl_is_hook_model(const mpcx_nlmpc *h) { return h->launch_solve != mpcx::nlmpc_launch_solve || h->dev.model_id == 0; }
 
@@ -475,7 +488,7 @@ static int nl_capture_tick(const mpcx_nlmpc_loop &l, const mpcx_nlmpc_batch *b, 
     using mpcx::capi_fail;
     if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipStreamBeginCapture failed");
     int rc = mpcx_nlmpc_solve_batch(l.owner, b, s);
-    const int la = rc == MPCX_OK ? mpcx::nlmpc_loop_advance(&l.owner->dev, &l.L, s) : 0;
+    const int la = rc == MPCX_OK ? l.advance(s) : 0;
     hipGraph_t graph = nullptr;
     const hipError_t ec = hipStreamEndCapture(s, &graph);
     if (rc == MPCX_OK && la != 0) rc = capi_fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
@@ -485,7 +498,20 @@ static int nl_capture_tick(const mpcx_nlmpc_loop &l, const mpcx_nlmpc_batch *b, 
     return rc;
 }
 
-int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *stream, mpcx_nlmpc_loop_t *out)
+// the filter's constant block Cm | Q | R (| P0) as the kernels read it; Cm = null: the identity.  False: an entry is not finite
+static bool nl_ekf_block(int nx, int ny, const double *Cm, const double *Q, const double *R, const double *P0, std::vector<double> &cb)
+{
+    cb.clear();
+    for (int i = 0; i < ny * nx; ++i) cb.push_back(Cm ? Cm[i] : (i % ny == i / ny ? 1.0 : 0.0));
+    cb.insert(cb.end(), Q, Q + nx * nx);
+    cb.insert(cb.end(), R, R + ny * ny);
+    if (P0) cb.insert(cb.end(), P0, P0 + nx * nx);
+    for (double v : cb) if (!std::isfinite(v)) return false;
+    return true;
+}
+
+// the one build path of a loop; e: the filter of an observed loop, or null
+static int nl_loop_build(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, const mpcx_nlmpc_ekf_desc *e, void *stream, mpcx_nlmpc_loop_t *out)
 {
     using mpcx::capi_fail;
     if (!h || !d || !out) return capi_fail(MPCX_E_INVALID, "null argument");
@@ -497,9 +523,15 @@ int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *
     if (!stream) return capi_fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
     if (nl_is_hook_model(h)) return capi_fail(MPCX_E_UNSUPPORTED, "loops run the built-in systems only: hook models come later");
     if ((d->params || d->plant_params) && h->n_params <= 0) return capi_fail(MPCX_E_INVALID, "this model has no parameters to give per instance");
+    const mpcx::NlmpcDev &m = h->dev;
+    std::vector<double> cb;
+    if (e) {
+        if (e->ny > m.nx) return capi_fail(MPCX_E_INVALID, "the filter measures at most nx outputs (ny <= nx)");
+        if (!e->Cm && e->ny != m.nx) return capi_fail(MPCX_E_INVALID, "Cm = NULL is the identity: ny must be nx");
+        if (!nl_ekf_block(m.nx, e->ny, e->Cm, e->Q, e->R, e->P0, cb)) return capi_fail(MPCX_E_INVALID, "Cm, Q, R and P0 must be finite");
+    }
     if (hipSetDevice(h->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const mpcx::NlmpcDev &m = h->dev;
 
     std::unique_ptr<mpcx_nlmpc_loop> l(new mpcx_nlmpc_loop);
     l->owner = h; l->device = h->device; l->ticks = d->ticks;
@@ -509,6 +541,8 @@ int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *
     auto take = [&](size_t bytes) { const size_t at = total; total = (total + bytes + 255) / 256 * 256; return at; };
     const size_t o_x = take(B * m.nx * sizeof(double)), o_u = take(B * m.nu * sizeof(double)), o_cmd = take(B * m.nu * sizeof(double));
     const size_t o_cost = take(B * sizeof(double)), o_int = take(4 * B * sizeof(int32_t)), o_z = take(B * m.nz * sizeof(double)), o_state = take(2 * sizeof(int));
+    const size_t o_xt = e ? take(B * m.nx * sizeof(double)) : 0, o_P = e ? take(B * m.nx * m.nx * sizeof(double)) : 0, o_cb = e ? take(cb.size() * sizeof(double)) : 0,
+                 o_fl = e && !e->ekf_flags ? take(B * sizeof(int32_t)) : 0;
     if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return capi_fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
     if (hipMemset(l->slab, 0, total) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipMemset failed");
     char *base = l->slab;
@@ -523,6 +557,14 @@ int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *
     L.traj_x = d->traj_x; L.traj_u = d->traj_u; L.traj_cost = d->traj_cost;
     L.traj_status = d->traj_status; L.traj_solver_status = d->traj_solver_status; L.traj_is_feasible = d->traj_is_feasible; L.traj_iterations = d->traj_iterations;
     L.state = reinterpret_cast<int *>(base + o_state);
+    if (e) {
+        if (hipMemcpy(base + o_cb, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "copy of the filter's matrices failed");
+        mpcx::NlmpcEkfDev &E = l->E;
+        l->observed = true;
+        E.ny = e->ny; E.cb = dp(o_cb); E.xhat0 = e->xhat0; E.meas_noise = e->meas_noise;
+        E.xt = dp(o_xt); E.P = dp(o_P); E.traj_xhat = e->traj_xhat; E.traj_y = e->traj_y; E.traj_P = e->traj_P;
+        E.flags = e->ekf_flags ? e->ekf_flags : reinterpret_cast<int *>(base + o_fl);
+    }
 
     // the step's descriptor: the loop's own state, input and result buffers; z and z_warm one buffer (the solve shifts its start itself)
     mpcx_nlmpc_batch cold{};
@@ -535,9 +577,9 @@ int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *
 
     // one plain pass first: it uploads pending bounds and sizes the workspace, neither of which can be captured, and leaves the handle in the state
     // in which the warm descriptor is given the carried curvature estimate (prepare_solve: a solve of the same batch before it)
-    if (mpcx::nlmpc_loop_begin(&m, &L, s) != 0) return capi_fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    if (l->begin(s) != 0) return capi_fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
     int rc = mpcx_nlmpc_solve_batch(h, &cold, s);
-    if (rc == MPCX_OK && mpcx::nlmpc_loop_advance(&m, &L, s) != 0) rc = capi_fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
+    if (rc == MPCX_OK && l->advance(s) != 0) rc = capi_fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
     if (rc == MPCX_OK && two) rc = mpcx_nlmpc_solve_batch(h, &warm, s);
     if (rc != MPCX_OK) return rc;
     if (hipStreamSynchronize(s) != hipSuccess) { h->solved_batch = 0; return capi_fail(MPCX_E_DEVICE, "the warm-up ticks failed"); }
@@ -548,6 +590,22 @@ int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *
     l->gen = h->setup_gen;
     *out = l.release();
     return MPCX_OK;
+}
+
+int mpcx_nlmpc_loop_create(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, void *stream, mpcx_nlmpc_loop_t *out)
+{
+    return nl_loop_build(h, d, nullptr, stream, out);
+}
+
+int mpcx_nlmpc_loop_create_observed(mpcx_nlmpc_t h, const mpcx_nlmpc_loop_desc *d, const mpcx_nlmpc_ekf_desc *e, void *stream, mpcx_nlmpc_loop_t *out)
+{
+    using mpcx::capi_fail;
+    // the filter's descriptor first: nothing of the handle is looked at before it is known to be a filter's
+    if (!e) return capi_fail(MPCX_E_INVALID, "null filter descriptor");
+    if (!e->Q || !e->R || !e->P0) return capi_fail(MPCX_E_INVALID, "the filter needs Q, R and P0");
+    if (e->ny < 1) return capi_fail(MPCX_E_INVALID, "the filter needs ny >= 1");
+    if (!e->traj_xhat || !e->traj_y) return capi_fail(MPCX_E_INVALID, "traj_xhat and traj_y are required");
+    return nl_loop_build(h, d, e, stream, out);
 }
 
 static int nl_loop_usable(mpcx_nlmpc_loop_t l)
@@ -567,7 +625,7 @@ int mpcx_nlmpc_loop_run(mpcx_nlmpc_loop_t l, void *stream)
     if (rc != MPCX_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     l->owner->solved_batch = 0;
-    if (mpcx::nlmpc_loop_begin(&l->owner->dev, &l->L, stream) != 0) return capi_fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    if (l->begin(stream) != 0) return capi_fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
     for (int k = 0; k < l->ticks; ++k)
         if (hipGraphLaunch(k > 0 && l->next ? l->next : l->first, s) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
     return MPCX_OK;
@@ -614,6 +672,38 @@ int mpcx_nlmpc_plant_step_batch(mpcx_nlmpc_t h, int batch, const double *x, cons
     if (hipSetDevice(h->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
     if (mpcx::nlmpc_plant_step(&h->dev, batch, x, u, params, h->n_params, noise, substeps, x_next, stream) != 0)
         return capi_fail(MPCX_E_DEVICE, "launch of the plant-step kernel failed");
+    return MPCX_OK;
+}
+
+int mpcx_nlmpc_ekf_step_batch(mpcx_nlmpc_t h, int batch, const double *xhat, const double *P, const double *u, const double *y, const double *params,
+                              const double *Cm, const double *Q, const double *R, int ny, int substeps, double *xhat_next, double *P_next, int32_t *flags,
+                              void *stream)
+{
+    using mpcx::capi_fail;
+    if (!h) return capi_fail(MPCX_E_INVALID, "null handle");
+    if (batch < 0) return capi_fail(MPCX_E_INVALID, "negative batch");
+    if (substeps <= 0) return capi_fail(MPCX_E_INVALID, "a filter step needs substeps >= 1");
+    if (ny < 1) return capi_fail(MPCX_E_INVALID, "the filter needs ny >= 1");
+    if (!Q || !R) return capi_fail(MPCX_E_INVALID, "the filter needs Q and R");
+    if (nl_is_hook_model(h)) return capi_fail(MPCX_E_UNSUPPORTED, "the filter step runs the built-in systems only: hook models come later");
+    if (batch == 0) return MPCX_OK;
+    if (!xhat || !P || !u || !y || !xhat_next || !P_next || !flags) return capi_fail(MPCX_E_INVALID, "xhat, P, u, y, xhat_next, P_next and flags are required");
+    if (params && h->n_params <= 0) return capi_fail(MPCX_E_INVALID, "this model has no parameters to give per instance");
+    const int nx = h->dev.nx;
+    if (ny > nx) return capi_fail(MPCX_E_INVALID, "the filter measures at most nx outputs (ny <= nx)");
+    if (!Cm && ny != nx) return capi_fail(MPCX_E_INVALID, "Cm = NULL is the identity: ny must be nx");
+    std::vector<double> &cb = h->ekf_cb_host;
+    if (!nl_ekf_block(nx, ny, Cm, Q, R, nullptr, cb)) return capi_fail(MPCX_E_INVALID, "Cm, Q and R must be finite");
+    if (hipSetDevice(h->device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (!h->ekf_cb && hipMalloc(reinterpret_cast<void **>(&h->ekf_cb), 3 * (size_t)nx * nx * sizeof(double)) != hipSuccess) {
+        h->ekf_cb = nullptr;
+        return capi_fail(MPCX_E_DEVICE, "allocation of the filter's staging buffer failed");
+    }
+    // stream-ordered behind the previous call's kernel, which may still be reading the block
+    if (hipMemcpyAsync(h->ekf_cb, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+        return capi_fail(MPCX_E_DEVICE, "copy of the filter's matrices failed");
+    if (mpcx::nlmpc_ekf_step(&h->dev, batch, xhat, P, u, y, params, h->n_params, h->ekf_cb, ny, substeps, xhat_next, P_next, flags, stream) != 0)
+        return capi_fail(MPCX_E_DEVICE, "launch of the filter-step kernel failed");
     return MPCX_OK;
 }
 

@@ -29,7 +29,9 @@ VANDERPOL, UGV, OSCILLATORS6, OSCILLATORS8, VANDERPOL_TERMINAL, VANDERPOL_RATE =
 @dataclass
 class NLClosedLoopResult:
     """A closed-loop run on the device (NLMPC.simulate), tick-major device tensors: x [ticks+1, B, nx] (row 0 = the initial
-    state), u [ticks, B, nu], the others [ticks, B]."""
+    state), u [ticks, B, nu], the others [ticks, B].  An observed loop (ekf=) adds xhat [ticks+1, B, nx] (row 0 = the initial estimate),
+    y [ticks, B, ny] (row k = the measurement of x[k+1]), ekf_flags [B] (bit 0: an update was skipped) and, with log_P, P [ticks+1, B, nx, nx]
+    (every matrix symmetric); x is then the truth.  They are None for an unobserved loop."""
     x: "object"
     u: "object"
     cost: "object"
@@ -37,6 +39,20 @@ class NLClosedLoopResult:
     solver_status: "object"
     is_feasible: "object"
     iterations: "object"
+    xhat: "object" = None
+    y: "object" = None
+    P: "object" = None
+    ekf_flags: "object" = None
+
+
+@dataclass
+class NLEkf:
+    """The extended Kalman filter of an observed loop (mpcx_nlmpc_ekf_desc): process and measurement noise covariances Q [nx, nx], R [ny, ny], the
+    initial covariance P0 [nx, nx] and the measurement matrix C [ny, nx] (None: the identity, ny = nx).  One set for the batch."""
+    Q: "object"
+    R: "object"
+    P0: "object"
+    C: "object" = None
 
 
 @dataclass
@@ -255,7 +271,53 @@ class NLMPC(NLMPCEvaluator):
         check(self._lib.mpcx_nlmpc_plant_step_batch(self._h, B, x.data_ptr(), u.data_ptr(), ptr(pb), ptr(w), int(substeps), out.data_ptr(), s))
         return out
 
-    def make_loop(self, x0, u0, ticks, *, params=None, plant_params=None, noise=None, warm=True, substeps=1, stream=None) -> NLLoop:
+    def _ekf_matrices(self, C_, Q, R, P0=None):
+        """the filter's host matrices, column-major (kept alive by the caller): (ny, [Cm, Q, R, P0])"""
+        nx = self.nx
+        Cm = None if C_ is None else np.atleast_2d(np.asarray(C_, dtype=np.float64))
+        ny = nx if Cm is None else Cm.shape[0]
+        if Cm is not None and Cm.shape != (ny, nx):
+            raise ValueError("C must be [ny, %d], got %s" % (nx, list(Cm.shape)))
+        out = [None if Cm is None else np.asfortranarray(Cm)]
+        for a, n, what in ((Q, nx, "Q"), (R, ny, "R"), (P0, nx, "P0")):
+            if a is None and what == "P0":
+                out.append(None)
+                continue
+            a = np.atleast_2d(np.asarray(a, dtype=np.float64))
+            if a.shape != (n, n):
+                raise ValueError("%s must be [%d, %d], got %s" % (what, n, n, list(a.shape)))
+            out.append(np.asfortranarray(a))
+        return ny, out
+
+    def ekf_step(self, xhat, P, u, y, ekf, params=None, substeps=1, stream=None, out=None):
+        """The filter step of an observed loop alone (mpcx_nlmpc_ekf_step_batch), for callers who drive the loop themselves: from the estimate
+        xhat [B, nx], its covariance P [B, nx, nx], the command u [B, nu] and the measurement y [B, ny] of the new state to
+        (xhat_next, P_next, flags [B] int32); `ekf`: an NLEkf (its P0 is not used), `params` [B, n_params]: per-instance model parameters.
+        `out`: (xhat_next, P_next) tensors to write to; they may be xhat and P.  The device function of the observed loop's advance kernel:
+        the two agree bit for bit."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B = int(xhat.shape[0])
+        ny, (Cm, Q, R, _) = self._ekf_matrices(ekf.C, ekf.Q, ekf.R)
+        xhat = self._rows(torch, dev, xhat, (B, self.nx), "xhat"); P = self._rows(torch, dev, P, (B, self.nx, self.nx), "P")
+        u = self._rows(torch, dev, u, (B, self.nu), "u"); y = self._rows(torch, dev, y, (B, ny), "y")
+        pb = self._rows(torch, dev, params, (B, self.n_params), "params")
+        if out is None:
+            out = (torch.empty_like(xhat), torch.empty_like(P))
+        else:
+            for t, like in zip(out, (xhat, P)):
+                if not (isinstance(t, torch.Tensor) and t.is_contiguous() and t.dtype == torch.float64 and t.device == like.device and t.shape == like.shape):
+                    raise ValueError("out must be contiguous float64 tensors [%d, %d] and [%d, %d, %d] on the controller's device" % (B, self.nx, B, self.nx, self.nx))
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        hp = lambda a: None if a is None else a.ctypes.data
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(self._lib.mpcx_nlmpc_ekf_step_batch(self._h, B, xhat.data_ptr(), P.data_ptr(), u.data_ptr(), y.data_ptr(), ptr(pb), hp(Cm), hp(Q), hp(R),
+                                                  int(ny), int(substeps), out[0].data_ptr(), out[1].data_ptr(), flags.data_ptr(), s))
+        return out[0], out[1], flags
+
+    def make_loop(self, x0, u0, ticks, *, params=None, plant_params=None, noise=None, warm=True, substeps=1, stream=None,
+                  ekf=None, xhat0=None, meas_noise=None, log_P=False) -> NLLoop:
         """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by the
         plant step (`plant_step`) on the device, with no host work in between.
 
@@ -263,7 +325,12 @@ class NLMPC(NLMPCEvaluator):
         plant's where they differ from the controller's (model mismatch); noise [ticks, B, nx]: additive process disturbance the
         controller does not know about; warm: ticks >= 1 start from the shifted previous solution with the carried curvature estimate
         (tick 0 is cold); substeps: Euler sub-steps of a continuous plant per tick.
-        x0 / u0 are read again by every run_loop: refill NLLoop.keep[0], keep[1] in place for another start."""
+        x0 / u0 are read again by every run_loop: refill NLLoop.keep[0], keep[1] in place for another start.
+
+        ekf: an NLEkf -- output feedback.  The solves then read the estimate of an extended Kalman filter that runs in the advance step
+        (mpcx_nlmpc_loop_create_observed) on measurements y = C x + v of the plant's true state; xhat0 [B, nx]: the initial estimate
+        (default x0), meas_noise [ticks, B, ny]: v, log_P: also keep every P.  xhat0 / meas_noise are read again by every run_loop: refill
+        NLLoop.keep[6], keep[7] in place."""
         import torch
         ticks = int(ticks)
         dev = torch.device("cuda", self.device)
@@ -283,15 +350,33 @@ class NLMPC(NLMPCEvaluator):
         d.x0, d.u0, d.params, d.plant_params, d.noise = ptr(x0), ptr(u0), ptr(pb), ptr(pp), ptr(w)
         d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
         d.traj_status, d.traj_solver_status, d.traj_is_feasible, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.is_feasible), ptr(res.iterations)
+        xh0 = v = None
+        if ekf is None:
+            if xhat0 is not None or meas_noise is not None or log_P:
+                raise ValueError("xhat0, meas_noise and log_P belong to an observed loop: give ekf=NLEkf(...)")
+        else:
+            ny, mats = self._ekf_matrices(ekf.C, ekf.Q, ekf.R, ekf.P0)
+            xh0 = self._rows(torch, dev, xhat0, (B, self.nx), "xhat0"); v = self._rows(torch, dev, meas_noise, (ticks, B, ny), "meas_noise")
+            res.xhat = torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev); res.y = torch.zeros((T, B, ny), dtype=f64, device=dev)
+            res.ekf_flags = torch.zeros(B, dtype=i32, device=dev)
+            if log_P:
+                res.P = torch.zeros((T + 1, B, self.nx, self.nx), dtype=f64, device=dev)
+            e = _capi.NlmpcEkfDesc()
+            e.ny = ny
+            e.Cm, e.Q, e.R, e.P0 = (None if a is None else C.c_void_p(a.ctypes.data) for a in mats)
+            e.xhat0, e.meas_noise, e.traj_xhat, e.traj_y, e.traj_P, e.ekf_flags = ptr(xh0), ptr(v), ptr(res.xhat), ptr(res.y), ptr(res.P), ptr(res.ekf_flags)
         cur = torch.cuda.current_stream(dev)
         s = stream if stream is not None else torch.cuda.Stream(device=dev)
         if s.cuda_stream == 0:
             raise ValueError("a loop is captured on a non-default stream")
         s.wait_stream(cur)                      # the tensors above were filled on the current stream
         h = C.c_void_p()
-        check(self._lib.mpcx_nlmpc_loop_create(self._h, C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        if ekf is None:
+            check(self._lib.mpcx_nlmpc_loop_create(self._h, C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        else:
+            check(self._lib.mpcx_nlmpc_loop_create_observed(self._h, C.byref(d), C.byref(e), C.c_void_p(s.cuda_stream), C.byref(h)))
         cur.wait_stream(s)
-        return NLLoop(h, res, ticks, (x0, u0, pb, pp, w, s))
+        return NLLoop(h, res, ticks, (x0, u0, pb, pp, w, s, xh0, v))
 
     def run_loop(self, loop: NLLoop, stream=None) -> NLClosedLoopResult:
         """One asynchronous run of a loop from its x0 / u0 tensors: `loop.result` is filled once the stream has been synchronised.  A loop
@@ -309,10 +394,12 @@ class NLMPC(NLMPCEvaluator):
             check(self._lib.mpcx_nlmpc_loop_destroy(loop.handle))
             loop.handle = None
 
-    def simulate(self, x0, u0, ticks, *, params=None, plant_params=None, noise=None, warm=True, substeps=1, stream=None) -> NLClosedLoopResult:
+    def simulate(self, x0, u0, ticks, *, params=None, plant_params=None, noise=None, warm=True, substeps=1, stream=None,
+                 ekf=None, xhat0=None, meas_noise=None, log_P=False) -> NLClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
         import torch
-        loop = self.make_loop(x0, u0, ticks, params=params, plant_params=plant_params, noise=noise, warm=warm, substeps=substeps)
+        loop = self.make_loop(x0, u0, ticks, params=params, plant_params=plant_params, noise=noise, warm=warm, substeps=substeps,
+                              ekf=ekf, xhat0=xhat0, meas_noise=meas_noise, log_P=log_P)
         try:
             self.run_loop(loop, stream)
             (stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))).synchronize()
