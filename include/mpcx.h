@@ -7,7 +7,8 @@
  *                 (include/mpc/LMPC/LOptimizer.hpp:189-368, LMPC/ProblemBuilder.hpp);
  *   mpcx_nlmpc_*  the non-linear back-end, NLOptimizer::run with Mapping / Model /
  *                 Objective / Constraints (include/mpc/NLMPC/NLOptimizer.hpp:412-638);
- *   mpcx_discretize_batch  the c2d set-up helper (include/mpc/Utils.hpp:23-89).
+ *   mpcx_discretize_batch  the c2d set-up helper (include/mpc/Utils.hpp:23-89);
+ *   mpcx_dare_batch        Kalman and LQR gains for a batch of models (no reference counterpart).
  *
  * Conventions
  *   - plain C, opaque handle, no C++/torch types in any signature;
@@ -556,6 +557,24 @@ int mpcx_nlmpc_ekf_step_batch(mpcx_nlmpc_t h, int batch, const double *xhat, con
 int mpcx_discretize_batch(int device, int nx, int nu, int batch, const double *A, const double *B, const double *Ts,
                           int ts_per_instance, double *Ad, double *Bd, void *stream);
 
+/* A batch of discrete algebraic Riccati equations on the device (no reference counterpart; kernel dare_sda of dare_kernels.hip, a
+ * structure-preserving doubling iteration, one equation per wavefront):
+ *   MPCX_DARE_CONTROL    X = A'XA - A'XB (R + B'XB)^-1 B'XA + Q,  gain K = (R + B'XB)^-1 B'XA [m x n]; BorC is B [n x m]
+ *   MPCX_DARE_ESTIMATOR  P = APA' - APC' (CPC' + R)^-1 CPA' + Q,  gain L = APC' (CPC' + R)^-1 [n x m]; BorC is C [m x n]
+ * The estimator gain is the predictor gain of mpcx_lmpc_observer_desc and is written in gain_batch's layout: hand it over as it is.
+ * Device pointers, column-major matrices per instance: A [B x n x n], BorC [B x n m], Q [n x n] and R [m x m] one for the batch or
+ * (q_per_instance, r_per_instance) one per instance, both symmetric (their symmetric parts are used); X [B x n x n]; gain [B x n m],
+ * flags [B] and iterations [B] (the doublings taken) may each be NULL.  1 <= n <= 32, 1 <= m <= 32 (m may exceed n).
+ * flags: 0 converged; 1 R is not positive definite; 2 no convergence within 40 doublings; 3 a non-finite value, a vanishing pivot or a
+ * failed Cholesky factorisation of R + B'XB during the iteration (an unstable mode that BorC does not reach ends here).  An instance
+ * with a non-zero flag has NaN in every entry of X and of its gain; the others are not affected, and an instance's bits depend on its
+ * own inputs alone.  MPCX_E_INVALID for another form, sizes outside the limits, a negative batch or a null A, BorC, Q, R or X: checked
+ * before anything touches a device. */
+#define MPCX_DARE_CONTROL   0
+#define MPCX_DARE_ESTIMATOR 1
+int mpcx_dare_batch(int device, int form, int n, int m, int batch, const double *A, const double *BorC, const double *Q, const double *R,
+                    int q_per_instance, int r_per_instance, double *X, double *gain, int32_t *flags, int32_t *iterations, void *stream);
+
 /* ---- multi-GPU: the one collective on the path --------------------------------- */
 /* The reference solves one controller per object and has no coupling between objects (LMPC.hpp:751), so a batch shards
  * as contiguous slices, one process per GPU, and nothing is exchanged during the solve.  Afterwards every rank
@@ -658,6 +677,9 @@ int mpcx_nlmpc_debug_set_tolerances(mpcx_nlmpc_t h, double tol_step, double tol_
  * -1 = none yet.  This one: the last launch of the process.  MPCX_NLMPC_FORM=wg|wave, MPCX_NLMPC_WAVES=1|2|4|8 and MPCX_NLMPC_BLOCKS=1|0 in
  * the environment force a form for the handles created afterwards (measurements, tests/test_nlmpc_forms.py). */
 int mpcx_nlmpc_debug_last_form(void);
+/* which form of the n x n products the following mpcx_dare_batch calls of the process take: 0 the one of the size class (the default),
+ * 1 lanes over the entries, 2 the f64 matrix pipe (tools/dare_bench.py measures one against the other); returns the previous value */
+int mpcx_dare_debug_product(int product);
 /* the same for the last solve of this handle (the form is a property of the controller: chosen when its bounds are set, from the plan of the
  * workgroup form, the same for every batch size -- a shard of a batch takes the kernel the whole batch would; the overrides are read when
  * the handle is created) */

@@ -12,6 +12,7 @@ OK = 0
 E_INVALID, E_UNSUPPORTED, E_DEVICE, E_NUMERIC, E_STATE = -1, -2, -3, -4, -5
 STATUS_SUCCESS, STATUS_MAX_ITERATION, STATUS_INFEASIBLE, STATUS_ERROR, STATUS_UNKNOWN = range(5)
 REF_SHARED, REF_PER_INSTANCE, REF_PER_STEP = 0, 1, 2
+DARE_CONTROL, DARE_ESTIMATOR = 0, 1
 REF_PREVIEW = 3          # loops only: [B x (ticks + ph) x n], a window of ph rows per tick
 
 
@@ -88,7 +89,7 @@ EXPORTS = [
     "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
     "mpcx_lmpc_loop_create_observed", "mpcx_lmpc_hetero_loop_create_observed", "mpcx_lmpc_observer_desc_size", "mpcx_lmpc_kalman_gain",
     "mpcx_nlmpc_create", "mpcx_nlmpc_destroy", "mpcx_nlmpc_get_dims", "mpcx_nlmpc_evaluate_batch",
-    "mpcx_nlparams_default", "mpcx_nlmpc_set_optimizer_parameters", "mpcx_nlmpc_solve_batch", "mpcx_nlmpc_time_solve_batch", "mpcx_discretize_batch",
+    "mpcx_nlparams_default", "mpcx_nlmpc_set_optimizer_parameters", "mpcx_nlmpc_solve_batch", "mpcx_nlmpc_time_solve_batch", "mpcx_discretize_batch", "mpcx_dare_batch",
     "mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice", "mpcx_nlmpc_solve_host",
     "mpcx_nlmpc_create_custom", "mpcx_nlmpc_create_from_source", "mpcx_nlmpc_set_input_scale", "mpcx_nlmpc_set_state_scale",
     "mpcx_nlmpc_loop_create", "mpcx_nlmpc_loop_run", "mpcx_nlmpc_loop_destroy", "mpcx_nlmpc_loop_desc_size", "mpcx_nlmpc_plant_step_batch",
@@ -100,7 +101,7 @@ EXPORTS = [
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
     "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer",
     "mpcx_lmpc_loop_debug_replay", "mpcx_lmpc_loop_debug_tick", "mpcx_nlmpc_loop_debug_replay", "mpcx_nlmpc_loop_debug_tick",
-    "mpcx_nlmpc_debug_set_tolerances", "mpcx_nlmpc_debug_last_form", "mpcx_nlmpc_last_form", "mpcx_nlmpc_debug_get_ws", "mpcx_nlmpc_debug_generated_source", "mpcx_nlmpc_debug_compile_source",
+    "mpcx_dare_debug_product", "mpcx_nlmpc_debug_set_tolerances", "mpcx_nlmpc_debug_last_form", "mpcx_nlmpc_last_form", "mpcx_nlmpc_debug_get_ws", "mpcx_nlmpc_debug_generated_source", "mpcx_nlmpc_debug_compile_source",
 ]
 
 
@@ -191,6 +192,8 @@ def lib():
         for _n in ("mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice"):
             getattr(_lib, _n).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         _lib.mpcx_discretize_batch.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+        _lib.mpcx_dare_batch.argtypes = [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 5
+        _lib.mpcx_dare_debug_product.argtypes = [C.c_int]
         _lib.mpcx_nlmpc_set_optimizer_parameters.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_solve_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_time_solve_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

@@ -114,6 +114,7 @@ class LMPCHetero:
         self.count, self.active_words, self.m_ref, self.bytes_per_model = n.value, aw.value, mref.value, bpm.value
         self._template = c0
         self._models = [(c._A, c._B, c._Bd) for c in controllers]        # as given to the setters: what plants=(A, None, None) completes
+        self._outputs = [c._C for c in controllers]
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -176,6 +177,25 @@ class LMPCHetero:
         if any(m[0] is None for m in self._models):
             raise _capi.MpcxError(_capi.E_STATE, "state-space model not set")
         return tuple(np.stack([m[j] for m in self._models])[idx] for j in range(3))
+
+    def kalman_gains(self, Qw, Rv):
+        """The steady-state Kalman predictor gain of every controller's own (A, C), [count, nx, ny] on the device, for the process-noise
+        covariance Qw ([nx, nx], or [count, nx, nx] one per controller) and the sensor-noise covariance Rv ([ny, ny] or [count, ny, ny]):
+        one batched device call (libmpc_amd.utils.kalman_gains) where LMPC.kalman_gain iterates one controller on the host.  Index it by
+        the instances' controllers (gains[model]) for observer=.  Raises MpcxError naming the first controller whose equation was not
+        solved."""
+        from .utils import kalman_gains
+        if any(m[0] is None for m in self._models):
+            raise _capi.MpcxError(_capi.E_STATE, "state-space model not set")
+        A = np.stack([m[0] for m in self._models]); Cm = np.stack(self._outputs)
+        L, _, flags = kalman_gains(A, Cm, Qw, Rv, device=self.device)
+        bad = torch.nonzero(flags).reshape(-1)
+        if bad.numel():
+            k = int(bad[0])
+            why = {1: "Rv is not positive definite", 2: "the doubling iteration has not converged",
+                   3: "the doubling iteration broke down: is (A, C) detectable?"}[int(flags[k])]
+            raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {k}: {why}")
+        return L
 
     def make_loop(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
                   noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None) -> Loop:

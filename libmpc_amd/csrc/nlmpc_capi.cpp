@@ -728,6 +728,35 @@ extern "C" int mpcx_discretize_batch(int device, int nx, int nu, int batch, cons
     return MPCX_OK;
 }
 
+namespace mpcx {
+int dare_launch(int form, int n, int m, int batch, const double *A, const double *BorC, const double *Q, const double *R, int q_per_instance,
+                int r_per_instance, double *X, double *gain, int *flags, int *iterations, int product, void *stream);
+}
+static int g_dare_product = 0;
+extern "C" int mpcx_dare_debug_product(int product)
+{
+    const int before = g_dare_product;
+    if (product >= 0 && product <= 2) g_dare_product = product;
+    return before;
+}
+
+extern "C" int mpcx_dare_batch(int device, int form, int n, int m, int batch, const double *A, const double *BorC, const double *Q,
+                               const double *R, int q_per_instance, int r_per_instance, double *X, double *gain, int32_t *flags,
+                               int32_t *iterations, void *stream)
+{
+    using mpcx::capi_fail;
+    if (form != MPCX_DARE_CONTROL && form != MPCX_DARE_ESTIMATOR) return capi_fail(MPCX_E_INVALID, "form is MPCX_DARE_CONTROL or MPCX_DARE_ESTIMATOR");
+    if (n < 1 || n > 32 || m < 1 || m > 32) return capi_fail(MPCX_E_INVALID, "need 1 <= n <= 32 and 1 <= m <= 32");
+    if (batch < 0) return capi_fail(MPCX_E_INVALID, "negative batch");
+    if (!A || !BorC || !Q || !R || !X) return capi_fail(MPCX_E_INVALID, "A, BorC, Q, R and X are required");
+    if (batch == 0) return MPCX_OK;
+    if (hipSetDevice(device) != hipSuccess) return capi_fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    const int rc = mpcx::dare_launch(form, n, m, batch, A, BorC, Q, R, q_per_instance, r_per_instance, X, gain, flags, iterations,
+                                     g_dare_product, stream);
+    if (rc != 0) return capi_fail(MPCX_E_DEVICE, "Riccati kernel launch failed");
+    return MPCX_OK;
+}
+
 // Which kernel the last solve of a built-in system went through (bench.py names it): 0 = nlmpc_sqp (one wavefront per instance),
 // 1 | 2 | 4 = nlmpc_sqp_wg with that many wavefronts per instance, -1 = none yet
 extern "C" int mpcx_nlmpc_debug_last_form(void) { return mpcx::nlmpc_last_form(); }

@@ -29,3 +29,61 @@ def discretization(A, B, Ts, device=0, stream=None):
     check(_capi.lib().mpcx_discretize_batch(device, nx, nu, n, Ac.data_ptr(), Bc.data_ptr(), ts.data_ptr(), int(per),
                                             Ad.data_ptr(), Bd.data_ptr(), s))
     return Ad.transpose(1, 2), Bd.transpose(1, 2)
+
+
+def _as_f64(a):
+    import numpy as np
+    import torch
+    return a.to(torch.float64) if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))      # (a copy: arrays may be read-only)
+
+
+def dare(A, B, Q, R, form="control", device=0, stream=None, want_iterations=False):
+    """A batch of discrete algebraic Riccati equations on the device (mpcx_dare_batch, no reference counterpart), row-major tensors or
+    arrays: A [Bn, n, n]; form "control": B [Bn, n, m], X = A'XA - A'XB (R + B'XB)^-1 B'XA + Q and the gain K = (R + B'XB)^-1 B'XA
+    [Bn, m, n]; form "estimator": B is the output matrix C [Bn, m, n], P = APA' - APC' (CPC' + R)^-1 CPA' + Q and the predictor gain
+    L = APC' (CPC' + R)^-1 [Bn, n, m].  Q [n, n] and R [m, m] for the batch, or [Bn, ., .] per instance.  2-D A and B are a batch of one.
+    1 <= n, m <= 32.  Returns (gain, X, flags) on the device (and the doublings taken, with want_iterations); flags [Bn] int32: 0
+    converged, 1 R not positive definite, 2 no convergence, 3 a non-finite value or a failed factorisation on the way -- X and the gain
+    of such an instance are NaN.  Shape errors are a ValueError before any device call."""
+    import torch
+    if form not in ("control", "estimator"):
+        raise ValueError(f"form is 'control' or 'estimator', got {form!r}")
+    est = form == "estimator"
+    A, B, Q, R = _as_f64(A), _as_f64(B), _as_f64(Q), _as_f64(R)
+    if A.dim() == 2 and B.dim() == 2:
+        A, B = A[None], B[None]
+    second = "C" if est else "B"
+    if A.dim() != 3 or B.dim() != 3 or A.shape[1] != A.shape[2] or B.shape[0] != A.shape[0] or B.shape[2 if est else 1] != A.shape[1]:
+        want = "[Bn, m, n]" if est else "[Bn, n, m]"
+        raise ValueError(f"A {tuple(A.shape)} and {second} {tuple(B.shape)} are not [Bn, n, n] and {want}")
+    bn, n, m = A.shape[0], A.shape[1], B.shape[1 if est else 2]
+    if not (1 <= n <= 32 and 1 <= m <= 32):
+        raise ValueError(f"n = {n}, m = {m}: 1 <= n <= 32 and 1 <= m <= 32 expected")
+    for name, M, k in (("Q", Q, n), ("R", R, m)):
+        if tuple(M.shape) not in ((k, k), (bn, k, k)):
+            raise ValueError(f"{name} {tuple(M.shape)} is neither [{k}, {k}] nor [{bn}, {k}, {k}]")
+    dev = torch.device("cuda", device)
+    # the C ABI takes Eigen's column-major layout: transpose the last two axes
+    Ac, Bc, Qc, Rc = (M.to(dev).transpose(-1, -2).contiguous() for M in (A, B, Q, R))
+    X = torch.empty((bn, n, n), dtype=torch.float64, device=dev)
+    G = torch.empty((bn, n, m) if not est else (bn, m, n), dtype=torch.float64, device=dev)       # column-major [m x n] / [n x m]
+    flags = torch.empty(bn, dtype=torch.int32, device=dev)
+    its = torch.empty(bn, dtype=torch.int32, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    check(_capi.lib().mpcx_dare_batch(device, _capi.DARE_ESTIMATOR if est else _capi.DARE_CONTROL, n, m, bn, Ac.data_ptr(), Bc.data_ptr(),
+                                      Qc.data_ptr(), Rc.data_ptr(), int(Q.dim() == 3), int(R.dim() == 3), X.data_ptr(), G.data_ptr(),
+                                      flags.data_ptr(), its.data_ptr(), s))
+    out = (G.transpose(1, 2), X.transpose(1, 2), flags)
+    return out + (its,) if want_iterations else out
+
+
+def kalman_gains(A, C, Qw, Rv, device=0, stream=None):
+    """Steady-state Kalman predictor gains for a batch: (L [Bn, n, m], P [Bn, n, n], flags) of dare(A, C, Qw, Rv, "estimator").  L is a
+    view of the layout mpcx_lmpc_observer_desc.gain_batch takes: an observed loop's observer= accepts it as it is."""
+    return dare(A, C, Qw, Rv, "estimator", device, stream)
+
+
+def lqr_gains(A, B, Q, R, device=0, stream=None):
+    """Infinite-horizon LQR for a batch: (K [Bn, m, n] with u = -K x, X [Bn, n, n] the cost-to-go -- a terminal weight --, flags) of
+    dare(A, B, Q, R, "control")."""
+    return dare(A, B, Q, R, "control", device, stream)
