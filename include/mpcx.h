@@ -263,6 +263,40 @@ typedef struct mpcx_lmpc_observer_desc {
  * and for neither or both of gain / gain_batch. */
 int mpcx_lmpc_loop_create_observed(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out);
 int mpcx_lmpc_observer_desc_size(void);           /* sizeof(mpcx_lmpc_observer_desc), for bindings that mirror the struct */
+/* Offset-free tracking for that loop (no reference counterpart): an observed loop whose estimator carries [xhat; dhat], the integrating disturbance
+ * model of the controller's own Bd / Dd (mpcx_lmpc_set_disturbances).  When the plant is not the model, or a constant load acts on it that nobody
+ * measures, a state observer alone settles on a biased estimate and every instance beside its reference; here the bias is estimated and handed to
+ * the solve.  The solve of tick k reads xhat_k, u_{k-1} and dhat_k -- the loop's own [B x ndu] buffer as its MPCX_REF_PER_INSTANCE exogenous
+ * input, hence constant along the horizon -- and the loop descriptor's dmeas, in every mode it has, is no longer what the controller is told: it
+ * is the TRUE disturbance d_k (step 0 of the tick's array) that acts on the plant and on the measurement, unseen by the controller.  dmeas = NULL
+ * in MPCX_REF_SHARED mode means the controller's own exogenous input (a bank: each controller's own): zeros unless it was set.  Per tick,
+ * everything from tick-k data:
+ *     y_k      = C x_k + Dd d_k + v_k
+ *     e_k      = y_k - (C xhat_k + Dd dhat_k)
+ *     x_k+1    = A_p x_k + B_p cmd_k + Bd_p d_k + w_k
+ *     xhat_k+1 = A xhat_k + B cmd_k + Bd dhat_k + Lx e_k
+ *     dhat_k+1 = dhat_k + Ld e_k
+ * with the gain [(nx + ndu) x ny] = [Lx; Ld].  Every row is summed from 0 with fused multiply-adds by ascending column -- y over C, Dd (operand
+ * d_k), then + v_k; yhat over C, Dd (operand dhat_k); xhat over A, B, Bd (operand dhat_k), Lx, nothing added at the store; the correction of dhat
+ * over Ld from 0, added to dhat_k once -- so that with Ld = 0, dhat_0 = d bitwise and d constant per instance the loop reproduces, bit for bit,
+ * mpcx_lmpc_loop_create_observed given the same d as per-instance dmeas.  gain_batch is what mpcx_dare_batch (MPCX_DARE_ESTIMATOR, n = nx + ndu,
+ * m = ny) writes for the augmented pair ([[A, Bd], [0, I]], [C, Dd]): hand it over as it is.  The augmented pair is detectable only where
+ * rank [[I - A, -Bd], [C, Dd]] = nx + ndu, which needs ndu <= ny.  No steady-state target is computed from dhat: the output settles on its
+ * reference where the input weight is zero (or the input reference is the steady-state input); offset-free tracking with a non-zero input weight
+ * is not claimed.  The loop is an mpcx_lmpc_loop_t as before; gain is copied at creation; gain_batch, xhat0, dhat0 and meas_noise are read by
+ * every run: refill them in place. */
+typedef struct mpcx_lmpc_disturbance_observer_desc {
+    const double *gain;                           /* HOST, column-major [(nx+ndu) x ny] (rows 0 .. nx-1 = Lx, then Ld): one gain for the batch, or NULL */
+    const double *gain_batch;                     /* device, [B x (nx+ndu)*ny], per instance, column-major; excludes gain */
+    const double *xhat0;                          /* device [B x nx] or NULL (= x0) */
+    const double *dhat0;                          /* device [B x ndu] or NULL (= 0) */
+    const double *meas_noise;                     /* device [ticks x B x ny] or NULL */
+    double *traj_xhat, *traj_dhat, *traj_y;       /* device, optional: [(ticks+1) x B x nx], [(ticks+1) x B x ndu], [ticks x B x ny] */
+} mpcx_lmpc_disturbance_observer_desc;
+/* MPCX_E_INVALID, ahead of any look at the handle's state, for a null descriptor, for neither or both of gain / gain_batch, and for a controller
+ * without exogenous inputs (ndu = 0: there is no disturbance model to estimate). */
+int mpcx_lmpc_loop_create_offset_free(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out);
+int mpcx_lmpc_disturbance_observer_desc_size(void);   /* sizeof(mpcx_lmpc_disturbance_observer_desc), for bindings that mirror the struct */
 /* The steady-state Kalman predictor gain of the controller's own (A, C) (no reference counterpart), on the host in doubles; works on a host-only
  * handle.  L = A P C' (C P C' + Rv)^-1 with P the fixed point of P <- A P A' - A P C' (C P C' + Rv)^-1 C P A' + Qw, iterated from P = Qw and
  * symmetrised every time, until the largest change of an entry is <= 1e-14 times the largest entry.  Qw [nx x nx], Rv [ny x ny], gain_out
@@ -631,6 +665,10 @@ int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc
  * it.  The controllers of a bank differ, so one gain for all is refused: gain_batch is required (MPCX_E_INVALID for gain). */
 int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
                                           void *stream, mpcx_lmpc_loop_t *out);
+/* The offset-free loop of a bank: instance b is estimated with the model and the disturbance model of its controller; gain_batch is required
+ * (MPCX_E_INVALID for gain, as above).  dmeas in MPCX_REF_SHARED mode: each controller's own exogenous input, step 0, as the true disturbance. */
+int mpcx_lmpc_hetero_loop_create_offset_free(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
+                                             const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out);
 
 /* Sharding: this handle solves contiguous shards of a batch of `total` instances -- the kernel form is chosen for
  * the whole batch's size, so that a shard's results are bit for bit the rows of the unsharded solve (0 = every call is a whole batch). */

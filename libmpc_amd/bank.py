@@ -115,6 +115,7 @@ class LMPCHetero:
         self._template = c0
         self._models = [(c._A, c._B, c._Bd) for c in controllers]        # as given to the setters: what plants=(A, None, None) completes
         self._outputs = [c._C for c in controllers]
+        self._feedthrough = [c._Dd for c in controllers]
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -169,6 +170,7 @@ class LMPCHetero:
     # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create; the loop itself is LMPC's) -------------------------------
     _loop_ref, _check_plants, _make_loop, pack_plants = LMPC._loop_ref, LMPC._check_plants, LMPC._make_loop, staticmethod(LMPC.pack_plants)
     _check_observer, pack_gains = LMPC._check_observer, staticmethod(LMPC.pack_gains)
+    _check_disturbance_observer, _check_observers = LMPC._check_disturbance_observer, LMPC._check_observers
     run_loop, destroy_loop = LMPC.run_loop, LMPC.destroy_loop
 
     def _own_plant(self, B, model=None):
@@ -197,18 +199,38 @@ class LMPCHetero:
             raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {k}: {why}")
         return L
 
+    def disturbance_gains(self, Qw, Qd, Rv):
+        """LMPC.disturbance_gain for every controller of the bank, [count, nx+ndu, ny] on the device, in one batched call
+        (libmpc_amd.utils.disturbance_gains): the gains [Lx; Ld] of each controller's model augmented with its integrating disturbance model.
+        Index it by the instances' controllers (gains[model]) for disturbance_observer=.  ValueError, before any device call, naming the first
+        controller whose augmented pair is not detectable; MpcxError naming the first whose equation was not solved."""
+        from .utils import disturbance_gains
+        if any(m[0] is None for m in self._models):
+            raise _capi.MpcxError(_capi.E_STATE, "state-space model not set")
+        A = np.stack([m[0] for m in self._models]); Bd = np.stack([m[2] for m in self._models])
+        L, _, flags = disturbance_gains(A, Bd, np.stack(self._outputs), np.stack(self._feedthrough), Qw, Qd, Rv, device=self.device)
+        bad = torch.nonzero(flags).reshape(-1)
+        if bad.numel():
+            k = int(bad[0])
+            why = {1: "Rv is not positive definite", 2: "the doubling iteration has not converged",
+                   3: "the doubling iteration broke down"}[int(flags[k])]
+            raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {k}: {why}")
+        return L
+
     def make_loop(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                  noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None) -> Loop:
+                  noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None, disturbance_observer=None, dhat0=None) -> Loop:
         """LMPC.make_loop for a bank: every tick is the bank's batched solve (instance b by controller model[b]; None: controller b)
         followed by the plant step.  plant: one plant for all, (A_p, B_p, Bd_p); plants: a plant per instance, (A [B,nx,nx],
         B [B,nx,nu] | None, Bd | None); a None entry of either, and no plant at all, mean each instance's own controller.  References:
         None is each controller's own, also for the exogenous input that drives the plant.  observer, xhat0, meas_noise: output feedback as
         in LMPC.make_loop, instance b estimated with its own controller's model; the gain is per instance, [B, nx, ny] (the controllers
-        differ: one gain for all raises ValueError).  Destroy the loop before the bank."""
+        differ: one gain for all raises ValueError).  disturbance_observer, dhat0: offset-free tracking as in LMPC.make_loop, the gain
+        [B, nx+ndu, ny] (LMPCHetero.disturbance_gains indexed by the instances' controllers); dmeas= is then the true disturbance, None each
+        controller's own exogenous input.  Destroy the loop before the bank."""
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
         plants = self._check_plants(B, plant, plants)
-        self._check_observer(B, int(ticks), observer, xhat0, meas_noise, bank=True)
+        checked = self._check_observers(B, int(ticks), observer, disturbance_observer, xhat0, dhat0, meas_noise, bank=True)
         mi = None
         if model is not None:
             mi = torch.as_tensor(model).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
@@ -225,17 +247,19 @@ class LMPCHetero:
             mp = None if mi is None else C.c_void_p(mi.data_ptr())
             if od is None:
                 return self._lib.mpcx_lmpc_hetero_loop_create(self._h, d, mp, s, out)
+            if disturbance_observer is not None:
+                return self._lib.mpcx_lmpc_hetero_loop_create_offset_free(self._h, d, od, mp, s, out)
             return self._lib.mpcx_lmpc_hetero_loop_create_observed(self._h, d, od, mp, s, out)
         loop = self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi,
-                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, bank=True)
+                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, bank=True, disturbance_observer=disturbance_observer, dhat0=dhat0, checked=checked)
         loop.keep += (mi,)
         return loop
 
     def simulate(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                 noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None) -> ClosedLoopResult:
+                 noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None, disturbance_observer=None, dhat0=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
         loop = self.make_loop(x0, lastU, ticks, model, plant, plants, yref, uref, duref, dmeas, preview, noise, warm,
-                              observer=observer, xhat0=xhat0, meas_noise=meas_noise)
+                              observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0)
         try:
             self.run_loop(loop, stream)
             (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()

@@ -197,16 +197,24 @@ struct LmpcLoopDev {
     const double *xhat0;                          // [B x nx] or null (= x0), read by lmpc_loop_begin
     const double *meas_noise;                     // [ticks x B x ny] or null
     double *traj_xhat, *traj_y;                   // [(ticks + 1) x B x nx], [ticks x B x ny], or null
+    // offset-free loops (dobs 0: none): an observed loop whose estimator carries [xhat; dhat].  dmeas above is then the true disturbance, which drives
+    // the plant and the measurement and which the controller does not see; the solve reads dhat as its per-instance exogenous input; gain and
+    // gain_batch are [(nx + ndu) x ny], rows 0 .. nx - 1 the estimator block's L, the others Ld
+    int dobs;                                     // (before lmpc_loop_plan_lds: so is then the stride of [x | xhat | cmd | dhat | e | d])
+    double *dhat;                                 // [B x ndu]
+    double *dk; long dk_ts;                       // Ld of the instance's controller: ny terms of ndu rows, a fourth packed block
+    const double *dhat0;                          // [B x ndu] or null (= 0), read by lmpc_loop_begin
+    double *traj_dhat;                            // [(ticks + 1) x B x ndu] or null
 };
-void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv, so (ny before the call)
+void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv, so (ny and dobs before the call)
 size_t lmpc_loop_packed_len(const LmpcLoopDev &L);   // doubles of pk (whole tiles)
-// doubles of an observed loop's blocks with `tiles` tiles each: 0 the plant, 1 the estimator, 2 the measurement
+// doubles of an observed loop's blocks with `tiles` tiles each: 0 the plant, 1 the estimator, 2 the measurement, 3 the disturbance gain Ld
 size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles);
 size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L);
 int lmpc_loop_prepare(const LmpcLoopDev &L);      // once per loop, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
 int lmpc_loop_begin(const LmpcLoopDev &L, void *stream);
 int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of every run, next to lmpc_loop_begin: fills pk and d_own (no launch when both are null)
-int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills ok (unless it is pk), ek and mk
+int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills ok (unless it is pk), ek, mk and (offset-free) dk
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
 
 }  // namespace mpcx

@@ -28,6 +28,12 @@
 //   lmpc_loop_advance_observed  the per-instance kernel's shape for every plant: an instance's [x | xhat | cmd | d | e] side by side in LDS; first
 //                               the lanes of an instance take its output rows (y and yhat share a coefficient load, e to LDS, y to its log), then,
 //                               a barrier later, its state rows: the plant's sum and the estimator's, both straight out
+//
+// Offset-free tracking (mpcx_lmpc_loop_create_offset_free): an observed loop whose estimator carries [xhat; dhat].  The solve reads dhat_k as its
+// per-instance exogenous input, and the descriptor's dmeas becomes the true disturbance d_k, which the controller never sees:
+//   y = C x + Dd d_k + v_k,  e = y - (C xhat + Dd dhat),  x <- A_p x + B_p cmd + Bd_p d_k + w_k,  xhat <- A xhat + B cmd + Bd dhat + Lx e,  dhat <- dhat + Ld e
+//   the same two kernels, instantiated a second time: an instance's LDS row is [x | xhat | cmd | dhat | e | d], Ld a fourth packed block, and the
+//   lanes that took the state rows also take the ndu rows of dhat
 #include <hip/hip_runtime.h>
 
 #include "lmpc_device.hpp"
@@ -82,6 +88,14 @@ __global__ __launch_bounds__(kTile) void lmpc_loop_begin_kernel(const LmpcLoopDe
         }
     }
     for (int idx = tid; idx < nvalid * L.nu; idx += kTile) gout(L.u)[uo + idx] = gin(L.u0)[uo + idx];
+    if (L.dobs) {
+        const size_t eo = (size_t)b0 * L.ndu;
+        for (int idx = tid; idx < nvalid * L.ndu; idx += kTile) {
+            const double v = L.dhat0 ? gin(L.dhat0)[eo + idx] : 0.0;
+            gout(L.dhat)[eo + idx] = v;
+            if (L.traj_dhat) gout(L.traj_dhat)[eo + idx] = v;
+        }
+    }
     gather_windows(L, b0, nvalid, 0, tid);
     if (blockIdx.x == 0 && tid == 0) { gout(L.state)[0] = 0; gout(L.state)[1] = 0; }
 }
@@ -281,6 +295,10 @@ __device__ __forceinline__ void output_terms(const double LOOP_GAS *M, const siz
 // at its own tile stride.  Sum order, every row from acc = 0 by ascending column: y over C, then Dd, then + v_k; yhat the same without v_k; x as
 // above; xhat over A, B, Bd -- the plant's order -- then L, nothing added at the store.  Hence e = 0 exactly where xhat = x bitwise and v_k is
 // absent, and xhat <- x's own bits where the plant is the controller's model and no w_k comes on top.
+// kOff, the tick of an offset-free loop: the slot behind cmd holds dhat_k (the operand of yhat's Dd terms and of the estimator's Bd terms, so the
+// estimator's row is still one chain over hin ...), the true d_k has a slot of its own behind e (the operand of y's Dd terms and of the plant's Bd_p
+// terms), and dhat <- dhat + (Ld e summed from 0 by ascending column).  With Ld = 0 and dhat = d bitwise every sum is the observed tick's.
+template <bool kOff>
 __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *lds)
 {
     const int tid = threadIdx.x;
@@ -291,6 +309,8 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
     const int b0 = blockIdx.x * nt;
     const int nvalid = min(nt, B - b0);
     double *xin = lds, *hin = xin + nx, *cin = hin + nx, *din = cin + nu, *ein = din + ndu;   // an instance's row: the estimator's operands are hin ... in its terms' order
+    double *tin = din;                            // the disturbance that acts on the plant and on the measurement
+    if constexpr (kOff) tin = ein + ny;
     const size_t xo = (size_t)b0 * nx, uo = (size_t)b0 * nu;
 
     // in: the tile's true states, estimates, commands and exogenous-input samples, one contiguous run each
@@ -311,7 +331,8 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
         const double LOOP_GAS *dk = gin(L.dmeas) + (size_t)k * L.d_tick;
         for (int idx = tid; idx < nvalid * ndu; idx += kTile) {
             const int r = idx / ndu, c = idx - r * ndu;
-            din[r * so + c] = dk[(size_t)(b0 + r) * L.d_bs + c];
+            tin[r * so + c] = dk[(size_t)(b0 + r) * L.d_bs + c];
+            if constexpr (kOff) din[r * so + c] = gin(L.dhat)[(size_t)b0 * ndu + idx];      // dhat_k: no read of it behind this barrier
         }
     }
     __syncthreads();
@@ -323,13 +344,13 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
     if (mine) {
         const size_t width = (size_t)nt * ny;
         const double LOOP_GAS *M = gin(L.mk) + (size_t)blockIdx.x * L.mk_ts + q * ny;
-        const double *xr = xin + q * so, *hr = hin + q * so, *dr = din + q * so;
+        const double *xr = xin + q * so, *hr = hin + q * so, *dr = din + q * so, *tr = tin + q * so;
         const size_t yo = ((size_t)k * B + b0 + q) * ny;
         const double LOOP_GAS *vn = L.meas_noise ? gin(L.meas_noise) + yo : nullptr;
         for (int i = tid - q * lpi; i < ny; i += lpi) {
             double y = 0.0, yh = 0.0;
             output_terms(M + i, width, xr, hr, nx, y, yh);
-            output_terms(M + i + nx * width, width, dr, dr, ndu, y, yh);
+            output_terms(M + i + nx * width, width, tr, dr, ndu, y, yh);
             if (vn) y += vn[i];
             ein[q * so + i] = y - yh;
             if (L.traj_y) gout(L.traj_y)[yo + i] = y;
@@ -348,7 +369,10 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
         const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
         for (int i = tid - q * lpi; i < nx; i += lpi) {
             double acc = row_terms(P + i, width, xr, nx, 0.0);
-            acc = row_terms(P + i + nx * width, width, cr, nu + ndu, acc);
+            if constexpr (kOff) {
+                acc = row_terms(P + i + nx * width, width, cr, nu, acc);
+                acc = row_terms(P + i + (nx + nu) * width, width, tin + q * so, ndu, acc);
+            } else acc = row_terms(P + i + nx * width, width, cr, nu + ndu, acc);
             const double est = row_terms(E + i, width, hr, nx + nu + ndu + ny, 0.0);
             const size_t at = xo + q * nx + i;
             if (w) acc += w[at];
@@ -356,6 +380,18 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
             tx[at] = acc;
             gout(L.x)[at] = est;
             if (th) th[at] = est;
+        }
+        if constexpr (kOff) {                     // the rows of dhat, by the same lanes: ny terms of Ld, lane (q, i) reading element q * ndu + i of a term
+            const size_t wd = (size_t)nt * ndu;
+            const double LOOP_GAS *G = gin(L.dk) + (size_t)blockIdx.x * L.dk_ts + q * ndu;
+            const double *er = ein + q * so, *dr = din + q * so;
+            double LOOP_GAS *td = L.traj_dhat ? gout(L.traj_dhat) + (size_t)(k + 1) * B * ndu : nullptr;
+            for (int i = tid - q * lpi; i < ndu; i += lpi) {
+                const double v = dr[i] + row_terms(G + i, wd, er, ny, 0.0);
+                const size_t at = (size_t)(b0 + q) * ndu + i;
+                gout(L.dhat)[at] = v;
+                if (td) td[at] = v;
+            }
         }
     }
     finish_tick(L, b0, nvalid, k, tid);
@@ -377,7 +413,13 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) v
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) void lmpc_loop_advance_observed_kernel(const LmpcLoopDev L)
 {
     extern __shared__ double lds[];
-    advance_observed(L, lds);
+    advance_observed<false>(L, lds);
+}
+
+__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) void lmpc_loop_advance_offset_free_kernel(const LmpcLoopDev L)
+{
+    extern __shared__ double lds[];
+    advance_observed<true>(L, lds);
 }
 
 constexpr int kPackThreads = 256;
@@ -420,13 +462,15 @@ __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_plants_kernel(con
 // Head of a run of an observed loop: its blocks in the advance kernel's order.  The plant where it is one for the batch (from the row-major
 // `plant`: one tile, every instance of it the same), the estimator [A | B | Bd | L] and the measurement [C | Dd] from the handle's model or from
 // the model struct of each instance's controller, the gain from the one for the batch or from the caller's per-instance array.  A block with tile
-// stride 0 is one tile.
-__global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(const LmpcLoopDev L)
+// stride 0 is one tile.  kOff, an offset-free loop: the gain is [(nx + ndu) x ny], its first nx rows the estimator block's, the others the fourth block.
+template <bool kOff>
+__device__ __forceinline__ void pack_observer(const LmpcLoopDev &L)
 {
     const int nx = L.nx, nu = L.nu, ndu = L.ndu, ny = L.ny, B = L.batch, ipw = L.ipw;
     const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
     const size_t tiles = (size_t)((B + ipw - 1) / ipw);
     const int npl = nx + nu + ndu;
+    const int ldg = kOff ? nx + ndu : nx;         // rows of a gain
     if (L.ok != L.pk) {
         const size_t width = (size_t)ipw * nx, total = (size_t)npl * width;
         const double *Ap = L.plant, *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
@@ -445,7 +489,7 @@ __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(c
             const size_t b = L.ek_ts ? t * ipw + q : 0;
             double v = 0.0;
             if (b < (size_t)B) {
-                if (j >= npl) v = L.gain_batch ? gin(L.gain_batch)[(b * ny + (j - npl)) * nx + i] : L.gain[(j - npl) * nx + i];
+                if (j >= npl) v = L.gain_batch ? gin(L.gain_batch)[(b * ny + (j - npl)) * ldg + i] : L.gain[(j - npl) * ldg + i];
                 else if (L.mA) v = j < nx ? L.mA[j * nx + i] : j < nx + nu ? L.mB[(j - nx) * nx + i] : L.mBd[(j - nx - nu) * nx + i];
                 else {
                     const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
@@ -474,7 +518,23 @@ __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(c
             gout(L.mk)[idx] = v;
         }
     }
+    if constexpr (kOff) {
+        const size_t width = (size_t)ipw * ndu, per_tile = (size_t)ny * width;
+        const size_t total = (L.dk_ts ? tiles : 1) * per_tile;
+        for (size_t idx = first; idx < total; idx += step) {
+            const size_t t = idx / per_tile, rem = idx - t * per_tile;
+            const int j = (int)(rem / width), qi = (int)(rem - j * width);
+            const int q = qi / ndu, i = qi - q * ndu;
+            const size_t b = L.dk_ts ? t * ipw + q : 0;
+            double v = 0.0;
+            if (b < (size_t)B) v = L.gain_batch ? gin(L.gain_batch)[(b * ny + j) * ldg + nx + i] : L.gain[j * ldg + nx + i];
+            gout(L.dk)[idx] = v;
+        }
+    }
 }
+
+__global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(const LmpcLoopDev L) { pack_observer<false>(L); }
+__global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_offset_free_kernel(const LmpcLoopDev L) { pack_observer<true>(L); }
 
 inline int odd(int n) { return n | 1; }
 
@@ -484,15 +544,15 @@ void lmpc_loop_plan_lds(LmpcLoopDev &L)
 {
     L.sx = odd(L.nx); L.su = odd(L.nu); L.sd = L.ndu > 0 ? odd(L.ndu) : 0;
     L.ipw = L.nx < kTile ? kTile / L.nx : 1; L.sv = odd(L.nx + L.nu + L.ndu);
-    L.so = odd(2 * L.nx + L.nu + L.ndu + L.ny);
+    L.so = odd(2 * L.nx + L.nu + L.ndu + L.ny + (L.dobs ? L.ndu : 0));
 }
 
 size_t lmpc_loop_packed_len(const LmpcLoopDev &L) { return (size_t)((L.batch + L.ipw - 1) / L.ipw) * (L.nx + L.nu + L.ndu) * L.ipw * L.nx; }
 
 size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles)
 {
-    const size_t terms = which == 0 ? L.nx + L.nu + L.ndu : which == 1 ? L.nx + L.nu + L.ndu + L.ny : L.nx + L.ndu;
-    return tiles * terms * L.ipw * (which == 2 ? L.ny : L.nx);
+    const size_t terms = which == 0 ? L.nx + L.nu + L.ndu : which == 1 ? L.nx + L.nu + L.ndu + L.ny : which == 2 ? L.nx + L.ndu : L.ny;
+    return tiles * terms * L.ipw * (which == 2 ? L.ny : which == 3 ? L.ndu : L.nx);
 }
 
 static size_t observed_lds_bytes(const LmpcLoopDev &L) { return (size_t)L.ipw * L.so * sizeof(double); }
@@ -504,9 +564,8 @@ int lmpc_loop_prepare(const LmpcLoopDev &L)
     if (L.ek) {                                   // the observed kernel's tile: a few KB unless one instance has thousands of states
         const size_t bytes = observed_lds_bytes(L);
         if (bytes > lmpc_lds_limit()) return -2;
-        if (bytes > 48 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(lmpc_loop_advance_observed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-            return -3;
+        const void *kernel = L.dobs ? reinterpret_cast<const void *>(lmpc_loop_advance_offset_free_kernel) : reinterpret_cast<const void *>(lmpc_loop_advance_observed_kernel);
+        if (bytes > 48 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -3;
         return 0;
     }
     if (L.pk) return 0;                           // the per-instance kernel's tile: [x | cmd | d] of at most 64 instances of 1 state ... one of many
@@ -542,10 +601,12 @@ int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream)
     const size_t tiles = (size_t)((L.batch + L.ipw - 1) / L.ipw);
     size_t n = lmpc_loop_block_len(L, 1, L.ek_ts ? tiles : 1);
     if (lmpc_loop_block_len(L, 2, L.mk_ts ? tiles : 1) > n) n = lmpc_loop_block_len(L, 2, L.mk_ts ? tiles : 1);
+    if (L.dobs && lmpc_loop_block_len(L, 3, L.dk_ts ? tiles : 1) > n) n = lmpc_loop_block_len(L, 3, L.dk_ts ? tiles : 1);
     size_t blocks = (n + kPackThreads - 1) / kPackThreads;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(lmpc_loop_pack_observer_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    if (L.dobs) hipLaunchKernelGGL(lmpc_loop_pack_offset_free_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    else hipLaunchKernelGGL(lmpc_loop_pack_observer_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -553,7 +614,8 @@ int lmpc_loop_advance(const LmpcLoopDev &L, void *stream)
 {
     if (L.ek) {
         const int tiles = (L.batch + L.ipw - 1) / L.ipw;
-        hipLaunchKernelGGL(lmpc_loop_advance_observed_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
+        if (L.dobs) hipLaunchKernelGGL(lmpc_loop_advance_offset_free_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
+        else hipLaunchKernelGGL(lmpc_loop_advance_observed_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (L.pk) {

@@ -771,6 +771,7 @@ struct mpcx_lmpc_loop {
 
 int mpcx_lmpc_loop_desc_size(void) { return (int)sizeof(mpcx_lmpc_loop_desc); }
 int mpcx_lmpc_observer_desc_size(void) { return (int)sizeof(mpcx_lmpc_observer_desc); }
+int mpcx_lmpc_disturbance_observer_desc_size(void) { return (int)sizeof(mpcx_lmpc_disturbance_observer_desc); }
 
 // one tick -- the step of descriptor `b`, then the advance kernel -- captured on `s`
 static int capture_tick(const mpcx_lmpc_loop &l, const mpcx_lmpc_batch *b, hipStream_t s, hipGraphExec_t *exec)
@@ -816,11 +817,38 @@ static int check_observer_desc(const mpcx_lmpc_observer_desc *o, bool bank)
     return MPCX_OK;
 }
 
-// The loop of a controller (h) or of a bank (f, model_index), once the descriptor and the owner's state have been checked and the owner is set
-// up on the current device.  dm, active_words: the owner's.  o: the observer of an observed loop (checked), or null.
-static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words,
-                      const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, hipStream_t s, mpcx_lmpc_loop_t *out)
+// ... and a disturbance observer, likewise
+static int check_disturbance_observer_desc(const mpcx_lmpc_disturbance_observer_desc *o, bool bank)
 {
+    if (!o) return fail(MPCX_E_INVALID, "null observer: an offset-free loop needs an mpcx_lmpc_disturbance_observer_desc");
+    if (o->gain && o->gain_batch) return fail(MPCX_E_INVALID, "gain (one gain for the batch) and gain_batch (a gain per instance) exclude each other");
+    if (bank && o->gain) return fail(MPCX_E_INVALID, "a bank's controllers differ: its offset-free loop takes gain_batch, not gain");
+    if (!o->gain && !o->gain_batch) return fail(MPCX_E_INVALID, "a disturbance observer needs gain or gain_batch");
+    return MPCX_OK;
+}
+// ... and the owner's dimensions (not its state): without exogenous inputs there is no disturbance model
+static int check_disturbance_dims(const mpcx_dims &dm)
+{
+    if (dm.ndu == 0) return fail(MPCX_E_INVALID, "ndu = 0: the controller has no disturbance model (Bd, Dd) to estimate a disturbance with");
+    return MPCX_OK;
+}
+
+// what kind of loop an entry makes
+enum class LoopKind { Plain, Observed, OffsetFree };
+
+// The loop of a controller (h) or of a bank (f, model_index), once the descriptor and the owner's state have been checked and the owner is set
+// up on the current device.  dm, active_words: the owner's.  o: the observer of an observed loop (checked), or null; od: the disturbance observer of
+// an offset-free loop (checked), or null -- such a loop is an observed loop with the fields the two descriptors share, and what differs asks for od.
+static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words,
+                      const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const mpcx_lmpc_disturbance_observer_desc *od, hipStream_t s,
+                      mpcx_lmpc_loop_t *out)
+{
+    mpcx_lmpc_observer_desc shared_fields{};
+    if (od) {
+        shared_fields.gain = od->gain; shared_fields.gain_batch = od->gain_batch; shared_fields.xhat0 = od->xhat0; shared_fields.meas_noise = od->meas_noise;
+        shared_fields.traj_xhat = od->traj_xhat; shared_fields.traj_y = od->traj_y;
+        o = &shared_fields;
+    }
     const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
     const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode};
     const int ref_n[4] = {dm.ny, dm.nu, dm.nu, dm.ndu};
@@ -829,7 +857,7 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     if (h) { l->device = h->device; l->setups = h->n_full_setups; } else l->device = f->device;
     mpcx::LmpcLoopDev &L = l->L;
     const size_t B = (size_t)d->batch, aw = (size_t)active_words;
-    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw; L.ny = dm.ny;
+    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw; L.ny = dm.ny; L.dobs = od ? 1 : 0;
     mpcx::lmpc_loop_plan_lds(L);
     // which plant: one per instance (the caller's array; in a bank also the default, each instance's own controller), or one for the batch
     const bool uniform = d->plant_A || d->plant_B || d->plant_Bd;
@@ -845,20 +873,25 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     const size_t o_act = take(4 * B * aw * sizeof(uint32_t)), o_state = take(2 * sizeof(int));
     size_t o_pv[4] = {0, 0, 0, 0};
     for (int a = 0; a < 4; ++a)
-        if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
+        if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0 && !(od && a == 3)) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
     const size_t o_pk = packed ? take(mpcx::lmpc_loop_packed_len(L) * sizeof(double)) : 0;
     const size_t o_down = own_d ? take(B * dm.ndu * sizeof(double)) : 0;
     // an observed loop: the true state, and the packed blocks -- one tile where a block is the same for every instance (one plant for the batch; a
     // controller's own model, with one gain; a controller's own outputs), else a tile per ipw instances
     const size_t tiles = (B + L.ipw - 1) / L.ipw;
     const bool est_shared = o && h && o->gain, meas_shared = o && h;
-    size_t o_xt = 0, o_ok = 0, o_ek = 0, o_mk = 0, o_gain = 0;
+    size_t o_xt = 0, o_ok = 0, o_ek = 0, o_mk = 0, o_gain = 0, o_dhat = 0, o_dk = 0;
+    const size_t gain_len = (size_t)(dm.nx + (od ? dm.ndu : 0)) * dm.ny;
     if (o) {
         o_xt = take(B * dm.nx * sizeof(double));
         if (!packed) o_ok = take(mpcx::lmpc_loop_block_len(L, 0, 1) * sizeof(double));
         o_ek = take(mpcx::lmpc_loop_block_len(L, 1, est_shared ? 1 : tiles) * sizeof(double));
         o_mk = take(mpcx::lmpc_loop_block_len(L, 2, meas_shared ? 1 : tiles) * sizeof(double));
-        if (o->gain) o_gain = take((size_t)dm.nx * dm.ny * sizeof(double));
+        if (o->gain) o_gain = take(gain_len * sizeof(double));
+    }
+    if (od) {                                    // the estimate the solve reads, and Ld beside the estimator block, shared where that is
+        o_dhat = take(B * dm.ndu * sizeof(double));
+        o_dk = take(mpcx::lmpc_loop_block_len(L, 3, est_shared ? 1 : tiles) * sizeof(double));
     }
     if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
     if (hipMemset(l->slab, 0, total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
@@ -904,18 +937,24 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
         L.mk = dp(o_mk); L.mk_ts = meas_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 2, 1);
         if (h) { L.mA = h->dev.A; L.mB = h->dev.B; L.mBd = h->dev.Bd; L.mC = h->dev.C; L.mDd = h->dev.Dd; }
         if (o->gain) {
-            if (hipMemcpy(base + o_gain, o->gain, (size_t)dm.nx * dm.ny * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the observer gain failed");
+            if (hipMemcpy(base + o_gain, o->gain, gain_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the observer gain failed");
             L.gain = dp(o_gain);
         }
         L.gain_batch = o->gain_batch; L.xhat0 = o->xhat0; L.meas_noise = o->meas_noise; L.traj_xhat = o->traj_xhat; L.traj_y = o->traj_y;
     }
+    if (od) {
+        L.dhat = dp(o_dhat); L.dk = dp(o_dk); L.dk_ts = est_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 3, 1);
+        L.dhat0 = od->dhat0; L.traj_dhat = od->traj_dhat;
+    }
 
-    // the step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step
+    // the step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step; an
+    // offset-free loop's exogenous input is the loop's own estimate (the descriptor's drives the plant alone: no window)
     mpcx_lmpc_batch cold{};
     cold.batch = d->batch; cold.x0 = L.x; cold.u0 = L.u;
     const double *sp[4]; int sm[4];
     for (int a = 0; a < 4; ++a) {
         sp[a] = ref_p[a]; sm[a] = ref_m[a];
+        if (od && a == 3) { sp[a] = L.dhat; sm[a] = MPCX_REF_PER_INSTANCE; continue; }
         if (ref_m[a] != MPCX_REF_PREVIEW) continue;
         if (ref_n[a] == 0) { sp[a] = nullptr; sm[a] = MPCX_REF_SHARED; continue; }      // (no exogenous inputs: nothing to preview)
         L.pv_src[a] = ref_p[a]; L.pv_dst[a] = dp(o_pv[a]); L.pv_n[a] = ref_n[a];
@@ -961,13 +1000,16 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     return MPCX_OK;
 }
 
-// mpcx_lmpc_loop_create (observed false: o is not looked at) and mpcx_lmpc_loop_create_observed
-static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, bool observed, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
+// mpcx_lmpc_loop_create (neither o nor od is looked at), mpcx_lmpc_loop_create_observed (o) and mpcx_lmpc_loop_create_offset_free (od)
+static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, LoopKind kind, const mpcx_lmpc_observer_desc *o,
+                            const mpcx_lmpc_disturbance_observer_desc *od, void *stream, mpcx_lmpc_loop_t *out)
 {
     CHECK_H(h);
     if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
     int rc = check_loop_desc(d);
-    if (rc == MPCX_OK && observed) rc = check_observer_desc(o, false);
+    if (rc == MPCX_OK && kind == LoopKind::Observed) rc = check_observer_desc(o, false);
+    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_observer_desc(od, false);
+    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_dims(h->ctl.d);
     if (rc != MPCX_OK) return rc;
     if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
     if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
@@ -975,25 +1017,33 @@ static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, bool ob
     rc = mpcx_lmpc_setup(h);
     if (rc != MPCX_OK) return rc;
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, observed ? o : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, kind == LoopKind::Observed ? o : nullptr,
+                      kind == LoopKind::OffsetFree ? od : nullptr, reinterpret_cast<hipStream_t>(stream), out);
 }
 
 int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, false, nullptr, stream, out);
+    return lmpc_loop_create(h, d, LoopKind::Plain, nullptr, nullptr, stream, out);
 }
 
 int mpcx_lmpc_loop_create_observed(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, true, o, stream, out);
+    return lmpc_loop_create(h, d, LoopKind::Observed, o, nullptr, stream, out);
 }
 
-static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, bool observed, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
-                              void *stream, mpcx_lmpc_loop_t *out)
+int mpcx_lmpc_loop_create_offset_free(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return lmpc_loop_create(h, d, LoopKind::OffsetFree, nullptr, o, stream, out);
+}
+
+static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, LoopKind kind, const mpcx_lmpc_observer_desc *o,
+                              const mpcx_lmpc_disturbance_observer_desc *od, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
     if (!f || !d || !out) return fail(MPCX_E_INVALID, "null argument");
     int rc = check_loop_desc(d);
-    if (rc == MPCX_OK && observed) rc = check_observer_desc(o, true);
+    if (rc == MPCX_OK && kind == LoopKind::Observed) rc = check_observer_desc(o, true);
+    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_observer_desc(od, true);
+    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_dims(f->d);      // (the bank is followed only behind a good descriptor)
     if (rc != MPCX_OK) return rc;
     if (!model_index && d->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
     // a bank keeps no host copy of its controllers' models: there is no "the controller's own" to complete a one-for-all plant with
@@ -1001,18 +1051,25 @@ static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d
         return fail(MPCX_E_INVALID, "a bank's loop takes plant_A, plant_B and plant_Bd together (or plant_batch, or none: each instance's own controller)");
     if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
     if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, observed ? o : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, kind == LoopKind::Observed ? o : nullptr,
+                      kind == LoopKind::OffsetFree ? od : nullptr, reinterpret_cast<hipStream_t>(stream), out);
 }
 
 int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, false, nullptr, model_index, stream, out);
+    return hetero_loop_create(f, d, LoopKind::Plain, nullptr, nullptr, model_index, stream, out);
 }
 
 int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
                                           void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, true, o, model_index, stream, out);
+    return hetero_loop_create(f, d, LoopKind::Observed, o, nullptr, model_index, stream, out);
+}
+
+int mpcx_lmpc_hetero_loop_create_offset_free(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
+                                             const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return hetero_loop_create(f, d, LoopKind::OffsetFree, nullptr, o, model_index, stream, out);
 }
 
 // The steady-state Kalman predictor gain of the controller's own (A, C) by Riccati iteration (include/mpcx.h), host doubles throughout.

@@ -123,7 +123,8 @@ class BatchResult:
 class ClosedLoopResult:
     """A closed-loop run on the device (LMPC.simulate), tick-major device tensors: x [ticks+1, B, nx] (row 0 = the initial
     state), u [ticks, B, nu], the others [ticks, B].  An observed loop (observer=) also fills xhat [ticks+1, B, nx], the estimates
-    the solves read (row 0 = xhat0), and y [ticks, B, ny], the measurements; x is then the plant's true state."""
+    the solves read (row 0 = xhat0), and y [ticks, B, ny], the measurements; x is then the plant's true state.  An offset-free loop
+    (disturbance_observer=) fills those and dhat [ticks+1, B, ndu], the disturbance estimates the solves read (row 0 = dhat0)."""
     x: "object"
     u: "object"
     cost: "object"
@@ -134,13 +135,15 @@ class ClosedLoopResult:
     active_count: "object"
     xhat: "object" = None
     y: "object" = None
+    dhat: "object" = None
 
 
 @dataclass
 class Loop:
     """a loop made by LMPC.make_loop / LMPCHetero.make_loop: the native handle, the result whose tensors every run fills, the tensors the graph
     points at, and (plants=) the per-instance plants as every run reads them, [B, nx (nx+nu+ndu)] in LMPC.pack_plants' layout.  An observed
-    loop: gains (per-instance observer=) [B, nx ny] in LMPC.pack_gains' layout, xhat0 and meas_noise as every run reads them (refill in place)"""
+    loop: gains (per-instance observer=) [B, nx ny] in LMPC.pack_gains' layout, xhat0 and meas_noise as every run reads them (refill in place);
+    an offset-free loop: gains [B, (nx+ndu) ny] in the same layout, and dhat0"""
     handle: "object"
     result: ClosedLoopResult
     ticks: int
@@ -149,6 +152,7 @@ class Loop:
     gains: "object" = None
     xhat0: "object" = None
     meas_noise: "object" = None
+    dhat0: "object" = None
 
 
 def _cm(a, rows, cols):
@@ -519,6 +523,38 @@ class LMPC:
             raise ValueError(f"meas_noise must be [{ticks},{B},{self.ny}], got {shape(meas_noise)}")
         return len(sh) == 3
 
+    def _check_disturbance_observer(self, B, ticks, observer, gain, xhat0, dhat0, meas_noise, bank=False):
+        """disturbance_observer= ([nx+ndu, ny] one gain, [B, nx+ndu, ny] a gain per instance), xhat0=, dhat0= and meas_noise=, checked like
+        observer=, with which it is exclusive; True for a gain per instance"""
+        def shape(a):
+            return tuple((a if hasattr(a, "shape") else np.asarray(a)).shape)
+        if gain is None:
+            if dhat0 is not None:
+                raise ValueError("dhat0= belongs to an offset-free loop: give disturbance_observer=")
+            return False
+        if observer is not None:
+            raise ValueError("observer= (a state observer) and disturbance_observer= (its offset-free form) exclude each other")
+        if self.ndu == 0:
+            raise ValueError("disturbance_observer= needs a controller with exogenous inputs (ndu > 0) and a disturbance model (setDisturbances)")
+        n, sh = self.nx + self.ndu, shape(gain)
+        if sh not in ((n, self.ny), (B, n, self.ny)):
+            raise ValueError(f"disturbance_observer must be [{n},{self.ny}] or [{B},{n},{self.ny}], got {sh}")
+        if bank and len(sh) == 2:
+            raise ValueError(f"a bank's controllers differ: disturbance_observer must be a gain per instance, [{B},{n},{self.ny}]")
+        if xhat0 is not None and shape(xhat0) != (B, self.nx):
+            raise ValueError(f"xhat0 must be [{B},{self.nx}], got {shape(xhat0)}")
+        if dhat0 is not None and shape(dhat0) != (B, self.ndu):
+            raise ValueError(f"dhat0 must be [{B},{self.ndu}], got {shape(dhat0)}")
+        if meas_noise is not None and shape(meas_noise) != (ticks, B, self.ny):
+            raise ValueError(f"meas_noise must be [{ticks},{B},{self.ny}], got {shape(meas_noise)}")
+        return len(sh) == 3
+
+    def _check_observers(self, B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank=False):
+        """the checks of observer= or of disturbance_observer=, whichever is given: (offset-free?, a gain per instance?)"""
+        if disturbance_observer is not None or dhat0 is not None:
+            return disturbance_observer is not None, self._check_disturbance_observer(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
+        return False, self._check_observer(B, ticks, observer, xhat0, meas_noise, bank)
+
     @staticmethod
     def pack_gains(L):
         """[B, nx ny]: per instance L_b column-major -- mpcx_lmpc_observer_desc.gain_batch; a torch tensor [B, nx, ny] in, a tensor out
@@ -535,6 +571,23 @@ class LMPC:
         check(self._lib.mpcx_lmpc_kalman_gain(self._h, _p(Q), _p(R), _p(L), _p(P), C.byref(it)))
         return (L, P, it.value) if want_P else L
 
+    def disturbance_gain(self, Qw, Qd, Rv, want_P=False):
+        """The steady-state Kalman predictor gain [nx+ndu, ny] = [Lx; Ld] of the controller's model augmented with its integrating
+        disturbance model, ([[A, Bd], [0, I]], [C, Dd]), for the covariances Qw [nx, nx] of the process noise, Qd [ndu, ndu] of the
+        disturbance's random walk and Rv [ny, ny] of the sensor noise: what disturbance_observer= takes (libmpc_amd.utils.disturbance_gains,
+        one device call).  ValueError, before any device call, where the augmented pair is not detectable; MpcxError where the equation was
+        not solved.  want_P: (L, P) instead."""
+        from .utils import disturbance_gains
+        if self._A is None:
+            raise MpcxError(_capi.E_STATE, "state-space model not set")
+        L, P, flags = disturbance_gains(self._A, self._Bd, self._C, self._Dd, Qw, Qd, Rv, device=max(self.device, 0))
+        if int(flags[0]):
+            why = {1: "Rv is not positive definite", 2: "the doubling iteration has not converged",
+                   3: "the doubling iteration broke down"}[int(flags[0])]
+            raise MpcxError(_capi.E_NUMERIC, why)
+        L, P = L[0].cpu().numpy().copy(), P[0].cpu().numpy().copy()
+        return (L, P) if want_P else L
+
     def _own_plant(self, B, model=None):
         """the controller's own A, B, Bd for B instances (numpy, broadcast)"""
         if self._A is None:
@@ -550,14 +603,15 @@ class LMPC:
         return torch.cat([m.transpose(1, 2).reshape(n, m.shape[1] * m.shape[2]) for m in (A, B, Bd)], dim=1).contiguous()
 
     def _make_loop(self, create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None,
-                   observer=None, xhat0=None, meas_noise=None, bank=False):
+                   observer=None, xhat0=None, meas_noise=None, bank=False, disturbance_observer=None, dhat0=None, checked=None):
         """the descriptor of a loop, its result tensors and the create call: shared by LMPC and LMPCHetero (whose `create` takes the model index);
-        `create` is given the observer's descriptor, or None for an unobserved loop"""
+        `create` is given the observer's descriptor (an ObserverDesc or a DisturbanceObserverDesc), or None for an unobserved loop; checked:
+        what _check_observers returned where the caller has run it already"""
         ticks = int(ticks)
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
         plants = self._check_plants(B, plant, plants)
-        per_instance_gain = self._check_observer(B, ticks, observer, xhat0, meas_noise, bank)
+        offset_free, per_instance_gain = checked or self._check_observers(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
         torch, dev = self._torch()
         x0 = self._dev(torch, dev, x0, (B, self.nx))
         u0 = self._dev(torch, dev, lastU, (B, self.nu))
@@ -598,20 +652,30 @@ class LMPC:
         d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
         d.traj_status, d.traj_solver_status, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.iterations)
         d.traj_polish_rounds, d.traj_active_count = ptr(res.polish_rounds), ptr(res.active_count)
-        od, gains, gain_h, xh, v = None, None, None, None, None
+        od, gains, gain_h, xh, v, dh = None, None, None, None, None, None
+        if offset_free:
+            observer = disturbance_observer
         if observer is not None:
-            od = _capi.ObserverDesc()
+            od = _capi.DisturbanceObserverDesc() if offset_free else _capi.ObserverDesc()
+            rows = self.nx + (self.ndu if offset_free else 0)
             if per_instance_gain:
-                gains = self.pack_gains(self._dev(torch, dev, observer, (B, self.nx, self.ny)))
+                # not through _dev: its .contiguous() would copy what utils.kalman_gains / disturbance_gains return -- a view of this very
+                # layout, which pack_gains then takes as it is (Loop.gains is in that case the caller's own tensor); the shape has been checked
+                g = observer if isinstance(observer, torch.Tensor) else torch.as_tensor(np.asarray(observer, dtype=np.float64))
+                gains = self.pack_gains(g.to(device=dev, dtype=torch.float64))
                 od.gain_batch = ptr(gains)
             else:
-                gain_h = _cm(observer.cpu().numpy() if isinstance(observer, torch.Tensor) else observer, self.nx, self.ny)
+                gain_h = _cm(observer.cpu().numpy() if isinstance(observer, torch.Tensor) else observer, rows, self.ny)
                 od.gain = gain_h.ctypes.data
             xh = self._dev(torch, dev, xhat0, (B, self.nx))
             v = self._dev(torch, dev, meas_noise, (ticks, B, self.ny))
             res.xhat = torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev)
             res.y = torch.zeros((T, B, self.ny), dtype=f64, device=dev)
             od.xhat0, od.meas_noise, od.traj_xhat, od.traj_y = ptr(xh), ptr(v), ptr(res.xhat), ptr(res.y)
+            if offset_free:
+                dh = self._dev(torch, dev, dhat0, (B, self.ndu))
+                res.dhat = torch.zeros((T + 1, B, self.ndu), dtype=f64, device=dev)
+                od.dhat0, od.traj_dhat = ptr(dh), ptr(res.dhat)
         cur = torch.cuda.current_stream(self.device)
         s = stream if stream is not None else torch.cuda.Stream(device=dev)
         if s.cuda_stream == 0:
@@ -620,10 +684,11 @@ class LMPC:
         h = C.c_void_p()
         check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h), None if od is None else C.byref(od)))
         cur.wait_stream(s)
-        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v), pb, gains, xh, v)
+        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v, dh), pb, gains, xh, v, dh)
 
     def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                  noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None) -> Loop:
+                  noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,
+                  disturbance_observer=None, dhat0=None) -> Loop:
         """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by
         the plant step x <- A_p x + B_p cmd + Bd_p d_k + w_k on the device, with no host work in between.
 
@@ -637,13 +702,23 @@ class LMPC:
         observer: output feedback.  The solves then read an estimate xhat instead of the state: each tick measures y = C x + Dd d_k + v_k and
         updates xhat <- A xhat + B cmd + Bd d_k + L (y - C xhat - Dd d_k) with the controller's own model.  observer is the gain L, [nx, ny]
         for the batch (LMPC.kalman_gain) or [B, nx, ny] per instance (Loop.gains, refill with LMPC.pack_gains); xhat0: [B, nx], the first
-        estimate (None: x0); meas_noise: [ticks, B, ny] sensor noise v_k.  The result's xhat and y are then filled, and x is the true state."""
+        estimate (None: x0); meas_noise: [ticks, B, ny] sensor noise v_k.  The result's xhat and y are then filled, and x is the true state.
+
+        disturbance_observer: offset-free tracking, exclusive with observer=.  The estimator carries [xhat; dhat] with the controller's own
+        disturbance model (setDisturbances), dhat <- dhat + Ld e beside xhat <- A xhat + B cmd + Bd dhat + Lx e, and the solves read dhat as
+        their exogenous input, constant along the horizon.  dmeas= is then the TRUE disturbance, in every layout it has: it drives the plant
+        and the measurement and the controller never sees it (None: the controller's own exogenous input, zeros unless set).  The gain is
+        [Lx; Ld], [nx+ndu, ny] for the batch (LMPC.disturbance_gain) or [B, nx+ndu, ny] per instance (utils.disturbance_gains' as it is);
+        dhat0: [B, ndu], the first estimate (None: 0).  The result's dhat is filled as well.  The output settles on its reference where the
+        input weight is zero: no steady-state target is computed from dhat."""
         def create(d, s, out, od):
             if od is None:
                 return self._lib.mpcx_lmpc_loop_create(self._h, d, s, out)
+            if disturbance_observer is not None:
+                return self._lib.mpcx_lmpc_loop_create_offset_free(self._h, d, od, s, out)
             return self._lib.mpcx_lmpc_loop_create_observed(self._h, d, od, s, out)
         return self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream,
-                               observer=observer, xhat0=xhat0, meas_noise=meas_noise)
+                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0)
 
     def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
         """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
@@ -662,10 +737,11 @@ class LMPC:
             loop.handle = None
 
     def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                 noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None) -> ClosedLoopResult:
+                 noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,
+                 disturbance_observer=None, dhat0=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
         loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm, plants=plants,
-                              observer=observer, xhat0=xhat0, meas_noise=meas_noise)
+                              observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0)
         torch, _ = self._torch()
         try:
             self.run_loop(loop, stream)

@@ -87,3 +87,46 @@ def lqr_gains(A, B, Q, R, device=0, stream=None):
     """Infinite-horizon LQR for a batch: (K [Bn, m, n] with u = -K x, X [Bn, n, n] the cost-to-go -- a terminal weight --, flags) of
     dare(A, B, Q, R, "control")."""
     return dare(A, B, Q, R, "control", device, stream)
+
+
+def disturbance_gains(A, Bd, C, Dd, Qw, Qd, Rv, device=0, stream=None):
+    """Steady-state Kalman predictor gains of models augmented with an integrating disturbance, for offset-free loops
+    (disturbance_observer=): per instance Aa = [[A, Bd], [0, I]], Ca = [C, Dd], Q = blkdiag(Qw, Qd), and (L [Bn, nx+ndu, ny] -- rows
+    0 .. nx-1 are Lx, the others Ld --, P [Bn, nx+ndu, nx+ndu], flags) of dare(Aa, Ca, Q, Rv, "estimator").  A [Bn, nx, nx], Bd
+    [Bn, nx, ndu], C [Bn, ny, nx], Dd [Bn, ny, ndu] (2-D: a batch of one); Qw, Qd, Rv one for the batch or one per instance.  L is a view
+    of the layout mpcx_lmpc_disturbance_observer_desc.gain_batch takes.  ValueError before any device call: shapes, nx + ndu > 32, and an
+    augmented pair that is not detectable -- rank [[I - A, -Bd], [C, Dd]] = nx + ndu is required, which needs ndu <= ny."""
+    import numpy as np
+    import torch
+    A, Bd, C, Dd, Qw, Qd = (_as_f64(M) for M in (A, Bd, C, Dd, Qw, Qd))
+    if A.dim() == 2:
+        A, Bd, C, Dd = (M[None] if M.dim() == 2 else M for M in (A, Bd, C, Dd))
+    if A.dim() != 3 or A.shape[1] != A.shape[2] or Bd.dim() != 3 or C.dim() != 3 or Dd.dim() != 3:
+        raise ValueError(f"A {tuple(A.shape)} is not [Bn, nx, nx] with 3-D Bd, C and Dd beside it")
+    bn, nx, ndu, ny = A.shape[0], A.shape[1], Bd.shape[2], C.shape[1]
+    for name, M, sh in (("Bd", Bd, (bn, nx, ndu)), ("C", C, (bn, ny, nx)), ("Dd", Dd, (bn, ny, ndu))):
+        if tuple(M.shape) != sh:
+            raise ValueError(f"{name} {tuple(M.shape)} is not {list(sh)}")
+    for name, M, k in (("Qw", Qw, nx), ("Qd", Qd, ndu)):
+        if tuple(M.shape) not in ((k, k), (bn, k, k)):
+            raise ValueError(f"{name} {tuple(M.shape)} is neither [{k}, {k}] nor [{bn}, {k}, {k}]")
+    n = nx + ndu
+    if ndu < 1:
+        raise ValueError("ndu = 0: there is no disturbance model to estimate")
+    if not (1 <= n <= 32 and 1 <= ny <= 32):
+        raise ValueError(f"n = {n}, m = {ny}: 1 <= n <= 32 and 1 <= m <= 32 expected")
+    Aa = torch.zeros((bn, n, n), dtype=torch.float64)
+    Aa[:, :nx, :nx] = A; Aa[:, :nx, nx:] = Bd; Aa[:, nx:, nx:] = torch.eye(ndu, dtype=torch.float64)
+    Ca = torch.cat([C, Dd], dim=2)
+    # detectability of the integrators: the augmented pair has them observable exactly where this matrix has full column rank
+    M = np.concatenate([np.concatenate([np.eye(nx) - A.numpy(), -Bd.numpy()], axis=2), Ca.numpy()], axis=1)
+    sv = np.linalg.svd(M, compute_uv=False)                    # [bn, min(nx + ny, n)], descending
+    rank = (sv > sv[:, :1] * max(M.shape[1:]) * np.finfo(np.float64).eps).sum(axis=1)
+    if (rank < n).any():
+        k = int(np.argmax(rank < n))
+        raise ValueError(f"instance {k}: rank [[I - A, -Bd], [C, Dd]] = {int(rank[k])} < nx + ndu = {n}: the augmented pair ([[A, Bd], [0, I]], "
+                         f"[C, Dd]) is not detectable (ndu <= ny is necessary; so is a disturbance model that reaches the outputs)")
+    per = Qw.dim() == 3 or Qd.dim() == 3
+    Q = torch.zeros((bn, n, n) if per else (n, n), dtype=torch.float64)
+    Q[..., :nx, :nx] = Qw; Q[..., nx:, nx:] = Qd
+    return dare(Aa, Ca, Q, Rv, "estimator", device, stream)

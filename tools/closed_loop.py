@@ -8,7 +8,11 @@ bench.py): the host-driven loop is LMPCHetero.optimizeBatch plus a batched torch
 LMPCHetero.make_loop / run_loop, every instance stepped by its own controller's model.
 The observed leg (lines with "observed": true; not part of "all") is the device loop with output feedback beside the device loop without, the same
 build and the same inputs, run alternately: the observer's gain is LMPC.kalman_gain(0.01 I, 0.04 I), the sensor noise has standard deviation 0.2.
-Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|observed|all]"""
+The offset_free leg (lines with "offset_free": true; not part of "all") is the offset-free loop beside the observed loop, the same build and the
+same inputs, run alternately: the quadrotor with an input-disturbance model (Bd = B, Dd = 0), a constant load of 0.1 per rotor and sensor noise of
+standard deviation 0.01.  The observed loop is told the load as its per-instance dmeas (so both loops' solves take the same kernels) and estimates
+with LMPC.kalman_gain(0.01 I, 0.04 I); the offset-free loop is told nothing and estimates with LMPC.disturbance_gain(0.01 I, 0.01 I, 0.04 I).
+Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|observed|offset_free|all]"""
 import json
 import sys
 import time
@@ -56,6 +60,21 @@ def make_observed(B, ticks, warm):
     L = c.kalman_gain(0.01 * np.eye(c.nx), 0.04 * np.eye(c.ny))
     v = 0.2 * np.random.default_rng(1).normal(size=(ticks, B, c.ny))
     return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm, observer=L, meas_noise=v)
+
+
+def make_disturbed(B, ticks, warm, offset_free):
+    """the observed loop that is told the load, or the offset-free loop that estimates it: (controller, loop)"""
+    c = quadrotor_lmpc(20, device=0)
+    _, Bq, _ = quadrotor_matrices()
+    assert c.setDisturbances(Bq, np.zeros((c.ny, c.ndu)))
+    x0, u0, yref = quadrotor_batch(B)
+    load = np.full((B, c.ndu), 0.1)
+    v = 0.01 * np.random.default_rng(1).normal(size=(ticks, B, c.ny))
+    if offset_free:
+        L = c.disturbance_gain(0.01 * np.eye(c.nx), 0.01 * np.eye(c.ndu), 0.04 * np.eye(c.ny))
+        return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm, disturbance_observer=L, dmeas=load, meas_noise=v)
+    L = c.kalman_gain(0.01 * np.eye(c.nx), 0.04 * np.eye(c.ny))
+    return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm, observer=L, dmeas=load, meas_noise=v)
 
 
 def run_device(c, loop):
@@ -142,6 +161,20 @@ if __name__ == "__main__":
                               unobserved_mean_rounds=plain[-1]["mean_rounds"], observed_mean_rounds=obs[-1]["mean_rounds"],
                               unobserved_solved=plain[-1]["solved"], observed_solved=obs[-1]["solved"])))
         c.destroy_loop(loop); co.destroy_loop(loopo)
+    for w in (False, True) if legs == "offset_free" else ():
+        co, loopo = make_disturbed(B, ticks, w, False)
+        cf, loopf = make_disturbed(B, ticks, w, True)
+        run_device(co, loopo); run_device(cf, loopf)          # warm-up of both legs
+        obs, off = [], []
+        for _ in range(repeats):                              # alternating, as above
+            obs.append(run_device(co, loopo)); off.append(run_device(cf, loopf))
+        om, olo, ohi = median_spread([r["ms_per_tick"] for r in obs])
+        fm, flo, fhi = median_spread([r["ms_per_tick"] for r in off])
+        print(json.dumps(dict(offset_free=True, warm=w, batch=B, ticks=ticks, repeats=repeats,
+                              observed_ms_per_tick=dict(median=om, min=olo, max=ohi), offset_free_ms_per_tick=dict(median=fm, min=flo, max=fhi),
+                              observed_mean_rounds=obs[-1]["mean_rounds"], offset_free_mean_rounds=off[-1]["mean_rounds"],
+                              observed_solved=obs[-1]["solved"], offset_free_solved=off[-1]["solved"])))
+        co.destroy_loop(loopo); cf.destroy_loop(loopf)
     if legs in ("bank", "all"):
         het, (x0, u0, yref), dev = make_bank(B)
         run_bank(het, dev, 5, True)
