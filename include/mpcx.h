@@ -9,6 +9,7 @@
  *                 Objective / Constraints (include/mpc/NLMPC/NLOptimizer.hpp:412-638);
  *   mpcx_discretize_batch  the c2d set-up helper (include/mpc/Utils.hpp:23-89);
  *   mpcx_dare_batch        Kalman and LQR gains for a batch of models (no reference counterpart).
+ *   mpcx_target_map_batch  steady-state target maps for a batch of models (no reference counterpart).
  *
  * Conventions
  *   - plain C, opaque handle, no C++/torch types in any signature;
@@ -281,9 +282,9 @@ int mpcx_lmpc_observer_desc_size(void);           /* sizeof(mpcx_lmpc_observer_d
  * over Ld from 0, added to dhat_k once -- so that with Ld = 0, dhat_0 = d bitwise and d constant per instance the loop reproduces, bit for bit,
  * mpcx_lmpc_loop_create_observed given the same d as per-instance dmeas.  gain_batch is what mpcx_dare_batch (MPCX_DARE_ESTIMATOR, n = nx + ndu,
  * m = ny) writes for the augmented pair ([[A, Bd], [0, I]], [C, Dd]): hand it over as it is.  The augmented pair is detectable only where
- * rank [[I - A, -Bd], [C, Dd]] = nx + ndu, which needs ndu <= ny.  No steady-state target is computed from dhat: the output settles on its
- * reference where the input weight is zero (or the input reference is the steady-state input); offset-free tracking with a non-zero input weight
- * is not claimed.  The loop is an mpcx_lmpc_loop_t as before; gain is copied at creation; gain_batch, xhat0, dhat0 and meas_noise are read by
+ * rank [[I - A, -Bd], [C, Dd]] = nx + ndu, which needs ndu <= ny.  This loop computes no steady-state target from dhat: the output settles on its
+ * reference where the input weight is zero (or the input reference is the steady-state input); with a non-zero input weight use
+ * mpcx_lmpc_loop_create_offset_free_target below, which does.  The loop is an mpcx_lmpc_loop_t as before; gain is copied at creation; gain_batch, xhat0, dhat0 and meas_noise are read by
  * every run: refill them in place. */
 typedef struct mpcx_lmpc_disturbance_observer_desc {
     const double *gain;                           /* HOST, column-major [(nx+ndu) x ny] (rows 0 .. nx-1 = Lx, then Ld): one gain for the batch, or NULL */
@@ -297,6 +298,26 @@ typedef struct mpcx_lmpc_disturbance_observer_desc {
  * without exogenous inputs (ndu = 0: there is no disturbance model to estimate). */
 int mpcx_lmpc_loop_create_offset_free(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out);
 int mpcx_lmpc_disturbance_observer_desc_size(void);   /* sizeof(mpcx_lmpc_disturbance_observer_desc), for bindings that mirror the struct */
+/* An offset-free loop with steady-state targets (no reference counterpart): with a non-zero input weight the input term of the cost pulls the
+ * steady state away from yref unless the input reference is the steady-state input, so the loop computes that input from dhat at every tick,
+ *     us_k = T [r_k; dhat_k; ubar_k],      T = [Tr | Td | Tu]  [nu x nrhs], nrhs = ny + ndu + nu, column-major: what mpcx_target_map_batch writes
+ * and the solve of tick k reads the loop's own [B x nu] buffer us_k as its MPCX_REF_PER_INSTANCE uref (as it reads dhat_k for dmeas).  The loop
+ * descriptor's uref, in every mode it has, becomes ubar_k: step 0 of the tick's array (a bank's "shared": each controller's own); r_k is step 0
+ * of the tick's yref, taken the same way; yref still reaches the solve unchanged in every mode.  us_0 comes from dhat0, r_0, ubar_0 when a run
+ * begins, us_{k+1} from the advance kernel of tick k; every row is summed from 0 with fused multiply-adds by ascending column (Tr, Td, Tu), the
+ * sum of mpcx_target_apply_batch, bit for bit.  us is not clipped to the input bounds and yref is not replaced by a steady-state output: targets
+ * under active bounds are a QP, which is out of scope -- traj_us shows what the solve was given.  map is copied at creation; map_batch is read
+ * at the head of every run: refill it in place. */
+typedef struct mpcx_lmpc_target_desc {
+    const double *map;                            /* HOST, column-major [nu x nrhs]: one map for the batch, or NULL */
+    const double *map_batch;                      /* device, [B x nu*nrhs], per instance, column-major; excludes map */
+    double *traj_us;                              /* device, optional: [(ticks+1) x B x nu] */
+} mpcx_lmpc_target_desc;
+/* MPCX_E_INVALID, ahead of any look at the handle's state, for a null target descriptor, for neither or both of map / map_batch, and for
+ * everything mpcx_lmpc_loop_create_offset_free refuses. */
+int mpcx_lmpc_loop_create_offset_free_target(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
+                                             const mpcx_lmpc_target_desc *t, void *stream, mpcx_lmpc_loop_t *out);
+int mpcx_lmpc_target_desc_size(void);             /* sizeof(mpcx_lmpc_target_desc), for bindings that mirror the struct */
 /* The steady-state Kalman predictor gain of the controller's own (A, C) (no reference counterpart), on the host in doubles; works on a host-only
  * handle.  L = A P C' (C P C' + Rv)^-1 with P the fixed point of P <- A P A' - A P C' (C P C' + Rv)^-1 C P A' + Qw, iterated from P = Qw and
  * symmetrised every time, until the largest change of an entry is <= 1e-14 times the largest entry.  Qw [nx x nx], Rv [ny x ny], gain_out
@@ -609,6 +630,25 @@ int mpcx_discretize_batch(int device, int nx, int nu, int batch, const double *A
 int mpcx_dare_batch(int device, int form, int n, int m, int batch, const double *A, const double *BorC, const double *Q, const double *R,
                     int q_per_instance, int r_per_instance, double *X, double *gain, int32_t *flags, int32_t *iterations, void *stream);
 
+/* A batch of steady-state target maps on the device (no reference counterpart; kernel target_map of target_kernels.hip, one instance per
+ * wavefront).  For a model (A, B, Bd, C, Dd) the target of a reference r, a disturbance estimate dhat and an input reference ubar is
+ *     minimise 1/2 |us - ubar|^2   subject to   (I - A) xs - B us = Bd dhat,   C xs = r - Dd dhat
+ * and linear in them: us = map_u [r; dhat; ubar], xs = map_x [r; dhat; ubar].  The maps come from the KKT system of order 2 nx + nu + ny by Gaussian
+ * elimination with partial pivoting.  Device pointers, column-major per instance: A [B x nx nx], B [B x nx nu], Bd [B x nx ndu], C [B x ny nx],
+ * Dd [B x ny ndu]; map_u [B x nu nrhs] with nrhs = ny + ndu + nu (the layout mpcx_lmpc_target_desc.map_batch takes); map_x [B x nx nrhs] and
+ * flags [B] may be NULL.  flags: 0 fine; 1 singular (a vanishing or non-finite pivot: a reference that cannot be reached -- ny > nu, or a rank
+ * deficient [[I - A, -B], [C, 0]] -- or an integrator the outputs do not see).  An instance with a non-zero flag has NaN in every entry of its
+ * maps; the others are not affected, and an instance's bits depend on its own inputs alone.  MPCX_E_INVALID for nx, nu, ny < 1, ndu < 0, a
+ * negative batch or a null A, B, C, map_u (Bd, Dd with ndu > 0); MPCX_E_UNSUPPORTED where the augmented matrix -- (2 nx + nu + ny) (2 nx + 2 nu
+ * + 2 ny + ndu) doubles -- exceeds the LDS a workgroup may request: both checked before anything touches a device. */
+int mpcx_target_map_batch(int device, int nx, int nu, int ndu, int ny, int batch, const double *A, const double *B, const double *Bd, const double *C,
+                          const double *Dd, double *map_u, double *map_x, int32_t *flags, void *stream);
+/* us[b] = map_u[b, or the one map] [r_b; dhat_b; ubar_b] for host-driven loops: every row summed from 0 with fused multiply-adds by ascending
+ * column, by the device function the closed loop uses (bit-identical to it).  Device pointers: map_u [B x nu nrhs] (map_per_instance) or
+ * [nu nrhs], r [B x ny], dhat [B x ndu], ubar [B x nu], us [B x nu]. */
+int mpcx_target_apply_batch(int device, int nu, int ndu, int ny, int batch, const double *map_u, int map_per_instance, const double *r,
+                            const double *dhat, const double *ubar, double *us, void *stream);
+
 /* ---- multi-GPU: the one collective on the path --------------------------------- */
 /* The reference solves one controller per object and has no coupling between objects (LMPC.hpp:751), so a batch shards
  * as contiguous slices, one process per GPU, and nothing is exchanged during the solve.  Afterwards every rank
@@ -669,6 +709,10 @@ int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_
  * (MPCX_E_INVALID for gain, as above).  dmeas in MPCX_REF_SHARED mode: each controller's own exogenous input, step 0, as the true disturbance. */
 int mpcx_lmpc_hetero_loop_create_offset_free(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
                                              const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out);
+/* ... and with steady-state targets: a bank's controllers differ, so map_batch is required (MPCX_E_INVALID for map, ahead of any look at the
+ * bank).  uref and yref in MPCX_REF_SHARED mode: each controller's own references, step 0, as ubar and r. */
+int mpcx_lmpc_hetero_loop_create_offset_free_target(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
+                                                    const mpcx_lmpc_target_desc *t, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out);
 
 /* Sharding: this handle solves contiguous shards of a batch of `total` instances -- the kernel form is chosen for
  * the whole batch's size, so that a shard's results are bit for bit the rows of the unsharded solve (0 = every call is a whole batch). */

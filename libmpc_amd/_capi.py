@@ -72,6 +72,11 @@ class DisturbanceObserverDesc(C.Structure):
                 ("traj_xhat", C.c_void_p), ("traj_dhat", C.c_void_p), ("traj_y", C.c_void_p)]
 
 
+class TargetDesc(C.Structure):
+    """mpcx_lmpc_target_desc: the steady-state targets of an offset-free loop (map is a host pointer, everything else device pointers)"""
+    _fields_ = [("map", C.c_void_p), ("map_batch", C.c_void_p), ("traj_us", C.c_void_p)]
+
+
 class Info(C.Structure):
     _fields_ = [("n_ref", C.c_int), ("m_ref", C.c_int), ("neq_ref", C.c_int), ("nz", C.c_int), ("mg", C.c_int),
                 ("active_words", C.c_int), ("kernel_variant", C.c_int),
@@ -95,6 +100,8 @@ EXPORTS = [
     "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
     "mpcx_lmpc_loop_create_observed", "mpcx_lmpc_hetero_loop_create_observed", "mpcx_lmpc_observer_desc_size", "mpcx_lmpc_kalman_gain",
     "mpcx_lmpc_loop_create_offset_free", "mpcx_lmpc_hetero_loop_create_offset_free", "mpcx_lmpc_disturbance_observer_desc_size",
+    "mpcx_lmpc_loop_create_offset_free_target", "mpcx_lmpc_hetero_loop_create_offset_free_target", "mpcx_lmpc_target_desc_size",
+    "mpcx_target_map_batch", "mpcx_target_apply_batch",
     "mpcx_nlmpc_create", "mpcx_nlmpc_destroy", "mpcx_nlmpc_get_dims", "mpcx_nlmpc_evaluate_batch",
     "mpcx_nlparams_default", "mpcx_nlmpc_set_optimizer_parameters", "mpcx_nlmpc_solve_batch", "mpcx_nlmpc_time_solve_batch", "mpcx_discretize_batch", "mpcx_dare_batch",
     "mpcx_nlmpc_set_state_bounds_slice", "mpcx_nlmpc_set_input_bounds_slice", "mpcx_nlmpc_solve_host",
@@ -190,6 +197,10 @@ def lib():
         _lib.mpcx_lmpc_hetero_loop_create_observed.argtypes = [C.c_void_p] * 6
         _lib.mpcx_lmpc_loop_create_offset_free.argtypes = [C.c_void_p] * 5
         _lib.mpcx_lmpc_hetero_loop_create_offset_free.argtypes = [C.c_void_p] * 6
+        _lib.mpcx_lmpc_loop_create_offset_free_target.argtypes = [C.c_void_p] * 6
+        _lib.mpcx_lmpc_hetero_loop_create_offset_free_target.argtypes = [C.c_void_p] * 7
+        _lib.mpcx_target_map_batch.argtypes = [C.c_int] * 6 + [C.c_void_p] * 9
+        _lib.mpcx_target_apply_batch.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mpcx_lmpc_kalman_gain.argtypes = [C.c_void_p] * 6
         _lib.mpcx_lmpc_loop_run.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_loop_destroy.argtypes = [C.c_void_p]

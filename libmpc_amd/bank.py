@@ -170,7 +170,7 @@ class LMPCHetero:
     # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create; the loop itself is LMPC's) -------------------------------
     _loop_ref, _check_plants, _make_loop, pack_plants = LMPC._loop_ref, LMPC._check_plants, LMPC._make_loop, staticmethod(LMPC.pack_plants)
     _check_observer, pack_gains = LMPC._check_observer, staticmethod(LMPC.pack_gains)
-    _check_disturbance_observer, _check_observers = LMPC._check_disturbance_observer, LMPC._check_observers
+    _check_disturbance_observer, _check_observers, _check_target = LMPC._check_disturbance_observer, LMPC._check_observers, LMPC._check_target
     run_loop, destroy_loop = LMPC.run_loop, LMPC.destroy_loop
 
     def _own_plant(self, B, model=None):
@@ -217,8 +217,23 @@ class LMPCHetero:
             raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {k}: {why}")
         return L
 
+    def target_maps(self):
+        """LMPC.target_map for every controller of the bank, [count, nu, ny+ndu+nu] on the device, in one batched call
+        (libmpc_amd.utils.target_maps).  Index it by the instances' controllers (maps[model]) for target=.  ValueError, before any device call,
+        naming the first controller that misses a rank condition; MpcxError naming the first whose KKT system is singular all the same."""
+        from .utils import target_maps
+        if any(m[0] is None for m in self._models):
+            raise _capi.MpcxError(_capi.E_STATE, "state-space model not set")
+        A, B, Bd = (np.stack([m[j] for m in self._models]) for j in range(3))
+        T, flags = target_maps(A, B, Bd, np.stack(self._outputs), np.stack(self._feedthrough), device=self.device)
+        bad = torch.nonzero(flags).reshape(-1)
+        if bad.numel():
+            raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {int(bad[0])}: the KKT system of the target is singular")
+        return T
+
     def make_loop(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                  noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None, disturbance_observer=None, dhat0=None) -> Loop:
+                  noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None, disturbance_observer=None, dhat0=None,
+                  target=None) -> Loop:
         """LMPC.make_loop for a bank: every tick is the bank's batched solve (instance b by controller model[b]; None: controller b)
         followed by the plant step.  plant: one plant for all, (A_p, B_p, Bd_p); plants: a plant per instance, (A [B,nx,nx],
         B [B,nx,nu] | None, Bd | None); a None entry of either, and no plant at all, mean each instance's own controller.  References:
@@ -226,11 +241,14 @@ class LMPCHetero:
         in LMPC.make_loop, instance b estimated with its own controller's model; the gain is per instance, [B, nx, ny] (the controllers
         differ: one gain for all raises ValueError).  disturbance_observer, dhat0: offset-free tracking as in LMPC.make_loop, the gain
         [B, nx+ndu, ny] (LMPCHetero.disturbance_gains indexed by the instances' controllers); dmeas= is then the true disturbance, None each
-        controller's own exogenous input.  Destroy the loop before the bank."""
+        controller's own exogenous input.  target: steady-state targets as in LMPC.make_loop, the map [B, nu, ny+ndu+nu]
+        (LMPCHetero.target_maps indexed by the instances' controllers); yref / uref None: each controller's own as r and ubar.  Destroy the
+        loop before the bank."""
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
         plants = self._check_plants(B, plant, plants)
         checked = self._check_observers(B, int(ticks), observer, disturbance_observer, xhat0, dhat0, meas_noise, bank=True)
+        self._check_target(B, target, disturbance_observer, bank=True)
         mi = None
         if model is not None:
             mi = torch.as_tensor(model).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
@@ -243,23 +261,28 @@ class LMPCHetero:
                 plants = tuple(None if m is None else np.broadcast_to(np.asarray(m, dtype=np.float64), (B,) + np.shape(m)) for m in plant)
                 plant = None
 
-        def create(d, s, out, od):
+        def create(d, s, out, od, td=None):
             mp = None if mi is None else C.c_void_p(mi.data_ptr())
             if od is None:
                 return self._lib.mpcx_lmpc_hetero_loop_create(self._h, d, mp, s, out)
+            if td is not None:
+                return self._lib.mpcx_lmpc_hetero_loop_create_offset_free_target(self._h, d, od, td, mp, s, out)
             if disturbance_observer is not None:
                 return self._lib.mpcx_lmpc_hetero_loop_create_offset_free(self._h, d, od, mp, s, out)
             return self._lib.mpcx_lmpc_hetero_loop_create_observed(self._h, d, od, mp, s, out)
         loop = self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi,
-                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, bank=True, disturbance_observer=disturbance_observer, dhat0=dhat0, checked=checked)
+                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, bank=True, disturbance_observer=disturbance_observer, dhat0=dhat0, checked=checked,
+                               target=target)
         loop.keep += (mi,)
         return loop
 
     def simulate(self, x0, lastU, ticks, model=None, plant=None, plants=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
-                 noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None, disturbance_observer=None, dhat0=None) -> ClosedLoopResult:
+                 noise=None, warm=True, stream=None, observer=None, xhat0=None, meas_noise=None, disturbance_observer=None, dhat0=None,
+                 target=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
         loop = self.make_loop(x0, lastU, ticks, model, plant, plants, yref, uref, duref, dmeas, preview, noise, warm,
-                              observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0)
+                              observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0,
+                              target=target)
         try:
             self.run_loop(loop, stream)
             (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()

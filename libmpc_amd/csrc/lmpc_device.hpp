@@ -205,16 +205,35 @@ struct LmpcLoopDev {
     double *dk; long dk_ts;                       // Ld of the instance's controller: ny terms of ndu rows, a fourth packed block
     const double *dhat0;                          // [B x ndu] or null (= 0), read by lmpc_loop_begin
     double *traj_dhat;                            // [(ticks + 1) x B x ndu] or null
+    // steady-state targets (tgt 0: none; needs dobs): us = T [r; dhat; ubar] with T [nu x (ny + ndu + nu)] column-major is what the solve reads as its
+    // per-instance uref.  r and ubar are step 0 of the tick's yref and uref: value(b, k, a) = src[b * bs + k * tick + a]; a null source is a bank's
+    // "shared" mode, each controller's own (models / model_index)
+    int tgt;                                      // (before lmpc_loop_plan_lds: so then also holds [r | dhat+ | ubar] of tick k + 1)
+    double *us;                                   // [B x nu]
+    double *tk; long tk_ts;                       // T of the instance's controller: ny + ndu + nu terms of nu rows, a fifth packed block
+    const double *tmap, *tmap_batch;              // one map for the batch (device copy), or the caller's [B x nu nrhs]
+    const double *r_src; long r_bs, r_tick;
+    const double *ub_src; long ub_bs, ub_tick;
+    double *traj_us;                              // [(ticks + 1) x B x nu] or null
 };
-void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv, so (ny and dobs before the call)
+void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv, so (ny, dobs and tgt before the call)
 size_t lmpc_loop_packed_len(const LmpcLoopDev &L);   // doubles of pk (whole tiles)
-// doubles of an observed loop's blocks with `tiles` tiles each: 0 the plant, 1 the estimator, 2 the measurement, 3 the disturbance gain Ld
+// doubles of an observed loop's blocks with `tiles` tiles each: 0 the plant, 1 the estimator, 2 the measurement, 3 the disturbance gain Ld,
+// 4 the target map
 size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles);
 size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L);
 int lmpc_loop_prepare(const LmpcLoopDev &L);      // once per loop, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
 int lmpc_loop_begin(const LmpcLoopDev &L, void *stream);
 int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of every run, next to lmpc_loop_begin: fills pk and d_own (no launch when both are null)
-int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills ok (unless it is pk), ek, mk and (offset-free) dk
+int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills ok (unless it is pk), ek, mk, (offset-free) dk and (targets) tk
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
+
+// Steady-state target maps (target_kernels.hip): the KKT system of each instance's target, one instance per wavefront, and the product with a map
+size_t target_map_lds_bytes(int nx, int nu, int ndu, int ny);         // the augmented matrix [K | rhs] of one instance
+// 0; -2: the augmented matrix exceeds lds_limit; -3: a launch or its configuration failed
+int target_map_launch(int nx, int nu, int ndu, int ny, int batch, const double *A, const double *B, const double *Bd, const double *C, const double *Dd,
+                      double *map_u, double *map_x, int *flags, size_t lds_limit, void *stream);
+int target_apply_launch(int nu, int ndu, int ny, int batch, const double *map_u, int map_per_instance, const double *r, const double *dhat,
+                        const double *ubar, double *us, void *stream);
 
 }  // namespace mpcx

@@ -34,9 +34,17 @@
 //   y = C x + Dd d_k + v_k,  e = y - (C xhat + Dd dhat),  x <- A_p x + B_p cmd + Bd_p d_k + w_k,  xhat <- A xhat + B cmd + Bd dhat + Lx e,  dhat <- dhat + Ld e
 //   the same two kernels, instantiated a second time: an instance's LDS row is [x | xhat | cmd | dhat | e | d], Ld a fourth packed block, and the
 //   lanes that took the state rows also take the ndu rows of dhat
+//
+// Steady-state targets (mpcx_lmpc_loop_create_offset_free_target): an offset-free loop whose solve reads us_k = T [r_k; dhat_k; ubar_k] as its
+// per-instance input reference, r_k and ubar_k step 0 of the tick's yref and uref.  us_0 is the begin kernel's (from dhat0, the caller's map as it
+// lies); us_{k+1} the advance kernel's of tick k, a third instantiation: the instance's LDS row also holds [r_{k+1} | dhat_{k+1} | ubar_{k+1}] --
+// dhat_{k+1} in a slot of its own, the dhat_k slot is still being read by the estimator rows of other lanes -- and, one barrier behind the rows of
+// dhat, the instance's lanes take the nu rows of us over T, a fifth packed block.  The row's sum is target_us_row (target_device.hpp), the one
+// mpcx_target_apply_batch uses.
 #include <hip/hip_runtime.h>
 
 #include "lmpc_device.hpp"
+#include "target_device.hpp"
 
 namespace mpcx {
 
@@ -67,6 +75,18 @@ __device__ __forceinline__ void gather_windows(const LmpcLoopDev &L, const int b
     }
 }
 
+// step 0 of tick k's yref (which = 0: r_k) or uref (1: ubar_k) of instance b; a null source is a bank's "shared" mode: each controller's own
+__device__ __forceinline__ const double *target_ref(const LmpcLoopDev &L, const int which, const int b, const int k)
+{
+    const double *src = which ? L.ub_src : L.r_src;
+    if (!src) {
+        const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : b];
+        return which ? M.uref_s : M.yref_s;
+    }
+    return src + (size_t)b * (which ? L.ub_bs : L.r_bs) + (size_t)k * (which ? L.ub_tick : L.r_tick);
+}
+struct ZeroOperand { __device__ double operator[](int) const { return 0.0; } };      // dhat0 = NULL
+
 __global__ __launch_bounds__(kTile) void lmpc_loop_begin_kernel(const LmpcLoopDev L)
 {
     const int tid = threadIdx.x;
@@ -94,6 +114,19 @@ __global__ __launch_bounds__(kTile) void lmpc_loop_begin_kernel(const LmpcLoopDe
             const double v = L.dhat0 ? gin(L.dhat0)[eo + idx] : 0.0;
             gout(L.dhat)[eo + idx] = v;
             if (L.traj_dhat) gout(L.traj_dhat)[eo + idx] = v;
+        }
+    }
+    if (L.tgt) {                                  // us_0 = T [r_0; dhat0; ubar_0], a thread per (instance, row), T as the caller has it: column-major [nu x nrhs]
+        const int nu = L.nu, ndu = L.ndu, ny = L.ny;
+        for (int idx = tid; idx < nvalid * nu; idx += kTile) {
+            const int b = b0 + idx / nu, i = idx % nu;
+            const double *T = (L.tmap_batch ? L.tmap_batch + (size_t)b * nu * (ny + ndu + nu) : L.tmap) + i;
+            const double *d = L.dhat0 ? L.dhat0 + (size_t)b * ndu : nullptr;
+            double v;
+            if (d) v = target_us_row(T, (size_t)nu, target_ref(L, 0, b, 0), ny, d, ndu, target_ref(L, 1, b, 0), nu);
+            else v = target_us_row(T, (size_t)nu, target_ref(L, 0, b, 0), ny, ZeroOperand{}, ndu, target_ref(L, 1, b, 0), nu);
+            gout(L.us)[uo + idx] = v;
+            if (L.traj_us) gout(L.traj_us)[uo + idx] = v;
         }
     }
     gather_windows(L, b0, nvalid, 0, tid);
@@ -298,9 +331,13 @@ __device__ __forceinline__ void output_terms(const double LOOP_GAS *M, const siz
 // kOff, the tick of an offset-free loop: the slot behind cmd holds dhat_k (the operand of yhat's Dd terms and of the estimator's Bd terms, so the
 // estimator's row is still one chain over hin ...), the true d_k has a slot of its own behind e (the operand of y's Dd terms and of the plant's Bd_p
 // terms), and dhat <- dhat + (Ld e summed from 0 by ascending column).  With Ld = 0 and dhat = d bitwise every sum is the observed tick's.
-template <bool kOff>
+// kTgt (with kOff), the tick of a loop with steady-state targets: behind d the row holds [r_{k+1} | dhat_{k+1} | ubar_{k+1}], the operands of
+// us_{k+1} in T's column order; r and ubar come in with everything else, dhat_{k+1} from the lane that stores it, and a barrier later the lanes of
+// the instance take the nu rows of us.  Nothing else of the tick changes: with T = [0 | 0 | I] the solve is given ubar's bits.
+template <bool kOff, bool kTgt = false>
 __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *lds)
 {
+    static_assert(kOff || !kTgt, "targets need the disturbance estimate");
     const int tid = threadIdx.x;
     const int k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(L.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     if (k >= L.ticks) return;                     // a replay past the run's end: nothing is written
@@ -311,6 +348,7 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
     double *xin = lds, *hin = xin + nx, *cin = hin + nx, *din = cin + nu, *ein = din + ndu;   // an instance's row: the estimator's operands are hin ... in its terms' order
     double *tin = din;                            // the disturbance that acts on the plant and on the measurement
     if constexpr (kOff) tin = ein + ny;
+    double *rin = tin + ndu, *nin = rin + ny, *bin = nin + ndu;      // (kTgt) r, dhat and ubar of tick k + 1
     const size_t xo = (size_t)b0 * nx, uo = (size_t)b0 * nu;
 
     // in: the tile's true states, estimates, commands and exogenous-input samples, one contiguous run each
@@ -333,6 +371,16 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
             const int r = idx / ndu, c = idx - r * ndu;
             tin[r * so + c] = dk[(size_t)(b0 + r) * L.d_bs + c];
             if constexpr (kOff) din[r * so + c] = gin(L.dhat)[(size_t)b0 * ndu + idx];      // dhat_k: no read of it behind this barrier
+        }
+    }
+    if constexpr (kTgt) {
+        for (int idx = tid; idx < nvalid * ny; idx += kTile) {
+            const int r = idx / ny, c = idx - r * ny;
+            rin[r * so + c] = target_ref(L, 0, b0 + r, k + 1)[c];
+        }
+        for (int idx = tid; idx < nvalid * nu; idx += kTile) {
+            const int r = idx / nu, c = idx - r * nu;
+            bin[r * so + c] = target_ref(L, 1, b0 + r, k + 1)[c];
         }
     }
     __syncthreads();
@@ -391,6 +439,21 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
                 const size_t at = (size_t)(b0 + q) * ndu + i;
                 gout(L.dhat)[at] = v;
                 if (td) td[at] = v;
+                if constexpr (kTgt) nin[q * so + i] = v;
+            }
+        }
+    }
+    if constexpr (kTgt) {
+        __syncthreads();
+        if (mine) {                               // the rows of us_{k+1}: nrhs terms of T, lane (q, i) reading element q * nu + i of a term
+            const size_t wt = (size_t)nt * nu;
+            const double LOOP_GAS *T = gin(L.tk) + (size_t)blockIdx.x * L.tk_ts + q * nu;
+            double LOOP_GAS *ts = L.traj_us ? gout(L.traj_us) + (size_t)(k + 1) * B * nu : nullptr;
+            for (int i = tid - q * lpi; i < nu; i += lpi) {
+                const double v = target_us_row(T + i, wt, rin + q * so, ny, nin + q * so, ndu, bin + q * so, nu);
+                const size_t at = (size_t)(b0 + q) * nu + i;
+                gout(L.us)[at] = v;
+                if (ts) ts[at] = v;
             }
         }
     }
@@ -420,6 +483,12 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) v
 {
     extern __shared__ double lds[];
     advance_observed<true>(L, lds);
+}
+
+__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) void lmpc_loop_advance_offset_free_target_kernel(const LmpcLoopDev L)
+{
+    extern __shared__ double lds[];
+    advance_observed<true, true>(L, lds);
 }
 
 constexpr int kPackThreads = 256;
@@ -536,6 +605,26 @@ __device__ __forceinline__ void pack_observer(const LmpcLoopDev &L)
 __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(const LmpcLoopDev L) { pack_observer<false>(L); }
 __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_offset_free_kernel(const LmpcLoopDev L) { pack_observer<true>(L); }
 
+// ... and of a loop with targets, behind the two above: T in the advance kernel's order, from the one map for the batch (one tile) or the caller's
+// per-instance array, both column-major [nu x nrhs]
+__global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_target_kernel(const LmpcLoopDev L)
+{
+    const int nu = L.nu, B = L.batch, ipw = L.ipw, nrhs = L.ny + L.ndu + L.nu;
+    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
+    const size_t tiles = (size_t)((B + ipw - 1) / ipw);
+    const size_t width = (size_t)ipw * nu, per_tile = (size_t)nrhs * width;
+    const size_t total = (L.tk_ts ? tiles : 1) * per_tile;
+    for (size_t idx = first; idx < total; idx += step) {
+        const size_t t = idx / per_tile, rem = idx - t * per_tile;
+        const int j = (int)(rem / width), qi = (int)(rem - j * width);
+        const int q = qi / nu, i = qi - q * nu;
+        const size_t b = L.tk_ts ? t * ipw + q : 0;
+        double v = 0.0;
+        if (b < (size_t)B) v = L.tmap_batch ? gin(L.tmap_batch)[(b * nrhs + j) * nu + i] : L.tmap[j * nu + i];
+        gout(L.tk)[idx] = v;
+    }
+}
+
 inline int odd(int n) { return n | 1; }
 
 }  // namespace
@@ -544,15 +633,15 @@ void lmpc_loop_plan_lds(LmpcLoopDev &L)
 {
     L.sx = odd(L.nx); L.su = odd(L.nu); L.sd = L.ndu > 0 ? odd(L.ndu) : 0;
     L.ipw = L.nx < kTile ? kTile / L.nx : 1; L.sv = odd(L.nx + L.nu + L.ndu);
-    L.so = odd(2 * L.nx + L.nu + L.ndu + L.ny + (L.dobs ? L.ndu : 0));
+    L.so = odd(2 * L.nx + L.nu + L.ndu + L.ny + (L.dobs ? L.ndu : 0) + (L.tgt ? L.ny + L.ndu + L.nu : 0));
 }
 
 size_t lmpc_loop_packed_len(const LmpcLoopDev &L) { return (size_t)((L.batch + L.ipw - 1) / L.ipw) * (L.nx + L.nu + L.ndu) * L.ipw * L.nx; }
 
 size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles)
 {
-    const size_t terms = which == 0 ? L.nx + L.nu + L.ndu : which == 1 ? L.nx + L.nu + L.ndu + L.ny : which == 2 ? L.nx + L.ndu : L.ny;
-    return tiles * terms * L.ipw * (which == 2 ? L.ny : which == 3 ? L.ndu : L.nx);
+    const size_t terms = which == 0 ? L.nx + L.nu + L.ndu : which == 1 ? L.nx + L.nu + L.ndu + L.ny : which == 2 ? L.nx + L.ndu : which == 3 ? L.ny : L.ny + L.ndu + L.nu;
+    return tiles * terms * L.ipw * (which == 2 ? L.ny : which == 3 ? L.ndu : which == 4 ? L.nu : L.nx);
 }
 
 static size_t observed_lds_bytes(const LmpcLoopDev &L) { return (size_t)L.ipw * L.so * sizeof(double); }
@@ -564,7 +653,9 @@ int lmpc_loop_prepare(const LmpcLoopDev &L)
     if (L.ek) {                                   // the observed kernel's tile: a few KB unless one instance has thousands of states
         const size_t bytes = observed_lds_bytes(L);
         if (bytes > lmpc_lds_limit()) return -2;
-        const void *kernel = L.dobs ? reinterpret_cast<const void *>(lmpc_loop_advance_offset_free_kernel) : reinterpret_cast<const void *>(lmpc_loop_advance_observed_kernel);
+        const void *kernel = L.tgt    ? reinterpret_cast<const void *>(lmpc_loop_advance_offset_free_target_kernel)
+                             : L.dobs ? reinterpret_cast<const void *>(lmpc_loop_advance_offset_free_kernel)
+                                      : reinterpret_cast<const void *>(lmpc_loop_advance_observed_kernel);
         if (bytes > 48 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -3;
         return 0;
     }
@@ -607,6 +698,12 @@ int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream)
     if (blocks < 1) blocks = 1;
     if (L.dobs) hipLaunchKernelGGL(lmpc_loop_pack_offset_free_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
     else hipLaunchKernelGGL(lmpc_loop_pack_observer_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    if (L.tgt) {
+        blocks = (lmpc_loop_block_len(L, 4, L.tk_ts ? tiles : 1) + kPackThreads - 1) / kPackThreads;
+        if (blocks > 2048) blocks = 2048;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(lmpc_loop_pack_target_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -614,7 +711,8 @@ int lmpc_loop_advance(const LmpcLoopDev &L, void *stream)
 {
     if (L.ek) {
         const int tiles = (L.batch + L.ipw - 1) / L.ipw;
-        if (L.dobs) hipLaunchKernelGGL(lmpc_loop_advance_offset_free_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
+        if (L.tgt) hipLaunchKernelGGL(lmpc_loop_advance_offset_free_target_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
+        else if (L.dobs) hipLaunchKernelGGL(lmpc_loop_advance_offset_free_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
         else hipLaunchKernelGGL(lmpc_loop_advance_observed_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }

@@ -772,6 +772,7 @@ struct mpcx_lmpc_loop {
 int mpcx_lmpc_loop_desc_size(void) { return (int)sizeof(mpcx_lmpc_loop_desc); }
 int mpcx_lmpc_observer_desc_size(void) { return (int)sizeof(mpcx_lmpc_observer_desc); }
 int mpcx_lmpc_disturbance_observer_desc_size(void) { return (int)sizeof(mpcx_lmpc_disturbance_observer_desc); }
+int mpcx_lmpc_target_desc_size(void) { return (int)sizeof(mpcx_lmpc_target_desc); }
 
 // one tick -- the step of descriptor `b`, then the advance kernel -- captured on `s`
 static int capture_tick(const mpcx_lmpc_loop &l, const mpcx_lmpc_batch *b, hipStream_t s, hipGraphExec_t *exec)
@@ -826,6 +827,15 @@ static int check_disturbance_observer_desc(const mpcx_lmpc_disturbance_observer_
     if (!o->gain && !o->gain_batch) return fail(MPCX_E_INVALID, "a disturbance observer needs gain or gain_batch");
     return MPCX_OK;
 }
+// ... and the targets of an offset-free loop, likewise
+static int check_target_desc(const mpcx_lmpc_target_desc *t, bool bank)
+{
+    if (!t) return fail(MPCX_E_INVALID, "null target: a loop with steady-state targets needs an mpcx_lmpc_target_desc");
+    if (t->map && t->map_batch) return fail(MPCX_E_INVALID, "map (one map for the batch) and map_batch (a map per instance) exclude each other");
+    if (bank && t->map) return fail(MPCX_E_INVALID, "a bank's controllers differ: its loop takes map_batch, not map");
+    if (!t->map && !t->map_batch) return fail(MPCX_E_INVALID, "steady-state targets need map or map_batch");
+    return MPCX_OK;
+}
 // ... and the owner's dimensions (not its state): without exogenous inputs there is no disturbance model
 static int check_disturbance_dims(const mpcx_dims &dm)
 {
@@ -834,14 +844,15 @@ static int check_disturbance_dims(const mpcx_dims &dm)
 }
 
 // what kind of loop an entry makes
-enum class LoopKind { Plain, Observed, OffsetFree };
+enum class LoopKind { Plain, Observed, OffsetFree, OffsetFreeTarget };
 
 // The loop of a controller (h) or of a bank (f, model_index), once the descriptor and the owner's state have been checked and the owner is set
 // up on the current device.  dm, active_words: the owner's.  o: the observer of an observed loop (checked), or null; od: the disturbance observer of
 // an offset-free loop (checked), or null -- such a loop is an observed loop with the fields the two descriptors share, and what differs asks for od.
+// td: the targets of an offset-free loop (checked; od is then not null), or null.
 static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words,
-                      const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const mpcx_lmpc_disturbance_observer_desc *od, hipStream_t s,
-                      mpcx_lmpc_loop_t *out)
+                      const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const mpcx_lmpc_disturbance_observer_desc *od,
+                      const mpcx_lmpc_target_desc *td, hipStream_t s, mpcx_lmpc_loop_t *out)
 {
     mpcx_lmpc_observer_desc shared_fields{};
     if (od) {
@@ -857,7 +868,7 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     if (h) { l->device = h->device; l->setups = h->n_full_setups; } else l->device = f->device;
     mpcx::LmpcLoopDev &L = l->L;
     const size_t B = (size_t)d->batch, aw = (size_t)active_words;
-    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw; L.ny = dm.ny; L.dobs = od ? 1 : 0;
+    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw; L.ny = dm.ny; L.dobs = od ? 1 : 0; L.tgt = td ? 1 : 0;
     mpcx::lmpc_loop_plan_lds(L);
     // which plant: one per instance (the caller's array; in a bank also the default, each instance's own controller), or one for the batch
     const bool uniform = d->plant_A || d->plant_B || d->plant_Bd;
@@ -873,14 +884,15 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     const size_t o_act = take(4 * B * aw * sizeof(uint32_t)), o_state = take(2 * sizeof(int));
     size_t o_pv[4] = {0, 0, 0, 0};
     for (int a = 0; a < 4; ++a)
-        if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0 && !(od && a == 3)) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
+        if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0 && !(od && a == 3) && !(td && a == 1)) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
     const size_t o_pk = packed ? take(mpcx::lmpc_loop_packed_len(L) * sizeof(double)) : 0;
     const size_t o_down = own_d ? take(B * dm.ndu * sizeof(double)) : 0;
     // an observed loop: the true state, and the packed blocks -- one tile where a block is the same for every instance (one plant for the batch; a
     // controller's own model, with one gain; a controller's own outputs), else a tile per ipw instances
     const size_t tiles = (B + L.ipw - 1) / L.ipw;
     const bool est_shared = o && h && o->gain, meas_shared = o && h;
-    size_t o_xt = 0, o_ok = 0, o_ek = 0, o_mk = 0, o_gain = 0, o_dhat = 0, o_dk = 0;
+    size_t o_xt = 0, o_ok = 0, o_ek = 0, o_mk = 0, o_gain = 0, o_dhat = 0, o_dk = 0, o_us = 0, o_tk = 0, o_map = 0;
+    const size_t map_len = (size_t)dm.nu * (dm.ny + dm.ndu + dm.nu);
     const size_t gain_len = (size_t)(dm.nx + (od ? dm.ndu : 0)) * dm.ny;
     if (o) {
         o_xt = take(B * dm.nx * sizeof(double));
@@ -892,6 +904,11 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     if (od) {                                    // the estimate the solve reads, and Ld beside the estimator block, shared where that is
         o_dhat = take(B * dm.ndu * sizeof(double));
         o_dk = take(mpcx::lmpc_loop_block_len(L, 3, est_shared ? 1 : tiles) * sizeof(double));
+    }
+    if (td) {                                    // the input reference the solve reads, and T: one tile where it is one map for the batch
+        o_us = take(B * dm.nu * sizeof(double));
+        o_tk = take(mpcx::lmpc_loop_block_len(L, 4, td->map ? 1 : tiles) * sizeof(double));
+        if (td->map) o_map = take(map_len * sizeof(double));
     }
     if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
     if (hipMemset(l->slab, 0, total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
@@ -946,6 +963,27 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
         L.dhat = dp(o_dhat); L.dk = dp(o_dk); L.dk_ts = est_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 3, 1);
         L.dhat0 = od->dhat0; L.traj_dhat = od->traj_dhat;
     }
+    if (td) {
+        L.us = dp(o_us); L.tk = dp(o_tk); L.tk_ts = td->map ? 0 : (long)mpcx::lmpc_loop_block_len(L, 4, 1);
+        if (td->map) {
+            if (hipMemcpy(base + o_map, td->map, map_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the target map failed");
+            L.tmap = dp(o_map);
+        }
+        L.tmap_batch = td->map_batch; L.traj_us = td->traj_us;
+        // r_k and ubar_k: step 0 of the tick's yref and uref in whichever layout they have; "shared" is the controller's own (a bank: a null source,
+        // each instance's controller)
+        auto source = [&](int a, const double *own, const double *&src, long &bs, long &tick) {
+            const long n = ref_n[a];
+            switch (ref_m[a]) {
+            case MPCX_REF_SHARED: src = own; bs = 0; tick = 0; break;
+            case MPCX_REF_PER_INSTANCE: src = ref_p[a]; bs = n; tick = 0; break;
+            case MPCX_REF_PER_STEP: src = ref_p[a]; bs = (long)dm.ph * n; tick = 0; break;
+            default: src = ref_p[a]; bs = (long)(d->ticks + dm.ph) * n; tick = n; break;
+            }
+        };
+        source(0, h ? h->dev.yref_s : nullptr, L.r_src, L.r_bs, L.r_tick);
+        source(1, h ? h->dev.uref_s : nullptr, L.ub_src, L.ub_bs, L.ub_tick);
+    }
 
     // the step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step; an
     // offset-free loop's exogenous input is the loop's own estimate (the descriptor's drives the plant alone: no window)
@@ -955,6 +993,7 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     for (int a = 0; a < 4; ++a) {
         sp[a] = ref_p[a]; sm[a] = ref_m[a];
         if (od && a == 3) { sp[a] = L.dhat; sm[a] = MPCX_REF_PER_INSTANCE; continue; }
+        if (td && a == 1) { sp[a] = L.us; sm[a] = MPCX_REF_PER_INSTANCE; continue; }      // (the descriptor's uref is ubar, read by the loop's kernels: no window)
         if (ref_m[a] != MPCX_REF_PREVIEW) continue;
         if (ref_n[a] == 0) { sp[a] = nullptr; sm[a] = MPCX_REF_SHARED; continue; }      // (no exogenous inputs: nothing to preview)
         L.pv_src[a] = ref_p[a]; L.pv_dst[a] = dp(o_pv[a]); L.pv_n[a] = ref_n[a];
@@ -1000,16 +1039,19 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     return MPCX_OK;
 }
 
-// mpcx_lmpc_loop_create (neither o nor od is looked at), mpcx_lmpc_loop_create_observed (o) and mpcx_lmpc_loop_create_offset_free (od)
+// mpcx_lmpc_loop_create (neither o nor od is looked at), mpcx_lmpc_loop_create_observed (o), mpcx_lmpc_loop_create_offset_free (od) and
+// mpcx_lmpc_loop_create_offset_free_target (od and td)
 static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, LoopKind kind, const mpcx_lmpc_observer_desc *o,
-                            const mpcx_lmpc_disturbance_observer_desc *od, void *stream, mpcx_lmpc_loop_t *out)
+                            const mpcx_lmpc_disturbance_observer_desc *od, const mpcx_lmpc_target_desc *td, void *stream, mpcx_lmpc_loop_t *out)
 {
     CHECK_H(h);
     if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
+    const bool targets = kind == LoopKind::OffsetFreeTarget, offset_free = targets || kind == LoopKind::OffsetFree;
     int rc = check_loop_desc(d);
     if (rc == MPCX_OK && kind == LoopKind::Observed) rc = check_observer_desc(o, false);
-    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_observer_desc(od, false);
-    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_dims(h->ctl.d);
+    if (rc == MPCX_OK && offset_free) rc = check_disturbance_observer_desc(od, false);
+    if (rc == MPCX_OK && targets) rc = check_target_desc(td, false);
+    if (rc == MPCX_OK && offset_free) rc = check_disturbance_dims(h->ctl.d);
     if (rc != MPCX_OK) return rc;
     if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
     if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
@@ -1017,33 +1059,42 @@ static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, LoopKin
     rc = mpcx_lmpc_setup(h);
     if (rc != MPCX_OK) return rc;
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, kind == LoopKind::Observed ? o : nullptr,
-                      kind == LoopKind::OffsetFree ? od : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, kind == LoopKind::Observed ? o : nullptr, offset_free ? od : nullptr,
+                      targets ? td : nullptr, reinterpret_cast<hipStream_t>(stream), out);
 }
 
 int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::Plain, nullptr, nullptr, stream, out);
+    return lmpc_loop_create(h, d, LoopKind::Plain, nullptr, nullptr, nullptr, stream, out);
 }
 
 int mpcx_lmpc_loop_create_observed(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::Observed, o, nullptr, stream, out);
+    return lmpc_loop_create(h, d, LoopKind::Observed, o, nullptr, nullptr, stream, out);
 }
 
 int mpcx_lmpc_loop_create_offset_free(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::OffsetFree, nullptr, o, stream, out);
+    return lmpc_loop_create(h, d, LoopKind::OffsetFree, nullptr, o, nullptr, stream, out);
+}
+
+int mpcx_lmpc_loop_create_offset_free_target(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
+                                             const mpcx_lmpc_target_desc *t, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return lmpc_loop_create(h, d, LoopKind::OffsetFreeTarget, nullptr, o, t, stream, out);
 }
 
 static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, LoopKind kind, const mpcx_lmpc_observer_desc *o,
-                              const mpcx_lmpc_disturbance_observer_desc *od, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
+                              const mpcx_lmpc_disturbance_observer_desc *od, const mpcx_lmpc_target_desc *td, const int32_t *model_index, void *stream,
+                              mpcx_lmpc_loop_t *out)
 {
     if (!f || !d || !out) return fail(MPCX_E_INVALID, "null argument");
+    const bool targets = kind == LoopKind::OffsetFreeTarget, offset_free = targets || kind == LoopKind::OffsetFree;
     int rc = check_loop_desc(d);
     if (rc == MPCX_OK && kind == LoopKind::Observed) rc = check_observer_desc(o, true);
-    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_observer_desc(od, true);
-    if (rc == MPCX_OK && kind == LoopKind::OffsetFree) rc = check_disturbance_dims(f->d);      // (the bank is followed only behind a good descriptor)
+    if (rc == MPCX_OK && offset_free) rc = check_disturbance_observer_desc(od, true);
+    if (rc == MPCX_OK && targets) rc = check_target_desc(td, true);
+    if (rc == MPCX_OK && offset_free) rc = check_disturbance_dims(f->d);      // (the bank is followed only behind a good descriptor)
     if (rc != MPCX_OK) return rc;
     if (!model_index && d->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
     // a bank keeps no host copy of its controllers' models: there is no "the controller's own" to complete a one-for-all plant with
@@ -1051,25 +1102,61 @@ static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d
         return fail(MPCX_E_INVALID, "a bank's loop takes plant_A, plant_B and plant_Bd together (or plant_batch, or none: each instance's own controller)");
     if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
     if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, kind == LoopKind::Observed ? o : nullptr,
-                      kind == LoopKind::OffsetFree ? od : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, kind == LoopKind::Observed ? o : nullptr, offset_free ? od : nullptr,
+                      targets ? td : nullptr, reinterpret_cast<hipStream_t>(stream), out);
 }
 
 int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::Plain, nullptr, nullptr, model_index, stream, out);
+    return hetero_loop_create(f, d, LoopKind::Plain, nullptr, nullptr, nullptr, model_index, stream, out);
 }
 
 int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
                                           void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::Observed, o, nullptr, model_index, stream, out);
+    return hetero_loop_create(f, d, LoopKind::Observed, o, nullptr, nullptr, model_index, stream, out);
 }
 
 int mpcx_lmpc_hetero_loop_create_offset_free(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
                                              const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::OffsetFree, nullptr, o, model_index, stream, out);
+    return hetero_loop_create(f, d, LoopKind::OffsetFree, nullptr, o, nullptr, model_index, stream, out);
+}
+
+int mpcx_lmpc_hetero_loop_create_offset_free_target(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
+                                                    const mpcx_lmpc_target_desc *t, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
+{
+    return hetero_loop_create(f, d, LoopKind::OffsetFreeTarget, nullptr, o, t, model_index, stream, out);
+}
+
+// Steady-state target maps and the product with them (include/mpcx.h; kernels in target_kernels.hip, declared in lmpc_device.hpp)
+int mpcx_target_map_batch(int device, int nx, int nu, int ndu, int ny, int batch, const double *A, const double *B, const double *Bd, const double *C,
+                          const double *Dd, double *map_u, double *map_x, int32_t *flags, void *stream)
+{
+    if (nx < 1 || nu < 1 || ny < 1 || ndu < 0) return fail(MPCX_E_INVALID, "need nx, nu, ny >= 1 and ndu >= 0");
+    if (batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (!A || !B || !C || !map_u || (ndu > 0 && (!Bd || !Dd))) return fail(MPCX_E_INVALID, "A, B, C and map_u (with ndu > 0 also Bd and Dd) are required");
+    if ((size_t)nx + nu + ny + ndu > 4096 || mpcx::target_map_lds_bytes(nx, nu, ndu, ny) > mpcx::lmpc_lds_limit())
+        return fail(MPCX_E_UNSUPPORTED, "the augmented KKT matrix exceeds the LDS a workgroup may request");
+    if (batch == 0) return MPCX_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    const int rc = mpcx::target_map_launch(nx, nu, ndu, ny, batch, A, B, Bd, C, Dd, map_u, map_x, flags, mpcx::lmpc_lds_limit(), stream);
+    if (rc == -2) return fail(MPCX_E_UNSUPPORTED, "the augmented KKT matrix exceeds the LDS a workgroup may request");
+    if (rc != 0) return fail(MPCX_E_DEVICE, "target map kernel launch failed");
+    return MPCX_OK;
+}
+
+int mpcx_target_apply_batch(int device, int nu, int ndu, int ny, int batch, const double *map_u, int map_per_instance, const double *r,
+                            const double *dhat, const double *ubar, double *us, void *stream)
+{
+    if (nu < 1 || ny < 1 || ndu < 0) return fail(MPCX_E_INVALID, "need nu, ny >= 1 and ndu >= 0");
+    if (batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (!map_u || !r || !ubar || !us || (ndu > 0 && !dhat)) return fail(MPCX_E_INVALID, "map_u, r, ubar and us (with ndu > 0 also dhat) are required");
+    if (batch == 0) return MPCX_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (mpcx::target_apply_launch(nu, ndu, ny, batch, map_u, map_per_instance ? 1 : 0, r, dhat, ubar, us, stream) != 0)
+        return fail(MPCX_E_DEVICE, "target product kernel launch failed");
+    return MPCX_OK;
 }
 
 // The steady-state Kalman predictor gain of the controller's own (A, C) by Riccati iteration (include/mpcx.h), host doubles throughout.

@@ -124,7 +124,9 @@ class ClosedLoopResult:
     """A closed-loop run on the device (LMPC.simulate), tick-major device tensors: x [ticks+1, B, nx] (row 0 = the initial
     state), u [ticks, B, nu], the others [ticks, B].  An observed loop (observer=) also fills xhat [ticks+1, B, nx], the estimates
     the solves read (row 0 = xhat0), and y [ticks, B, ny], the measurements; x is then the plant's true state.  An offset-free loop
-    (disturbance_observer=) fills those and dhat [ticks+1, B, ndu], the disturbance estimates the solves read (row 0 = dhat0)."""
+    (disturbance_observer=) fills those and dhat [ticks+1, B, ndu], the disturbance estimates the solves read (row 0 = dhat0); with
+    steady-state targets (target=) also us [ticks+1, B, nu], the input references the solves read (row k: tick k's; the last row is computed
+    and not used)."""
     x: "object"
     u: "object"
     cost: "object"
@@ -136,6 +138,7 @@ class ClosedLoopResult:
     xhat: "object" = None
     y: "object" = None
     dhat: "object" = None
+    us: "object" = None
 
 
 @dataclass
@@ -143,7 +146,8 @@ class Loop:
     """a loop made by LMPC.make_loop / LMPCHetero.make_loop: the native handle, the result whose tensors every run fills, the tensors the graph
     points at, and (plants=) the per-instance plants as every run reads them, [B, nx (nx+nu+ndu)] in LMPC.pack_plants' layout.  An observed
     loop: gains (per-instance observer=) [B, nx ny] in LMPC.pack_gains' layout, xhat0 and meas_noise as every run reads them (refill in place);
-    an offset-free loop: gains [B, (nx+ndu) ny] in the same layout, and dhat0"""
+    an offset-free loop: gains [B, (nx+ndu) ny] in the same layout, and dhat0; with targets: maps (per-instance target=) [B, nu (ny+ndu+nu)] in
+    LMPC.pack_gains' layout (refill in place)"""
     handle: "object"
     result: ClosedLoopResult
     ticks: int
@@ -153,6 +157,7 @@ class Loop:
     xhat0: "object" = None
     meas_noise: "object" = None
     dhat0: "object" = None
+    maps: "object" = None
 
 
 def _cm(a, rows, cols):
@@ -555,6 +560,35 @@ class LMPC:
             return disturbance_observer is not None, self._check_disturbance_observer(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
         return False, self._check_observer(B, ticks, observer, xhat0, meas_noise, bank)
 
+    def _check_target(self, B, target, disturbance_observer, bank=False):
+        """target= ([nu, ny+ndu+nu] one map, [B, nu, ny+ndu+nu] a map per instance): True for a map per instance"""
+        if target is None:
+            return False
+        if disturbance_observer is None:
+            raise ValueError("target= (steady-state targets) needs disturbance_observer=: the targets are computed from its disturbance estimate")
+        sh = tuple((target if hasattr(target, "shape") else np.asarray(target)).shape)
+        n = self.ny + self.ndu + self.nu
+        if sh not in ((self.nu, n), (B, self.nu, n)):
+            raise ValueError(f"target must be [{self.nu},{n}] or [{B},{self.nu},{n}], got {sh}")
+        if bank and len(sh) == 2:
+            raise ValueError(f"a bank's controllers differ: target must be a map per instance, [{B},{self.nu},{n}]")
+        return len(sh) == 3
+
+    def target_map(self, want_x=False):
+        """The steady-state target map [nu, ny+ndu+nu] = [Tr | Td | Tu] of the controller's own model and disturbance model: us = Tr r + Td dhat +
+        Tu ubar is the input that holds the outputs on r against the disturbance dhat, as close to ubar as that allows -- what target= takes
+        (libmpc_amd.utils.target_maps, one device call).  ValueError, before any device call, where a reference cannot be reached or an
+        integrator is not seen by the outputs; MpcxError where the elimination met a vanishing pivot all the same.  want_x: (map_u, map_x
+        [nx, ny+ndu+nu]) instead."""
+        from .utils import target_maps
+        if self._A is None:
+            raise MpcxError(_capi.E_STATE, "state-space model not set")
+        out = target_maps(self._A, self._B, self._Bd, self._C, self._Dd, want_x=want_x, device=max(self.device, 0))
+        if int(out[-1][0]):
+            raise MpcxError(_capi.E_NUMERIC, "the KKT system of the target is singular")
+        maps = tuple(m[0].cpu().numpy().copy() for m in out[:-1])
+        return maps if want_x else maps[0]
+
     @staticmethod
     def pack_gains(L):
         """[B, nx ny]: per instance L_b column-major -- mpcx_lmpc_observer_desc.gain_batch; a torch tensor [B, nx, ny] in, a tensor out
@@ -603,15 +637,16 @@ class LMPC:
         return torch.cat([m.transpose(1, 2).reshape(n, m.shape[1] * m.shape[2]) for m in (A, B, Bd)], dim=1).contiguous()
 
     def _make_loop(self, create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None,
-                   observer=None, xhat0=None, meas_noise=None, bank=False, disturbance_observer=None, dhat0=None, checked=None):
+                   observer=None, xhat0=None, meas_noise=None, bank=False, disturbance_observer=None, dhat0=None, checked=None, target=None):
         """the descriptor of a loop, its result tensors and the create call: shared by LMPC and LMPCHetero (whose `create` takes the model index);
-        `create` is given the observer's descriptor (an ObserverDesc or a DisturbanceObserverDesc), or None for an unobserved loop; checked:
-        what _check_observers returned where the caller has run it already"""
+        `create` is given the observer's descriptor (an ObserverDesc or a DisturbanceObserverDesc), or None for an unobserved loop, and the
+        TargetDesc of a loop with steady-state targets, or None; checked: what _check_observers returned where the caller has run it already"""
         ticks = int(ticks)
         x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
         B = int(x0t.shape[0])
         plants = self._check_plants(B, plant, plants)
         offset_free, per_instance_gain = checked or self._check_observers(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
+        per_instance_map = self._check_target(B, target, disturbance_observer, bank)
         torch, dev = self._torch()
         x0 = self._dev(torch, dev, x0, (B, self.nx))
         u0 = self._dev(torch, dev, lastU, (B, self.nu))
@@ -676,19 +711,31 @@ class LMPC:
                 dh = self._dev(torch, dev, dhat0, (B, self.ndu))
                 res.dhat = torch.zeros((T + 1, B, self.ndu), dtype=f64, device=dev)
                 od.dhat0, od.traj_dhat = ptr(dh), ptr(res.dhat)
+        td, maps, map_h = None, None, None
+        if target is not None:
+            td = _capi.TargetDesc()
+            if per_instance_map:                # (not through _dev, as the gains: utils.target_maps' view is this very layout)
+                t = target if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target, dtype=np.float64))
+                maps = self.pack_gains(t.to(device=dev, dtype=torch.float64))
+                td.map_batch = ptr(maps)
+            else:
+                map_h = _cm(target.cpu().numpy() if isinstance(target, torch.Tensor) else target, self.nu, self.ny + self.ndu + self.nu)
+                td.map = map_h.ctypes.data
+            res.us = torch.zeros((T + 1, B, self.nu), dtype=f64, device=dev)
+            td.traj_us = ptr(res.us)
         cur = torch.cuda.current_stream(self.device)
         s = stream if stream is not None else torch.cuda.Stream(device=dev)
         if s.cuda_stream == 0:
             raise ValueError("a loop is captured on a non-default stream")
         s.wait_stream(cur)                      # the tensors above were filled on the current stream
         h = C.c_void_p()
-        check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h), None if od is None else C.byref(od)))
+        check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h), None if od is None else C.byref(od), None if td is None else C.byref(td)))
         cur.wait_stream(s)
-        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v, dh), pb, gains, xh, v, dh)
+        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v, dh, maps), pb, gains, xh, v, dh, maps)
 
     def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
                   noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,
-                  disturbance_observer=None, dhat0=None) -> Loop:
+                  disturbance_observer=None, dhat0=None, target=None) -> Loop:
         """A closed-loop run of `ticks` receding-horizon steps captured for `run_loop`: every tick is the batched solve followed by
         the plant step x <- A_p x + B_p cmd + Bd_p d_k + w_k on the device, with no host work in between.
 
@@ -709,16 +756,25 @@ class LMPC:
         their exogenous input, constant along the horizon.  dmeas= is then the TRUE disturbance, in every layout it has: it drives the plant
         and the measurement and the controller never sees it (None: the controller's own exogenous input, zeros unless set).  The gain is
         [Lx; Ld], [nx+ndu, ny] for the batch (LMPC.disturbance_gain) or [B, nx+ndu, ny] per instance (utils.disturbance_gains' as it is);
-        dhat0: [B, ndu], the first estimate (None: 0).  The result's dhat is filled as well.  The output settles on its reference where the
-        input weight is zero: no steady-state target is computed from dhat."""
-        def create(d, s, out, od):
+        dhat0: [B, ndu], the first estimate (None: 0).  The result's dhat is filled as well.  Without target= the output settles on its reference only
+        where the input weight is zero (or uref is the steady-state input).
+
+        target: steady-state targets, with disturbance_observer= only.  The map [nu, ny+ndu+nu] for the batch (LMPC.target_map) or
+        [B, nu, ny+ndu+nu] per instance (utils.target_maps' as it is; Loop.maps, refill with LMPC.pack_gains).  At every tick the loop
+        computes us_k = T [r_k; dhat_k; ubar_k] -- r_k and ubar_k step 0 of the tick's yref and uref, in every layout they have -- and the
+        solve reads us_k as its input reference, constant along the horizon: uref= is then ubar, what the input is held close to where the
+        outputs leave it free.  yref reaches the solve unchanged.  us is not clipped to the input bounds (the result's us shows it)."""
+        def create(d, s, out, od, td=None):
             if od is None:
                 return self._lib.mpcx_lmpc_loop_create(self._h, d, s, out)
+            if td is not None:
+                return self._lib.mpcx_lmpc_loop_create_offset_free_target(self._h, d, od, td, s, out)
             if disturbance_observer is not None:
                 return self._lib.mpcx_lmpc_loop_create_offset_free(self._h, d, od, s, out)
             return self._lib.mpcx_lmpc_loop_create_observed(self._h, d, od, s, out)
         return self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream,
-                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0)
+                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0,
+                               target=target)
 
     def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
         """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
@@ -738,10 +794,11 @@ class LMPC:
 
     def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
                  noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,
-                 disturbance_observer=None, dhat0=None) -> ClosedLoopResult:
+                 disturbance_observer=None, dhat0=None, target=None) -> ClosedLoopResult:
         """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
         loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm, plants=plants,
-                              observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0)
+                              observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0,
+                              target=target)
         torch, _ = self._torch()
         try:
             self.run_loop(loop, stream)

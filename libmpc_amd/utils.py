@@ -130,3 +130,79 @@ def disturbance_gains(A, Bd, C, Dd, Qw, Qd, Rv, device=0, stream=None):
     Q = torch.zeros((bn, n, n) if per else (n, n), dtype=torch.float64)
     Q[..., :nx, :nx] = Qw; Q[..., nx:, nx:] = Qd
     return dare(Aa, Ca, Q, Rv, "estimator", device, stream)
+
+
+def target_maps(A, B, Bd, C, Dd, want_x=False, device=0, stream=None, check_rank=True):
+    """Steady-state target maps for a batch of models on the device (mpcx_target_map_batch, no reference counterpart), row-major tensors or
+    arrays: A [Bn, nx, nx], B [Bn, nx, nu], Bd [Bn, nx, ndu], C [Bn, ny, nx], Dd [Bn, ny, ndu] (2-D: a batch of one).  The target of a
+    reference r, a disturbance estimate dhat and an input reference ubar is
+        minimise 1/2 |us - ubar|^2   subject to   (I - A) xs - B us = Bd dhat,   C xs = r - Dd dhat
+    and us = map_u [r; dhat; ubar], xs = map_x [r; dhat; ubar].  Returns (map_u [Bn, nu, ny+ndu+nu], flags) or, with want_x, (map_u, map_x
+    [Bn, nx, ny+ndu+nu], flags) on the device; flags [Bn] int32: 0 fine, 1 singular -- the maps of such an instance are NaN.  map_u is a view
+    of the layout mpcx_lmpc_target_desc.map_batch takes: a loop's target= accepts it as it is.  ValueError before any device call: shapes, and
+    (check_rank) an instance that misses one of the two rank conditions -- rank [[I - A, -B], [C, 0]] = nx + ny (every reference can be reached;
+    needs ny <= nu) and rank [I - A; C] = nx (no integrator that the outputs do not see)."""
+    import numpy as np
+    import torch
+    A, B, Bd, C, Dd = (_as_f64(M) for M in (A, B, Bd, C, Dd))
+    if A.dim() == 2:
+        A, B, Bd, C, Dd = (M[None] if M.dim() == 2 else M for M in (A, B, Bd, C, Dd))
+    if A.dim() != 3 or A.shape[1] != A.shape[2] or B.dim() != 3 or Bd.dim() != 3 or C.dim() != 3 or Dd.dim() != 3:
+        raise ValueError(f"A {tuple(A.shape)} is not [Bn, nx, nx] with 3-D B, Bd, C and Dd beside it")
+    bn, nx, nu, ndu, ny = A.shape[0], A.shape[1], B.shape[2], Bd.shape[2], C.shape[1]
+    for name, M, sh in (("B", B, (bn, nx, nu)), ("Bd", Bd, (bn, nx, ndu)), ("C", C, (bn, ny, nx)), ("Dd", Dd, (bn, ny, ndu))):
+        if tuple(M.shape) != sh:
+            raise ValueError(f"{name} {tuple(M.shape)} is not {list(sh)}")
+    if nx < 1 or nu < 1 or ny < 1:
+        raise ValueError(f"nx = {nx}, nu = {nu}, ny = {ny}: at least one state, one input and one output expected")
+    if check_rank and bn:
+        An, Bn, Cn = (M.cpu().numpy() for M in (A, B, C))
+        IA = np.eye(nx) - An
+
+        def rank(M):
+            sv = np.linalg.svd(M, compute_uv=False)            # descending
+            return (sv > sv[:, :1] * max(M.shape[1:]) * np.finfo(np.float64).eps).sum(axis=1)
+        rs = rank(np.concatenate([np.concatenate([IA, -Bn], axis=2), np.concatenate([Cn, np.zeros((bn, ny, nu))], axis=2)], axis=1))
+        if (rs < nx + ny).any():
+            k = int(np.argmax(rs < nx + ny))
+            raise ValueError(f"instance {k}: rank [[I - A, -B], [C, 0]] = {int(rs[k])} < nx + ny = {nx + ny}: not every reference can be reached "
+                             f"in steady state (ny <= nu is necessary)")
+        ro = rank(np.concatenate([IA, Cn], axis=1))
+        if (ro < nx).any():
+            k = int(np.argmax(ro < nx))
+            raise ValueError(f"instance {k}: rank [I - A; C] = {int(ro[k])} < nx = {nx}: the model has an integrator that the outputs do not see")
+    dev = torch.device("cuda", device)
+    # the C ABI takes Eigen's column-major layout: transpose the last two axes
+    Ac, Bc, Bdc, Cc, Ddc = (M.to(dev).transpose(-1, -2).contiguous() for M in (A, B, Bd, C, Dd))
+    nrhs = ny + ndu + nu
+    Tu = torch.empty((bn, nrhs, nu), dtype=torch.float64, device=dev)          # column-major [nu x nrhs]
+    Tx = torch.empty((bn, nrhs, nx), dtype=torch.float64, device=dev) if want_x else None
+    flags = torch.empty(bn, dtype=torch.int32, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    check(_capi.lib().mpcx_target_map_batch(device, nx, nu, ndu, ny, bn, Ac.data_ptr(), Bc.data_ptr(), Bdc.data_ptr(), Cc.data_ptr(), Ddc.data_ptr(),
+                                            Tu.data_ptr(), Tx.data_ptr() if want_x else None, flags.data_ptr(), s))
+    return (Tu.transpose(1, 2), Tx.transpose(1, 2), flags) if want_x else (Tu.transpose(1, 2), flags)
+
+
+def steady_state_inputs(map_u, r, dhat, ubar, device=0, stream=None):
+    """us [Bn, nu] = map_u [r; dhat; ubar] on the device (mpcx_target_apply_batch), for host-driven loops: the sum the closed loop's kernels
+    form, bit for bit -- every row from 0 with fused multiply-adds by ascending column.  map_u [nu, ny+ndu+nu] for the batch or
+    [Bn, nu, ny+ndu+nu] per instance (target_maps' as it is), r [Bn, ny], dhat [Bn, ndu], ubar [Bn, nu]."""
+    import torch
+    T, r, dhat, ubar = (_as_f64(M) for M in (map_u, r, dhat, ubar))
+    if r.dim() != 2 or dhat.dim() != 2 or ubar.dim() != 2 or dhat.shape[0] != r.shape[0] or ubar.shape[0] != r.shape[0]:
+        raise ValueError(f"r {tuple(r.shape)}, dhat {tuple(dhat.shape)} and ubar {tuple(ubar.shape)} are not [Bn, ny], [Bn, ndu] and [Bn, nu]")
+    bn, ny, ndu, nu = r.shape[0], r.shape[1], dhat.shape[1], ubar.shape[1]
+    nrhs = ny + ndu + nu
+    if tuple(T.shape) not in ((nu, nrhs), (bn, nu, nrhs)):
+        raise ValueError(f"map_u {tuple(T.shape)} is neither [{nu}, {nrhs}] nor [{bn}, {nu}, {nrhs}]")
+    if nu < 1 or ny < 1:
+        raise ValueError(f"nu = {nu}, ny = {ny}: at least one input and one output expected")
+    dev = torch.device("cuda", device)
+    Tc = T.to(dev).transpose(-1, -2).contiguous()
+    rc, dc, uc = (M.to(dev).contiguous() for M in (r, dhat, ubar))
+    us = torch.empty((bn, nu), dtype=torch.float64, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    check(_capi.lib().mpcx_target_apply_batch(device, nu, ndu, ny, bn, Tc.data_ptr(), int(T.dim() == 3), rc.data_ptr(), dc.data_ptr(), uc.data_ptr(),
+                                              us.data_ptr(), s))
+    return us

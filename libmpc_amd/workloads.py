@@ -103,3 +103,31 @@ def quadrotor_variant(k, ph=20, ch=None, device=0, maximum_iteration=250, into=N
     if into is None:
         c.setOptimizerParameters(LParameters(maximum_iteration=maximum_iteration))
     return c
+
+
+def quadrotor_target_model():
+    """The quadrotor with the outputs a steady-state target can reach: (x, y, z, yaw) = rows [3, 4, 5, 2] of the state, four outputs for four
+    rotors (the example's C = I has twelve), and an input disturbance, Bd = B, Dd = 0.  (A, B, Bd, C, Dd)"""
+    Ad, Bd, _ = quadrotor_matrices()
+    C = np.zeros((4, 12))
+    for i, j in enumerate((3, 4, 5, 2)):
+        C[i, j] = 1.0
+    return Ad, Bd, Bd.copy(), C, np.zeros((4, 4))
+
+
+def quadrotor_target_lmpc(ph=10, ch=None, device=0, input_weight=0.1, maximum_iteration=250) -> LMPC:
+    """The example's controller on quadrotor_target_model: its input weight (0.1), bounds and set-point (z = 1), the output weights of the four
+    outputs kept"""
+    ch = ph if ch is None else ch
+    A, B, Bd, C, Dd = quadrotor_target_model()
+    c = LMPC(12, 4, 4, 4, ph, ch, device=device)
+    c.setStateSpaceModel(A, B, C)
+    c.setDisturbances(Bd, Dd)
+    c.setObjectiveWeights([10.0] * 4, [input_weight] * 4, [0] * 4, (0, ph))
+    u0 = 10.5916
+    c.setStateBounds([-math.pi / 6, -math.pi / 6, -inf, -inf, -inf, -1] + [-inf] * 6, [math.pi / 6, math.pi / 6] + [inf] * 10, (0, ph))
+    c.setOutputBounds([-inf] * 4, [inf] * 4, (0, ph))
+    c.setInputBounds([9.6 - u0] * 4, [13 - u0] * 4, (0, ch))
+    c.setReferences([0.0, 0.0, 1.0, 0.0], np.zeros(4), np.zeros(4), (0, ph))
+    c.setOptimizerParameters(LParameters(maximum_iteration=maximum_iteration))
+    return c

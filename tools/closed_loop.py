@@ -12,7 +12,14 @@ The offset_free leg (lines with "offset_free": true; not part of "all") is the o
 same inputs, run alternately: the quadrotor with an input-disturbance model (Bd = B, Dd = 0), a constant load of 0.1 per rotor and sensor noise of
 standard deviation 0.01.  The observed loop is told the load as its per-instance dmeas (so both loops' solves take the same kernels) and estimates
 with LMPC.kalman_gain(0.01 I, 0.04 I); the offset-free loop is told nothing and estimates with LMPC.disturbance_gain(0.01 I, 0.01 I, 0.04 I).
-Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|observed|offset_free|all]"""
+The target leg (lines with "target": true; not part of "all") is the offset-free loop beside the offset-free loop with steady-state targets, the
+same build and the same inputs, run alternately: the quadrotor with the four outputs a target can reach (workloads.quadrotor_target_lmpc: x, y, z,
+yaw; Bd = B, Dd = 0; the example's input weight 0.1), the same load and sensor noise, both estimating with LMPC.disturbance_gain(0.01 I, 0.01 I,
+0.04 I); the second computes us from LMPC.target_map() at every tick.  Both loops' solves read a per-instance uref (zeros for the first).  A
+third loop has the pass-through map [0 | 0 | I]: its us is ubar = 0, so its solves are the first loop's bit for bit and what its tick costs more
+is what the begin, pack and advance kernels cost more -- the second loop's solves see other input references and take other rounds.  The final
+errors are max |y - yref| of the last tick over the outputs, as the median and the maximum over the instances (the maximum is an unsolved one's).
+Usage: python tools/closed_loop.py [batch] [ticks] [repeats] [single|bank|observed|offset_free|target|all]"""
 import json
 import sys
 import time
@@ -75,6 +82,20 @@ def make_disturbed(B, ticks, warm, offset_free):
         return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm, disturbance_observer=L, dmeas=load, meas_noise=v)
     L = c.kalman_gain(0.01 * np.eye(c.nx), 0.04 * np.eye(c.ny))
     return c, c.make_loop(x0, u0, ticks, yref=yref, warm=warm, observer=L, dmeas=load, meas_noise=v)
+
+
+def make_targeted(B, ticks, warm, targets):
+    """the offset-free loop of the four-output quadrotor, without or with steady-state targets: (controller, loop)"""
+    from libmpc_amd.workloads import quadrotor_target_lmpc
+    c = quadrotor_target_lmpc(20, device=0)
+    x0, u0, yref = quadrotor_batch(B)
+    yref = np.ascontiguousarray(yref[:, [3, 4, 5, 2]])
+    load = np.full((B, c.ndu), 0.1)
+    v = 0.01 * np.random.default_rng(1).normal(size=(ticks, B, c.ny))
+    L = c.disturbance_gain(0.01 * np.eye(c.nx), 0.01 * np.eye(c.ndu), 0.04 * np.eye(c.ny))
+    kw = dict(yref=yref, uref=np.zeros((B, c.nu)), warm=warm, disturbance_observer=L, dmeas=load, meas_noise=v)
+    T = None if not targets else c.target_map() if targets == "map" else np.concatenate([np.zeros((c.nu, c.ny + c.ndu)), np.eye(c.nu)], axis=1)
+    return c, c.make_loop(x0, u0, ticks, target=T, **kw)
 
 
 def run_device(c, loop):
@@ -175,6 +196,28 @@ if __name__ == "__main__":
                               observed_mean_rounds=obs[-1]["mean_rounds"], offset_free_mean_rounds=off[-1]["mean_rounds"],
                               observed_solved=obs[-1]["solved"], offset_free_solved=off[-1]["solved"])))
         co.destroy_loop(loopo); cf.destroy_loop(loopf)
+    for w in (False, True) if legs == "target" else ():
+        cf, loopf = make_targeted(B, ticks, w, None)
+        ct, loopt = make_targeted(B, ticks, w, "map")
+        cp, loopp = make_targeted(B, ticks, w, "pass")
+        run_device(cf, loopf); run_device(ct, loopt); run_device(cp, loopp)          # warm-up of the three legs
+        off, tgt, thru = [], [], []
+        for _ in range(repeats):                              # alternating, as above
+            off.append(run_device(cf, loopf)); tgt.append(run_device(ct, loopt)); thru.append(run_device(cp, loopp))
+        fm, flo, fhi = median_spread([r["ms_per_tick"] for r in off])
+        tm, tlo, thi = median_spread([r["ms_per_tick"] for r in tgt])
+        pm, plo, phi = median_spread([r["ms_per_tick"] for r in thru])
+        assert torch.equal(loopp.result.u, loopf.result.u)
+        yr = torch.as_tensor(quadrotor_batch(B)[2][:, [3, 4, 5, 2]]).cuda()
+        err = lambda loop: (loop.result.y[-1] - yr).abs().max(dim=1).values
+        print(json.dumps(dict(target=True, warm=w, batch=B, ticks=ticks, repeats=repeats,
+                              offset_free_ms_per_tick=dict(median=fm, min=flo, max=fhi), target_ms_per_tick=dict(median=tm, min=tlo, max=thi),
+                              pass_through_ms_per_tick=dict(median=pm, min=plo, max=phi),
+                              offset_free_mean_rounds=off[-1]["mean_rounds"], target_mean_rounds=tgt[-1]["mean_rounds"],
+                              offset_free_solved=off[-1]["solved"], target_solved=tgt[-1]["solved"],
+                              offset_free_final_error=dict(median=float(err(loopf).median()), max=float(err(loopf).max())),
+                              target_final_error=dict(median=float(err(loopt).median()), max=float(err(loopt).max())))))
+        cf.destroy_loop(loopf); ct.destroy_loop(loopt); cp.destroy_loop(loopp)
     if legs in ("bank", "all"):
         het, (x0, u0, yref), dev = make_bank(B)
         run_bank(het, dev, 5, True)
