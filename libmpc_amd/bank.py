@@ -19,7 +19,7 @@ import ctypes as C
 
 from . import _capi
 from ._capi import check
-from .lmpc import LMPC, BatchResult, ClosedLoopResult, Loop
+from .lmpc import LMPC, BatchResult, ClosedLoopResult, Loop, _LoopFrontEnd
 
 
 def group_by_model(model, n_models: int):
@@ -92,7 +92,7 @@ class LMPCBank:
         return out
 
 
-class LMPCHetero:
+class LMPCHetero(_LoopFrontEnd):
     """K configured `libmpc_amd.LMPC` controllers (host-only handles, `device=-1`, are enough) of equal dimensions and equal
     pattern of finite bounds, solved together by one set of kernels: instance b uses controller `model[b]` (default: b).
     In the reference each of them is its own `mpc::LMPC<>` object (LMPC.hpp:751)."""
@@ -133,11 +133,8 @@ class LMPCHetero:
         check(f(self._h, int(k), name.encode(), out.ctypes.data_as(C.c_void_p), n))
         return out
 
-    # the descriptor is the single-controller one: borrow its builder (it only needs the dimensions and info())
-    _torch, _dev, _ref = LMPC._torch, LMPC._dev, LMPC._ref
-
     def make_batch(self, x0, u0, model=None, **kw):
-        b, res, keep = LMPC.make_batch(self, x0, u0, **kw)
+        b, res, keep = LMPC.make_batch(self, x0, u0, **kw)      # the descriptor is the single-controller one: it only needs the dimensions and info()
         mi = None
         if model is not None:
             mi = torch.as_tensor(model).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
@@ -167,11 +164,8 @@ class LMPCHetero:
         res._inputs = keep
         return res
 
-    # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create; the loop itself is LMPC's) -------------------------------
-    _loop_ref, _check_plants, _make_loop, pack_plants = LMPC._loop_ref, LMPC._check_plants, LMPC._make_loop, staticmethod(LMPC.pack_plants)
-    _check_observer, pack_gains = LMPC._check_observer, staticmethod(LMPC.pack_gains)
-    _check_disturbance_observer, _check_observers, _check_target = LMPC._check_disturbance_observer, LMPC._check_observers, LMPC._check_target
-    run_loop, destroy_loop = LMPC.run_loop, LMPC.destroy_loop
+    # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create*; the loop itself is _LoopFrontEnd's) ---------------------
+    _loop_entry = "mpcx_lmpc_hetero_loop_create"
 
     def _own_plant(self, B, model=None):
         """A, B, Bd of each instance's own controller, [B, nx, .] numpy"""
@@ -261,16 +255,7 @@ class LMPCHetero:
                 plants = tuple(None if m is None else np.broadcast_to(np.asarray(m, dtype=np.float64), (B,) + np.shape(m)) for m in plant)
                 plant = None
 
-        def create(d, s, out, od, td=None):
-            mp = None if mi is None else C.c_void_p(mi.data_ptr())
-            if od is None:
-                return self._lib.mpcx_lmpc_hetero_loop_create(self._h, d, mp, s, out)
-            if td is not None:
-                return self._lib.mpcx_lmpc_hetero_loop_create_offset_free_target(self._h, d, od, td, mp, s, out)
-            if disturbance_observer is not None:
-                return self._lib.mpcx_lmpc_hetero_loop_create_offset_free(self._h, d, od, mp, s, out)
-            return self._lib.mpcx_lmpc_hetero_loop_create_observed(self._h, d, od, mp, s, out)
-        loop = self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi,
+        loop = self._make_loop(x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=mi,
                                observer=observer, xhat0=xhat0, meas_noise=meas_noise, bank=True, disturbance_observer=disturbance_observer, dhat0=dhat0, checked=checked,
                                target=target)
         loop.keep += (mi,)

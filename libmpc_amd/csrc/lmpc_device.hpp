@@ -159,13 +159,24 @@ size_t lmpc_condense_lds(const LmpcDev &m, int *NP_out, int *NQ_out, size_t *big
 int lmpc_condense_launch(LmpcDev *models_d, const LmpcDev &m0, int count, void *stream);
 
 // The closed loop around the solve (lmpc_loop.hip): everything the advance kernel touches.  All device pointers; the same struct at every tick.
+// The packed blocks: per-instance coefficients in the order the advance kernels read them (lmpc_loop.hip, DESIGN 4.3b has the table)
+enum LoopBlock : int {
+    kPlantBlock,                                  // [A_p | B_p | Bd_p] of the instance's plant
+    kEstimatorBlock,                              // [A | B | Bd | L] of the instance's controller
+    kMeasurementBlock,                            // [C | Dd] of the instance's controller
+    kDisturbanceGainBlock,                        // Ld of the instance's controller
+    kTargetMapBlock,                              // T of the instance's controller
+    kLoopBlocks
+};
+struct LoopBlockShape { int terms, rows; };       // a block is `terms` columns of `rows` coefficients per instance
+struct LoopBlockBuf { double *p; long ts; };      // null: the loop has no such block; tile stride 0: one tile
 struct LmpcLoopDev {
     int batch, ticks, nx, nu, ndu, ph, aw;        // aw: active-set words per instance
     int sx, su, sd;                               // LDS row strides of the state, command and exogenous-input tiles (lmpc_loop_plan_lds)
     const double *plant;                          // [A_p (nx x nx) | B_p (nx x nu) | Bd_p (nx x ndu)], each row-major: read by scalar loads
     // per-instance plants (pk null: the one plant above)
-    int ipw, sv;                                  // instances per wavefront of the per-instance advance kernel, LDS stride of an instance's [x | cmd | d] (lmpc_loop_plan_lds)
-    double *pk;                                   // lmpc_loop_packed_len doubles, written by lmpc_loop_pack_plants in the order lmpc_loop.hip describes
+    int ipw, sv;                                  // instances per wavefront where a lane is an (instance, row), LDS stride of an instance's [x | cmd | d] (lmpc_loop_plan_lds)
+    double *pk;                                   // the plant block with a tile per ipw instances, written by lmpc_loop_pack_plants
     const double *pk_src;                         // the caller's [B x nx (nx + nu + ndu)], A_b | B_b | Bd_b column-major; null: each instance's controller
     const LmpcDev *models;                        // a bank's model structs and its instance -> controller map (null map: instance b = controller b)
     const int32_t *model_index;
@@ -185,11 +196,12 @@ struct LmpcLoopDev {
     // preview references (yref, uref, duref, dmeas): source [B x (ticks + ph) x n], staging [B x ph x n]; null source: not a preview array
     const double *pv_src[4]; double *pv_dst[4]; int pv_n[4];
     int *state;                                   // [tick, blocks of the running advance kernel that are through]
-    // observed loops (ek null: none): x above is then the estimate -- what the solve reads -- and xt the plant's true state.  The three packed blocks
-    // are written by lmpc_loop_pack_observer in the order lmpc_loop.hip describes; a tile stride of 0: one tile, read by every block
+    // observed loops (ek null: none): x above is then the estimate -- what the solve reads -- and xt the plant's true state.  The packed blocks
+    // (LoopBlock above; reached by name here and through lmpc_loop_block_buf) are written by lmpc_loop_pack_observer; a tile stride of 0: one tile,
+    // the same for every instance, read by every block of a launch
     int ny, so;                                   // outputs; LDS stride of an instance's [x | xhat | cmd | d | e] (lmpc_loop_plan_lds)
     double *xt;
-    double *ok; long ok_ts;                       // the plant [A_p | B_p | Bd_p]: pk (a plant per instance), or one tile packed from `plant`
+    double *ok; long ok_ts;                       // the plant [A_p | B_p | Bd_p]: pk (a plant per instance; set with pk in every such loop), or one tile packed from `plant`
     double *ek; long ek_ts;                       // the estimator [A | B | Bd | L] of the instance's controller
     double *mk; long mk_ts;                       // the measurement [C | Dd] of the instance's controller
     const double *mA, *mB, *mBd, *mC, *mDd;       // a handle's model on the device, column-major (null in a bank: models / model_index)
@@ -202,7 +214,7 @@ struct LmpcLoopDev {
     // gain_batch are [(nx + ndu) x ny], rows 0 .. nx - 1 the estimator block's L, the others Ld
     int dobs;                                     // (before lmpc_loop_plan_lds: so is then the stride of [x | xhat | cmd | dhat | e | d])
     double *dhat;                                 // [B x ndu]
-    double *dk; long dk_ts;                       // Ld of the instance's controller: ny terms of ndu rows, a fourth packed block
+    double *dk; long dk_ts;                       // Ld of the instance's controller
     const double *dhat0;                          // [B x ndu] or null (= 0), read by lmpc_loop_begin
     double *traj_dhat;                            // [(ticks + 1) x B x ndu] or null
     // steady-state targets (tgt 0: none; needs dobs): us = T [r; dhat; ubar] with T [nu x (ny + ndu + nu)] column-major is what the solve reads as its
@@ -210,22 +222,49 @@ struct LmpcLoopDev {
     // "shared" mode, each controller's own (models / model_index)
     int tgt;                                      // (before lmpc_loop_plan_lds: so then also holds [r | dhat+ | ubar] of tick k + 1)
     double *us;                                   // [B x nu]
-    double *tk; long tk_ts;                       // T of the instance's controller: ny + ndu + nu terms of nu rows, a fifth packed block
+    double *tk; long tk_ts;                       // T of the instance's controller
     const double *tmap, *tmap_batch;              // one map for the batch (device copy), or the caller's [B x nu nrhs]
     const double *r_src; long r_bs, r_tick;
     const double *ub_src; long ub_bs, ub_tick;
     double *traj_us;                              // [(ticks + 1) x B x nu] or null
 };
+// The one description of a packed block; its length, its tile stride, the pack launches and what the kernels index with all derive from it
+__host__ __device__ inline LoopBlockShape lmpc_loop_block_shape(const LmpcLoopDev &L, LoopBlock b)
+{
+    switch (b) {
+    case kPlantBlock: return {L.nx + L.nu + L.ndu, L.nx};
+    case kEstimatorBlock: return {L.nx + L.nu + L.ndu + L.ny, L.nx};
+    case kMeasurementBlock: return {L.nx + L.ndu, L.ny};
+    case kDisturbanceGainBlock: return {L.ny, L.ndu};
+    default: return {L.ny + L.ndu + L.nu, L.nu};  // kTargetMapBlock
+    }
+}
+// ... and where it lies.  The blocks keep a named pointer and stride each, where they have always been in the struct: the advance kernels hold most
+// of it in scalar registers, and how many of those spill has followed every move of a field (profiles/loop_refactor.txt)
+__host__ __device__ inline LoopBlockBuf lmpc_loop_block_buf(const LmpcLoopDev &L, LoopBlock b)
+{
+    switch (b) {
+    case kPlantBlock: return {L.ok, L.ok_ts};
+    case kEstimatorBlock: return {L.ek, L.ek_ts};
+    case kMeasurementBlock: return {L.mk, L.mk_ts};
+    case kDisturbanceGainBlock: return {L.dk, L.dk_ts};
+    default: return {L.tk, L.tk_ts};              // kTargetMapBlock
+    }
+}
+__host__ __device__ inline size_t lmpc_loop_tiles(const LmpcLoopDev &L) { return (size_t)((L.batch + L.ipw - 1) / L.ipw); }
+// doubles of a tile (ipw instances, the last tile padded): the tile stride of a block that differs from instance to instance
+__host__ __device__ inline size_t lmpc_loop_tile_len(const LmpcLoopDev &L, LoopBlock b)
+{
+    const LoopBlockShape s = lmpc_loop_block_shape(L, b);
+    return (size_t)s.terms * L.ipw * s.rows;
+}
+// doubles of the block as its tile stride says: a tile per ipw instances, or one
+__host__ __device__ inline size_t lmpc_loop_block_len(const LmpcLoopDev &L, LoopBlock b) { return (lmpc_loop_block_buf(L, b).ts ? lmpc_loop_tiles(L) : 1) * lmpc_loop_tile_len(L, b); }
 void lmpc_loop_plan_lds(LmpcLoopDev &L);          // fills sx, su, sd, ipw, sv, so (ny, dobs and tgt before the call)
-size_t lmpc_loop_packed_len(const LmpcLoopDev &L);   // doubles of pk (whole tiles)
-// doubles of an observed loop's blocks with `tiles` tiles each: 0 the plant, 1 the estimator, 2 the measurement, 3 the disturbance gain Ld,
-// 4 the target map
-size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles);
-size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L);
 int lmpc_loop_prepare(const LmpcLoopDev &L);      // once per loop, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
 int lmpc_loop_begin(const LmpcLoopDev &L, void *stream);
-int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of every run, next to lmpc_loop_begin: fills pk and d_own (no launch when both are null)
-int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills ok (unless it is pk), ek, mk, (offset-free) dk and (targets) tk
+int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of every run, next to lmpc_loop_begin: fills a per-instance plant block and d_own (no launch without either)
+int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills every other block the loop has
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
 
 // Steady-state target maps (target_kernels.hip): the KKT system of each instance's target, one instance per wavefront, and the product with a map

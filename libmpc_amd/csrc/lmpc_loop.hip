@@ -15,7 +15,7 @@
 // Per-instance plants (a Monte-Carlo run over B plants, a bank whose every controller is its own plant) cannot be scalar operands:
 //   lmpc_loop_pack_plants     head of every run: the plants, from the caller's array or from the bank's model structs, into the order below; a
 //                             bank's "shared" exogenous input (each controller's own) into a [B x ndu] array
-//   lmpc_loop_advance_plants  the same tick with lane <-> (instance, state row): a wavefront holds 64 / nx instances, its lanes accumulate their
+//   lmpc_loop_advance_plants  the same tick with lane <-> (instance, state row): a wavefront holds ipw = 64 / nx instances, its lanes accumulate their
 //                             rows' nx + nu + ndu terms in the uniform kernel's order (the two agree bit for bit on equal plants); term j of a
 //                             tile is one contiguous run of the packed array, read by consecutive lanes, the loads of a group of terms in flight
 //                             together; the lane's sum is an element of the tile's run of x and goes straight out
@@ -41,6 +41,15 @@
 // dhat_{k+1} in a slot of its own, the dhat_k slot is still being read by the estimator rows of other lanes -- and, one barrier behind the rows of
 // dhat, the instance's lanes take the nu rows of us over T, a fifth packed block.  The row's sum is target_us_row (target_device.hpp), the one
 // mpcx_target_apply_batch uses.
+//
+// Lanes and rows.  mpcx_lmpc_create refuses nx, nu, ndu or ny above 64 ("one lane per component"), so where a lane is an (instance, row) an instance
+// has lpi = nx lanes and a wavefront ipw = 64 / nx instances: 1 for nx = 33 .. 64 (64 - nx idle lanes), 2 for nx = 32 (none idle), more below.  Every
+// state row has its lane.  The other rows of an instance (ny, ndu, nu of them) are taken by the same nx lanes and can outnumber them (nx = 2, ny = 3):
+// those loops stride by lpi.
+//
+// The packed blocks (LoopBlock, lmpc_loop_block_shape in lmpc_device.hpp): a block is `terms` columns of `rows` coefficients per instance, laid out
+// tile t, term j, instance q of the tile, row i at ((t * terms + j) * ipw + q) * rows + i -- a term of a tile is one run of ipw * rows doubles of which
+// lane (q, i) reads element q * rows + i.  A tile stride of 0 is one tile, the same for every instance; the padding of the last tile is zero.
 #include <hip/hip_runtime.h>
 
 #include "lmpc_device.hpp"
@@ -170,118 +179,6 @@ __device__ __forceinline__ void finish_tick(const LmpcLoopDev &L, const int b0, 
     }
 }
 
-// kPlants: a plant per instance.  The tile is then the ipw = 64 / nx instances whose rows fill the wavefront's lanes (from nx = 33 on one instance,
-// a lane taking rows lane, lane + 64, ...; lanes past ipw * nx idle), and the packed coefficients are read as: tile t, term j (the nx columns of
-// A_b, then the nu of B_b, then the ndu of Bd_b), instance q of the tile, row i at ((t * nterms + j) * ipw + q) * nx + i -- a term is one run of
-// ipw * nx doubles of which lane (q, i) reads element q * nx + i, and the terms of a row are one loop.  Sum order per row in both forms: acc = 0,
-// fma over A by ascending column, then B, then Bd, the noise added at the store.
-template <bool kPlants>
-__device__ __forceinline__ void advance_tick(const LmpcLoopDev &L, double *lds)
-{
-    const int tid = threadIdx.x;
-    const int k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(L.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    if (k >= L.ticks) return;                     // a replay past the run's end: nothing is written
-    const int nx = L.nx, nu = L.nu, ndu = L.ndu, B = L.batch;
-    // LDS rows: the uniform form keeps a tile of x, of cmd and of d apart; the per-instance form keeps an instance's [x | cmd | d] side by side, the
-    // operands of its terms in the terms' order
-    const int sx = kPlants ? L.sv : L.sx, su = kPlants ? L.sv : L.su, sd = kPlants ? L.sv : L.sd;
-    const int nt = kPlants ? L.ipw : kTile;       // instances of the block's tile
-    const int b0 = blockIdx.x * nt;
-    const int nvalid = min(nt, B - b0);
-    double *xin = lds, *cin = kPlants ? xin + nx : xin + nt * sx, *din = kPlants ? cin + nu : cin + nt * su, *xout = din + nt * sd;
-    const size_t xo = (size_t)b0 * nx, uo = (size_t)b0 * nu;
-
-    // in: the tile's states, commands and exogenous-input samples, one contiguous run each
-    for (int idx = tid; idx < nvalid * nx; idx += kTile) {
-        const int r = idx / nx, c = idx - r * nx;
-        xin[r * sx + c] = gin(L.x)[xo + idx];
-    }
-    double LOOP_GAS *tu = gout(L.traj_u) + (size_t)k * B * nu;
-    for (int idx = tid; idx < nvalid * nu; idx += kTile) {
-        const int r = idx / nu, c = idx - r * nu;
-        const double v = gin(L.cmd)[uo + idx];
-        cin[r * su + c] = v;
-        gout(L.u)[uo + idx] = v;                  // lastU of the next tick: the command as it is
-        tu[uo + idx] = v;
-    }
-    if (ndu > 0) {                                // d_k: column 0 of this tick's exogenous input, wherever its layout keeps it
-        const double LOOP_GAS *dk = gin(L.dmeas) + (size_t)k * L.d_tick;
-        for (int idx = tid; idx < nvalid * ndu; idx += kTile) {
-            const int r = idx / ndu, c = idx - r * ndu;
-            din[r * sd + c] = dk[(size_t)(b0 + r) * L.d_bs + c];
-        }
-    }
-    __syncthreads();
-
-    if constexpr (kPlants) {
-        // the plant step of the lane's (instance, row): every term one coalesced request of the wavefront, eight of them (then four) in flight
-        // together; the sum is element q * nx + i of the tile's run of x (every read of which the barrier above put ahead of these stores)
-        const int lpi = min(nx, kTile);           // lanes per instance
-        const int q = tid / lpi;
-        if (q < nvalid) {
-            const int nterms = nx + nu + ndu;
-            const size_t width = (size_t)nt * nx;
-            const double LOOP_GAS *P = gin(L.pk) + (size_t)blockIdx.x * nterms * width + q * nx;
-            const double *v = xin + q * sx;
-            double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
-            const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
-            for (int i = tid - q * lpi; i < nx; i += lpi) {
-                const double LOOP_GAS *Pi = P + i;
-                double acc = 0.0;
-                int j = 0;
-#pragma unroll 1
-                for (; j + 8 <= nterms; j += 8) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc = fma(Pi[(j + e) * width], v[j + e], acc);
-                }
-#pragma unroll 1
-                for (; j + 4 <= nterms; j += 4) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc = fma(Pi[(j + e) * width], v[j + e], acc);
-                }
-#pragma unroll 1
-                for (; j < nterms; ++j) acc = fma(Pi[j * width], v[j], acc);
-                const size_t at = xo + q * nx + i;
-                if (w) acc += w[at];
-                gout(L.x)[at] = acc;
-                tx[at] = acc;
-            }
-        }
-    } else {
-        // the plant step of the lane's instance, row by row of [A_p | B_p | Bd_p] (row-major, the rows of the three side by side per matrix)
-        if (tid < nvalid) {
-            const double LOOP_CAS *Ap = (const double LOOP_CAS *)L.plant;
-            const double LOOP_CAS *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
-            const double *xr = xin + tid * sx, *ur = cin + tid * su, *dr = din + tid * sd;
-            for (int i = 0; i < nx; ++i) {
-                double acc = 0.0;
-#pragma unroll 8
-                for (int j = 0; j < nx; ++j) acc = fma(Ap[i * nx + j], xr[j], acc);
-#pragma unroll 4
-                for (int j = 0; j < nu; ++j) acc = fma(Bp[i * nu + j], ur[j], acc);
-#pragma unroll 2
-                for (int j = 0; j < ndu; ++j) acc = fma(Dp[i * ndu + j], dr[j], acc);
-                xout[tid * sx + i] = acc;
-            }
-        }
-        __syncthreads();
-
-        // out: the new state (plus the process disturbance the controller knows nothing about) to the loop's x and to row k + 1 of traj_x
-        {
-            double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
-            const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
-            for (int idx = tid; idx < nvalid * nx; idx += kTile) {
-                const int r = idx / nx, c = idx - r * nx;
-                double v = xout[r * sx + c];
-                if (w) v += w[xo + idx];
-                gout(L.x)[xo + idx] = v;
-                tx[xo + idx] = v;
-            }
-        }
-    }
-    finish_tick(L, b0, nvalid, k, tid);
-}
-
 // n terms behind acc in ascending order: term j is P[j * width] -- one coalesced request of the wavefront -- times v[j] from LDS, the loads of eight
 // terms (then four) in flight together
 __device__ __forceinline__ double row_terms(const double LOOP_GAS *P, const size_t width, const double *v, const int n, double acc)
@@ -323,11 +220,127 @@ __device__ __forceinline__ void output_terms(const double LOOP_GAS *M, const siz
     }
 }
 
-// The tick of an observed loop.  Tiles, lanes and the packed order are the per-instance kernel's (above); the estimator block has nx + nu + ndu + ny
-// terms of nx rows, the measurement block nx + ndu terms of ny rows (lane (q, i) reads element q * ny + i of a term's run of ipw * ny), each block
-// at its own tile stride.  Sum order, every row from acc = 0 by ascending column: y over C, then Dd, then + v_k; yhat the same without v_k; x as
-// above; xhat over A, B, Bd -- the plant's order -- then L, nothing added at the store.  Hence e = 0 exactly where xhat = x bitwise and v_k is
-// absent, and xhat <- x's own bits where the plant is the controller's model and no w_k comes on top.
+// What every tick begins with, in two parts with the kernel's own staging of its states between them (the order of the global loads -- states,
+// commands, d_k -- is the one the kernels' register allocation was measured with).  begin_tick: the tick number and the block's tile of nt
+// instances; false past the run's end, where a replay writes nothing.
+struct Tick { int k, b0, nvalid; };
+__device__ __forceinline__ bool begin_tick(const LmpcLoopDev &L, const int nt, Tick &T)
+{
+    T.k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(L.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    T.b0 = blockIdx.x * nt;
+    T.nvalid = min(nt, L.batch - T.b0);
+    return T.k < L.ticks;
+}
+// stage_inputs: the tile's commands, one contiguous run, into LDS at row stride su, to u (lastU of the next tick: the command as it is) and to the
+// tick's row of traj_u.  And d_k, column 0 of this tick's exogenous input wherever its layout keeps it, into LDS at row stride sd; an offset-free
+// loop's dhat_k ([B x ndu]) rides in that loop, into hin at the same stride (null: there is none).
+__device__ __forceinline__ void stage_inputs(const LmpcLoopDev &L, const Tick T, double *cin, const int su, double *din, const int sd, const double *dhat, double *hin)
+{
+    const int tid = threadIdx.x;
+    const int nu = L.nu, ndu = L.ndu, B = L.batch;
+    const size_t uo = (size_t)T.b0 * nu;
+    double LOOP_GAS *tu = gout(L.traj_u) + (size_t)T.k * B * nu;
+    for (int idx = tid; idx < T.nvalid * nu; idx += kTile) {
+        const int r = idx / nu, c = idx - r * nu;
+        const double v = gin(L.cmd)[uo + idx];
+        cin[r * su + c] = v;
+        gout(L.u)[uo + idx] = v;
+        tu[uo + idx] = v;
+    }
+    if (ndu > 0) {
+        const double LOOP_GAS *dk = gin(L.dmeas) + (size_t)T.k * L.d_tick;
+        for (int idx = tid; idx < T.nvalid * ndu; idx += kTile) {
+            const int r = idx / ndu, c = idx - r * ndu;
+            din[r * sd + c] = dk[(size_t)(T.b0 + r) * L.d_bs + c];
+            if (dhat) hin[r * sd + c] = gin(dhat)[(size_t)T.b0 * ndu + idx];
+        }
+    }
+}
+
+// kPlants: a plant per instance, lane <-> (instance, state row) of a tile of ipw instances (the file's head), the plant block's terms -- the nx
+// columns of A_b, then the nu of B_b, then the ndu of Bd_b -- one loop per row.  Sum order per row in both forms: acc = 0, fma over A by ascending
+// column, then B, then Bd, the noise added at the store.
+template <bool kPlants>
+__device__ __forceinline__ void advance_tick(const LmpcLoopDev &L, double *lds)
+{
+    const int tid = threadIdx.x;
+    const int nx = L.nx, nu = L.nu, B = L.batch;
+    // LDS rows: the uniform form keeps a tile of x, of cmd and of d apart; the per-instance form keeps an instance's [x | cmd | d] side by side, the
+    // operands of its terms in the terms' order
+    const int sx = kPlants ? L.sv : L.sx, su = kPlants ? L.sv : L.su, sd = kPlants ? L.sv : L.sd;
+    const int nt = kPlants ? L.ipw : kTile;       // instances of the block's tile
+    double *xin = lds, *cin = kPlants ? xin + nx : xin + nt * sx, *din = kPlants ? cin + nu : cin + nt * su, *xout = din + nt * sd;
+    Tick T;
+    if (!begin_tick(L, nt, T)) return;
+    const int k = T.k, b0 = T.b0, nvalid = T.nvalid;
+    const size_t xo = (size_t)b0 * nx;
+    for (int idx = tid; idx < nvalid * nx; idx += kTile) {      // the tile's states, one contiguous run
+        const int r = idx / nx, c = idx - r * nx;
+        xin[r * sx + c] = gin(L.x)[xo + idx];
+    }
+    stage_inputs(L, T, cin, su, din, sd, nullptr, nullptr);
+    __syncthreads();
+
+    if constexpr (kPlants) {
+        // the plant step of the lane's (instance, row): every term one coalesced request of the wavefront; the sum is element q * nx + i of the
+        // tile's run of x (every read of which the barrier above put ahead of these stores)
+        const int lpi = min(nx, kTile);           // lanes per instance: nx (the file's head)
+        const int q = tid / lpi;
+        if (q < nvalid) {
+            const LoopBlockShape s = lmpc_loop_block_shape(L, kPlantBlock);
+            const size_t width = (size_t)nt * s.rows;
+            const double LOOP_GAS *P = gin(L.pk) + (size_t)blockIdx.x * s.terms * width + q * nx;      // (a tile per block: the stride is a tile's length)
+            const double *v = xin + q * sx;
+            double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
+            const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
+            for (int i = tid - q * lpi; i < nx; i += lpi) {
+                double acc = row_terms(P + i, width, v, s.terms, 0.0);
+                const size_t at = xo + q * nx + i;
+                if (w) acc += w[at];
+                gout(L.x)[at] = acc;
+                tx[at] = acc;
+            }
+        }
+    } else {
+        // the plant step of the lane's instance, row by row of [A_p | B_p | Bd_p] (row-major, the rows of the three side by side per matrix)
+        const int ndu = L.ndu;
+        if (tid < nvalid) {
+            const double LOOP_CAS *Ap = (const double LOOP_CAS *)L.plant;
+            const double LOOP_CAS *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
+            const double *xr = xin + tid * sx, *ur = cin + tid * su, *dr = din + tid * sd;
+            for (int i = 0; i < nx; ++i) {
+                double acc = 0.0;
+#pragma unroll 8
+                for (int j = 0; j < nx; ++j) acc = fma(Ap[i * nx + j], xr[j], acc);
+#pragma unroll 4
+                for (int j = 0; j < nu; ++j) acc = fma(Bp[i * nu + j], ur[j], acc);
+#pragma unroll 2
+                for (int j = 0; j < ndu; ++j) acc = fma(Dp[i * ndu + j], dr[j], acc);
+                xout[tid * sx + i] = acc;
+            }
+        }
+        __syncthreads();
+
+        // out: the new state (plus the process disturbance the controller knows nothing about) to the loop's x and to row k + 1 of traj_x
+        {
+            double LOOP_GAS *tx = gout(L.traj_x) + (size_t)(k + 1) * B * nx;
+            const double LOOP_GAS *w = L.noise ? gin(L.noise) + (size_t)k * B * nx : nullptr;
+            for (int idx = tid; idx < nvalid * nx; idx += kTile) {
+                const int r = idx / nx, c = idx - r * nx;
+                double v = xout[r * sx + c];
+                if (w) v += w[xo + idx];
+                gout(L.x)[xo + idx] = v;
+                tx[xo + idx] = v;
+            }
+        }
+    }
+    finish_tick(L, b0, nvalid, k, tid);
+}
+
+// The tick of an observed loop.  Tiles and lanes are the per-instance kernel's; each block at its own tile stride.  Sum order, every row from
+// acc = 0 by ascending column: y over C, then Dd, then + v_k; yhat the same without v_k; x as above; xhat over A, B, Bd -- the plant's order -- then
+// L, nothing added at the store.  Hence e = 0 exactly where xhat = x bitwise and v_k is absent, and xhat <- x's own bits where the plant is the
+// controller's model and no w_k comes on top.
 // kOff, the tick of an offset-free loop: the slot behind cmd holds dhat_k (the operand of yhat's Dd terms and of the estimator's Bd terms, so the
 // estimator's row is still one chain over hin ...), the true d_k has a slot of its own behind e (the operand of y's Dd terms and of the plant's Bd_p
 // terms), and dhat <- dhat + (Ld e summed from 0 by ascending column).  With Ld = 0 and dhat = d bitwise every sum is the observed tick's.
@@ -339,40 +352,22 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
 {
     static_assert(kOff || !kTgt, "targets need the disturbance estimate");
     const int tid = threadIdx.x;
-    const int k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(L.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    if (k >= L.ticks) return;                     // a replay past the run's end: nothing is written
     const int nx = L.nx, nu = L.nu, ndu = L.ndu, ny = L.ny, B = L.batch, so = L.so;
     const int nt = L.ipw;
-    const int b0 = blockIdx.x * nt;
-    const int nvalid = min(nt, B - b0);
     double *xin = lds, *hin = xin + nx, *cin = hin + nx, *din = cin + nu, *ein = din + ndu;   // an instance's row: the estimator's operands are hin ... in its terms' order
     double *tin = din;                            // the disturbance that acts on the plant and on the measurement
     if constexpr (kOff) tin = ein + ny;
     double *rin = tin + ndu, *nin = rin + ny, *bin = nin + ndu;      // (kTgt) r, dhat and ubar of tick k + 1
-    const size_t xo = (size_t)b0 * nx, uo = (size_t)b0 * nu;
-
-    // in: the tile's true states, estimates, commands and exogenous-input samples, one contiguous run each
-    for (int idx = tid; idx < nvalid * nx; idx += kTile) {
+    Tick T;
+    if (!begin_tick(L, nt, T)) return;
+    const int k = T.k, b0 = T.b0, nvalid = T.nvalid;
+    const size_t xo = (size_t)b0 * nx;
+    for (int idx = tid; idx < nvalid * nx; idx += kTile) {      // the tile's true states and estimates, one contiguous run each
         const int r = idx / nx, c = idx - r * nx;
         xin[r * so + c] = gin(L.xt)[xo + idx];
         hin[r * so + c] = gin(L.x)[xo + idx];
     }
-    double LOOP_GAS *tu = gout(L.traj_u) + (size_t)k * B * nu;
-    for (int idx = tid; idx < nvalid * nu; idx += kTile) {
-        const int r = idx / nu, c = idx - r * nu;
-        const double v = gin(L.cmd)[uo + idx];
-        cin[r * so + c] = v;
-        gout(L.u)[uo + idx] = v;                  // lastU of the next tick: the command as it is
-        tu[uo + idx] = v;
-    }
-    if (ndu > 0) {
-        const double LOOP_GAS *dk = gin(L.dmeas) + (size_t)k * L.d_tick;
-        for (int idx = tid; idx < nvalid * ndu; idx += kTile) {
-            const int r = idx / ndu, c = idx - r * ndu;
-            tin[r * so + c] = dk[(size_t)(b0 + r) * L.d_bs + c];
-            if constexpr (kOff) din[r * so + c] = gin(L.dhat)[(size_t)b0 * ndu + idx];      // dhat_k: no read of it behind this barrier
-        }
-    }
+    stage_inputs(L, T, cin, so, tin, so, kOff ? L.dhat : nullptr, din);      // (dhat_k: no read of it behind this barrier)
     if constexpr (kTgt) {
         for (int idx = tid; idx < nvalid * ny; idx += kTile) {
             const int r = idx / ny, c = idx - r * ny;
@@ -385,10 +380,10 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
     }
     __syncthreads();
 
-    const int lpi = min(nx, kTile);               // lanes per instance
+    const int lpi = min(nx, kTile);               // lanes per instance: nx (the file's head)
     const int q = tid / lpi;
     const bool mine = q < nvalid;
-    // the measurement and the innovation of the lane's (instance, output row)
+    // the measurement and the innovation of the lane's (instance, output row): the measurement block's nx terms of C, then its ndu of Dd
     if (mine) {
         const size_t width = (size_t)nt * ny;
         const double LOOP_GAS *M = gin(L.mk) + (size_t)blockIdx.x * L.mk_ts + q * ny;
@@ -421,7 +416,7 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
                 acc = row_terms(P + i + nx * width, width, cr, nu, acc);
                 acc = row_terms(P + i + (nx + nu) * width, width, tin + q * so, ndu, acc);
             } else acc = row_terms(P + i + nx * width, width, cr, nu + ndu, acc);
-            const double est = row_terms(E + i, width, hr, nx + nu + ndu + ny, 0.0);
+            const double est = row_terms(E + i, width, hr, lmpc_loop_block_shape(L, kEstimatorBlock).terms, 0.0);
             const size_t at = xo + q * nx + i;
             if (w) acc += w[at];
             gout(L.xt)[at] = acc;
@@ -429,7 +424,7 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
             gout(L.x)[at] = est;
             if (th) th[at] = est;
         }
-        if constexpr (kOff) {                     // the rows of dhat, by the same lanes: ny terms of Ld, lane (q, i) reading element q * ndu + i of a term
+        if constexpr (kOff) {                     // the rows of dhat, by the same lanes: the ny terms of Ld
             const size_t wd = (size_t)nt * ndu;
             const double LOOP_GAS *G = gin(L.dk) + (size_t)blockIdx.x * L.dk_ts + q * ndu;
             const double *er = ein + q * so, *dr = din + q * so;
@@ -445,12 +440,12 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
     }
     if constexpr (kTgt) {
         __syncthreads();
-        if (mine) {                               // the rows of us_{k+1}: nrhs terms of T, lane (q, i) reading element q * nu + i of a term
+        if (mine) {                               // the rows of us_{k+1}: the ny + ndu + nu terms of T
             const size_t wt = (size_t)nt * nu;
-            const double LOOP_GAS *T = gin(L.tk) + (size_t)blockIdx.x * L.tk_ts + q * nu;
+            const double LOOP_GAS *Tm = gin(L.tk) + (size_t)blockIdx.x * L.tk_ts + q * nu;
             double LOOP_GAS *ts = L.traj_us ? gout(L.traj_us) + (size_t)(k + 1) * B * nu : nullptr;
             for (int i = tid - q * lpi; i < nu; i += lpi) {
-                const double v = target_us_row(T + i, wt, rin + q * so, ny, nin + q * so, ndu, bin + q * so, nu);
+                const double v = target_us_row(Tm + i, wt, rin + q * so, ny, nin + q * so, ndu, bin + q * so, nu);
                 const size_t at = (size_t)(b0 + q) * nu + i;
                 gout(L.us)[at] = v;
                 if (ts) ts[at] = v;
@@ -459,6 +454,8 @@ __device__ __forceinline__ void advance_observed(const LmpcLoopDev &L, double *l
     }
     finish_tick(L, b0, nvalid, k, tid);
 }
+
+using LoopKernel = void (*)(const LmpcLoopDev);
 
 __global__ __launch_bounds__(kTile) void lmpc_loop_advance_kernel(const LmpcLoopDev L)
 {
@@ -493,34 +490,70 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(1, 4))) v
 
 constexpr int kPackThreads = 256;
 
-// Head of a run: the plants in the advance kernel's order, from the caller's array ([B x nx (nx + nu + ndu)], A_b | B_b | Bd_b column-major: term j
-// of instance b is the run of nx doubles at (b nterms + j) nx) or from the model struct of each instance's controller; the padding of the last
-// tile is zero.  And each controller's own exogenous input, step 0, as the [B x ndu] array the advance kernel addresses per instance.
+// Head of a run: one packed block in the advance kernels' order (the file's head), a grid-stride loop over its elements.  value(b, j, i) is the
+// coefficient of term j, row i of instance b; a block of one tile is filled from instance 0.
+template <typename Value>
+__device__ __forceinline__ void pack_block(const LmpcLoopDev &L, const LoopBlock blk, Value value)
+{
+    const LoopBlockShape s = lmpc_loop_block_shape(L, blk);
+    const LoopBlockBuf buf = lmpc_loop_block_buf(L, blk);
+    const int ipw = L.ipw;
+    const bool per_instance = buf.ts != 0;
+    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
+    const size_t width = (size_t)ipw * s.rows, per_tile = (size_t)s.terms * width, total = lmpc_loop_block_len(L, blk);
+    double LOOP_GAS *out = gout(buf.p);
+    for (size_t idx = first; idx < total; idx += step) {
+        const size_t t = idx / per_tile, rem = idx - t * per_tile;
+        const int j = (int)(rem / width), qi = (int)(rem - j * width);
+        const int q = qi / s.rows, i = qi - q * s.rows;
+        const size_t b = per_instance ? t * ipw + q : 0;
+        out[idx] = b < (size_t)L.batch ? value(b, j, i) : 0.0;
+    }
+}
+
+// The model of instance b's controller is the handle's, or in a bank the struct of the controller the instance uses; column-major all.
+// Column j, row i of its [A | B | Bd] ...
+__device__ __forceinline__ double state_coeff(const LmpcLoopDev &L, const size_t b, const int j, const int i)
+{
+    const int nx = L.nx, nu = L.nu;
+    const auto of = [=](const double *A, const double *Bm, const double *Bd) {
+        return j < nx ? A[j * nx + i] : j < nx + nu ? Bm[(j - nx) * nx + i] : Bd[(j - nx - nu) * nx + i];
+    };
+    if (L.mA) return of(L.mA, L.mB, L.mBd);
+    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
+    return of(M.A, M.B, M.Bd);
+}
+// ... and of its [C | Dd]
+__device__ __forceinline__ double output_coeff(const LmpcLoopDev &L, const size_t b, const int j, const int i)
+{
+    const int nx = L.nx, ny = L.ny;
+    const auto of = [=](const double *Cm, const double *Dd) { return j < nx ? Cm[j * ny + i] : Dd[(j - nx) * ny + i]; };
+    if (L.mC) return of(L.mC, L.mDd);
+    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
+    return of(M.C, M.Dd);
+}
+// column c, row r of instance b's observer gain [ldg x ny], column-major: the one for the batch, or the caller's per-instance array
+__device__ __forceinline__ double gain_coeff(const LmpcLoopDev &L, const int ldg, const size_t b, const int c, const int r)
+{
+    return L.gain_batch ? gin(L.gain_batch)[(b * L.ny + c) * ldg + r] : L.gain[c * ldg + r];
+}
+
+// The plants of a loop that has one per instance, from the caller's array ([B x nx (nx + nu + ndu)], A_b | B_b | Bd_b column-major: term j of
+// instance b is the run of nx doubles at (b nterms + j) nx) or from each instance's controller.  And each controller's own exogenous input, step 0,
+// as the [B x ndu] array the advance kernel addresses per instance.
 __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_plants_kernel(const LmpcLoopDev L)
 {
-    const int nx = L.nx, nu = L.nu, ndu = L.ndu, B = L.batch, ipw = L.ipw;
-    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
     if (L.pk) {
-        const size_t nterms = (size_t)(nx + nu + ndu), width = (size_t)ipw * nx, per_tile = nterms * width;
-        const size_t total = (size_t)((B + ipw - 1) / ipw) * per_tile;
-        for (size_t idx = first; idx < total; idx += step) {
-            const size_t t = idx / per_tile, rem = idx - t * per_tile;
-            const int j = (int)(rem / width), qi = (int)(rem - j * width);
-            const int q = qi / nx, i = qi - q * nx;
-            const size_t b = t * ipw + q;
-            double v = 0.0;
-            if (b < (size_t)B) {
-                if (L.pk_src) v = gin(L.pk_src)[(b * nterms + j) * nx + i];
-                else {
-                    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
-                    v = j < nx ? M.A[j * nx + i] : j < nx + nu ? M.B[(j - nx) * nx + i] : M.Bd[(j - nx - nu) * nx + i];
-                }
-            }
-            gout(L.pk)[idx] = v;
-        }
+        const size_t nterms = (size_t)lmpc_loop_block_shape(L, kPlantBlock).terms;
+        const int nx = L.nx;
+        pack_block(L, kPlantBlock, [&](const size_t b, const int j, const int i) {
+            return L.pk_src ? gin(L.pk_src)[(b * nterms + j) * nx + i] : state_coeff(L, b, j, i);
+        });
     }
     if (L.d_own) {
-        for (size_t idx = first; idx < (size_t)B * ndu; idx += step) {
+        const int ndu = L.ndu;
+        const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
+        for (size_t idx = first; idx < (size_t)L.batch * ndu; idx += step) {
             const size_t b = idx / ndu;
             const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
             gout(L.d_own)[idx] = M.dmeas_s[idx - b * ndu];
@@ -528,107 +561,63 @@ __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_plants_kernel(con
     }
 }
 
-// Head of a run of an observed loop: its blocks in the advance kernel's order.  The plant where it is one for the batch (from the row-major
-// `plant`: one tile, every instance of it the same), the estimator [A | B | Bd | L] and the measurement [C | Dd] from the handle's model or from
-// the model struct of each instance's controller, the gain from the one for the batch or from the caller's per-instance array.  A block with tile
-// stride 0 is one tile.  kOff, an offset-free loop: the gain is [(nx + ndu) x ny], its first nx rows the estimator block's, the others the fourth block.
+// The blocks of an observed loop: the plant where it is one for the batch (one tile from the row-major `plant`), the estimator [A | B | Bd | L] and
+// the measurement [C | Dd].  kOff, an offset-free loop: the gain is [(nx + ndu) x ny], its first nx rows the estimator block's, the others Ld's.
 template <bool kOff>
 __device__ __forceinline__ void pack_observer(const LmpcLoopDev &L)
 {
-    const int nx = L.nx, nu = L.nu, ndu = L.ndu, ny = L.ny, B = L.batch, ipw = L.ipw;
-    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
-    const size_t tiles = (size_t)((B + ipw - 1) / ipw);
+    const int nx = L.nx, nu = L.nu, ndu = L.ndu;
     const int npl = nx + nu + ndu;
     const int ldg = kOff ? nx + ndu : nx;         // rows of a gain
-    if (L.ok != L.pk) {
-        const size_t width = (size_t)ipw * nx, total = (size_t)npl * width;
+    if (!L.pk) {                                  // one plant for the batch: one tile of it, from the row-major `plant`
         const double *Ap = L.plant, *Bp = Ap + nx * nx, *Dp = Bp + nx * nu;
-        for (size_t idx = first; idx < total; idx += step) {
-            const int j = (int)(idx / width), i = (int)((idx - j * width) % nx);
-            gout(L.ok)[idx] = j < nx ? Ap[i * nx + j] : j < nx + nu ? Bp[i * nu + (j - nx)] : Dp[i * ndu + (j - nx - nu)];
-        }
+        pack_block(L, kPlantBlock, [&](const size_t, const int j, const int i) {
+            return j < nx ? Ap[i * nx + j] : j < nx + nu ? Bp[i * nu + (j - nx)] : Dp[i * ndu + (j - nx - nu)];
+        });
     }
-    {
-        const size_t width = (size_t)ipw * nx, per_tile = (size_t)(npl + ny) * width;
-        const size_t total = (L.ek_ts ? tiles : 1) * per_tile;
-        for (size_t idx = first; idx < total; idx += step) {
-            const size_t t = idx / per_tile, rem = idx - t * per_tile;
-            const int j = (int)(rem / width), qi = (int)(rem - j * width);
-            const int q = qi / nx, i = qi - q * nx;
-            const size_t b = L.ek_ts ? t * ipw + q : 0;
-            double v = 0.0;
-            if (b < (size_t)B) {
-                if (j >= npl) v = L.gain_batch ? gin(L.gain_batch)[(b * ny + (j - npl)) * ldg + i] : L.gain[(j - npl) * ldg + i];
-                else if (L.mA) v = j < nx ? L.mA[j * nx + i] : j < nx + nu ? L.mB[(j - nx) * nx + i] : L.mBd[(j - nx - nu) * nx + i];
-                else {
-                    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
-                    v = j < nx ? M.A[j * nx + i] : j < nx + nu ? M.B[(j - nx) * nx + i] : M.Bd[(j - nx - nu) * nx + i];
-                }
-            }
-            gout(L.ek)[idx] = v;
-        }
-    }
-    {
-        const size_t width = (size_t)ipw * ny, per_tile = (size_t)(nx + ndu) * width;
-        const size_t total = (L.mk_ts ? tiles : 1) * per_tile;
-        for (size_t idx = first; idx < total; idx += step) {
-            const size_t t = idx / per_tile, rem = idx - t * per_tile;
-            const int j = (int)(rem / width), qi = (int)(rem - j * width);
-            const int q = qi / ny, i = qi - q * ny;
-            const size_t b = L.mk_ts ? t * ipw + q : 0;
-            double v = 0.0;
-            if (b < (size_t)B) {
-                if (L.mC) v = j < nx ? L.mC[j * ny + i] : L.mDd[(j - nx) * ny + i];
-                else {
-                    const LmpcDev &M = L.models[L.model_index ? L.model_index[b] : (int)b];
-                    v = j < nx ? M.C[j * ny + i] : M.Dd[(j - nx) * ny + i];
-                }
-            }
-            gout(L.mk)[idx] = v;
-        }
-    }
-    if constexpr (kOff) {
-        const size_t width = (size_t)ipw * ndu, per_tile = (size_t)ny * width;
-        const size_t total = (L.dk_ts ? tiles : 1) * per_tile;
-        for (size_t idx = first; idx < total; idx += step) {
-            const size_t t = idx / per_tile, rem = idx - t * per_tile;
-            const int j = (int)(rem / width), qi = (int)(rem - j * width);
-            const int q = qi / ndu, i = qi - q * ndu;
-            const size_t b = L.dk_ts ? t * ipw + q : 0;
-            double v = 0.0;
-            if (b < (size_t)B) v = L.gain_batch ? gin(L.gain_batch)[(b * ny + j) * ldg + nx + i] : L.gain[j * ldg + nx + i];
-            gout(L.dk)[idx] = v;
-        }
-    }
+    pack_block(L, kEstimatorBlock, [&](const size_t b, const int j, const int i) { return j < npl ? state_coeff(L, b, j, i) : gain_coeff(L, ldg, b, j - npl, i); });
+    pack_block(L, kMeasurementBlock, [&](const size_t b, const int j, const int i) { return output_coeff(L, b, j, i); });
+    if constexpr (kOff) pack_block(L, kDisturbanceGainBlock, [&](const size_t b, const int j, const int i) { return gain_coeff(L, ldg, b, j, nx + i); });
 }
 
 __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_observer_kernel(const LmpcLoopDev L) { pack_observer<false>(L); }
 __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_offset_free_kernel(const LmpcLoopDev L) { pack_observer<true>(L); }
 
-// ... and of a loop with targets, behind the two above: T in the advance kernel's order, from the one map for the batch (one tile) or the caller's
-// per-instance array, both column-major [nu x nrhs]
+// ... and of a loop with targets, behind the two above: T from the one map for the batch or the caller's per-instance array, both column-major
+// [nu x nrhs]
 __global__ __launch_bounds__(kPackThreads) void lmpc_loop_pack_target_kernel(const LmpcLoopDev L)
 {
-    const int nu = L.nu, B = L.batch, ipw = L.ipw, nrhs = L.ny + L.ndu + L.nu;
-    const size_t first = (size_t)blockIdx.x * kPackThreads + threadIdx.x, step = (size_t)gridDim.x * kPackThreads;
-    const size_t tiles = (size_t)((B + ipw - 1) / ipw);
-    const size_t width = (size_t)ipw * nu, per_tile = (size_t)nrhs * width;
-    const size_t total = (L.tk_ts ? tiles : 1) * per_tile;
-    for (size_t idx = first; idx < total; idx += step) {
-        const size_t t = idx / per_tile, rem = idx - t * per_tile;
-        const int j = (int)(rem / width), qi = (int)(rem - j * width);
-        const int q = qi / nu, i = qi - q * nu;
-        const size_t b = L.tk_ts ? t * ipw + q : 0;
-        double v = 0.0;
-        if (b < (size_t)B) v = L.tmap_batch ? gin(L.tmap_batch)[(b * nrhs + j) * nu + i] : L.tmap[j * nu + i];
-        gout(L.tk)[idx] = v;
-    }
+    const int nu = L.nu, nrhs = L.ny + L.ndu + L.nu;
+    pack_block(L, kTargetMapBlock, [&](const size_t b, const int j, const int i) {
+        return L.tmap_batch ? gin(L.tmap_batch)[(b * nrhs + j) * nu + i] : L.tmap[j * nu + i];
+    });
 }
 
 inline int odd(int n) { return n | 1; }
 
+// Which advance kernel a loop runs, on how many blocks of one wavefront, with how much dynamic LDS
+struct AdvanceLaunch { LoopKernel kernel; unsigned grid; size_t lds; };
+AdvanceLaunch advance_launch(const LmpcLoopDev &L)
+{
+    const unsigned tiles = (unsigned)lmpc_loop_tiles(L);
+    if (L.ek) {                                   // an instance's row of operands, ipw of them
+        const LoopKernel kernel = L.tgt ? lmpc_loop_advance_offset_free_target_kernel : L.dobs ? lmpc_loop_advance_offset_free_kernel : lmpc_loop_advance_observed_kernel;
+        return {kernel, tiles, (size_t)L.ipw * L.so * sizeof(double)};
+    }
+    if (L.pk) return {lmpc_loop_advance_plants_kernel, tiles, (size_t)L.ipw * L.sv * sizeof(double)};      // [x | cmd | d] of ipw instances
+    return {lmpc_loop_advance_kernel, (unsigned)((L.batch + kTile - 1) / kTile), (size_t)kTile * (2 * L.sx + L.su + L.sd) * sizeof(double)};   // x, cmd, d and x+ of 64
+}
+
+// blocks of a pack launch over n elements
+dim3 pack_grid(const size_t n)
+{
+    const size_t blocks = (n + kPackThreads - 1) / kPackThreads;
+    return dim3((unsigned)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks));
+}
+
 }  // namespace
 
+// (nx <= 64: ipw >= 1 instances of nx lanes each fill, or nearly fill, the wavefront)
 void lmpc_loop_plan_lds(LmpcLoopDev &L)
 {
     L.sx = odd(L.nx); L.su = odd(L.nu); L.sd = L.ndu > 0 ? odd(L.ndu) : 0;
@@ -636,35 +625,11 @@ void lmpc_loop_plan_lds(LmpcLoopDev &L)
     L.so = odd(2 * L.nx + L.nu + L.ndu + L.ny + (L.dobs ? L.ndu : 0) + (L.tgt ? L.ny + L.ndu + L.nu : 0));
 }
 
-size_t lmpc_loop_packed_len(const LmpcLoopDev &L) { return (size_t)((L.batch + L.ipw - 1) / L.ipw) * (L.nx + L.nu + L.ndu) * L.ipw * L.nx; }
-
-size_t lmpc_loop_block_len(const LmpcLoopDev &L, int which, size_t tiles)
-{
-    const size_t terms = which == 0 ? L.nx + L.nu + L.ndu : which == 1 ? L.nx + L.nu + L.ndu + L.ny : which == 2 ? L.nx + L.ndu : which == 3 ? L.ny : L.ny + L.ndu + L.nu;
-    return tiles * terms * L.ipw * (which == 2 ? L.ny : which == 3 ? L.ndu : which == 4 ? L.nu : L.nx);
-}
-
-static size_t observed_lds_bytes(const LmpcLoopDev &L) { return (size_t)L.ipw * L.so * sizeof(double); }
-
-size_t lmpc_loop_lds_bytes(const LmpcLoopDev &L) { return (size_t)kTile * (2 * L.sx + L.su + L.sd) * sizeof(double); }
-
 int lmpc_loop_prepare(const LmpcLoopDev &L)
 {
-    if (L.ek) {                                   // the observed kernel's tile: a few KB unless one instance has thousands of states
-        const size_t bytes = observed_lds_bytes(L);
-        if (bytes > lmpc_lds_limit()) return -2;
-        const void *kernel = L.tgt    ? reinterpret_cast<const void *>(lmpc_loop_advance_offset_free_target_kernel)
-                             : L.dobs ? reinterpret_cast<const void *>(lmpc_loop_advance_offset_free_kernel)
-                                      : reinterpret_cast<const void *>(lmpc_loop_advance_observed_kernel);
-        if (bytes > 48 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -3;
-        return 0;
-    }
-    if (L.pk) return 0;                           // the per-instance kernel's tile: [x | cmd | d] of at most 64 instances of 1 state ... one of many
-    const size_t bytes = lmpc_loop_lds_bytes(L);
-    if (bytes > lmpc_lds_limit()) return -2;
-    if (bytes > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(lmpc_loop_advance_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return -3;
+    const AdvanceLaunch a = advance_launch(L);
+    if (a.lds > lmpc_lds_limit()) return -2;
+    if (a.lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(a.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds) != hipSuccess) return -3;
     return 0;
 }
 
@@ -678,52 +643,28 @@ int lmpc_loop_begin(const LmpcLoopDev &L, void *stream)
 int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream)
 {
     if (!L.pk && !L.d_own) return 0;
-    const size_t n = L.pk ? lmpc_loop_packed_len(L) : (size_t)L.batch * L.ndu;
-    size_t blocks = (n + kPackThreads - 1) / kPackThreads;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(lmpc_loop_pack_plants_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    const size_t n = L.pk ? lmpc_loop_block_len(L, kPlantBlock) : (size_t)L.batch * L.ndu;
+    hipLaunchKernelGGL(lmpc_loop_pack_plants_kernel, pack_grid(n), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream)
 {
     if (!L.ek) return 0;
-    const size_t tiles = (size_t)((L.batch + L.ipw - 1) / L.ipw);
-    size_t n = lmpc_loop_block_len(L, 1, L.ek_ts ? tiles : 1);
-    if (lmpc_loop_block_len(L, 2, L.mk_ts ? tiles : 1) > n) n = lmpc_loop_block_len(L, 2, L.mk_ts ? tiles : 1);
-    if (L.dobs && lmpc_loop_block_len(L, 3, L.dk_ts ? tiles : 1) > n) n = lmpc_loop_block_len(L, 3, L.dk_ts ? tiles : 1);
-    size_t blocks = (n + kPackThreads - 1) / kPackThreads;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    if (L.dobs) hipLaunchKernelGGL(lmpc_loop_pack_offset_free_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
-    else hipLaunchKernelGGL(lmpc_loop_pack_observer_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
-    if (L.tgt) {
-        blocks = (lmpc_loop_block_len(L, 4, L.tk_ts ? tiles : 1) + kPackThreads - 1) / kPackThreads;
-        if (blocks > 2048) blocks = 2048;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(lmpc_loop_pack_target_kernel, dim3((unsigned)blocks), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
-    }
+    size_t n = 0;                                 // the first kernel fills several blocks: a grid for the longest
+    for (const LoopBlock b : {kEstimatorBlock, kMeasurementBlock, kDisturbanceGainBlock})
+        if (lmpc_loop_block_buf(L, b).p && lmpc_loop_block_len(L, b) > n) n = lmpc_loop_block_len(L, b);
+    const LoopKernel pack = L.dobs ? lmpc_loop_pack_offset_free_kernel : lmpc_loop_pack_observer_kernel;
+    hipLaunchKernelGGL(pack, pack_grid(n), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+    if (L.tgt)
+        hipLaunchKernelGGL(lmpc_loop_pack_target_kernel, pack_grid(lmpc_loop_block_len(L, kTargetMapBlock)), dim3(kPackThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream)
 {
-    if (L.ek) {
-        const int tiles = (L.batch + L.ipw - 1) / L.ipw;
-        if (L.tgt) hipLaunchKernelGGL(lmpc_loop_advance_offset_free_target_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
-        else if (L.dobs) hipLaunchKernelGGL(lmpc_loop_advance_offset_free_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
-        else hipLaunchKernelGGL(lmpc_loop_advance_observed_kernel, dim3(tiles), dim3(kTile), observed_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    if (L.pk) {
-        const int tiles = (L.batch + L.ipw - 1) / L.ipw;
-        const size_t lds = (size_t)L.ipw * L.sv * sizeof(double);
-        hipLaunchKernelGGL(lmpc_loop_advance_plants_kernel, dim3(tiles), dim3(kTile), lds, reinterpret_cast<hipStream_t>(stream), L);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    const int blocks = (L.batch + kTile - 1) / kTile;
-    hipLaunchKernelGGL(lmpc_loop_advance_kernel, dim3(blocks), dim3(kTile), lmpc_loop_lds_bytes(L), reinterpret_cast<hipStream_t>(stream), L);
+    const AdvanceLaunch a = advance_launch(L);
+    hipLaunchKernelGGL(a.kernel, dim3(a.grid), dim3(kTile), a.lds, reinterpret_cast<hipStream_t>(stream), L);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -808,226 +808,315 @@ static int check_loop_desc(const mpcx_lmpc_loop_desc *d)
     return MPCX_OK;
 }
 
-// what an observer must satisfy, likewise without a look at the owner's state; bank: its controllers differ, one gain cannot serve them all
-static int check_observer_desc(const mpcx_lmpc_observer_desc *o, bool bank)
-{
-    if (!o) return fail(MPCX_E_INVALID, "null observer: an observed loop needs an mpcx_lmpc_observer_desc");
-    if (o->gain && o->gain_batch) return fail(MPCX_E_INVALID, "gain (one gain for the batch) and gain_batch (a gain per instance) exclude each other");
-    if (bank && o->gain) return fail(MPCX_E_INVALID, "a bank's controllers differ: its observed loop takes gain_batch, not gain");
-    if (!o->gain && !o->gain_batch) return fail(MPCX_E_INVALID, "an observer needs gain or gain_batch");
-    return MPCX_OK;
-}
+// "one for the batch (a host array) or one per instance (a device array)": what every observer and target descriptor must satisfy, likewise
+// without a look at the owner's state.  bank: its controllers differ, one for the batch cannot serve them all
+struct PerInstanceNouns {
+    const char *what, *loop, *type;              // "null <what>: <loop> needs an <type>"
+    const char *one;                             // the field with one for the batch; <one>_batch has one per instance
+    const char *its_loop, *needs;                // "... <its_loop> takes <one>_batch, not <one>", "<needs> <one> or <one>_batch"
+};
+static const PerInstanceNouns kObserverNouns = {"observer", "an observed loop", "mpcx_lmpc_observer_desc", "gain", "its observed loop", "an observer needs"};
+static const PerInstanceNouns kDisturbanceObserverNouns = {"observer", "an offset-free loop", "mpcx_lmpc_disturbance_observer_desc", "gain", "its offset-free loop",
+                                                           "a disturbance observer needs"};
+static const PerInstanceNouns kTargetNouns = {"target", "a loop with steady-state targets", "mpcx_lmpc_target_desc", "map", "its loop", "steady-state targets need"};
 
-// ... and a disturbance observer, likewise
-static int check_disturbance_observer_desc(const mpcx_lmpc_disturbance_observer_desc *o, bool bank)
+static int check_one_or_per_instance(const void *desc, const void *one, const void *per_instance, bool bank, const PerInstanceNouns &n)
 {
-    if (!o) return fail(MPCX_E_INVALID, "null observer: an offset-free loop needs an mpcx_lmpc_disturbance_observer_desc");
-    if (o->gain && o->gain_batch) return fail(MPCX_E_INVALID, "gain (one gain for the batch) and gain_batch (a gain per instance) exclude each other");
-    if (bank && o->gain) return fail(MPCX_E_INVALID, "a bank's controllers differ: its offset-free loop takes gain_batch, not gain");
-    if (!o->gain && !o->gain_batch) return fail(MPCX_E_INVALID, "a disturbance observer needs gain or gain_batch");
-    return MPCX_OK;
-}
-// ... and the targets of an offset-free loop, likewise
-static int check_target_desc(const mpcx_lmpc_target_desc *t, bool bank)
-{
-    if (!t) return fail(MPCX_E_INVALID, "null target: a loop with steady-state targets needs an mpcx_lmpc_target_desc");
-    if (t->map && t->map_batch) return fail(MPCX_E_INVALID, "map (one map for the batch) and map_batch (a map per instance) exclude each other");
-    if (bank && t->map) return fail(MPCX_E_INVALID, "a bank's controllers differ: its loop takes map_batch, not map");
-    if (!t->map && !t->map_batch) return fail(MPCX_E_INVALID, "steady-state targets need map or map_batch");
-    return MPCX_OK;
-}
-// ... and the owner's dimensions (not its state): without exogenous inputs there is no disturbance model
-static int check_disturbance_dims(const mpcx_dims &dm)
-{
-    if (dm.ndu == 0) return fail(MPCX_E_INVALID, "ndu = 0: the controller has no disturbance model (Bd, Dd) to estimate a disturbance with");
+    const std::string o = n.one, ob = o + "_batch";
+    if (!desc) return fail(MPCX_E_INVALID, std::string("null ") + n.what + ": " + n.loop + " needs an " + n.type);
+    if (one && per_instance) return fail(MPCX_E_INVALID, o + " (one " + o + " for the batch) and " + ob + " (a " + o + " per instance) exclude each other");
+    if (bank && one) return fail(MPCX_E_INVALID, std::string("a bank's controllers differ: ") + n.its_loop + " takes " + ob + ", not " + o);
+    if (!one && !per_instance) return fail(MPCX_E_INVALID, std::string(n.needs) + " " + o + " or " + ob);
     return MPCX_OK;
 }
 
 // what kind of loop an entry makes
 enum class LoopKind { Plain, Observed, OffsetFree, OffsetFreeTarget };
 
-// The loop of a controller (h) or of a bank (f, model_index), once the descriptor and the owner's state have been checked and the owner is set
-// up on the current device.  dm, active_words: the owner's.  o: the observer of an observed loop (checked), or null; od: the disturbance observer of
-// an offset-free loop (checked), or null -- such a loop is an observed loop with the fields the two descriptors share, and what differs asks for od.
-// td: the targets of an offset-free loop (checked; od is then not null), or null.
-static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words,
-                      const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const mpcx_lmpc_disturbance_observer_desc *od,
-                      const mpcx_lmpc_target_desc *td, hipStream_t s, mpcx_lmpc_loop_t *out)
+// the six fields the two observer descriptors share
+struct ObserverView {
+    const double *gain, *gain_batch, *xhat0, *meas_noise;
+    double *traj_xhat, *traj_y;
+};
+extern "C++" template <typename Desc> static ObserverView observer_view(const Desc *o) { return {o->gain, o->gain_batch, o->xhat0, o->meas_noise, o->traj_xhat, o->traj_y}; }
+
+// What an entry was given.  o: the observer of an observed loop; od: the disturbance observer of an offset-free loop; td: its targets; each null
+// where the kind has none.
+struct LoopRequest {
+    LoopKind kind;
+    const mpcx_lmpc_loop_desc *d;
+    const mpcx_lmpc_observer_desc *o;
+    const mpcx_lmpc_disturbance_observer_desc *od;
+    const mpcx_lmpc_target_desc *td;
+    void *stream;
+    mpcx_lmpc_loop_t *out;
+    bool offset_free() const { return kind == LoopKind::OffsetFree || kind == LoopKind::OffsetFreeTarget; }
+    bool targets() const { return kind == LoopKind::OffsetFreeTarget; }
+};
+
+// What all eight entries refuse before they look at the owner's state, in this order: the loop descriptor, the observer and target descriptors, the
+// owner's dimensions (dm; without exogenous inputs there is no disturbance model).  The owner itself is the caller's to check, ahead of this.
+static int check_loop_request(const LoopRequest &r, bool bank, const mpcx_dims &dm)
 {
-    mpcx_lmpc_observer_desc shared_fields{};
-    if (od) {
-        shared_fields.gain = od->gain; shared_fields.gain_batch = od->gain_batch; shared_fields.xhat0 = od->xhat0; shared_fields.meas_noise = od->meas_noise;
-        shared_fields.traj_xhat = od->traj_xhat; shared_fields.traj_y = od->traj_y;
-        o = &shared_fields;
-    }
-    const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
-    const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode};
-    const int ref_n[4] = {dm.ny, dm.nu, dm.nu, dm.ndu};
-    std::unique_ptr<mpcx_lmpc_loop> l(new mpcx_lmpc_loop);
-    l->owner = h; l->bank = f; l->model_index = model_index; l->ticks = d->ticks;
-    if (h) { l->device = h->device; l->setups = h->n_full_setups; } else l->device = f->device;
-    mpcx::LmpcLoopDev &L = l->L;
-    const size_t B = (size_t)d->batch, aw = (size_t)active_words;
-    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = (int)aw; L.ny = dm.ny; L.dobs = od ? 1 : 0; L.tgt = td ? 1 : 0;
-    mpcx::lmpc_loop_plan_lds(L);
-    // which plant: one per instance (the caller's array; in a bank also the default, each instance's own controller), or one for the batch
-    const bool uniform = d->plant_A || d->plant_B || d->plant_Bd;
-    const bool packed = d->plant_batch || (f && !uniform);
-    const bool own_d = f && dm.ndu > 0 && d->dmeas_mode == MPCX_REF_SHARED;      // a bank's "shared" exogenous input: each controller's own
+    if (!r.d || !r.out) return fail(MPCX_E_INVALID, "null argument");
+    int rc = check_loop_desc(r.d);
+    if (rc == MPCX_OK && r.kind == LoopKind::Observed) rc = check_one_or_per_instance(r.o, r.o ? r.o->gain : nullptr, r.o ? r.o->gain_batch : nullptr, bank, kObserverNouns);
+    if (rc == MPCX_OK && r.offset_free())
+        rc = check_one_or_per_instance(r.od, r.od ? r.od->gain : nullptr, r.od ? r.od->gain_batch : nullptr, bank, kDisturbanceObserverNouns);
+    if (rc == MPCX_OK && r.targets()) rc = check_one_or_per_instance(r.td, r.td ? r.td->map : nullptr, r.td ? r.td->map_batch : nullptr, bank, kTargetNouns);
+    if (rc == MPCX_OK && r.offset_free() && dm.ndu == 0)
+        rc = fail(MPCX_E_INVALID, "ndu = 0: the controller has no disturbance model (Bd, Dd) to estimate a disturbance with");
+    return rc;
+}
 
-    // the slab: offsets first, pointers once it is allocated
+// Where step 0 of tick k's reference lies in an array of the given mode, n values a step: value(b, k, a) = src[b * bs + k * tick + a]
+struct RefLayout { long bs, tick; };
+static RefLayout ref_layout(int mode, long n, int ph, int ticks)
+{
+    switch (mode) {
+    case MPCX_REF_SHARED: return {0, 0};
+    case MPCX_REF_PER_INSTANCE: return {n, 0};
+    case MPCX_REF_PER_STEP: return {ph * n, 0};
+    default: return {(ticks + ph) * n, n};       // MPCX_REF_PREVIEW
+    }
+}
+
+// The loop's private buffers, one allocation.  loop_slab runs twice over the same statements -- once without a base to size the slab, once with it to
+// hand out the pointers -- so a buffer is named in one place.
+extern "C++" struct LoopSlab {
+    char *base = nullptr;
     size_t total = 0;
-    auto take = [&](size_t bytes) { const size_t at = total; total = (total + bytes + 255) / 256 * 256; return at; };
-    const size_t plant_len = (size_t)dm.nx * (dm.nx + dm.nu + dm.ndu);
-    const size_t o_plant = take(plant_len * sizeof(double)), o_x = take(B * dm.nx * sizeof(double)), o_u = take(B * dm.nu * sizeof(double));
-    const size_t o_cmd = take(B * dm.nu * sizeof(double)), o_cost = take(B * sizeof(double)), o_int = take(6 * B * sizeof(int32_t));
-    const size_t o_act = take(4 * B * aw * sizeof(uint32_t)), o_state = take(2 * sizeof(int));
-    size_t o_pv[4] = {0, 0, 0, 0};
+    template <typename T> T *take(size_t count)
+    {
+        const size_t at = total;
+        total = (total + count * sizeof(T) + 255) / 256 * 256;
+        return base ? reinterpret_cast<T *>(base + at) : nullptr;
+    }
+};
+
+// What loop_build decides before it allocates anything
+struct LoopPlan {
+    mpcx_lmpc_t h;                               // the controller of a controller's loop; null: a bank's
+    mpcx_dims dm;
+    const mpcx_lmpc_loop_desc *d;
+    bool observed, offset_free, targets;
+    ObserverView o;                              // (observed)
+    const mpcx_lmpc_disturbance_observer_desc *od;
+    const mpcx_lmpc_target_desc *td;
+    const double *ref_p[4]; int ref_m[4], ref_n[4];   // yref, uref, duref, dmeas: array, mode, values a step
+    bool packed;                                 // a plant per instance: the caller's array; in a bank also the default, each instance's own controller
+    bool own_d;                                  // a bank's "shared" exogenous input: each controller's own
+    bool preview(int a) const                    // a preview array the solve sees through a staging window (dhat and us replace two of them)
+    {
+        return ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0 && !(offset_free && a == 3) && !(targets && a == 1);
+    }
+};
+
+// the solve's buffers, which the loop reads (LmpcLoopDev has them const) and the step descriptor writes
+struct LoopResults { double *cmd, *cost; int32_t *ints; uint32_t *sets; double *plant, *gain, *map; };
+
+static void loop_slab(const LoopPlan &p, LoopSlab &s, mpcx::LmpcLoopDev &L, LoopResults &r)
+{
+    const mpcx_dims &dm = p.dm;
+    const size_t B = (size_t)L.batch, aw = (size_t)L.aw;
+    auto block = [&](mpcx::LoopBlock b) { return s.take<double>(mpcx::lmpc_loop_block_len(L, b)); };
+    r.plant = s.take<double>((size_t)dm.nx * (dm.nx + dm.nu + dm.ndu));
+    L.x = s.take<double>(B * dm.nx);
+    L.u = s.take<double>(B * dm.nu);
+    r.cmd = s.take<double>(B * dm.nu);
+    r.cost = s.take<double>(B);
+    r.ints = s.take<int32_t>(6 * B);             // status, solver status, feasibility, iterations, polish rounds, active count
+    r.sets = s.take<uint32_t>(4 * B * aw);       // active lower and upper, warm lower and upper
+    L.state = s.take<int>(2);
     for (int a = 0; a < 4; ++a)
-        if (ref_m[a] == MPCX_REF_PREVIEW && ref_n[a] > 0 && !(od && a == 3) && !(td && a == 1)) o_pv[a] = take(B * dm.ph * ref_n[a] * sizeof(double));
-    const size_t o_pk = packed ? take(mpcx::lmpc_loop_packed_len(L) * sizeof(double)) : 0;
-    const size_t o_down = own_d ? take(B * dm.ndu * sizeof(double)) : 0;
-    // an observed loop: the true state, and the packed blocks -- one tile where a block is the same for every instance (one plant for the batch; a
-    // controller's own model, with one gain; a controller's own outputs), else a tile per ipw instances
-    const size_t tiles = (B + L.ipw - 1) / L.ipw;
-    const bool est_shared = o && h && o->gain, meas_shared = o && h;
-    size_t o_xt = 0, o_ok = 0, o_ek = 0, o_mk = 0, o_gain = 0, o_dhat = 0, o_dk = 0, o_us = 0, o_tk = 0, o_map = 0;
-    const size_t map_len = (size_t)dm.nu * (dm.ny + dm.ndu + dm.nu);
-    const size_t gain_len = (size_t)(dm.nx + (od ? dm.ndu : 0)) * dm.ny;
-    if (o) {
-        o_xt = take(B * dm.nx * sizeof(double));
-        if (!packed) o_ok = take(mpcx::lmpc_loop_block_len(L, 0, 1) * sizeof(double));
-        o_ek = take(mpcx::lmpc_loop_block_len(L, 1, est_shared ? 1 : tiles) * sizeof(double));
-        o_mk = take(mpcx::lmpc_loop_block_len(L, 2, meas_shared ? 1 : tiles) * sizeof(double));
-        if (o->gain) o_gain = take(gain_len * sizeof(double));
+        if (p.preview(a)) L.pv_dst[a] = s.take<double>(B * dm.ph * p.ref_n[a]);
+    if (p.packed) L.pk = L.ok = block(mpcx::kPlantBlock);
+    if (p.own_d) L.d_own = s.take<double>(B * dm.ndu);
+    if (p.observed) {
+        L.xt = s.take<double>(B * dm.nx);
+        if (!p.packed) L.ok = block(mpcx::kPlantBlock);      // (one plant for the batch: one tile)
+        L.ek = block(mpcx::kEstimatorBlock);
+        L.mk = block(mpcx::kMeasurementBlock);
+        if (p.o.gain) r.gain = s.take<double>((size_t)(dm.nx + (p.offset_free ? dm.ndu : 0)) * dm.ny);
     }
-    if (od) {                                    // the estimate the solve reads, and Ld beside the estimator block, shared where that is
-        o_dhat = take(B * dm.ndu * sizeof(double));
-        o_dk = take(mpcx::lmpc_loop_block_len(L, 3, est_shared ? 1 : tiles) * sizeof(double));
+    if (p.offset_free) {                         // the estimate the solve reads, and Ld
+        L.dhat = s.take<double>(B * dm.ndu);
+        L.dk = block(mpcx::kDisturbanceGainBlock);
     }
-    if (td) {                                    // the input reference the solve reads, and T: one tile where it is one map for the batch
-        o_us = take(B * dm.nu * sizeof(double));
-        o_tk = take(mpcx::lmpc_loop_block_len(L, 4, td->map ? 1 : tiles) * sizeof(double));
-        if (td->map) o_map = take(map_len * sizeof(double));
+    if (p.targets) {                             // the input reference the solve reads, and T
+        L.us = s.take<double>(B * dm.nu);
+        L.tk = block(mpcx::kTargetMapBlock);
+        if (p.td->map) r.map = s.take<double>((size_t)dm.nu * (dm.ny + dm.ndu + dm.nu));
     }
-    if (hipMalloc(reinterpret_cast<void **>(&l->slab), total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
-    if (hipMemset(l->slab, 0, total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
-    char *base = l->slab;
-    auto dp = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+}
 
-    if (packed) {
-        L.pk = dp(o_pk); L.pk_src = d->plant_batch;
-    } else {   // the one plant, row-major per matrix (the setters' and the descriptor's matrices are column-major)
-        const double *Ah = d->plant_A, *Bh = d->plant_B, *Dh = d->plant_Bd;
-        if (h) {
-            const auto &c = h->ctl;
-            if (!Ah) Ah = c.A.a.data();
-            if (!Bh) Bh = c.B.a.data();
-            if (!Dh) Dh = c.Bd.a.data();
-        }
-        std::vector<double> P(plant_len ? plant_len : 1);
-        double *pa = P.data(), *pb = pa + (size_t)dm.nx * dm.nx, *pd = pb + (size_t)dm.nx * dm.nu;
-        for (int i = 0; i < dm.nx; ++i) {
-            for (int j = 0; j < dm.nx; ++j) pa[(size_t)i * dm.nx + j] = Ah[(size_t)j * dm.nx + i];
-            for (int j = 0; j < dm.nu; ++j) pb[(size_t)i * dm.nu + j] = Bh[(size_t)j * dm.nx + i];
-            for (int j = 0; j < dm.ndu; ++j) pd[(size_t)i * dm.ndu + j] = Dh[(size_t)j * dm.nx + i];
-        }
-        if (hipMemcpy(base + o_plant, P.data(), plant_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the plant failed");
+// the one plant for the batch, row-major per matrix (the setters' and the descriptor's matrices are column-major), to the device
+static int upload_plant(const LoopPlan &p, double *plant_d)
+{
+    const mpcx_dims &dm = p.dm;
+    const double *Ah = p.d->plant_A, *Bh = p.d->plant_B, *Dh = p.d->plant_Bd;
+    if (p.h) {                                   // what the descriptor leaves out is the controller's own
+        const auto &c = p.h->ctl;
+        if (!Ah) Ah = c.A.a.data();
+        if (!Bh) Bh = c.B.a.data();
+        if (!Dh) Dh = c.Bd.a.data();
     }
-    if (f) { L.models = f->models_d; L.model_index = model_index; }
-    L.plant = dp(o_plant); L.x0 = d->x0; L.u0 = d->u0; L.x = dp(o_x); L.u = dp(o_u);
-    L.noise = d->noise;
-    int32_t *ib = reinterpret_cast<int32_t *>(base + o_int);
-    uint32_t *ab = reinterpret_cast<uint32_t *>(base + o_act);
-    L.cmd = dp(o_cmd); L.cost = dp(o_cost);
-    L.status = ib; L.solver_status = ib + B; L.iterations = ib + 3 * B; L.polish_rounds = ib + 4 * B; L.active_count = ib + 5 * B;
-    L.active_lower = ab; L.active_upper = ab + B * aw;
-    if (d->carry_working_set) { L.warm_lower = ab + 2 * B * aw; L.warm_upper = ab + 3 * B * aw; }
-    L.traj_x = d->traj_x; L.traj_u = d->traj_u; L.traj_cost = d->traj_cost;
-    L.traj_status = d->traj_status; L.traj_solver_status = d->traj_solver_status; L.traj_iterations = d->traj_iterations;
-    L.traj_polish_rounds = d->traj_polish_rounds; L.traj_active_count = d->traj_active_count;
-    L.state = reinterpret_cast<int *>(base + o_state);
-    if (o) {
-        L.xt = dp(o_xt);
-        if (packed) { L.ok = L.pk; L.ok_ts = (long)mpcx::lmpc_loop_block_len(L, 0, 1); } else L.ok = dp(o_ok);
-        L.ek = dp(o_ek); L.ek_ts = est_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 1, 1);
-        L.mk = dp(o_mk); L.mk_ts = meas_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 2, 1);
-        if (h) { L.mA = h->dev.A; L.mB = h->dev.B; L.mBd = h->dev.Bd; L.mC = h->dev.C; L.mDd = h->dev.Dd; }
-        if (o->gain) {
-            if (hipMemcpy(base + o_gain, o->gain, gain_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the observer gain failed");
-            L.gain = dp(o_gain);
-        }
-        L.gain_batch = o->gain_batch; L.xhat0 = o->xhat0; L.meas_noise = o->meas_noise; L.traj_xhat = o->traj_xhat; L.traj_y = o->traj_y;
+    const size_t plant_len = (size_t)dm.nx * (dm.nx + dm.nu + dm.ndu);
+    std::vector<double> P(plant_len ? plant_len : 1);
+    double *pa = P.data(), *pb = pa + (size_t)dm.nx * dm.nx, *pd = pb + (size_t)dm.nx * dm.nu;
+    for (int i = 0; i < dm.nx; ++i) {
+        for (int j = 0; j < dm.nx; ++j) pa[(size_t)i * dm.nx + j] = Ah[(size_t)j * dm.nx + i];
+        for (int j = 0; j < dm.nu; ++j) pb[(size_t)i * dm.nu + j] = Bh[(size_t)j * dm.nx + i];
+        for (int j = 0; j < dm.ndu; ++j) pd[(size_t)i * dm.ndu + j] = Dh[(size_t)j * dm.nx + i];
     }
-    if (od) {
-        L.dhat = dp(o_dhat); L.dk = dp(o_dk); L.dk_ts = est_shared ? 0 : (long)mpcx::lmpc_loop_block_len(L, 3, 1);
-        L.dhat0 = od->dhat0; L.traj_dhat = od->traj_dhat;
-    }
-    if (td) {
-        L.us = dp(o_us); L.tk = dp(o_tk); L.tk_ts = td->map ? 0 : (long)mpcx::lmpc_loop_block_len(L, 4, 1);
-        if (td->map) {
-            if (hipMemcpy(base + o_map, td->map, map_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the target map failed");
-            L.tmap = dp(o_map);
-        }
-        L.tmap_batch = td->map_batch; L.traj_us = td->traj_us;
-        // r_k and ubar_k: step 0 of the tick's yref and uref in whichever layout they have; "shared" is the controller's own (a bank: a null source,
-        // each instance's controller)
-        auto source = [&](int a, const double *own, const double *&src, long &bs, long &tick) {
-            const long n = ref_n[a];
-            switch (ref_m[a]) {
-            case MPCX_REF_SHARED: src = own; bs = 0; tick = 0; break;
-            case MPCX_REF_PER_INSTANCE: src = ref_p[a]; bs = n; tick = 0; break;
-            case MPCX_REF_PER_STEP: src = ref_p[a]; bs = (long)dm.ph * n; tick = 0; break;
-            default: src = ref_p[a]; bs = (long)(d->ticks + dm.ph) * n; tick = n; break;
-            }
-        };
-        source(0, h ? h->dev.yref_s : nullptr, L.r_src, L.r_bs, L.r_tick);
-        source(1, h ? h->dev.uref_s : nullptr, L.ub_src, L.ub_bs, L.ub_tick);
-    }
+    if (hipMemcpy(plant_d, P.data(), plant_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the plant failed");
+    return MPCX_OK;
+}
 
-    // the step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step; an
-    // offset-free loop's exogenous input is the loop's own estimate (the descriptor's drives the plant alone: no window)
+// an observed loop's model, gain and logs; an offset-free loop's on top
+static int wire_observer(const LoopPlan &p, mpcx::LmpcLoopDev &L, const LoopResults &r)
+{
+    const mpcx_dims &dm = p.dm;
+    if (p.h) { L.mA = p.h->dev.A; L.mB = p.h->dev.B; L.mBd = p.h->dev.Bd; L.mC = p.h->dev.C; L.mDd = p.h->dev.Dd; }
+    if (p.o.gain) {
+        const size_t gain_len = (size_t)(dm.nx + (p.offset_free ? dm.ndu : 0)) * dm.ny;
+        if (hipMemcpy(r.gain, p.o.gain, gain_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the observer gain failed");
+        L.gain = r.gain;
+    }
+    L.gain_batch = p.o.gain_batch; L.xhat0 = p.o.xhat0; L.meas_noise = p.o.meas_noise; L.traj_xhat = p.o.traj_xhat; L.traj_y = p.o.traj_y;
+    if (p.offset_free) { L.dhat0 = p.od->dhat0; L.traj_dhat = p.od->traj_dhat; }
+    return MPCX_OK;
+}
+
+// the map, and r_k and ubar_k: step 0 of the tick's yref and uref in whichever layout they have; "shared" is the controller's own (a bank: a null
+// source, each instance's controller)
+static int wire_targets(const LoopPlan &p, mpcx::LmpcLoopDev &L, const LoopResults &r)
+{
+    const mpcx_dims &dm = p.dm;
+    if (p.td->map) {
+        const size_t map_len = (size_t)dm.nu * (dm.ny + dm.ndu + dm.nu);
+        if (hipMemcpy(r.map, p.td->map, map_len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MPCX_E_DEVICE, "upload of the target map failed");
+        L.tmap = r.map;
+    }
+    L.tmap_batch = p.td->map_batch; L.traj_us = p.td->traj_us;
+    const RefLayout yl = ref_layout(p.ref_m[0], dm.ny, dm.ph, L.ticks), ul = ref_layout(p.ref_m[1], dm.nu, dm.ph, L.ticks);
+    L.r_src = p.ref_m[0] == MPCX_REF_SHARED ? (p.h ? p.h->dev.yref_s : nullptr) : p.ref_p[0]; L.r_bs = yl.bs; L.r_tick = yl.tick;
+    L.ub_src = p.ref_m[1] == MPCX_REF_SHARED ? (p.h ? p.h->dev.uref_s : nullptr) : p.ref_p[1]; L.ub_bs = ul.bs; L.ub_tick = ul.tick;
+    return MPCX_OK;
+}
+
+// The step's descriptor: the loop's own state, input and result buffers; a preview array is seen through its staging window, per step; an
+// offset-free loop's exogenous input is the loop's own estimate and a loop with targets' input reference its own us (the descriptor's dmeas drives the
+// plant alone and its uref is ubar, read by the loop's kernels: no windows)
+static mpcx_lmpc_batch step_descriptor(const LoopPlan &p, mpcx::LmpcLoopDev &L, const LoopResults &r)
+{
+    const size_t B = (size_t)L.batch, aw = (size_t)L.aw;
     mpcx_lmpc_batch cold{};
-    cold.batch = d->batch; cold.x0 = L.x; cold.u0 = L.u;
+    cold.batch = L.batch; cold.x0 = L.x; cold.u0 = L.u;
     const double *sp[4]; int sm[4];
     for (int a = 0; a < 4; ++a) {
-        sp[a] = ref_p[a]; sm[a] = ref_m[a];
-        if (od && a == 3) { sp[a] = L.dhat; sm[a] = MPCX_REF_PER_INSTANCE; continue; }
-        if (td && a == 1) { sp[a] = L.us; sm[a] = MPCX_REF_PER_INSTANCE; continue; }      // (the descriptor's uref is ubar, read by the loop's kernels: no window)
-        if (ref_m[a] != MPCX_REF_PREVIEW) continue;
-        if (ref_n[a] == 0) { sp[a] = nullptr; sm[a] = MPCX_REF_SHARED; continue; }      // (no exogenous inputs: nothing to preview)
-        L.pv_src[a] = ref_p[a]; L.pv_dst[a] = dp(o_pv[a]); L.pv_n[a] = ref_n[a];
+        sp[a] = p.ref_p[a]; sm[a] = p.ref_m[a];
+        if (p.offset_free && a == 3) { sp[a] = L.dhat; sm[a] = MPCX_REF_PER_INSTANCE; continue; }
+        if (p.targets && a == 1) { sp[a] = L.us; sm[a] = MPCX_REF_PER_INSTANCE; continue; }
+        if (p.ref_m[a] != MPCX_REF_PREVIEW) continue;
+        if (p.ref_n[a] == 0) { sp[a] = nullptr; sm[a] = MPCX_REF_SHARED; continue; }      // (no exogenous inputs: nothing to preview)
+        L.pv_src[a] = p.ref_p[a]; L.pv_n[a] = p.ref_n[a];
         sp[a] = L.pv_dst[a]; sm[a] = MPCX_REF_PER_STEP;
     }
     cold.yref = sp[0]; cold.yref_mode = sm[0]; cold.uref = sp[1]; cold.uref_mode = sm[1];
     cold.duref = sp[2]; cold.duref_mode = sm[2]; cold.dmeas = sp[3]; cold.dmeas_mode = sm[3];
-    cold.cmd = dp(o_cmd); cold.cost = dp(o_cost);
-    cold.status = ib; cold.solver_status = ib + B; cold.is_feasible = ib + 2 * B; cold.iterations = ib + 3 * B;
-    cold.polish_rounds = ib + 4 * B; cold.active_count = ib + 5 * B;
-    if (d->carry_working_set) { cold.active_lower = ab; cold.active_upper = ab + B * aw; }
+    cold.cmd = r.cmd; cold.cost = r.cost;
+    cold.status = r.ints; cold.solver_status = r.ints + B; cold.is_feasible = r.ints + 2 * B; cold.iterations = r.ints + 3 * B;
+    cold.polish_rounds = r.ints + 4 * B; cold.active_count = r.ints + 5 * B;
+    if (p.d->carry_working_set) { cold.active_lower = r.sets; cold.active_upper = r.sets + B * aw; }
+    return cold;
+}
+
+// The loop of a controller (h) or of a bank (f, model_index), once the request and the owner's state have been checked and the owner is set up on
+// the current device.  dm, active_words: the owner's.
+static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_index, const mpcx_dims &dm, int active_words, const LoopRequest &rq)
+{
+    const mpcx_lmpc_loop_desc *d = rq.d;
+    hipStream_t s = reinterpret_cast<hipStream_t>(rq.stream);
+    std::unique_ptr<mpcx_lmpc_loop> l(new mpcx_lmpc_loop);
+    l->owner = h; l->bank = f; l->model_index = model_index; l->ticks = d->ticks;
+    if (h) { l->device = h->device; l->setups = h->n_full_setups; } else l->device = f->device;
+    mpcx::LmpcLoopDev &L = l->L;
+
+    // the plan: what kind of loop, which plant, which blocks differ from instance to instance
+    LoopPlan p{};
+    p.h = h; p.dm = dm; p.d = d;
+    p.observed = rq.kind != LoopKind::Plain; p.offset_free = rq.offset_free(); p.targets = rq.targets();
+    if (p.observed) p.o = p.offset_free ? observer_view(rq.od) : observer_view(rq.o);
+    p.od = rq.od; p.td = rq.td;
+    const double *const ref_p[4] = {d->yref, d->uref, d->duref, d->dmeas};
+    const int ref_m[4] = {d->yref_mode, d->uref_mode, d->duref_mode, d->dmeas_mode}, ref_n[4] = {dm.ny, dm.nu, dm.nu, dm.ndu};
+    for (int a = 0; a < 4; ++a) { p.ref_p[a] = ref_p[a]; p.ref_m[a] = ref_m[a]; p.ref_n[a] = ref_n[a]; }
+    const bool uniform = d->plant_A || d->plant_B || d->plant_Bd;
+    p.packed = d->plant_batch || (f && !uniform);
+    p.own_d = f && dm.ndu > 0 && d->dmeas_mode == MPCX_REF_SHARED;
+    L.batch = d->batch; L.ticks = d->ticks; L.nx = dm.nx; L.nu = dm.nu; L.ndu = dm.ndu; L.ph = dm.ph; L.aw = active_words; L.ny = dm.ny;
+    L.dobs = p.offset_free ? 1 : 0; L.tgt = p.targets ? 1 : 0;
+    mpcx::lmpc_loop_plan_lds(L);
+    // a block is one tile (stride 0) where it is the same for every instance: one plant for the batch; a controller's own model with one gain (the
+    // estimator and Ld); a controller's own outputs (the measurement); one map for the batch (T).  Else a tile per ipw instances
+    auto stride = [&](mpcx::LoopBlock b, bool one_tile) { return one_tile ? 0L : (long)mpcx::lmpc_loop_tile_len(L, b); };
+    const bool one_gain = h && p.observed && p.o.gain;
+    L.ok_ts = stride(mpcx::kPlantBlock, !p.packed);
+    L.ek_ts = stride(mpcx::kEstimatorBlock, one_gain);
+    L.mk_ts = stride(mpcx::kMeasurementBlock, h != nullptr);
+    L.dk_ts = stride(mpcx::kDisturbanceGainBlock, one_gain);
+    L.tk_ts = stride(mpcx::kTargetMapBlock, p.targets && rq.td->map);
+
+    // the slab: sized, allocated, handed out
+    LoopSlab slab;
+    LoopResults r{};
+    loop_slab(p, slab, L, r);
+    if (hipMalloc(reinterpret_cast<void **>(&l->slab), slab.total) != hipSuccess) { l->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the loop's buffers failed"); }
+    if (hipMemset(l->slab, 0, slab.total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
+    slab.base = l->slab; slab.total = 0;
+    loop_slab(p, slab, L, r);
+
+    // the plant, the owner's models, the caller's arrays and logs
+    const size_t B = (size_t)d->batch, aw = (size_t)active_words;
+    int rc = MPCX_OK;
+    if (p.packed) L.pk_src = d->plant_batch;
+    else rc = upload_plant(p, r.plant);
+    if (rc != MPCX_OK) return rc;
+    if (f) { L.models = f->models_d; L.model_index = model_index; }
+    L.plant = r.plant; L.x0 = d->x0; L.u0 = d->u0; L.noise = d->noise;
+    L.cmd = r.cmd; L.cost = r.cost;
+    L.status = r.ints; L.solver_status = r.ints + B; L.iterations = r.ints + 3 * B; L.polish_rounds = r.ints + 4 * B; L.active_count = r.ints + 5 * B;
+    L.active_lower = r.sets; L.active_upper = r.sets + B * aw;
+    if (d->carry_working_set) { L.warm_lower = r.sets + 2 * B * aw; L.warm_upper = r.sets + 3 * B * aw; }
+    L.traj_x = d->traj_x; L.traj_u = d->traj_u; L.traj_cost = d->traj_cost;
+    L.traj_status = d->traj_status; L.traj_solver_status = d->traj_solver_status; L.traj_iterations = d->traj_iterations;
+    L.traj_polish_rounds = d->traj_polish_rounds; L.traj_active_count = d->traj_active_count;
+    if (p.observed) rc = wire_observer(p, L, r);
+    if (rc == MPCX_OK && p.targets) rc = wire_targets(p, L, r);
+    if (rc != MPCX_OK) return rc;
+
+    // the step's descriptors: tick 0 solves cold, the later ticks with the carried working sets
+    const mpcx_lmpc_batch cold = step_descriptor(p, L, r);
     mpcx_lmpc_batch warm = cold;
     warm.warm_active_lower = L.warm_lower; warm.warm_active_upper = L.warm_upper; warm.warm_shift = 1;
     const bool two = d->carry_working_set && d->ticks > 1;
 
-    // d_k, the sample that drives the plant: step 0 of the tick's exogenous input in whichever layout it has
+    // d_k, the sample that drives the plant: step 0 of the tick's exogenous input in whichever layout it has; a bank's "shared" is the per-instance
+    // array the pack kernel fills
     if (dm.ndu > 0) {
-        switch (d->dmeas_mode) {
-        case MPCX_REF_SHARED:
-            if (own_d) { L.d_own = dp(o_down); L.dmeas = L.d_own; L.d_bs = dm.ndu; }
-            else L.dmeas = h->dev.dmeas_s;
-            break;
-        case MPCX_REF_PER_INSTANCE: L.dmeas = d->dmeas; L.d_bs = dm.ndu; break;
-        case MPCX_REF_PER_STEP: L.dmeas = d->dmeas; L.d_bs = (long)dm.ph * dm.ndu; break;
-        default: L.dmeas = d->dmeas; L.d_bs = (long)(d->ticks + dm.ph) * dm.ndu; L.d_tick = dm.ndu; break;
-        }
+        const RefLayout dl = ref_layout(p.own_d ? MPCX_REF_PER_INSTANCE : d->dmeas_mode, dm.ndu, dm.ph, d->ticks);
+        L.dmeas = p.own_d ? L.d_own : d->dmeas_mode == MPCX_REF_SHARED ? h->dev.dmeas_s : d->dmeas;
+        L.d_bs = dl.bs; L.d_tick = dl.tick;
     }
 
+    // one plain pass first, as mpcx_lmpc_graph_create does: it sizes the workspace and configures the kernels, none of which can be captured; then
+    // the capture
     const int pr = mpcx::lmpc_loop_prepare(L);
     if (pr != 0) return pr == -2 ? fail(MPCX_E_UNSUPPORTED, "the advance kernel's tiles exceed a compute unit's LDS") : fail(MPCX_E_DEVICE, "hipFuncSetAttribute failed");
-    // one plain pass first, as mpcx_lmpc_graph_create does: it sizes the workspace and configures the kernels, none of which can be captured
     if (mpcx::lmpc_loop_begin(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
     if (mpcx::lmpc_loop_pack_plants(L, s) != 0 || mpcx::lmpc_loop_pack_observer(L, s) != 0) return fail(MPCX_E_DEVICE, "launch of the pack kernel failed");
-    int rc = l->solve(&cold, s);
+    rc = l->solve(&cold, s);
     if (rc == MPCX_OK && mpcx::lmpc_loop_advance(L, s) != 0) rc = fail(MPCX_E_DEVICE, "launch of the advance kernel failed");
     if (rc == MPCX_OK && two) rc = l->solve(&warm, s);
     if (rc != MPCX_OK) return rc;
@@ -1035,98 +1124,83 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
     rc = capture_tick(*l, &cold, s, &l->first);
     if (rc == MPCX_OK && two) rc = capture_tick(*l, &warm, s, &l->next);
     if (rc != MPCX_OK) return rc;
-    *out = l.release();
+    *rq.out = l.release();
     return MPCX_OK;
 }
 
-// mpcx_lmpc_loop_create (neither o nor od is looked at), mpcx_lmpc_loop_create_observed (o), mpcx_lmpc_loop_create_offset_free (od) and
-// mpcx_lmpc_loop_create_offset_free_target (od and td)
-static int lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, LoopKind kind, const mpcx_lmpc_observer_desc *o,
-                            const mpcx_lmpc_disturbance_observer_desc *od, const mpcx_lmpc_target_desc *td, void *stream, mpcx_lmpc_loop_t *out)
+// a controller's loop: its model must be set, it must live on a device, and it is set up before the loop is built
+static int lmpc_loop_create(mpcx_lmpc_t h, const LoopRequest &r)
 {
     CHECK_H(h);
-    if (!d || !out) return fail(MPCX_E_INVALID, "null argument");
-    const bool targets = kind == LoopKind::OffsetFreeTarget, offset_free = targets || kind == LoopKind::OffsetFree;
-    int rc = check_loop_desc(d);
-    if (rc == MPCX_OK && kind == LoopKind::Observed) rc = check_observer_desc(o, false);
-    if (rc == MPCX_OK && offset_free) rc = check_disturbance_observer_desc(od, false);
-    if (rc == MPCX_OK && targets) rc = check_target_desc(td, false);
-    if (rc == MPCX_OK && offset_free) rc = check_disturbance_dims(h->ctl.d);
+    int rc = check_loop_request(r, false, h->ctl.d);
     if (rc != MPCX_OK) return rc;
     if (!h->ctl.have_model) return fail(MPCX_E_STATE, "state-space model not set");
     if (h->host_only) return fail(MPCX_E_STATE, "host-only handle: a loop runs on a HIP device");
-    if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
+    if (!r.stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
     rc = mpcx_lmpc_setup(h);
     if (rc != MPCX_OK) return rc;
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, d, kind == LoopKind::Observed ? o : nullptr, offset_free ? od : nullptr,
-                      targets ? td : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+    return loop_build(h, nullptr, nullptr, h->ctl.d, h->dev.active_words, r);
+}
+
+// a bank's loop (the bank is followed only behind a good descriptor)
+static int hetero_loop_create(mpcx_lmpc_hetero_t f, const int32_t *model_index, const LoopRequest &r)
+{
+    if (!f) return fail(MPCX_E_INVALID, "null argument");
+    const int rc = check_loop_request(r, true, f->d);
+    if (rc != MPCX_OK) return rc;
+    const mpcx_lmpc_loop_desc *d = r.d;
+    if (!model_index && d->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
+    // a bank keeps no host copy of its controllers' models: there is no "the controller's own" to complete a one-for-all plant with
+    if ((d->plant_A || d->plant_B || d->plant_Bd) && (!d->plant_A || !d->plant_B || (f->d.ndu > 0 && !d->plant_Bd)))
+        return fail(MPCX_E_INVALID, "a bank's loop takes plant_A, plant_B and plant_Bd together (or plant_batch, or none: each instance's own controller)");
+    if (!r.stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    return loop_build(nullptr, f, model_index, f->d, f->active_words, r);
 }
 
 int mpcx_lmpc_loop_create(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::Plain, nullptr, nullptr, nullptr, stream, out);
+    return lmpc_loop_create(h, {LoopKind::Plain, d, nullptr, nullptr, nullptr, stream, out});
 }
 
 int mpcx_lmpc_loop_create_observed(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::Observed, o, nullptr, nullptr, stream, out);
+    return lmpc_loop_create(h, {LoopKind::Observed, d, o, nullptr, nullptr, stream, out});
 }
 
 int mpcx_lmpc_loop_create_offset_free(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::OffsetFree, nullptr, o, nullptr, stream, out);
+    return lmpc_loop_create(h, {LoopKind::OffsetFree, d, nullptr, o, nullptr, stream, out});
 }
 
 int mpcx_lmpc_loop_create_offset_free_target(mpcx_lmpc_t h, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
                                              const mpcx_lmpc_target_desc *t, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return lmpc_loop_create(h, d, LoopKind::OffsetFreeTarget, nullptr, o, t, stream, out);
-}
-
-static int hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, LoopKind kind, const mpcx_lmpc_observer_desc *o,
-                              const mpcx_lmpc_disturbance_observer_desc *od, const mpcx_lmpc_target_desc *td, const int32_t *model_index, void *stream,
-                              mpcx_lmpc_loop_t *out)
-{
-    if (!f || !d || !out) return fail(MPCX_E_INVALID, "null argument");
-    const bool targets = kind == LoopKind::OffsetFreeTarget, offset_free = targets || kind == LoopKind::OffsetFree;
-    int rc = check_loop_desc(d);
-    if (rc == MPCX_OK && kind == LoopKind::Observed) rc = check_observer_desc(o, true);
-    if (rc == MPCX_OK && offset_free) rc = check_disturbance_observer_desc(od, true);
-    if (rc == MPCX_OK && targets) rc = check_target_desc(td, true);
-    if (rc == MPCX_OK && offset_free) rc = check_disturbance_dims(f->d);      // (the bank is followed only behind a good descriptor)
-    if (rc != MPCX_OK) return rc;
-    if (!model_index && d->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
-    // a bank keeps no host copy of its controllers' models: there is no "the controller's own" to complete a one-for-all plant with
-    if ((d->plant_A || d->plant_B || d->plant_Bd) && (!d->plant_A || !d->plant_B || (f->d.ndu > 0 && !d->plant_Bd)))
-        return fail(MPCX_E_INVALID, "a bank's loop takes plant_A, plant_B and plant_Bd together (or plant_batch, or none: each instance's own controller)");
-    if (!stream) return fail(MPCX_E_INVALID, "a loop is captured on a non-default stream");
-    if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
-    return loop_build(nullptr, f, model_index, f->d, f->active_words, d, kind == LoopKind::Observed ? o : nullptr, offset_free ? od : nullptr,
-                      targets ? td : nullptr, reinterpret_cast<hipStream_t>(stream), out);
+    return lmpc_loop_create(h, {LoopKind::OffsetFreeTarget, d, nullptr, o, t, stream, out});
 }
 
 int mpcx_lmpc_hetero_loop_create(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::Plain, nullptr, nullptr, nullptr, model_index, stream, out);
+    return hetero_loop_create(f, model_index, {LoopKind::Plain, d, nullptr, nullptr, nullptr, stream, out});
 }
 
 int mpcx_lmpc_hetero_loop_create_observed(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_observer_desc *o, const int32_t *model_index,
                                           void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::Observed, o, nullptr, nullptr, model_index, stream, out);
+    return hetero_loop_create(f, model_index, {LoopKind::Observed, d, o, nullptr, nullptr, stream, out});
 }
 
 int mpcx_lmpc_hetero_loop_create_offset_free(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
                                              const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::OffsetFree, nullptr, o, nullptr, model_index, stream, out);
+    return hetero_loop_create(f, model_index, {LoopKind::OffsetFree, d, nullptr, o, nullptr, stream, out});
 }
 
 int mpcx_lmpc_hetero_loop_create_offset_free_target(mpcx_lmpc_hetero_t f, const mpcx_lmpc_loop_desc *d, const mpcx_lmpc_disturbance_observer_desc *o,
                                                     const mpcx_lmpc_target_desc *t, const int32_t *model_index, void *stream, mpcx_lmpc_loop_t *out)
 {
-    return hetero_loop_create(f, d, LoopKind::OffsetFreeTarget, nullptr, o, t, model_index, stream, out);
+    return hetero_loop_create(f, model_index, {LoopKind::OffsetFreeTarget, d, nullptr, o, t, stream, out});
 }
 
 // Steady-state target maps and the product with them (include/mpcx.h; kernels in target_kernels.hip, declared in lmpc_device.hpp)

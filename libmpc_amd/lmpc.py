@@ -181,7 +181,256 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class LMPC:
+def _shape(a):
+    return tuple((a if hasattr(a, "shape") else np.asarray(a)).shape)
+
+
+class _LoopFrontEnd:
+    """What LMPC and LMPCHetero share: device tensors for a descriptor, and the closed loop on the device (mpcx_lmpc_loop_*,
+    mpcx_lmpc_hetero_loop_*).  The class that inherits it has nx, nu, ndu, ny, ph, device, _lib, _h and _own_plant."""
+
+    def _torch(self):
+        import torch
+        if self.device < 0 or not torch.cuda.is_available():
+            raise MpcxError(_capi.E_DEVICE, "optimize needs an MI355X: libmpc_amd has no CPU solve path")
+        return torch, torch.device("cuda", self.device)
+
+    def _dev(self, torch, dev, a, shape):
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def _ref(self, torch, dev, a, B, n):
+        """classify a per-solve reference: None -> shared, [B,n] -> per instance, [B,ph,n] -> per step"""
+        if a is None:
+            return None, _capi.REF_SHARED
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(t.shape) == (B, n):
+            return t, _capi.REF_PER_INSTANCE
+        if tuple(t.shape) == (B, self.ph, n):
+            return t, _capi.REF_PER_STEP
+        raise ValueError(f"reference must be [B,{n}] or [B,{self.ph},{n}], got {tuple(t.shape)}")
+
+    def _loop_ref(self, torch, dev, a, B, n, ticks, preview):
+        """a loop's reference: None -> shared; [B,n] -> per instance; [B,ph,n] -> per step, the same at every tick; with
+        preview=True a 3-D array is [B, ticks+ph, n] and tick k sees rows k .. k+ph-1"""
+        if a is None:
+            return None, _capi.REF_SHARED
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(t.shape) == (B, n):
+            return t, _capi.REF_PER_INSTANCE
+        if preview and tuple(t.shape) == (B, ticks + self.ph, n):
+            return t, _capi.REF_PREVIEW
+        if not preview and tuple(t.shape) == (B, self.ph, n):
+            return t, _capi.REF_PER_STEP
+        want = f"[B,{ticks + self.ph},{n}] (preview)" if preview else f"[B,{self.ph},{n}]"
+        raise ValueError(f"reference must be [B,{n}] or {want}, got {tuple(t.shape)}")
+
+    def _check_plants(self, B, plant, plants):
+        """plants= as a triple (A [B,nx,nx], B [B,nx,nu] | None, Bd [B,nx,ndu] | None), its shapes checked -- on the host, ahead of any device call"""
+        if plant is not None and plants is not None:
+            raise ValueError("plant= (one plant for the batch) and plants= (a plant per instance) exclude each other")
+        if plants is None:
+            return None
+        plants = tuple(plants)
+        if not 1 <= len(plants) <= 3:
+            raise ValueError("plants is (A, B, Bd), the trailing entries optional")
+        plants += (None,) * (3 - len(plants))
+        for name, m, cols in zip(("A", "B", "Bd"), plants, (self.nx, self.nu, self.ndu)):
+            if m is not None and _shape(m) != (B, self.nx, cols):
+                raise ValueError(f"plants: {name} must be [{B},{self.nx},{cols}], got {_shape(m)}")
+        return plants
+
+    def _check_gain(self, name, gain, rows, B, ticks, xhat0, dhat0, meas_noise, bank):
+        """observer= or disturbance_observer= (`name`: [rows, ny] one gain, [B, rows, ny] a gain per instance), xhat0=, dhat0= and meas_noise=, their
+        shapes checked -- on the host, ahead of any device call; True for a gain per instance"""
+        sh = _shape(gain)
+        if sh not in ((rows, self.ny), (B, rows, self.ny)):
+            raise ValueError(f"{name} must be [{rows},{self.ny}] or [{B},{rows},{self.ny}], got {sh}")
+        if bank and len(sh) == 2:
+            raise ValueError(f"a bank's controllers differ: {name} must be a gain per instance, [{B},{rows},{self.ny}]")
+        for what, a, want in (("xhat0", xhat0, (B, self.nx)), ("dhat0", dhat0, (B, self.ndu)), ("meas_noise", meas_noise, (ticks, B, self.ny))):
+            if a is not None and _shape(a) != want:
+                raise ValueError(f"{what} must be [{','.join(map(str, want))}], got {_shape(a)}")
+        return len(sh) == 3
+
+    def _check_observers(self, B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank=False):
+        """the checks of observer= ([nx, ny] or [B, nx, ny]) or of disturbance_observer= ([nx+ndu, ny] or [B, nx+ndu, ny]; the two exclude each
+        other), whichever is given: (offset-free?, a gain per instance?)"""
+        if disturbance_observer is None and dhat0 is not None:
+            raise ValueError("dhat0= belongs to an offset-free loop: give disturbance_observer=")
+        if disturbance_observer is not None:
+            if observer is not None:
+                raise ValueError("observer= (a state observer) and disturbance_observer= (its offset-free form) exclude each other")
+            if self.ndu == 0:
+                raise ValueError("disturbance_observer= needs a controller with exogenous inputs (ndu > 0) and a disturbance model (setDisturbances)")
+            return True, self._check_gain("disturbance_observer", disturbance_observer, self.nx + self.ndu, B, ticks, xhat0, dhat0, meas_noise, bank)
+        if observer is None:
+            if xhat0 is not None or meas_noise is not None:
+                raise ValueError("xhat0= and meas_noise= belong to an observed loop: give observer=")
+            return False, False
+        return False, self._check_gain("observer", observer, self.nx, B, ticks, xhat0, None, meas_noise, bank)
+
+    def _check_target(self, B, target, disturbance_observer, bank=False):
+        """target= ([nu, ny+ndu+nu] one map, [B, nu, ny+ndu+nu] a map per instance): True for a map per instance"""
+        if target is None:
+            return False
+        if disturbance_observer is None:
+            raise ValueError("target= (steady-state targets) needs disturbance_observer=: the targets are computed from its disturbance estimate")
+        sh = _shape(target)
+        n = self.ny + self.ndu + self.nu
+        if sh not in ((self.nu, n), (B, self.nu, n)):
+            raise ValueError(f"target must be [{self.nu},{n}] or [{B},{self.nu},{n}], got {sh}")
+        if bank and len(sh) == 2:
+            raise ValueError(f"a bank's controllers differ: target must be a map per instance, [{B},{self.nu},{n}]")
+        return len(sh) == 3
+
+    @staticmethod
+    def pack_gains(L):
+        """[B, nx ny]: per instance L_b column-major -- mpcx_lmpc_observer_desc.gain_batch; a torch tensor [B, nx, ny] in, a tensor out
+        (what to copy_ into Loop.gains for the next run)"""
+        return L.transpose(1, 2).reshape(L.shape[0], L.shape[1] * L.shape[2]).contiguous()
+
+    _loop_entry = "mpcx_lmpc_loop_create"        # (LMPCHetero: mpcx_lmpc_hetero_loop_create)
+
+    def _create_loop(self, d, od, offset_free, td, bank, model, stream, out):
+        """the one of the library's entries that makes this loop: by owner (a controller, or a bank, whose entries also take the model index)
+        and by what the loop has -- no observer, an observer (od an ObserverDesc), a disturbance observer (od a DisturbanceObserverDesc),
+        targets on top (td)"""
+        kind = "" if od is None else "_offset_free_target" if td is not None else "_offset_free" if offset_free else "_observed"
+        descs = tuple(C.byref(a) for a in (d, od, td) if a is not None)
+        index = (None if model is None else C.c_void_p(model.data_ptr()),) if bank else ()
+        return getattr(self._lib, self._loop_entry + kind)(self._h, *descs, *index, stream, out)
+
+    @staticmethod
+    def pack_plants(A, B, Bd):
+        """[B, nx (nx+nu+ndu)]: per instance A_b | B_b | Bd_b, each column-major -- mpcx_lmpc_loop_desc.plant_batch; torch tensors in, a tensor out
+        (what to copy_ into Loop.plants for the next run)"""
+        import torch
+        n = A.shape[0]
+        return torch.cat([m.transpose(1, 2).reshape(n, m.shape[1] * m.shape[2]) for m in (A, B, Bd)], dim=1).contiguous()
+
+    def _make_loop(self, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None,
+                   observer=None, xhat0=None, meas_noise=None, bank=False, disturbance_observer=None, dhat0=None, checked=None, target=None):
+        """the descriptor of a loop, its result tensors and the create call; model: a bank's model index (a device tensor) or None; checked:
+        what _check_observers returned where the caller has run it already"""
+        ticks = int(ticks)
+        B = int(_shape(x0)[0])
+        plants = self._check_plants(B, plant, plants)
+        offset_free, per_instance_gain = checked or self._check_observers(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
+        per_instance_map = self._check_target(B, target, disturbance_observer, bank)
+        torch, dev = self._torch()
+        x0 = self._dev(torch, dev, x0, (B, self.nx))
+        u0 = self._dev(torch, dev, lastU, (B, self.nu))
+        refs = [self._loop_ref(torch, dev, a, B, n, ticks, preview)
+                for a, n in ((yref, self.ny), (uref, self.nu), (duref, self.nu), (dmeas, self.ndu))]
+        w = self._dev(torch, dev, noise, (ticks, B, self.nx))
+        f64, i32 = torch.float64, torch.int32
+        T = max(ticks, 0)
+        res = ClosedLoopResult(
+            x=torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev), u=torch.zeros((T, B, self.nu), dtype=f64, device=dev),
+            cost=torch.zeros((T, B), dtype=f64, device=dev), status=torch.zeros((T, B), dtype=i32, device=dev),
+            solver_status=torch.zeros((T, B), dtype=i32, device=dev), iterations=torch.zeros((T, B), dtype=i32, device=dev),
+            polish_rounds=torch.zeros((T, B), dtype=i32, device=dev), active_count=torch.zeros((T, B), dtype=i32, device=dev))
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        d = _capi.LoopDesc()
+        d.batch, d.ticks = B, ticks
+        mats, pb = [], None
+        if plant is not None:
+            plant = tuple(plant) + (None,) * (3 - len(plant))
+            for name, m, cols in zip(("plant_A", "plant_B", "plant_Bd"), plant, (self.nx, self.nu, self.ndu)):
+                if m is not None and cols > 0:
+                    mats.append(_cm(m, self.nx, cols))
+                    setattr(d, name, mats[-1].ctypes.data)
+        if plants is not None:
+            own = self._own_plant(B, model) if any(m is None for m in plants) else (None,) * 3
+            full = [self._dev(torch, dev, m if isinstance(m, torch.Tensor) else np.array(o if m is None else m, dtype=np.float64), (B, self.nx, cols))
+                    for m, o, cols in zip(plants, own, (self.nx, self.nu, self.ndu))]
+            pb = self.pack_plants(*full)
+            d.plant_batch = ptr(pb)
+        d.x0, d.u0 = ptr(x0), ptr(u0)
+        (yr, d.yref_mode), (ur, d.uref_mode), (dr, d.duref_mode), (de, d.dmeas_mode) = refs
+        d.yref, d.uref, d.duref, d.dmeas = ptr(yr), ptr(ur), ptr(dr), ptr(de)
+        d.noise = ptr(w)
+        d.carry_working_set = int(bool(warm))
+        d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
+        d.traj_status, d.traj_solver_status, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.iterations)
+        d.traj_polish_rounds, d.traj_active_count = ptr(res.polish_rounds), ptr(res.active_count)
+        od, gains, gain_h, xh, v, dh = None, None, None, None, None, None
+        if offset_free:
+            observer = disturbance_observer
+        if observer is not None:
+            od = _capi.DisturbanceObserverDesc() if offset_free else _capi.ObserverDesc()
+            rows = self.nx + (self.ndu if offset_free else 0)
+            if per_instance_gain:
+                # not through _dev: its .contiguous() would copy what utils.kalman_gains / disturbance_gains return -- a view of this very
+                # layout, which pack_gains then takes as it is (Loop.gains is in that case the caller's own tensor); the shape has been checked
+                g = observer if isinstance(observer, torch.Tensor) else torch.as_tensor(np.asarray(observer, dtype=np.float64))
+                gains = self.pack_gains(g.to(device=dev, dtype=torch.float64))
+                od.gain_batch = ptr(gains)
+            else:
+                gain_h = _cm(observer.cpu().numpy() if isinstance(observer, torch.Tensor) else observer, rows, self.ny)
+                od.gain = gain_h.ctypes.data
+            xh = self._dev(torch, dev, xhat0, (B, self.nx))
+            v = self._dev(torch, dev, meas_noise, (ticks, B, self.ny))
+            res.xhat = torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev)
+            res.y = torch.zeros((T, B, self.ny), dtype=f64, device=dev)
+            od.xhat0, od.meas_noise, od.traj_xhat, od.traj_y = ptr(xh), ptr(v), ptr(res.xhat), ptr(res.y)
+            if offset_free:
+                dh = self._dev(torch, dev, dhat0, (B, self.ndu))
+                res.dhat = torch.zeros((T + 1, B, self.ndu), dtype=f64, device=dev)
+                od.dhat0, od.traj_dhat = ptr(dh), ptr(res.dhat)
+        td, maps, map_h = None, None, None
+        if target is not None:
+            td = _capi.TargetDesc()
+            if per_instance_map:                # (not through _dev, as the gains: utils.target_maps' view is this very layout)
+                t = target if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target, dtype=np.float64))
+                maps = self.pack_gains(t.to(device=dev, dtype=torch.float64))
+                td.map_batch = ptr(maps)
+            else:
+                map_h = _cm(target.cpu().numpy() if isinstance(target, torch.Tensor) else target, self.nu, self.ny + self.ndu + self.nu)
+                td.map = map_h.ctypes.data
+            res.us = torch.zeros((T + 1, B, self.nu), dtype=f64, device=dev)
+            td.traj_us = ptr(res.us)
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else torch.cuda.Stream(device=dev)
+        if s.cuda_stream == 0:
+            raise ValueError("a loop is captured on a non-default stream")
+        s.wait_stream(cur)                      # the tensors above were filled on the current stream
+        h = C.c_void_p()
+        check(self._create_loop(d, od, offset_free, td, bank, model, C.c_void_p(s.cuda_stream), C.byref(h)))
+        cur.wait_stream(s)
+        # keep: what the graph points at; [0], [1]: x0 and lastU as every run reads them
+        return Loop(handle=h, result=res, ticks=ticks, keep=(x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v, dh, maps), plants=pb, gains=gains,
+                    xhat0=xh, meas_noise=v, dhat0=dh, maps=maps)
+
+    def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
+        """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
+        uses the controller's one workspace, like `launch`: one launch or run of a controller in flight at a time."""
+        torch, _ = self._torch()
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+        check(self._lib.mpcx_lmpc_loop_run(loop.handle, C.c_void_p(s.cuda_stream)))
+        return loop.result
+
+    def destroy_loop(self, loop: Loop):
+        if loop.handle:
+            check(self._lib.mpcx_lmpc_loop_destroy(loop.handle))
+            loop.handle = None
+
+
+class LMPC(_LoopFrontEnd):
     """Linear MPC controller whose optimize() runs on an MI355X.
 
     Mirrors mpc::LMPC<Tnx,Tnu,Tndu,Tny,Tph,Tch> with run-time sizes
@@ -357,33 +606,6 @@ class LMPC:
         forms only on request)"""
         check(self._lib.mpcx_lmpc_debug_use_fused(self._h, -1 if on is None else int(on)))
 
-    def _torch(self):
-        import torch
-        if self.device < 0 or not torch.cuda.is_available():
-            raise MpcxError(_capi.E_DEVICE, "optimize needs an MI355X: libmpc_amd has no CPU solve path")
-        return torch, torch.device("cuda", self.device)
-
-    def _dev(self, torch, dev, a, shape):
-        if a is None:
-            return None
-        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
-        t = t.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
-        return t
-
-    def _ref(self, torch, dev, a, B, n):
-        """classify a per-solve reference: None -> shared, [B,n] -> per instance, [B,ph,n] -> per step"""
-        if a is None:
-            return None, _capi.REF_SHARED
-        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
-        t = t.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(t.shape) == (B, n):
-            return t, _capi.REF_PER_INSTANCE
-        if tuple(t.shape) == (B, self.ph, n):
-            return t, _capi.REF_PER_STEP
-        raise ValueError(f"reference must be [B,{n}] or [B,{self.ph},{n}], got {tuple(t.shape)}")
-
     def make_batch(self, x0, u0, yref=None, uref=None, duref=None, dmeas=None,
                    want_active=False, want_sequence=False, warm=None, warm_shift=False):
         """Allocate outputs and fill the mpcx_lmpc_batch descriptor.  Returns (Batch, BatchResult, keepalive)."""
@@ -476,104 +698,6 @@ class LMPC:
     def destroy_graph(self, graph):
         check(self._lib.mpcx_lmpc_graph_destroy(graph))
 
-    # -- the closed loop on the device (mpcx_lmpc_loop_*) ----------------------------------------------------------------
-    def _loop_ref(self, torch, dev, a, B, n, ticks, preview):
-        """a loop's reference: None -> shared; [B,n] -> per instance; [B,ph,n] -> per step, the same at every tick; with
-        preview=True a 3-D array is [B, ticks+ph, n] and tick k sees rows k .. k+ph-1"""
-        if a is None:
-            return None, _capi.REF_SHARED
-        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
-        t = t.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(t.shape) == (B, n):
-            return t, _capi.REF_PER_INSTANCE
-        if preview and tuple(t.shape) == (B, ticks + self.ph, n):
-            return t, _capi.REF_PREVIEW
-        if not preview and tuple(t.shape) == (B, self.ph, n):
-            return t, _capi.REF_PER_STEP
-        want = f"[B,{ticks + self.ph},{n}] (preview)" if preview else f"[B,{self.ph},{n}]"
-        raise ValueError(f"reference must be [B,{n}] or {want}, got {tuple(t.shape)}")
-
-    def _check_plants(self, B, plant, plants):
-        """plants= as a triple (A [B,nx,nx], B [B,nx,nu] | None, Bd [B,nx,ndu] | None), its shapes checked -- on the host, ahead of any device call"""
-        if plant is not None and plants is not None:
-            raise ValueError("plant= (one plant for the batch) and plants= (a plant per instance) exclude each other")
-        if plants is None:
-            return None
-        plants = tuple(plants)
-        if not 1 <= len(plants) <= 3:
-            raise ValueError("plants is (A, B, Bd), the trailing entries optional")
-        plants += (None,) * (3 - len(plants))
-        for name, m, cols in zip(("A", "B", "Bd"), plants, (self.nx, self.nu, self.ndu)):
-            if m is not None and tuple((m if hasattr(m, "shape") else np.asarray(m)).shape) != (B, self.nx, cols):
-                raise ValueError(f"plants: {name} must be [{B},{self.nx},{cols}], got {tuple(np.shape(m))}")
-        return plants
-
-    def _check_observer(self, B, ticks, observer, xhat0, meas_noise, bank=False):
-        """observer= ([nx, ny] one gain, [B, nx, ny] a gain per instance), xhat0= and meas_noise=, their shapes checked -- on the host, ahead of
-        any device call; True for a gain per instance"""
-        def shape(a):
-            return tuple((a if hasattr(a, "shape") else np.asarray(a)).shape)
-        if observer is None:
-            if xhat0 is not None or meas_noise is not None:
-                raise ValueError("xhat0= and meas_noise= belong to an observed loop: give observer=")
-            return False
-        sh = shape(observer)
-        if sh not in ((self.nx, self.ny), (B, self.nx, self.ny)):
-            raise ValueError(f"observer must be [{self.nx},{self.ny}] or [{B},{self.nx},{self.ny}], got {sh}")
-        if bank and len(sh) == 2:
-            raise ValueError(f"a bank's controllers differ: observer must be a gain per instance, [{B},{self.nx},{self.ny}]")
-        if xhat0 is not None and shape(xhat0) != (B, self.nx):
-            raise ValueError(f"xhat0 must be [{B},{self.nx}], got {shape(xhat0)}")
-        if meas_noise is not None and shape(meas_noise) != (ticks, B, self.ny):
-            raise ValueError(f"meas_noise must be [{ticks},{B},{self.ny}], got {shape(meas_noise)}")
-        return len(sh) == 3
-
-    def _check_disturbance_observer(self, B, ticks, observer, gain, xhat0, dhat0, meas_noise, bank=False):
-        """disturbance_observer= ([nx+ndu, ny] one gain, [B, nx+ndu, ny] a gain per instance), xhat0=, dhat0= and meas_noise=, checked like
-        observer=, with which it is exclusive; True for a gain per instance"""
-        def shape(a):
-            return tuple((a if hasattr(a, "shape") else np.asarray(a)).shape)
-        if gain is None:
-            if dhat0 is not None:
-                raise ValueError("dhat0= belongs to an offset-free loop: give disturbance_observer=")
-            return False
-        if observer is not None:
-            raise ValueError("observer= (a state observer) and disturbance_observer= (its offset-free form) exclude each other")
-        if self.ndu == 0:
-            raise ValueError("disturbance_observer= needs a controller with exogenous inputs (ndu > 0) and a disturbance model (setDisturbances)")
-        n, sh = self.nx + self.ndu, shape(gain)
-        if sh not in ((n, self.ny), (B, n, self.ny)):
-            raise ValueError(f"disturbance_observer must be [{n},{self.ny}] or [{B},{n},{self.ny}], got {sh}")
-        if bank and len(sh) == 2:
-            raise ValueError(f"a bank's controllers differ: disturbance_observer must be a gain per instance, [{B},{n},{self.ny}]")
-        if xhat0 is not None and shape(xhat0) != (B, self.nx):
-            raise ValueError(f"xhat0 must be [{B},{self.nx}], got {shape(xhat0)}")
-        if dhat0 is not None and shape(dhat0) != (B, self.ndu):
-            raise ValueError(f"dhat0 must be [{B},{self.ndu}], got {shape(dhat0)}")
-        if meas_noise is not None and shape(meas_noise) != (ticks, B, self.ny):
-            raise ValueError(f"meas_noise must be [{ticks},{B},{self.ny}], got {shape(meas_noise)}")
-        return len(sh) == 3
-
-    def _check_observers(self, B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank=False):
-        """the checks of observer= or of disturbance_observer=, whichever is given: (offset-free?, a gain per instance?)"""
-        if disturbance_observer is not None or dhat0 is not None:
-            return disturbance_observer is not None, self._check_disturbance_observer(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
-        return False, self._check_observer(B, ticks, observer, xhat0, meas_noise, bank)
-
-    def _check_target(self, B, target, disturbance_observer, bank=False):
-        """target= ([nu, ny+ndu+nu] one map, [B, nu, ny+ndu+nu] a map per instance): True for a map per instance"""
-        if target is None:
-            return False
-        if disturbance_observer is None:
-            raise ValueError("target= (steady-state targets) needs disturbance_observer=: the targets are computed from its disturbance estimate")
-        sh = tuple((target if hasattr(target, "shape") else np.asarray(target)).shape)
-        n = self.ny + self.ndu + self.nu
-        if sh not in ((self.nu, n), (B, self.nu, n)):
-            raise ValueError(f"target must be [{self.nu},{n}] or [{B},{self.nu},{n}], got {sh}")
-        if bank and len(sh) == 2:
-            raise ValueError(f"a bank's controllers differ: target must be a map per instance, [{B},{self.nu},{n}]")
-        return len(sh) == 3
-
     def target_map(self, want_x=False):
         """The steady-state target map [nu, ny+ndu+nu] = [Tr | Td | Tu] of the controller's own model and disturbance model: us = Tr r + Td dhat +
         Tu ubar is the input that holds the outputs on r against the disturbance dhat, as close to ubar as that allows -- what target= takes
@@ -588,12 +712,6 @@ class LMPC:
             raise MpcxError(_capi.E_NUMERIC, "the KKT system of the target is singular")
         maps = tuple(m[0].cpu().numpy().copy() for m in out[:-1])
         return maps if want_x else maps[0]
-
-    @staticmethod
-    def pack_gains(L):
-        """[B, nx ny]: per instance L_b column-major -- mpcx_lmpc_observer_desc.gain_batch; a torch tensor [B, nx, ny] in, a tensor out
-        (what to copy_ into Loop.gains for the next run)"""
-        return L.transpose(1, 2).reshape(L.shape[0], L.shape[1] * L.shape[2]).contiguous()
 
     def kalman_gain(self, Qw, Rv, want_P=False):
         """The steady-state Kalman predictor gain L [nx, ny] of the controller's own (A, C) for process-noise covariance Qw [nx, nx] and
@@ -628,111 +746,6 @@ class LMPC:
             raise MpcxError(_capi.E_STATE, "state-space model not set")
         return tuple(np.broadcast_to(m, (B,) + m.shape) for m in (self._A, self._B, self._Bd))
 
-    @staticmethod
-    def pack_plants(A, B, Bd):
-        """[B, nx (nx+nu+ndu)]: per instance A_b | B_b | Bd_b, each column-major -- mpcx_lmpc_loop_desc.plant_batch; torch tensors in, a tensor out
-        (what to copy_ into Loop.plants for the next run)"""
-        import torch
-        n = A.shape[0]
-        return torch.cat([m.transpose(1, 2).reshape(n, m.shape[1] * m.shape[2]) for m in (A, B, Bd)], dim=1).contiguous()
-
-    def _make_loop(self, create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream, model=None,
-                   observer=None, xhat0=None, meas_noise=None, bank=False, disturbance_observer=None, dhat0=None, checked=None, target=None):
-        """the descriptor of a loop, its result tensors and the create call: shared by LMPC and LMPCHetero (whose `create` takes the model index);
-        `create` is given the observer's descriptor (an ObserverDesc or a DisturbanceObserverDesc), or None for an unobserved loop, and the
-        TargetDesc of a loop with steady-state targets, or None; checked: what _check_observers returned where the caller has run it already"""
-        ticks = int(ticks)
-        x0t = x0 if hasattr(x0, "shape") else np.asarray(x0)
-        B = int(x0t.shape[0])
-        plants = self._check_plants(B, plant, plants)
-        offset_free, per_instance_gain = checked or self._check_observers(B, ticks, observer, disturbance_observer, xhat0, dhat0, meas_noise, bank)
-        per_instance_map = self._check_target(B, target, disturbance_observer, bank)
-        torch, dev = self._torch()
-        x0 = self._dev(torch, dev, x0, (B, self.nx))
-        u0 = self._dev(torch, dev, lastU, (B, self.nu))
-        refs = [self._loop_ref(torch, dev, a, B, n, ticks, preview)
-                for a, n in ((yref, self.ny), (uref, self.nu), (duref, self.nu), (dmeas, self.ndu))]
-        w = self._dev(torch, dev, noise, (ticks, B, self.nx))
-        f64, i32 = torch.float64, torch.int32
-        T = max(ticks, 0)
-        res = ClosedLoopResult(
-            x=torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev), u=torch.zeros((T, B, self.nu), dtype=f64, device=dev),
-            cost=torch.zeros((T, B), dtype=f64, device=dev), status=torch.zeros((T, B), dtype=i32, device=dev),
-            solver_status=torch.zeros((T, B), dtype=i32, device=dev), iterations=torch.zeros((T, B), dtype=i32, device=dev),
-            polish_rounds=torch.zeros((T, B), dtype=i32, device=dev), active_count=torch.zeros((T, B), dtype=i32, device=dev))
-
-        def ptr(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
-        d = _capi.LoopDesc()
-        d.batch, d.ticks = B, ticks
-        mats, pb = [], None
-        if plant is not None:
-            plant = tuple(plant) + (None,) * (3 - len(plant))
-            for name, m, cols in zip(("plant_A", "plant_B", "plant_Bd"), plant, (self.nx, self.nu, self.ndu)):
-                if m is not None and cols > 0:
-                    mats.append(_cm(m, self.nx, cols))
-                    setattr(d, name, mats[-1].ctypes.data)
-        if plants is not None:
-            own = self._own_plant(B, model) if any(m is None for m in plants) else (None,) * 3
-            full = [self._dev(torch, dev, m if isinstance(m, torch.Tensor) else np.array(o if m is None else m, dtype=np.float64), (B, self.nx, cols))
-                    for m, o, cols in zip(plants, own, (self.nx, self.nu, self.ndu))]
-            pb = self.pack_plants(*full)
-            d.plant_batch = ptr(pb)
-        d.x0, d.u0 = ptr(x0), ptr(u0)
-        (yr, d.yref_mode), (ur, d.uref_mode), (dr, d.duref_mode), (de, d.dmeas_mode) = refs
-        d.yref, d.uref, d.duref, d.dmeas = ptr(yr), ptr(ur), ptr(dr), ptr(de)
-        d.noise = ptr(w)
-        d.carry_working_set = int(bool(warm))
-        d.traj_x, d.traj_u, d.traj_cost = ptr(res.x), ptr(res.u), ptr(res.cost)
-        d.traj_status, d.traj_solver_status, d.traj_iterations = ptr(res.status), ptr(res.solver_status), ptr(res.iterations)
-        d.traj_polish_rounds, d.traj_active_count = ptr(res.polish_rounds), ptr(res.active_count)
-        od, gains, gain_h, xh, v, dh = None, None, None, None, None, None
-        if offset_free:
-            observer = disturbance_observer
-        if observer is not None:
-            od = _capi.DisturbanceObserverDesc() if offset_free else _capi.ObserverDesc()
-            rows = self.nx + (self.ndu if offset_free else 0)
-            if per_instance_gain:
-                # not through _dev: its .contiguous() would copy what utils.kalman_gains / disturbance_gains return -- a view of this very
-                # layout, which pack_gains then takes as it is (Loop.gains is in that case the caller's own tensor); the shape has been checked
-                g = observer if isinstance(observer, torch.Tensor) else torch.as_tensor(np.asarray(observer, dtype=np.float64))
-                gains = self.pack_gains(g.to(device=dev, dtype=torch.float64))
-                od.gain_batch = ptr(gains)
-            else:
-                gain_h = _cm(observer.cpu().numpy() if isinstance(observer, torch.Tensor) else observer, rows, self.ny)
-                od.gain = gain_h.ctypes.data
-            xh = self._dev(torch, dev, xhat0, (B, self.nx))
-            v = self._dev(torch, dev, meas_noise, (ticks, B, self.ny))
-            res.xhat = torch.zeros((T + 1, B, self.nx), dtype=f64, device=dev)
-            res.y = torch.zeros((T, B, self.ny), dtype=f64, device=dev)
-            od.xhat0, od.meas_noise, od.traj_xhat, od.traj_y = ptr(xh), ptr(v), ptr(res.xhat), ptr(res.y)
-            if offset_free:
-                dh = self._dev(torch, dev, dhat0, (B, self.ndu))
-                res.dhat = torch.zeros((T + 1, B, self.ndu), dtype=f64, device=dev)
-                od.dhat0, od.traj_dhat = ptr(dh), ptr(res.dhat)
-        td, maps, map_h = None, None, None
-        if target is not None:
-            td = _capi.TargetDesc()
-            if per_instance_map:                # (not through _dev, as the gains: utils.target_maps' view is this very layout)
-                t = target if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target, dtype=np.float64))
-                maps = self.pack_gains(t.to(device=dev, dtype=torch.float64))
-                td.map_batch = ptr(maps)
-            else:
-                map_h = _cm(target.cpu().numpy() if isinstance(target, torch.Tensor) else target, self.nu, self.ny + self.ndu + self.nu)
-                td.map = map_h.ctypes.data
-            res.us = torch.zeros((T + 1, B, self.nu), dtype=f64, device=dev)
-            td.traj_us = ptr(res.us)
-        cur = torch.cuda.current_stream(self.device)
-        s = stream if stream is not None else torch.cuda.Stream(device=dev)
-        if s.cuda_stream == 0:
-            raise ValueError("a loop is captured on a non-default stream")
-        s.wait_stream(cur)                      # the tensors above were filled on the current stream
-        h = C.c_void_p()
-        check(create(C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h), None if od is None else C.byref(od), None if td is None else C.byref(td)))
-        cur.wait_stream(s)
-        return Loop(h, res, ticks, (x0, u0, yr, ur, dr, de, w, s, pb, gains, xh, v, dh, maps), pb, gains, xh, v, dh, maps)
-
     def make_loop(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
                   noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,
                   disturbance_observer=None, dhat0=None, target=None) -> Loop:
@@ -764,33 +777,9 @@ class LMPC:
         computes us_k = T [r_k; dhat_k; ubar_k] -- r_k and ubar_k step 0 of the tick's yref and uref, in every layout they have -- and the
         solve reads us_k as its input reference, constant along the horizon: uref= is then ubar, what the input is held close to where the
         outputs leave it free.  yref reaches the solve unchanged.  us is not clipped to the input bounds (the result's us shows it)."""
-        def create(d, s, out, od, td=None):
-            if od is None:
-                return self._lib.mpcx_lmpc_loop_create(self._h, d, s, out)
-            if td is not None:
-                return self._lib.mpcx_lmpc_loop_create_offset_free_target(self._h, d, od, td, s, out)
-            if disturbance_observer is not None:
-                return self._lib.mpcx_lmpc_loop_create_offset_free(self._h, d, od, s, out)
-            return self._lib.mpcx_lmpc_loop_create_observed(self._h, d, od, s, out)
-        return self._make_loop(create, x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream,
+        return self._make_loop(x0, lastU, ticks, plant, plants, yref, uref, duref, dmeas, preview, noise, warm, stream,
                                observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0,
                                target=target)
-
-    def run_loop(self, loop: Loop, stream=None) -> ClosedLoopResult:
-        """One asynchronous run of a loop from its x0 / lastU tensors: `loop.result` is filled once the stream has been synchronised.  A loop
-        uses the controller's one workspace, like `launch`: one launch or run of a controller in flight at a time."""
-        torch, _ = self._torch()
-        cur = torch.cuda.current_stream(self.device)
-        s = stream if stream is not None else cur
-        if s.cuda_stream != cur.cuda_stream:
-            s.wait_stream(cur)
-        check(self._lib.mpcx_lmpc_loop_run(loop.handle, C.c_void_p(s.cuda_stream)))
-        return loop.result
-
-    def destroy_loop(self, loop: Loop):
-        if loop.handle:
-            check(self._lib.mpcx_lmpc_loop_destroy(loop.handle))
-            loop.handle = None
 
     def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
                  noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,

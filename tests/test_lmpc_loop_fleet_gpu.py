@@ -128,12 +128,28 @@ def test_identical_plants_equal_the_uniform_loop_bit_for_bit(name, B, noisy):
 # ---------------------------------------------------------------------------------------------
 # 2. a plant per instance
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(CONTROLLERS))
-def test_different_plants_per_instance(name):
+def _wide(nx):
+    """(nx, 2, 2, 3) with ph = 3, ch = 2: nx = 32, two instances fill the wavefront's 64 lanes exactly; nx = 64, every lane a state row"""
+    from libmpc_amd import LMPC
+    sp = random_lmpc_spec(3, nx=nx, nu=2, ndu=2, ny=3, ph=3, ch=2)
+
+    def inputs(B):
+        r = np.random.default_rng(B)
+        return (3.0 / nx) ** 0.5 * r.uniform(-0.5, 0.5, size=(B, nx)), r.uniform(-0.4, 0.4, size=(B, 2)), {}
+    return (lambda: configure_random(LMPC(*sp["dims"], device=0), sp)), inputs, (sp["A"], sp["B"], sp["Bd"], sp["dmeas"][:, 0])
+
+
+# the shapes of the uniform loop's tests at B = 100, and the two at the edge of the lane <-> (instance, row) mapping: two full tiles and a half, three tiles
+PLANT_CASES = [(name, 100) for name in sorted(CONTROLLERS)] + [("n32", 5), ("n64", 3)]
+PLANT_SHAPES = dict(CONTROLLERS, n32=lambda: _wide(32), n64=lambda: _wide(64))
+
+
+@pytest.mark.parametrize("name,B", PLANT_CASES, ids=sorted(CONTROLLERS) + ["n32-B5", "n64-B3"])
+def test_different_plants_per_instance(name, B):
     import torch
     from libmpc_amd import LMPC
-    make, inputs, (A, Bm, Bd, d0) = CONTROLLERS[name]()
-    B, ticks = 100, 5
+    make, inputs, (A, Bm, Bd, d0) = PLANT_SHAPES[name]()
+    ticks = 5
     x0, u0, refs = inputs(B)
     rng = np.random.default_rng(12)
     P1 = tuple(_scaled(m, B, rng) for m in (A, Bm, Bd))

@@ -8,7 +8,8 @@ of the CPU oracle's solves and that numpy tick for the tracking error, and the 6
 Shapes (nx, nu, ndu, ny): (1,1,1,1) at B = 1, 64, 65 -- a full tile of 64 instances and one over; (3,2,1,2) at B = 22 -- 21 per wavefront; (2,2,3,3)
 at B = 33 -- more rows of dhat than lanes of an instance, 32 per wavefront and one over; (5,2,2,2) at B = 13 -- 12 per wavefront, 4 idle lanes, two
 tiles; the quadrotor 12/4/4/12 with Bd = B, Dd = 0 at B = 6 -- 5 per wavefront; (33,2,2,3) with ph = 3, ch = 2 at B = 3 -- one instance per
-wavefront, a lane taking rows lane and lane + 64 (the controller's set-up accepts nx = 33)."""
+wavefront, 31 idle lanes; (32,2,2,3) at B = 5 -- two instances fill the 64 lanes exactly, two full tiles and a half; (64,2,2,3) at B = 3 -- every
+lane a state row, the largest nx a controller accepts."""
 import dataclasses
 import functools
 import os
@@ -64,8 +65,11 @@ SHAPES = {
     "n5": lambda: _random_of(nx=5, nu=2, ndu=2, ny=2),
     "quadrotor": _quadrotor,
     "n33": lambda: _random_of(nx=33, nu=2, ndu=2, ny=3, ph=3, ch=2),
+    "n32": lambda: _random_of(nx=32, nu=2, ndu=2, ny=3, ph=3, ch=2),
+    "n64": lambda: _random_of(nx=64, nu=2, ndu=2, ny=3, ph=3, ch=2),
 }
-CASES = [("n1", 1), ("n1", 64), ("n1", 65), ("n3", 22), ("n2_d3", 33), ("n5", 13), ("quadrotor", 6), ("n33", 3)]
+CASES = [("n1", 1), ("n1", 64), ("n1", 65), ("n3", 22), ("n2_d3", 33), ("n5", 13), ("quadrotor", 6), ("n33", 3), ("n32", 5), ("n64", 3)]
+SINGLE_STEP_B = {"quadrotor": 6, "n33": 6, "n32": 5, "n64": 3}      # (every other shape: 22)
 CASE_IDS = ["%s-B%d" % c for c in CASES]
 
 
@@ -160,12 +164,12 @@ def test_a_bank_without_disturbance_gains_is_its_observed_loop_bit_for_bit(warm)
 # 2. every tick against the single-step call on the logged estimates, bit for bit
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("warm", [False, True], ids=["cold", "warm"])
-@pytest.mark.parametrize("name", ["n1", "n3", "n2_d3", "n5", "quadrotor", "n33"])
+@pytest.mark.parametrize("name", ["n1", "n3", "n2_d3", "n5", "quadrotor", "n33", "n32", "n64"])
 def test_ticks_equal_the_single_step_call_on_the_estimates(name, warm):
     import torch
     make, inputs, model = SHAPES[name]()
     nx, ndu, ny = model[0].shape[0], model[2].shape[1], model[3].shape[0]
-    B, ticks = (6 if name in ("quadrotor", "n33") else 22), 7
+    B, ticks = SINGLE_STEP_B.get(name, 22), 7
     x0, u0, refs = inputs(B)
     dx, dh0, delta, v, w = _disturbed(nx, ndu, ny, B, ticks, 64)
     L = _host_gain(model)

@@ -10,7 +10,8 @@ single-step call on the logged estimates and input references (bit for bit); the
 Shapes (nx, nu, ndu, ny): (1,1,1,1) at B = 1, 64, 65 -- a full tile of 64 instances and one over; (3,2,1,2) at B = 22 -- 21 per wavefront; (2,3,2,2)
 at B = 33 -- more rows of us than lanes of an instance, 32 per wavefront and one over; (5,4,2,2) at B = 13 -- 12 per wavefront, 4 idle lanes, two
 tiles; the quadrotor with outputs (x, y, z, yaw), Bd = B, Dd = 0 at B = 6 -- 5 per wavefront; (33,3,2,3) with ph = 3, ch = 2 at B = 3 -- one
-instance per wavefront."""
+instance per wavefront; (32,3,2,3) at B = 5 -- two instances fill the 64 lanes exactly, two full tiles and a half; (64,3,2,3) at B = 3 -- every lane a
+state row."""
 import dataclasses
 
 import numpy as np
@@ -21,7 +22,7 @@ import target_ref as R
 from helpers import OracleFrontEnd
 from test_lmpc_loop_gpu import EQUAL, _follow, _np
 from test_lmpc_loop_fleet_gpu import _bank_case, _scaled
-from test_lmpc_offset_free_gpu import _bank_models, _configure_tracking, _disturbed, _host_gain, _random_of, _tracking_spec
+from test_lmpc_offset_free_gpu import SINGLE_STEP_B, _bank_models, _configure_tracking, _disturbed, _host_gain, _random_of, _tracking_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -44,8 +45,10 @@ SHAPES = {
     "n5": lambda: _random_of(nx=5, nu=4, ndu=2, ny=2),
     "quadrotor": _quadrotor,
     "n33": lambda: _random_of(nx=33, nu=3, ndu=2, ny=3, ph=3, ch=2),
+    "n32": lambda: _random_of(nx=32, nu=3, ndu=2, ny=3, ph=3, ch=2),
+    "n64": lambda: _random_of(nx=64, nu=3, ndu=2, ny=3, ph=3, ch=2),
 }
-CASES = [("n1", 1), ("n1", 64), ("n1", 65), ("n3", 22), ("n2_u3", 33), ("n5", 13), ("quadrotor", 6), ("n33", 3)]
+CASES = [("n1", 1), ("n1", 64), ("n1", 65), ("n3", 22), ("n2_u3", 33), ("n5", 13), ("quadrotor", 6), ("n33", 3), ("n32", 5), ("n64", 3)]
 CASE_IDS = ["%s-B%d" % c for c in CASES]
 
 
@@ -212,13 +215,13 @@ def _assert_us(res, T, r_of_tick, ubar_of_tick, label):
 
 
 @pytest.mark.parametrize("warm", [False, True], ids=["cold", "warm"])
-@pytest.mark.parametrize("name", ["n1", "n3", "n2_u3", "n5", "quadrotor", "n33"])
+@pytest.mark.parametrize("name", ["n1", "n3", "n2_u3", "n5", "quadrotor", "n33", "n32", "n64"])
 def test_ticks_equal_the_single_step_call_on_the_estimates_and_targets(name, warm):
     import torch
     from libmpc_amd.utils import target_maps
     make, inputs, model = SHAPES[name]()
     nx, nu, ndu, ny = _dims(model)
-    B, ticks = (6 if name in ("quadrotor", "n33") else 22), 7
+    B, ticks = SINGLE_STEP_B.get(name, 22), 7
     x0, u0, refs = inputs(B)
     dx, dh0, delta, v, w = _disturbed(nx, ndu, ny, B, ticks, 85)
     rng = np.random.default_rng(86)
