@@ -144,6 +144,14 @@ int mpcx_lmpc_set_input_bounds(mpcx_lmpc_t h, const double *umin, const double *
 int mpcx_lmpc_set_input_bounds_slice(mpcx_lmpc_t h, const double *umin, const double *umax, int start, int end);
 int mpcx_lmpc_set_output_bounds(mpcx_lmpc_t h, const double *ymin, const double *ymax);
 int mpcx_lmpc_set_output_bounds_slice(mpcx_lmpc_t h, const double *ymin, const double *ymax, int start, int end);
+/* Bounds on the input rate, dumin <= u_k - u_{k-1} <= dumax.  The reference's QP carries these rows -- ProblemBuilder.hpp:768-793
+ * builds ph*nu inequality rows on the delta-u variables, free (+-inf) for steps i <= ch and pinned to 0 behind the control
+ * horizon -- but the reference has no setter for them: this one goes beyond its surface and stays inside its QP.
+ * [nu x ph] column-major; column i bounds delta_i = v_{i+1} - v_i with v_0 = lastU (DeltaUWeight's indexing, no column shift).
+ * Columns i > ch are stored and not read (those moves stay pinned).  Default +-inf.  The slice form takes a prediction-horizon
+ * slice like the delta-u weight's.  MPCX_E_INVALID: null pointer, NaN, or dumin > dumax in a column <= ch. */
+int mpcx_lmpc_set_input_rate_bounds(mpcx_lmpc_t h, const double *dumin, const double *dumax);
+int mpcx_lmpc_set_input_rate_bounds_slice(mpcx_lmpc_t h, const double *dumin, const double *dumax, int start, int end);
 /* LMPC::setScalarConstraint slice form (LMPC.hpp:355) and index form (LMPC.hpp:409) */
 int mpcx_lmpc_set_scalar_constraint_slice(mpcx_lmpc_t h, double smin, double smax, const double *X, const double *U,
                                           int start, int end);

@@ -198,6 +198,13 @@ public:
     {
         return ok(mpcx_lmpc_set_output_bounds_slice(h_, lo.data(), hi.data(), s.start, s.end));
     }
+    // extension: bounds on the input rate u_k - u_{k-1}.  The reference's QP has the rows (ProblemBuilder.hpp:768-793) and no setter;
+    // column i bounds delta_i = v_{i+1} - v_i with v_0 = lastU, columns past the control horizon are kept and not read
+    bool setInputRateBounds(const mat<Tnu, Tph> &lo, const mat<Tnu, Tph> &hi) { return ok(mpcx_lmpc_set_input_rate_bounds(h_, lo.data(), hi.data())); }
+    bool setInputRateBounds(const cvec<Tnu> &lo, const cvec<Tnu> &hi, const HorizonSlice &s)
+    {
+        return ok(mpcx_lmpc_set_input_rate_bounds_slice(h_, lo.data(), hi.data(), s.start, s.end));
+    }
     bool setScalarConstraint(const double mn, const double mx, const cvec<Tnx> X, const cvec<Tnu> U, const HorizonSlice &s)   // LMPC.hpp:355
     {
         return ok(mpcx_lmpc_set_scalar_constraint_slice(h_, mn, mx, X.data(), U.data(), s.start, s.end));

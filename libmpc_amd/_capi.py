@@ -91,6 +91,7 @@ EXPORTS = [
     "mpcx_lmpc_set_state_bounds", "mpcx_lmpc_set_state_bounds_slice",
     "mpcx_lmpc_set_input_bounds", "mpcx_lmpc_set_input_bounds_slice",
     "mpcx_lmpc_set_output_bounds", "mpcx_lmpc_set_output_bounds_slice",
+    "mpcx_lmpc_set_input_rate_bounds", "mpcx_lmpc_set_input_rate_bounds_slice",
     "mpcx_lmpc_set_scalar_constraint_slice", "mpcx_lmpc_set_scalar_constraint_index",
     "mpcx_lmpc_set_references", "mpcx_lmpc_set_references_slice",
     "mpcx_lmpc_set_exogenous_inputs", "mpcx_lmpc_set_exogenous_inputs_slice",

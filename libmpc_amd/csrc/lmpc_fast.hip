@@ -841,7 +841,7 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
             if (!Bt.warm_shift) return rr;
             if (rr < b_out) return rr + na < b_out ? rr + na : rr;
             if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
-            if (rr < b_sc) return rr;
+            if (rr < b_sc) return rr + M.nu < b_sc ? rr + M.nu : rr;
             return rr + 1 < M.m_ref ? rr + 1 : rr;
         };
 #pragma unroll

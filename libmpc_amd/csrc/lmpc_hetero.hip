@@ -151,11 +151,15 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
                 double v;
                 if (kind == 0) v = Sn[cp * ld + q];
                 else if (kind == 1) v = CS[cp * ld + q];
-                else {
+                else if (kind == 2) {
                     v = 0.0;
                     for (int c = 0; c < nx; ++c) v = fma(gsX[c], Sn[c * ld + q], v);
                     const int bq = q / nu, jq = q - bq * nu;
                     if (bq == blk[i]) v += gsU[jq];
+                } else {
+                    // an input-rate row: delta_{i-1} = v_i - v_{i-1}, the two in different blocks (a free move); v_0 is data
+                    const int bq = q / nu, jq = q - bq * nu;
+                    v = jq != cp ? 0.0 : (bq == blk[i] ? 1.0 : ((i > 1 && bq == blk[i - 1]) ? -1.0 : 0.0));
                 }
                 oGr[(size_t)r * ldz + q] = v;
                 oGc[(size_t)q * ldg + r] = v;

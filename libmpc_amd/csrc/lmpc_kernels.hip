@@ -201,9 +201,11 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
                 off = 0;
                 for (int c = 0; c < nx; ++c) off = fma(gC[cp + c * ny], xb[st * nx + c], off);
                 if (has_dist) for (int dd = 0; dd < ndu; ++dd) off = fma(gDd[cp + dd * ny], dm(st - 1, dd), off);
-            } else {
+            } else if (kind == 2) {
                 off = 0;
                 for (int c = 0; c < nx; ++c) off = fma(sxu[c], xb[st * nx + c], off);
+            } else {
+                off = st == 1 ? -u0s[cp] : 0.0;   // an input-rate row: delta_0 = v_1 - lastU, the later ones see decision variables only
             }
             lg[s] = rlg[s] - off; ug[s] = rug[s] - off;
         }
@@ -311,9 +313,12 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
                 if (kind == 0) v = xb[st * nx + cp];
                 else if (kind == 1) {
                     for (int c = 0; c < nx; ++c) v = fma(gC[cp + c * ny], xb[st * nx + c], v);
-                } else {
+                } else if (kind == 2) {
                     for (int c = 0; c < nx; ++c) v = fma(sxu[c], xb[st * nx + c], v);
                     for (int j = 0; j < nu; ++j) v = fma(sxu[nx + j], stage[blks[st] * nu + j], v);
+                } else {
+                    v = stage[blks[st] * nu + cp];
+                    if (st > 1) v -= stage[blks[st - 1] * nu + cp];
                 }
                 gt0[s] = v;
             }
@@ -606,7 +611,7 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
             if (!Bt.warm_shift) return rr;
             if (rr < b_out) return rr + na < b_out ? rr + na : rr;
             if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
-            if (rr < b_sc) return rr;
+            if (rr < b_sc) return rr + M.nu < b_sc ? rr + M.nu : rr;
             return rr + 1 < M.m_ref ? rr + 1 : rr;
         };
 #pragma unroll

@@ -84,6 +84,7 @@ LmpcController::LmpcController(const mpcx_dims &dims) : d(dims)
     minX = Mat(d.nx, d.ph + 1, -kInf); maxX = Mat(d.nx, d.ph + 1, kInf);
     minY = Mat(d.ny, d.ph + 1, -kInf); maxY = Mat(d.ny, d.ph + 1, kInf);
     minU = Mat(d.nu, d.ph, -kInf); maxU = Mat(d.nu, d.ph, kInf);
+    minDU = Mat(d.nu, d.ph, -kInf); maxDU = Mat(d.nu, d.ph, kInf);
     sMin.assign(d.ph + 1, -kInf); sMax.assign(d.ph + 1, kInf);
     sX.assign(d.nx, 0.0); sU.assign(d.nu, 0.0);
     yRef = Mat(d.ny, d.ph); uRef = Mat(d.nu, d.ph); duRef = Mat(d.nu, d.ph); dMeas = Mat(d.ndu, d.ph);
@@ -154,6 +155,16 @@ void LmpcController::set_input_bounds_idx(int idx, const double *lo, const doubl
     std::memcpy(minU.col(idx), lo, sizeof(double) * d.nu);
     std::memcpy(maxU.col(idx), hi, sizeof(double) * d.nu);
 }
+void LmpcController::set_rate_bounds(const double *lo, const double *hi)
+{
+    std::memcpy(minDU.a.data(), lo, sizeof(double) * d.nu * d.ph);
+    std::memcpy(maxDU.a.data(), hi, sizeof(double) * d.nu * d.ph);
+}
+void LmpcController::set_rate_bounds_idx(int idx, const double *lo, const double *hi)
+{
+    std::memcpy(minDU.col(idx), lo, sizeof(double) * d.nu);
+    std::memcpy(maxDU.col(idx), hi, sizeof(double) * d.nu);
+}
 void LmpcController::set_scalar_vec(const double *smin, const double *smax, const double *X, const double *U)
 {
     for (int k = 0; k < d.ph; k++) { sMin[k + 1] = smin[k]; sMax[k + 1] = smax[k]; }
@@ -182,7 +193,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
     const int nineq = (ph + 1) * na + (ph + 1) * ny + ph * nu + (ph + 1);
     o.m_ref = o.neq_ref + nineq;
     o.active_words = (o.m_ref + 31) / 32;
-    const int off_y = (ph + 1) * na, off_s = off_y + (ph + 1) * ny + ph * nu;
+    const int off_y = (ph + 1) * na, off_du = off_y + (ph + 1) * ny, off_s = off_du + ph * nu;
 
     // delta-u is free for steps 0..ch inclusive (ProblemBuilder.hpp:782-793): v_1..v_nf free
     const int nf = std::min(ph, ch + 1);
@@ -284,6 +295,17 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
             }
             for (int j = 0; j < nu; j++) g[o.blk[i] * nu + j] += sU[j];
             rows.push_back({G_SCALAR, i, 0, o.neq_ref + off_s + i, sMin[i], sMax[i]});
+            grow.push_back(std::move(g));
+        }
+        // delta_{i-1} = v_i - v_{i-1}: bounded for the free moves (i - 1 <= ch, :782-793); v_0 = lastU is data and goes into the offset.
+        // The two blocks differ for every free move, so such a row always sees the decision variables
+        for (int j = 0; j < nu && i - 1 <= ch; j++) {
+            double lo = minDU(j, i - 1), hi = maxDU(j, i - 1);
+            if (!finite_any(lo, hi)) continue;
+            std::vector<double> g(nz, 0.0);
+            g[o.blk[i] * nu + j] = 1.0;
+            if (i > 1) g[o.blk[i - 1] * nu + j] = -1.0;
+            rows.push_back({G_RATE, i, j, o.neq_ref + off_du + (i - 1) * nu + j, lo, hi});
             grow.push_back(std::move(g));
         }
     }
@@ -487,8 +509,10 @@ void LmpcController::assemble_host(const Condensed &o, const double *x0, const d
         else if (kind == G_OUTPUT) {
             for (int c = 0; c < nx; c++) v += C(cp, c) * xb[(size_t)st * nx + c];
             for (int dd = 0; dd < ndu; dd++) v += Dd(cp, dd) * dM(dd, st > 0 ? st - 1 : 0);
-        } else {
+        } else if (kind == G_SCALAR) {
             for (int c = 0; c < nx; c++) v += sX[c] * xb[(size_t)st * nx + c];
+        } else {
+            v = st == 1 ? -u0[cp] : 0.0;        // G_RATE: delta_0 = v_1 - lastU; no free response, no disturbance
         }
         return v;
     };

@@ -40,7 +40,8 @@ double cholesky_lower(Mat &A);
 // inverse of SPD matrix from its Cholesky factor
 Mat spd_inverse_from_chol(const Mat &L);
 
-enum GKind : int { G_STATE = 0, G_OUTPUT = 1, G_SCALAR = 2 };
+// G_RATE: a bound on the input increment delta_i = v_{i+1} - v_i (the reference's delta-u rows, ProblemBuilder.hpp:768-793); step = i + 1
+enum GKind : int { G_STATE = 0, G_OUTPUT = 1, G_SCALAR = 2, G_RATE = 3 };
 
 struct GeneralRow {
     int kind, step, comp;   // which functional of the predicted trajectory
@@ -98,6 +99,7 @@ struct LmpcController {
     // ProblemBuilder state (internal columns 0..ph, see ProblemBuilder.hpp:254-260)
     Mat wOutput, wU, wDeltaU;
     Mat minX, maxX, minY, maxY, minU, maxU;
+    Mat minDU, maxDU;       // [nu x ph], column i bounds delta_i (no column shift, as wDeltaU); columns past ch are kept and not read
     std::vector<double> sMin, sMax, sX, sU;
     // LOptimizer state
     Mat yRef, uRef, duRef, dMeas;
@@ -117,6 +119,9 @@ struct LmpcController {
     void set_input_bounds_idx(int idx, const double *lo, const double *hi);
     void set_output_bounds(const double *lo, const double *hi);
     void set_output_bounds_idx(int idx, const double *lo, const double *hi);
+    // bounds on the input increments: the reference builds these rows and offers no setter for them (ProblemBuilder.hpp:768-793)
+    void set_rate_bounds(const double *lo, const double *hi);
+    void set_rate_bounds_idx(int idx, const double *lo, const double *hi);
     void set_scalar_vec(const double *smin, const double *smax, const double *X, const double *U);
     void set_scalar_idx(int idx, double smin, double smax, const double *X, const double *U);
 

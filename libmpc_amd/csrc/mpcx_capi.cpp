@@ -420,6 +420,42 @@ int mpcx_lmpc_set_input_bounds_slice(mpcx_lmpc_t h, const double *lo, const doub
     h->dirty = true;
     return MPCX_OK;
 }
+// Bounds on the input increments.  The reference's QP has these rows (ProblemBuilder.hpp:768-793) and no setter for them; columns past
+// the control horizon are kept and not read (those moves stay pinned to zero).
+static bool rate_column_ok(const double *lo, const double *hi, int nu, bool read)
+{
+    for (int j = 0; j < nu; j++) {
+        if (std::isnan(lo[j]) || std::isnan(hi[j])) return false;
+        if (read && lo[j] > hi[j]) return false;
+    }
+    return true;
+}
+int mpcx_lmpc_set_input_rate_bounds(mpcx_lmpc_t h, const double *lo, const double *hi)
+{
+    CHECK_H(h);
+    if (!lo || !hi) return fail(MPCX_E_INVALID, "null matrix");
+    auto &c = h->ctl;
+    for (int k = 0; k < c.d.ph; k++)
+        if (!rate_column_ok(lo + (size_t)k * c.d.nu, hi + (size_t)k * c.d.nu, c.d.nu, k <= c.d.ch))
+            return fail(MPCX_E_INVALID, "input rate bounds: NaN, or dumin > dumax within the control horizon");
+    c.set_rate_bounds(lo, hi);
+    h->dirty = true;
+    return MPCX_OK;
+}
+int mpcx_lmpc_set_input_rate_bounds_slice(mpcx_lmpc_t h, const double *lo, const double *hi, int start, int end)
+{
+    CHECK_H(h);
+    if (!lo || !hi) return fail(MPCX_E_INVALID, "null vector");
+    auto &c = h->ctl;
+    int s = start, e = end;
+    if (start == -1 && end == -1) { s = 0; e = c.d.ph; }
+    else if (!c.pred_slice_valid(start, end)) return fail(MPCX_E_INVALID, "The prediction horizon slice is out of bounds");
+    if (!rate_column_ok(lo, hi, c.d.nu, s <= c.d.ch))
+        return fail(MPCX_E_INVALID, "input rate bounds: NaN, or dumin > dumax within the control horizon");
+    for (int i = s; i < e; i++) c.set_rate_bounds_idx(i, lo, hi);
+    h->dirty = true;
+    return MPCX_OK;
+}
 int mpcx_lmpc_set_output_bounds(mpcx_lmpc_t h, const double *lo, const double *hi)
 {
     CHECK_H(h);

@@ -539,6 +539,13 @@ class LMPC(_LoopFrontEnd):
         return self._bounds(YMin, YMax, self.ny, self.ph, self._lib.mpcx_lmpc_set_output_bounds,
                             self._lib.mpcx_lmpc_set_output_bounds_slice, slice)
 
+    def setInputRateBounds(self, DUMin, DUMax, slice=None):
+        """extension: dumin <= u_k - u_{k-1} <= dumax, the bounds of the reference QP's delta-u rows (ProblemBuilder.hpp:768-793; the
+        reference has no setter).  [nu x ph] matrices, column i bounding delta_i = v_{i+1} - v_i with v_0 = lastU, or vectors with a
+        prediction-horizon slice; columns past the control horizon are kept and not read."""
+        return self._bounds(DUMin, DUMax, self.nu, self.ph, self._lib.mpcx_lmpc_set_input_rate_bounds,
+                            self._lib.mpcx_lmpc_set_input_rate_bounds_slice, slice)
+
     def setScalarConstraint(self, *args):
         """(min, max, X, U, slice) as LMPC.hpp:355 or (index, min, max, X, U) as LMPC.hpp:409."""
         if len(args) != 5:
