@@ -152,6 +152,18 @@ int mpcx_lmpc_set_output_bounds_slice(mpcx_lmpc_t h, const double *ymin, const d
  * slice like the delta-u weight's.  MPCX_E_INVALID: null pointer, NaN, or dumin > dumax in a column <= ch. */
 int mpcx_lmpc_set_input_rate_bounds(mpcx_lmpc_t h, const double *dumin, const double *dumax);
 int mpcx_lmpc_set_input_rate_bounds_slice(mpcx_lmpc_t h, const double *dumin, const double *dumax, int start, int end);
+/* Soft constraints: a weight rho in (0, +inf] for each state row, output row and the scalar row; +inf (the default) keeps the row hard.  A
+ * finite weight replaces the row lo <= g <= hi by the term 0.5 rho dist^2(g, [lo, hi]) in the cost -- one free slack per row with cost
+ * 0.5 rho s^2.  The reference's LMPC has no counterpart (its NLMPC has one slack for all rows, NLOptimizer.hpp:182-186).  Input bounds and
+ * input-rate bounds stay hard.  xw[nx], yw[ny], sw[1]; a null pointer leaves that kind of row as it is.  The first form sets the whole
+ * horizon, steps 0 .. ph; the slice form has the slice semantics and the column shift of mpcx_lmpc_set_state_bounds_slice, so that a weight
+ * softens exactly the rows the same call of the bounds setter bounds (sw as mpcx_lmpc_set_scalar_constraint_slice).  A weight where no
+ * bound is finite is stored and has no effect.  A soft row never makes an instance infeasible, strict mode included (a soft step-0 row, which
+ * sees no decision variable, is then a pure cost term); `cost` includes the penalty; the active bit of a soft row is set when its multiplier is
+ * non-zero, i.e. when the row is violated or on its bound with a pull; row numbering, m_ref and active_words do not change.
+ * MPCX_E_INVALID: NaN, zero or a negative weight; a slice out of bounds. */
+int mpcx_lmpc_set_soft_constraint_weights(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw);
+int mpcx_lmpc_set_soft_constraint_weights_slice(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw, int start, int end);
 /* LMPC::setScalarConstraint slice form (LMPC.hpp:355) and index form (LMPC.hpp:409) */
 int mpcx_lmpc_set_scalar_constraint_slice(mpcx_lmpc_t h, double smin, double smax, const double *X, const double *U,
                                           int start, int end);

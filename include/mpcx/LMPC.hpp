@@ -205,6 +205,20 @@ public:
     {
         return ok(mpcx_lmpc_set_input_rate_bounds_slice(h_, lo.data(), hi.data(), s.start, s.end));
     }
+    // extension: soft state / output / scalar rows -- a weight rho in (0, inf] per row kind and component, inf = hard; a finite one replaces the row
+    // by 0.5 rho dist^2(row value, [lo, hi]) in the cost.  The reference's LMPC has no counterpart.  The first form sets steps 0 .. ph, the second
+    // has the slice semantics of setStateBounds
+    bool setSoftConstraintWeights(const cvec<Tnx> &xw, const cvec<Tny> &yw, const double sw) { return ok(mpcx_lmpc_set_soft_constraint_weights(h_, xw.data(), yw.data(), &sw)); }
+    bool setSoftConstraintWeights(const cvec<Tnx> &xw, const cvec<Tny> &yw, const double sw, const HorizonSlice &s)
+    {
+        return ok(mpcx_lmpc_set_soft_constraint_weights_slice(h_, xw.data(), yw.data(), &sw, s.start, s.end));
+    }
+    // ... and the form that can leave a kind of row as it is, as the C entry does: a null pointer keeps that kind's weights (xw[nx], yw[ny], sw[1]).
+    // The two overloads above always set all three kinds
+    bool setSoftConstraintWeights(const double *xw, const double *yw, const double *sw, const HorizonSlice &s = HorizonSlice::all())
+    {
+        return ok(mpcx_lmpc_set_soft_constraint_weights_slice(h_, xw, yw, sw, s.start, s.end));
+    }
     bool setScalarConstraint(const double mn, const double mx, const cvec<Tnx> X, const cvec<Tnu> U, const HorizonSlice &s)   // LMPC.hpp:355
     {
         return ok(mpcx_lmpc_set_scalar_constraint_slice(h_, mn, mx, X.data(), U.data(), s.start, s.end));

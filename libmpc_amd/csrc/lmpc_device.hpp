@@ -19,9 +19,12 @@ namespace mpcx {
 
 constexpr int kMaxActive = 28;          // working-set capacity of the in-kernel polish
 constexpr int kSld = kMaxActive + 1;    // LDS row stride of the Schur complement
-// capacity of the fallback polish's working-set lists (indices, bounds, multipliers): up to nz rows, the most independent rows the condensed
-// problem can have; the Schur complement of a set of more than kMaxActive rows goes to a device buffer of one nz x nz slot per wavefront
-__host__ __device__ inline int ws_capacity(int nz) { return nz > kMaxActive ? nz : kMaxActive; }
+// the most rows a working set can hold and still be independent: nz of them, and every soft general row on top -- its 1 / rho on the diagonal of
+// the dual Hessian keeps the Schur complement regular whatever else is in the set; never more than there are rows
+__host__ __device__ inline int ws_limit(int nz, int mg, int n_soft) { return nz + (n_soft < mg ? n_soft : mg); }
+// capacity of the fallback polish's working-set lists (indices, bounds, multipliers) for that limit; the Schur complement of a set of more than
+// kMaxActive rows goes to a device buffer of one limit x limit slot per wavefront.  Without soft rows: nz, as it has always been
+__host__ __device__ inline int ws_capacity(int limit) { return limit > kMaxActive ? limit : kMaxActive; }
 
 struct LmpcDev {
     int nx, nu, ndu, ny, ph, ch, nf, nz, mg;
@@ -35,6 +38,7 @@ struct LmpcDev {
                                                  // semidefinite; bit 1: the ADMM matrix is not positive definite; bit 2: a kept row of G is identically
                                                  // zero (the controller's constraint structure differs from controller 0's)
     int strict_infeasible;                       // 1: report INFEASIBLE / NaN; 0: behave as the reference does
+    int n_soft;                                  // soft general rows (in what was padding: every other field keeps its offset)
     double alpha, sigma, eps_abs, eps_rel, eps_prim_inf;
     int adaptive_rho; double rho_user;            // LParameters::adaptive_rho / rho (the ADMM step sizes of the set-up)
     // per-wave LDS carve (in doubles)
@@ -51,7 +55,7 @@ struct LmpcDev {
     // condensed QP
     const double *H, *Kinv, *Gr, *Gc, *Y;
     const double *lw, *uw, *rho_b;               // [ldz]
-    const double *lg0, *ug0, *rho_g;             // [ldg]
+    const double *lg0, *ug0, *rho_g;             // [ldg]; rho_g [2 ldg]: the step sizes, then MPCX_G_SOFT
     const int *g_kind, *g_step, *g_comp, *g_refrow;      // [ldg]
     const int *f_kind, *f_step, *f_comp; const double *f_lo, *f_hi;   // fixed rows [n_fixed]
     const int *boxrow_ptr, *boxrow_ref; const double *boxrow_lo, *boxrow_hi;
@@ -67,6 +71,9 @@ struct LmpcDev {
     int rowsF, nsp, fused_ok, group_ok;
     const double *MF0, *MF1;
 };
+// 1 / weight of a soft general row, 0 for a hard one and the padding, [ldg]: it rides behind the step sizes in rho_g's array.  The struct travels by
+// value in lmpc_solve_group's kernel arguments, sixteen cache lines to the byte (kernarg_touch): it has room for an int, not for a pointer
+#define MPCX_G_SOFT(M) ((M).rho_g + (M).ldg)
 
 struct LmpcBatchDev {
     int batch;
@@ -93,6 +100,8 @@ struct LmpcBatchDev {
     const int32_t *model_index;
     long long *dbg_cycles;       // optional [B x 8] per-phase cycle counts (profiling aid)
 };
+// doubles of one wavefront's slot of the large-working-set buffer (LmpcScratch::pbuf)
+__host__ __device__ inline size_t lmpc_slot_len(const LmpcDev &m) { const size_t n = (size_t)ws_limit(m.nz, m.mg, m.n_soft); return n * n; }
 // which entry of the model array instance b uses
 __host__ __device__ inline int lmpc_model_of(const LmpcBatchDev &Bt, int b) { return Bt.n_models <= 0 ? 0 : (Bt.model_index ? Bt.model_index[b] : b); }
 
@@ -115,7 +124,7 @@ int lmpc_kernel_variant(int ldz, int ldg);     // -1 if the dimensions are not c
 // One handle's scratch memory on the device, sized for batches of up to `cap` instances:
 //   ws       per-instance workspace between assemble and solve, cap records of wsld doubles
 //   fq       failure queue (above), a list of cap entries, count and ticket zeroed when allocated
-//   pbuf     the fallback kernel's slots for working sets of more than kMaxActive rows, pslots (lmpc_fallback_slots) x nz x nz doubles; the
+//   pbuf     the fallback kernel's slots for working sets of more than kMaxActive rows, pslots (lmpc_fallback_slots) x limit x limit doubles (ws_limit); the
 //            fallback's grid is capped at pslots wavefronts
 //   pcounter work counters of the persistent fused kernel, eight ints (single-controller handles only; null in a bank)
 struct LmpcScratch { double *ws; size_t cap; int *fq; double *pbuf; int pslots; int *pcounter; };

@@ -564,6 +564,17 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
 #pragma unroll
     for (int c = 0; c < CPZ; ++c) *reinterpret_cast<double2 *>(stage + 128 * c + 2 * lane) = make_double2(w[2 * c], w[2 * c + 1]);
     wave_sync();
+    // this lane's share of the soft rows' penalty at the verified point: the slack of a working row is lambda / rho.  Only the
+    // branches that take the cost from its definition add it; the multiplier identity below holds with the penalty in it
+    auto soft_penalty = [&]() {
+        double pen = 0.0;
+#pragma unroll
+        for (int s = 0; s < NGS; ++s) {
+            const int r = 128 * (s >> 1) + 2 * lane + (s & 1);
+            if (r < mg && actg[s] != 0) { const double l = lam[posg[s]]; pen = fma(0.5 * gl(MPCX_G_SOFT(M))[r] * l, l, pen); }
+        }
+        return pen;
+    };
     if (infeasible) {
         cost = 1e30;
     } else if (!M.cost_direct) {
@@ -581,6 +592,10 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
             const int e = 128 * c + 2 * lane;
             if (e < ldz) st2(ws + ldz + e, w[2 * c], w[2 * c + 1]);
         }
+        if (M.n_soft > 0) {                         // lmpc_cost_mfma adds the record's constant: the penalty rides in it
+            const double pen = wave_sum(soft_penalty());
+            if (lane == 0) ws[ldz + ldy + 2 * ldg] = c0 + pen;
+        }
         cost = 0.0;
         cost_pending = true;
     } else {
@@ -591,6 +606,7 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
         double j = 0;
 #pragma unroll
         for (int s = 0; s < NZS; ++s) j += w[s] * (0.5 * hw[s] + f[s]);
+        if constexpr (SRC != 1) { if (M.n_soft > 0) j += soft_penalty(); }      // (the fused mat-vec form is never taken with cost_direct: fused_ok)
         cost = wave_sum(j) + c0;
     }
 #pragma unroll

@@ -108,6 +108,7 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
         double *rb = wv + ((ny + 3) & ~3) + 4, *rg = rb + NP;                  // rho_b [NP], rho_g [NQ]
         const gdp gA = gl(M.A), gB = gl(M.B), gC = gl(M.C), gWy = gl(M.Wy), gWu = gl(M.Wu), gWdu = gl(M.Wdu), gsX = gl(M.sX), gsU = gl(M.sU);
         const gip blk = gl(M.blk), gk = gl(M.g_kind), gs = gl(M.g_step), gc = gl(M.g_comp);
+        const gdp gso = gl(MPCX_G_SOFT(M));                                           // 1 / weight of a soft row, 0 for a hard one
         gdw oH = glw(const_cast<double *>(M.H)), oK = glw(const_cast<double *>(M.Kinv)), oGr = glw(const_cast<double *>(M.Gr)),
             oGc = glw(const_cast<double *>(M.Gc)), oY = glw(const_cast<double *>(M.Y)), orb = glw(const_cast<double *>(M.rho_b)),
             org = glw(const_cast<double *>(M.rho_g));
@@ -300,7 +301,8 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
                      [&](int row, int k) { return (row < mg && k < nz) ? Q[row * ld + k] : 0.0; },
                      [&](int k, int col) { return (col < mg && k < nz) ? oGr[(size_t)col * ldz + k] : 0.0; },
                      [&](int row, int col, double v) {
-                         if (row < mg && col < mg) { oY[(size_t)(ldz + row) * ldy + ldz + col] = v; if (row == col) rg[row] = v; }
+                         // (a soft row: 1 / rho on its diagonal entry, and its step size from that -- a row without coefficients has nothing else there)
+                         if (row < mg && col < mg) { const double vd = row == col ? v + gso[row] : v; oY[(size_t)(ldz + row) * ldy + ldz + col] = vd; if (row == col) rg[row] = vd; }
                      }, wave, lane);
         __syncthreads();
         // ---- ADMM step sizes (Jacobi preconditioning of the dual problem; equality rows 1e3 x, as OSQP does)
@@ -349,7 +351,7 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
         for (int r0 = t; r0 < mg; r0 += blockDim.x) {
             double amax = 0.0;
             for (int q = 0; q < nz; ++q) amax = fmax(amax, fabs(oGr[(size_t)r0 * ldz + q]));
-            if (!(amax > 0.0)) atomicOr(&cstat, 4);
+            if (!(amax > 0.0) && !(gso[r0] > 0.0)) atomicOr(&cstat, 4);          // (a soft row is kept whatever its coefficients are)
         }
         __syncthreads();
         if (t == 0) M.cond_status = cstat;

@@ -200,10 +200,11 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
             else if (kind == 1) {
                 off = 0;
                 for (int c = 0; c < nx; ++c) off = fma(gC[cp + c * ny], xb[st * nx + c], off);
-                if (has_dist) for (int dd = 0; dd < ndu; ++dd) off = fma(gDd[cp + dd * ny], dm(st - 1, dd), off);
+                if (has_dist) for (int dd = 0; dd < ndu; ++dd) off = fma(gDd[cp + dd * ny], dm(st > 0 ? st - 1 : 0, dd), off);
             } else if (kind == 2) {
                 off = 0;
                 for (int c = 0; c < nx; ++c) off = fma(sxu[c], xb[st * nx + c], off);
+                if (st == 0) for (int c = 0; c < nu; ++c) off = fma(sxu[nx + c], u0s[c], off);      // (a soft step-0 row, as s0 above: lastU is data there)
             } else {
                 off = st == 1 ? -u0s[cp] : 0.0;   // an input-rate row: delta_0 = v_1 - lastU, the later ones see decision variables only
             }
@@ -315,7 +316,7 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
                     for (int c = 0; c < nx; ++c) v = fma(gC[cp + c * ny], xb[st * nx + c], v);
                 } else if (kind == 2) {
                     for (int c = 0; c < nx; ++c) v = fma(sxu[c], xb[st * nx + c], v);
-                    for (int j = 0; j < nu; ++j) v = fma(sxu[nx + j], stage[blks[st] * nu + j], v);
+                    if (st > 0) for (int j = 0; j < nu; ++j) v = fma(sxu[nx + j], stage[blks[st] * nu + j], v);
                 } else {
                     v = stage[blks[st] * nu + cp];
                     if (st > 1) v -= stage[blks[st - 1] * nu + cp];
@@ -553,14 +554,16 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
         rb[2 * c] = ok ? vr.x : 0.0; rb[2 * c + 1] = ok ? vr.y : 0.0;
     }
     double lg[NGS], ug[NGS], rg[NGS], gt0[NGS];
+    double gs[NGS];           // 1 / weight of a soft row, 0 for a hard one
     bool eqg[NGS];
 #pragma unroll
     for (int c = 0; c < CPG; ++c) {
         const int r = 128 * c + 2 * lane;
         const int ro = r < ldg ? r : 0;
         const d2 vt = rec2(2 * ldz + ro), vl = rec2(ldz + ldy + ro), vu = rec2(ldz + ldy + ldg + ro), vr = ld2(GP(rho_g) + ro);
-        const d2 l0 = ld2(GP(lg0) + ro), u0 = ld2(GP(ug0) + ro);
+        const d2 l0 = ld2(GP(lg0) + ro), u0 = ld2(GP(ug0) + ro), vs = ld2(gl(MPCX_G_SOFT(M)) + ro);
         const bool ok = r < ldg;
+        gs[2 * c] = ok ? vs.x : 0.0; gs[2 * c + 1] = ok ? vs.y : 0.0;
         gt0[2 * c] = ok ? vt.x : 0.0; gt0[2 * c + 1] = ok ? vt.y : 0.0;
         lg[2 * c] = ok ? vl.x : -INF; lg[2 * c + 1] = ok ? vl.y : -INF;
         ug[2 * c] = ok ? vu.x : INF; ug[2 * c + 1] = ok ? vu.y : INF;
@@ -642,9 +645,9 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
 #pragma unroll
     for (int s = 0; s < NGS; ++s) gw[s] = gt0[s];
 
-    // working sets of up to kMaxActive rows are factored in this LDS arena; larger ones (up to nz rows, the most independent rows there
-    // can be) in bigS, this wavefront's nz x nz slot of a device buffer (null: not available, such a set is left to ADMM)
-    const int wcap = ws_capacity(nz);
+    // working sets of up to kMaxActive rows are factored in this LDS arena; larger ones (up to nz rows and the soft rows, the most independent
+    // rows there can be: ws_limit) in bigS, this wavefront's slot of a device buffer (null: not available, such a set is left to ADMM)
+    const int wcap = ws_capacity(ws_limit(nz, mg, M.n_soft));
     double *S = arena;                               // Schur complement, kMaxActive x kSld
     double *lam = S + kMaxActive * kSld;             // rhs -> multipliers [wcap]
     double *wsb = lam + wcap;                        // bound values of the working set [wcap]
@@ -688,7 +691,7 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
                 if (act && pos < wcap) { wsidx[pos] = ldz + r; wsb[pos] = actg[s] < 0 ? lg[s] : ug[s]; }
                 na += __popcll(mk);
             }
-            if (na > kMaxActive && (!bigS || na > nz)) return false;      // (more than nz rows are dependent: never a verified optimum)
+            if (na > kMaxActive && (!bigS || na > wcap)) return false;    // (more hard rows than nz are dependent: never a verified optimum)
             hsh |= 1ull;
             bool cyc = false;
 #pragma unroll
@@ -1013,6 +1016,9 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
 
     // -------- one ADMM iteration (OSQP's splitting on the condensed QP)
     const double alpha = M.alpha, sigma = M.sigma;
+    double pf[NGS];           // rho_a / (rho_a + rho) written over 1 / rho: 0 for a hard row
+#pragma unroll
+    for (int s = 0; s < NGS; ++s) pf[s] = rg[s] * gs[s] / (rg[s] * gs[s] + 1.0);
     auto admm_iter = [&]() {
         double tmpg[NGS];
 #pragma unroll
@@ -1051,8 +1057,11 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
         }
 #pragma unroll
         for (int s = 0; s < NGS; ++s) {
+            // the prox of the row's term: the projection for a hard row (pf = 0), for a soft one the point between the projection and v that
+            // balances the penalty 0.5 rho dist^2 against the step's 0.5 rho_a (z - v)^2
             const double zr = alpha * ztg[s] + (1.0 - alpha) * zg[s];
-            const double zn = clampd(zr + yg[s] / rg[s], lg[s], ug[s]);
+            const double v = zr + yg[s] / rg[s], cl = clampd(v, lg[s], ug[s]);
+            const double zn = cl + (v - cl) * pf[s];
             dyg[s] = rg[s] * (zr - zn);
             yg[s] += dyg[s];
             zg[s] = zn;
@@ -1074,7 +1083,7 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
 #pragma unroll
         for (int s = 0; s < NGS; ++s) {
             double d = dyg[s];
-            const bool iu = !(ug[s] < INF), il = !(lg[s] > -INF);
+            const bool iu = !(ug[s] < INF) || gs[s] > 0.0, il = !(lg[s] > -INF) || gs[s] > 0.0;      // (a soft row cannot make the problem infeasible)
             if (iu && il) d = 0; else if (iu) d = fmin(d, 0.0); else if (il) d = fmax(d, 0.0);
             pg[s] = d; nrm = fmax(nrm, fabs(d));
             if (d > 0) lhs += ug[s] * d; else if (d < 0) lhs += lg[s] * d;
@@ -1193,6 +1202,22 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
         double j = 0;
 #pragma unroll
         for (int s = 0; s < NZS; ++s) j += w[s] * (0.5 * hw[s] + f[s]);
+        if (M.n_soft > 0) {
+            // the penalty of the soft rows: at a polished point the slack of a working row is lambda / rho; at an ADMM iterate from its definition
+            if (polished) {
+#pragma unroll
+                for (int s = 0; s < NGS; ++s)
+                    if (actg[s] != 0) { const double l = lam[posg[s]]; j = fma(0.5 * gs[s] * l, l, j); }
+            } else {
+                double gx[NGS];
+#pragma unroll
+                for (int s = 0; s < NGS; ++s) gx[s] = 0;
+                matvec_acc<CPG>(GP(Gc), ldg, ldg, nz, stage, gx, lane);
+#pragma unroll
+                for (int s = 0; s < NGS; ++s)
+                    if (gs[s] > 0.0) { const double dd = gx[s] - clampd(gx[s], lg[s], ug[s]); j = fma(0.5 * dd / gs[s], dd, j); }
+            }
+        }
         cost = wave_sum(j) + c0;
     }
 #pragma unroll
@@ -1340,7 +1365,7 @@ __device__ __noinline__ void admm_serve(const AdmmArgs *ap, double *smem, const 
     double *nt0 = stage + M.stage_len;
     double *arena = nt0 + M.ldy;
     // this wavefront's slot for working sets of more than kMaxActive rows (the host caps the grid at pslots wavefronts)
-    const gdw bigS = (A.pbuf && slot < A.pslots) ? glw(A.pbuf) + (size_t)slot * M.nz * M.nz : nullptr;
+    const gdw bigS = (A.pbuf && slot < A.pslots) ? glw(A.pbuf) + (size_t)slot * lmpc_slot_len(M) : nullptr;
     if (Bt.fq) {
         // wavefront w of W serves list[w], list[w + W], ...: which wavefront serves an instance changes nothing of its arithmetic
         const int n = nopen < Bt.fq_cap ? nopen : Bt.fq_cap;
@@ -1566,7 +1591,7 @@ int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len)
     st = (st + 1) / 2 * 2;
     int a1 = (m.ph + 1) * (m.nx + 2 * m.ny) + (m.ph + 2) * m.nx + 2 * m.ph * m.nu + m.nu + (m.nx + m.nu) + m.ph * m.ndu + (m.ph + 2) / 2 + 8 +
              m.nx * m.nx + m.nx * m.nu + m.ny * m.nx + m.nx * m.ndu + m.ny * m.ndu;      // assemble_one's plan, model matrices last
-    const int wcap = ws_capacity(m.nz);
+    const int wcap = ws_capacity(ws_limit(m.nz, m.mg, m.n_soft));
     int a2 = kMaxActive * kSld + 3 * wcap + (wcap + 1) / 2;      // S, lam, wsb, dg0, wsidx (ints)
     int ar = a1 > a2 ? a1 : a2;
     ar = (ar + 1) / 2 * 2;
@@ -1601,7 +1626,7 @@ int lmpc_fallback_reset(int *fq, void *stream)
 int lmpc_fallback_slots(const LmpcDev &m, int batch)
 {
     constexpr size_t kBudget = (size_t)256 << 20;           // bytes
-    const size_t per = (size_t)m.nz * m.nz * sizeof(double);
+    const size_t per = lmpc_slot_len(m) * sizeof(double);
     long long waves = lmpc_fallback_waves();
     const long long inst = ((long long)batch + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock;
     if (waves > inst) waves = inst;
@@ -1617,7 +1642,7 @@ int lmpc_scratch_reserve(LmpcScratch &s, const LmpcDev &m, int batch, bool with_
     const int slots = lmpc_fallback_slots(m, batch);
     if (hipMalloc(reinterpret_cast<void **>(&s.ws), (size_t)batch * m.wsld * sizeof(double)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&s.fq), lmpc_fallback_queue_bytes((size_t)batch)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&s.pbuf), (size_t)slots * m.nz * m.nz * sizeof(double)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s.pbuf), (size_t)slots * lmpc_slot_len(m) * sizeof(double)) != hipSuccess ||
         hipMemsetAsync(s.fq, 0, lmpc_fallback_queue_bytes(0), reinterpret_cast<hipStream_t>(stream)) != hipSuccess ||
         (with_pcounter && (hipMalloc(reinterpret_cast<void **>(&s.pcounter), 8 * sizeof(int)) != hipSuccess || hipMemset(s.pcounter, 0, 8 * sizeof(int)) != hipSuccess)))
         return -3;

@@ -85,6 +85,7 @@ LmpcController::LmpcController(const mpcx_dims &dims) : d(dims)
     minY = Mat(d.ny, d.ph + 1, -kInf); maxY = Mat(d.ny, d.ph + 1, kInf);
     minU = Mat(d.nu, d.ph, -kInf); maxU = Mat(d.nu, d.ph, kInf);
     minDU = Mat(d.nu, d.ph, -kInf); maxDU = Mat(d.nu, d.ph, kInf);
+    softX = Mat(d.nx, d.ph + 1, kInf); softY = Mat(d.ny, d.ph + 1, kInf); softS.assign(d.ph + 1, kInf);
     sMin.assign(d.ph + 1, -kInf); sMax.assign(d.ph + 1, kInf);
     sX.assign(d.nx, 0.0); sU.assign(d.nu, 0.0);
     yRef = Mat(d.ny, d.ph); uRef = Mat(d.nu, d.ph); duRef = Mat(d.nu, d.ph); dMeas = Mat(d.ndu, d.ph);
@@ -164,6 +165,20 @@ void LmpcController::set_rate_bounds_idx(int idx, const double *lo, const double
 {
     std::memcpy(minDU.col(idx), lo, sizeof(double) * d.nu);
     std::memcpy(maxDU.col(idx), hi, sizeof(double) * d.nu);
+}
+void LmpcController::set_soft_weights(const double *xw, const double *yw, const double *sw)
+{
+    for (int k = 0; k <= d.ph; k++) {
+        if (xw) std::memcpy(softX.col(k), xw, sizeof(double) * d.nx);
+        if (yw) std::memcpy(softY.col(k), yw, sizeof(double) * d.ny);
+        if (sw) softS[k] = *sw;
+    }
+}
+void LmpcController::set_soft_weights_idx(int idx, const double *xw, const double *yw, const double *sw)
+{
+    if (xw) put_idx(softX, idx, xw, d.nx);
+    if (yw) put_idx(softY, idx, yw, d.ny);
+    if (sw) { softS[idx + 1] = *sw; if (idx == 0) softS[0] = *sw; }
 }
 void LmpcController::set_scalar_vec(const double *smin, const double *smax, const double *X, const double *U)
 {
@@ -256,6 +271,23 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
     std::vector<GeneralRow> rows;
     std::vector<std::vector<double>> grow;     // coefficient rows of G
     auto finite_any = [](double lo, double hi) { return std::isfinite(lo) || std::isfinite(hi); };
+    auto inv_weight = [](double rho) { return std::isfinite(rho) ? 1.0 / rho : 0.0; };
+    // soft step-0 rows: no decision variable in them, so a hard one is a feasibility condition on (x0, lastU) (build_fast_maps, the assemble
+    // kernels); a soft one is a general row with zero coefficients -- 1 / rho on Y's diagonal makes it regular
+    for (int j = 0; j < nx; j++)
+        if (finite_any(minX(j, 0), maxX(j, 0)) && std::isfinite(softX(j, 0))) {
+            rows.push_back({G_STATE, 0, j, o.neq_ref + j, minX(j, 0), maxX(j, 0), inv_weight(softX(j, 0))});
+            grow.emplace_back(nz, 0.0);
+        }
+    for (int j = 0; j < ny; j++)
+        if (finite_any(minY(j, 0), maxY(j, 0)) && std::isfinite(softY(j, 0))) {
+            rows.push_back({G_OUTPUT, 0, j, o.neq_ref + off_y + j, minY(j, 0), maxY(j, 0), inv_weight(softY(j, 0))});
+            grow.emplace_back(nz, 0.0);
+        }
+    if (finite_any(sMin[0], sMax[0]) && std::isfinite(softS[0])) {
+        rows.push_back({G_SCALAR, 0, 0, o.neq_ref + off_s, sMin[0], sMax[0], inv_weight(softS[0])});
+        grow.emplace_back(nz, 0.0);
+    }
     for (int i = 1; i <= ph; i++) {
         int k = std::min(i, ph - 1);           // x_u(i) takes input-bound column min(i, ph-1) (:735-749)
         for (int j = 0; j < nx; j++) {
@@ -263,7 +295,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
             if (!finite_any(lo, hi)) continue;
             std::vector<double> g(nz);
             for (int q = 0; q < nz && !light; q++) g[q] = Sx[i](j, q);
-            rows.push_back({G_STATE, i, j, o.neq_ref + i * na + j, lo, hi});
+            rows.push_back({G_STATE, i, j, o.neq_ref + i * na + j, lo, hi, inv_weight(softX(j, i))});
             grow.push_back(std::move(g));
         }
         for (int j = 0; j < nu; j++) {
@@ -283,7 +315,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
                 for (int a = 0; a < nx; a++) s += C(j, a) * Sx[i](a, q);
                 g[q] = s;
             }
-            rows.push_back({G_OUTPUT, i, j, o.neq_ref + off_y + i * ny + j, lo, hi});
+            rows.push_back({G_OUTPUT, i, j, o.neq_ref + off_y + i * ny + j, lo, hi, inv_weight(softY(j, i))});
             grow.push_back(std::move(g));
         }
         if (finite_any(sMin[i], sMax[i])) {
@@ -294,7 +326,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
                 g[q] = s;
             }
             for (int j = 0; j < nu; j++) g[o.blk[i] * nu + j] += sU[j];
-            rows.push_back({G_SCALAR, i, 0, o.neq_ref + off_s + i, sMin[i], sMax[i]});
+            rows.push_back({G_SCALAR, i, 0, o.neq_ref + off_s + i, sMin[i], sMax[i], inv_weight(softS[i])});
             grow.push_back(std::move(g));
         }
         // delta_{i-1} = v_i - v_{i-1}: bounded for the free moves (i - 1 <= ch, :782-793); v_0 = lastU is data and goes into the offset.
@@ -309,7 +341,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
             grow.push_back(std::move(g));
         }
     }
-    // rows that do not see the decision variables are pure feasibility conditions
+    // rows that do not see the decision variables are pure feasibility conditions -- the hard ones: a soft one stays a general row
     {
         std::vector<GeneralRow> keep; std::vector<std::vector<double>> gk;
         for (size_t r = 0; r < rows.size(); r++) {
@@ -320,7 +352,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
                 for (const auto &fr : like->fixed_rows)
                     if (fr.kind == rows[r].kind && fr.step == rows[r].step && fr.comp == rows[r].comp) nrm = 0.0;
             }
-            if (nrm < 1e-14) o.fixed_rows.push_back(rows[r]);
+            if (nrm < 1e-14 && !(rows[r].soft > 0.0)) o.fixed_rows.push_back(rows[r]);
             else { keep.push_back(rows[r]); gk.push_back(std::move(grow[r])); }
         }
         rows.swap(keep); grow.swap(gk);
@@ -330,6 +362,11 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
     const int ldg = std::max(2, round_up(mg, 2));
     o.ldg = ldg;
     o.ldy = ldz + ldg;
+    o.g_soft.assign(ldg, 0.0);
+    for (int r = 0; r < mg; r++) {
+        o.g_soft[r] = rows[r].soft;
+        if (rows[r].soft > 0.0) o.n_soft++;
+    }
 
     if (light) {
         // everything the device fills: allocated, zero (padding stays zero)
@@ -393,6 +430,8 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
         }
     for (int r = 0; r < mg; r++)
         for (int s = 0; s < mg; s++) o.Y[(size_t)(ldz + r) * ldy + ldz + s] = GHG(r, s);
+    // a soft row: the hard row with 1 / rho on its diagonal entry of the dual Hessian (the slack's own curvature); nothing else of it differs
+    for (int r = 0; r < mg; r++) o.Y[(size_t)(ldz + r) * ldy + ldz + r] += o.g_soft[r];
 
     // ADMM step sizes.  adaptive_rho: rho_i = kappa / Y_ii (Jacobi preconditioning of the dual
     // problem -- the model-level equivalent of what OSQP's per-solve adaptation converges to);
@@ -411,7 +450,7 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
     o.g_kind.assign(ldg, 0); o.g_step.assign(ldg, 0); o.g_comp.assign(ldg, 0); o.g_refrow.assign(ldg, -1);
     for (int r = 0; r < mg; r++) {
         o.lg0[r] = rows[r].lo; o.ug0[r] = rows[r].hi;
-        double rr = prm.adaptive_rho ? kappa / std::max(GHG(r, r), 1e-300) : prm.rho;
+        double rr = prm.adaptive_rho ? kappa / std::max(GHG(r, r) + o.g_soft[r], 1e-300) : prm.rho;
         if (rows[r].lo == rows[r].hi) rr *= 1e3;
         o.rho_g[r] = clampr(rr);
         o.g_kind[r] = rows[r].kind; o.g_step[r] = rows[r].step; o.g_comp[r] = rows[r].comp;
@@ -511,6 +550,7 @@ void LmpcController::assemble_host(const Condensed &o, const double *x0, const d
             for (int dd = 0; dd < ndu; dd++) v += Dd(cp, dd) * dM(dd, st > 0 ? st - 1 : 0);
         } else if (kind == G_SCALAR) {
             for (int c = 0; c < nx; c++) v += sX[c] * xb[(size_t)st * nx + c];
+            if (st == 0) for (int j = 0; j < nu; j++) v += sU[j] * u0[j];      // (a soft step-0 row: lastU is data there)
         } else {
             v = st == 1 ? -u0[cp] : 0.0;        // G_RATE: delta_0 = v_1 - lastU; no free response, no disturbance
         }
@@ -586,10 +626,12 @@ void LmpcController::build_fast_maps(Condensed &o) const
     o.slo.assign(o.ns16, -kInf); o.shi.assign(o.ns16, kInf);
     {
         int q = 0;
-        for (int a = 0; a < nx; a++, q++) { o.slo[q] = minX(a, 0); o.shi[q] = maxX(a, 0); }
+        // (a soft step-0 row is a general row: its feasibility row stays in place, unbounded)
+        for (int a = 0; a < nx; a++, q++) if (!std::isfinite(softX(a, 0))) { o.slo[q] = minX(a, 0); o.shi[q] = maxX(a, 0); }
         for (int j = 0; j < nu; j++, q++) { o.slo[q] = minU(j, 0); o.shi[q] = maxU(j, 0); }
-        for (int a = 0; a < ny; a++, q++) { o.slo[q] = minY(a, 0); o.shi[q] = maxY(a, 0); }
-        o.slo[q] = sMin[0]; o.shi[q] = sMax[0]; q++;
+        for (int a = 0; a < ny; a++, q++) if (!std::isfinite(softY(a, 0))) { o.slo[q] = minY(a, 0); o.shi[q] = maxY(a, 0); }
+        if (!std::isfinite(softS[0])) { o.slo[q] = sMin[0]; o.shi[q] = sMax[0]; }
+        q++;
         for (auto &fr : o.fixed_rows) { o.slo[q] = fr.lo; o.shi[q] = fr.hi; q++; }
     }
 

@@ -47,6 +47,7 @@ struct GeneralRow {
     int kind, step, comp;   // which functional of the predicted trajectory
     int refrow;             // row in the reference QP's inequality block numbering + neq offset applied later
     double lo, hi;          // bounds before the per-instance free-response offset
+    double soft = 0.0;      // 1 / weight of a soft row, 0: hard
 };
 
 struct BoxRef {            // a reference row that bounds condensed variable `var`
@@ -63,6 +64,16 @@ struct Condensed {
     size_t big_n[5] = {0, 0, 0, 0, 0};           // structure-only condensing: the lengths H, Kinv, Gr, Gc, Y would have (they stay empty)
     std::vector<double> lw, uw, rho_b;           // [ldz]
     std::vector<double> lg0, ug0, rho_g;         // [ldg]
+    std::vector<double> g_soft;                  // [ldg] 1 / weight of a soft general row, 0 for a hard one and for the padding
+    int n_soft = 0;                              // soft general rows: by how many a working set may exceed nz
+    // what LmpcDev::rho_g points to, [2 ldg]: the step sizes, then g_soft (MPCX_G_SOFT in lmpc_device.hpp reads the second half).  The one place
+    // that builds the combined array: every upload of rho_g goes through it; the device condensing rewrites the first half only
+    std::vector<double> rho_g_device() const
+    {
+        std::vector<double> v(rho_g);
+        v.insert(v.end(), g_soft.begin(), g_soft.end());
+        return v;
+    }
     std::vector<int> g_kind, g_step, g_comp, g_refrow;      // [ldg]
     std::vector<GeneralRow> fixed_rows;          // rows that do not depend on the decision variables
     std::vector<int> boxrow_ptr, boxrow_ref;     // CSR var -> reference rows
@@ -100,6 +111,9 @@ struct LmpcController {
     Mat wOutput, wU, wDeltaU;
     Mat minX, maxX, minY, maxY, minU, maxU;
     Mat minDU, maxDU;       // [nu x ph], column i bounds delta_i (no column shift, as wDeltaU); columns past ch are kept and not read
+    // soft-constraint weights of the state / output / scalar rows, internal columns as the bounds they go with; +inf: the row is hard
+    Mat softX, softY;
+    std::vector<double> softS;
     std::vector<double> sMin, sMax, sX, sU;
     // LOptimizer state
     Mat yRef, uRef, duRef, dMeas;
@@ -122,6 +136,10 @@ struct LmpcController {
     // bounds on the input increments: the reference builds these rows and offers no setter for them (ProblemBuilder.hpp:768-793)
     void set_rate_bounds(const double *lo, const double *hi);
     void set_rate_bounds_idx(int idx, const double *lo, const double *hi);
+    // weights of the penalty 0.5 rho dist^2(row value, [lo, hi]) that replaces a state / output / scalar row (no counterpart in the reference's
+    // LMPC); a null pointer leaves that kind as it is.  idx form: the column shift of set_state_bounds_idx
+    void set_soft_weights(const double *xw, const double *yw, const double *sw);
+    void set_soft_weights_idx(int idx, const double *xw, const double *yw, const double *sw);
     void set_scalar_vec(const double *smin, const double *smax, const double *X, const double *U);
     void set_scalar_idx(int idx, double smin, double smax, const double *X, const double *U);
 

@@ -111,6 +111,7 @@ static void fill_dev_scalars(const mpcx_lmpc *h, const mpcx::LmpcController &c, 
     D.m_ref = o.m_ref; D.neq_ref = o.neq_ref; D.active_words = o.active_words;
     D.has_dist = o.has_dist ? 1 : 0;
     D.n_fixed = (int)o.fixed_rows.size();
+    D.n_soft = o.n_soft;                 // (before lmpc_lds_per_wave: the working-set lists are sized by it)
     D.max_iter = c.prm.maximum_iteration; D.polish = c.prm.polish ? 1 : 0;
     D.strict_infeasible = h->strict_infeasible ? 1 : 0;
     D.cost_direct = (o.h_regularised || o.inverse_residual > 1e-9) ? 1 : 0;
@@ -120,7 +121,9 @@ static void fill_dev_scalars(const mpcx_lmpc *h, const mpcx::LmpcController &c, 
     D.eps_abs = c.prm.eps_abs; D.eps_rel = c.prm.eps_rel; D.eps_prim_inf = c.prm.eps_prim_inf;
     D.lds_per_wave = mpcx::lmpc_lds_per_wave(D, &D.stage_len, &D.arena_len);
     D.wsld = D.ldz + D.ldy + 2 * D.ldg + 2;
-    D.s0lo = c.sMin[0]; D.s0hi = c.sMax[0];
+    // (a soft step-0 row is a general row, not a feasibility condition: Condensed::g_soft)
+    const bool soft0 = std::isfinite(c.softS[0]);
+    D.s0lo = soft0 ? -mpcx::kInf : c.sMin[0]; D.s0hi = soft0 ? mpcx::kInf : c.sMax[0];
 }
 
 // ... and arrays, through an uploader (one hipMalloc per array for a single controller, offsets into one slab for a bank of them)
@@ -134,9 +137,9 @@ static void fill_dev_arrays(const mpcx_lmpc *h, const mpcx::LmpcController &c, c
     D.duref_s = U.up(c.duRef.a, rc); D.dmeas_s = U.up(c.dMeas.a, rc);
     {
         std::vector<double> lo0x(c.d.nx), hi0x(c.d.nx), lo0u(c.d.nu), hi0u(c.d.nu), lo0y(c.d.ny), hi0y(c.d.ny);
-        for (int j = 0; j < c.d.nx; j++) { lo0x[j] = c.minX(j, 0); hi0x[j] = c.maxX(j, 0); }
+        for (int j = 0; j < c.d.nx; j++) { const bool soft = std::isfinite(c.softX(j, 0)); lo0x[j] = soft ? -mpcx::kInf : c.minX(j, 0); hi0x[j] = soft ? mpcx::kInf : c.maxX(j, 0); }
         for (int j = 0; j < c.d.nu; j++) { lo0u[j] = c.minU(j, 0); hi0u[j] = c.maxU(j, 0); }
-        for (int j = 0; j < c.d.ny; j++) { lo0y[j] = c.minY(j, 0); hi0y[j] = c.maxY(j, 0); }
+        for (int j = 0; j < c.d.ny; j++) { const bool soft = std::isfinite(c.softY(j, 0)); lo0y[j] = soft ? -mpcx::kInf : c.minY(j, 0); hi0y[j] = soft ? mpcx::kInf : c.maxY(j, 0); }
         D.lo0x = U.up(lo0x, rc); D.hi0x = U.up(hi0x, rc); D.lo0u = U.up(lo0u, rc); D.hi0u = U.up(hi0u, rc);
         D.lo0y = U.up(lo0y, rc); D.hi0y = U.up(hi0y, rc);
         D.sX = U.up(c.sX, rc); D.sU = U.up(c.sU, rc);
@@ -147,7 +150,7 @@ static void fill_dev_arrays(const mpcx_lmpc *h, const mpcx::LmpcController &c, c
         D.H = U.up_big(o.H, rc); D.Kinv = U.up_big(o.Kinv, rc); D.Gr = U.up_big(o.Gr, rc); D.Gc = U.up_big(o.Gc, rc); D.Y = U.up_big(o.Y, rc);
     }
     D.lw = U.up(o.lw, rc); D.uw = U.up(o.uw, rc); D.rho_b = U.up(o.rho_b, rc);
-    D.lg0 = U.up(o.lg0, rc); D.ug0 = U.up(o.ug0, rc); D.rho_g = U.up(o.rho_g, rc);
+    D.lg0 = U.up(o.lg0, rc); D.ug0 = U.up(o.ug0, rc); D.rho_g = U.up(o.rho_g_device(), rc);
     D.g_kind = U.up(o.g_kind, rc); D.g_step = U.up(o.g_step, rc); D.g_comp = U.up(o.g_comp, rc); D.g_refrow = U.up(o.g_refrow, rc);
     {
         std::vector<int> fk, fs, fc; std::vector<double> fl, fh;
@@ -482,6 +485,33 @@ int mpcx_lmpc_set_output_bounds_slice(mpcx_lmpc_t h, const double *lo, const dou
     }
     h->dirty = true;
     return MPCX_OK;
+}
+
+// Soft constraints: a weight per state / output / scalar row, +inf = hard.  No counterpart in the reference's LMPC (its NLMPC has one slack for all
+// rows, NLOptimizer.hpp:182-186).  A weight where no bound is finite is stored and has no effect.
+static bool soft_weights_ok(const double *w, int n)
+{
+    for (int j = 0; w && j < n; j++)
+        if (!(w[j] > 0.0)) return false;      // NaN, zero, negative
+    return true;
+}
+int mpcx_lmpc_set_soft_constraint_weights_slice(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw, int start, int end)
+{
+    CHECK_H(h);
+    auto &c = h->ctl;
+    if (!soft_weights_ok(xw, c.d.nx) || !soft_weights_ok(yw, c.d.ny) || !soft_weights_ok(sw, 1))
+        return fail(MPCX_E_INVALID, "soft constraint weights: NaN, zero or negative");
+    if (start == -1 && end == -1) c.set_soft_weights(xw, yw, sw);
+    else {
+        if (!c.pred_slice_valid(start, end)) return fail(MPCX_E_INVALID, "The prediction horizon slice is out of bounds");
+        for (int i = start; i < end; i++) c.set_soft_weights_idx(i, xw, yw, sw);
+    }
+    h->dirty = true;
+    return MPCX_OK;
+}
+int mpcx_lmpc_set_soft_constraint_weights(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw)
+{
+    return mpcx_lmpc_set_soft_constraint_weights_slice(h, xw, yw, sw, -1, -1);
 }
 
 int mpcx_lmpc_set_scalar_constraint_slice(mpcx_lmpc_t h, double smin, double smax, const double *X, const double *U, int start, int end)
@@ -1551,6 +1581,10 @@ int mpcx_lmpc_hetero_create_ex(const mpcx_lmpc_t *controllers, int count, int de
                           ok.nz == o0.nz && ok.mg == o0.mg && ok.g_refrow == o0.g_refrow && ok.boxrow_ptr == o0.boxrow_ptr && ok.boxrow_ref == o0.boxrow_ref &&
                           ok.fixed_rows.size() == o0.fixed_rows.size() && ok.blk == o0.blk;
         if (!same) return fail(MPCX_E_INVALID, "controller " + std::to_string(k) + " differs from controller 0 in dimensions or in which bounds are finite");
+        // ... and one pattern of soft rows; the weights may differ
+        for (size_t r = 0; r < o0.g_soft.size(); ++r)
+            if ((ok.g_soft[r] > 0.0) != (o0.g_soft[r] > 0.0))
+                return fail(MPCX_E_INVALID, "controller " + std::to_string(k) + " differs from controller 0 in which constraint rows are soft");
     }
     std::unique_ptr<mpcx_lmpc_hetero> f(new mpcx_lmpc_hetero);
     f->device = device; f->count = count; f->d = c0.d; f->active_words = o0.active_words; f->m_ref = o0.m_ref;
@@ -1647,7 +1681,7 @@ int mpcx_lmpc_hetero_debug_get(mpcx_lmpc_hetero_t f, int k, const char *name, do
     if (n == "H") { src = D.H; len = (size_t)D.ldz * D.ldz; } else if (n == "Kinv") { src = D.Kinv; len = (size_t)D.ldz * D.ldz; }
     else if (n == "Gr") { src = D.Gr; len = (size_t)D.ldg * D.ldz; } else if (n == "Gc") { src = D.Gc; len = (size_t)D.ldz * D.ldg; }
     else if (n == "Y") { src = D.Y; len = (size_t)D.ldy * D.ldy; } else if (n == "rho_b") { src = D.rho_b; len = (size_t)D.ldz; }
-    else if (n == "rho_g") { src = D.rho_g; len = (size_t)D.ldg; }
+    else if (n == "rho_g") { src = D.rho_g; len = (size_t)D.ldg; } else if (n == "g_soft") { src = MPCX_G_SOFT(D); len = (size_t)D.ldg; }
     else if (n == "flags") {       // cost_direct, condensed on the device, condensing kernel ms, whole create ms, set-up flops per controller
         if (out && cap >= 5) { out[0] = D.cost_direct; out[1] = f->condensed_on_device ? 1.0 : 0.0; out[2] = f->setup_kernel_ms; out[3] = f->setup_total_ms; out[4] = f->setup_flops; }
         return 5;
@@ -1827,7 +1861,7 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     if (n == "H") v = &o.H; else if (n == "Kinv") v = &o.Kinv; else if (n == "Gr") v = &o.Gr;
     else if (n == "Gc") v = &o.Gc; else if (n == "Y") v = &o.Y; else if (n == "lw") v = &o.lw;
     else if (n == "uw") v = &o.uw; else if (n == "rho_b") v = &o.rho_b; else if (n == "lg0") v = &o.lg0;
-    else if (n == "ug0") v = &o.ug0; else if (n == "rho_g") v = &o.rho_g;
+    else if (n == "ug0") v = &o.ug0; else if (n == "rho_g") v = &o.rho_g; else if (n == "g_soft") v = &o.g_soft;
     else if (n == "dims") {
         tmp = {(double)o.nz, (double)o.mg, (double)o.ldz, (double)o.ldg, (double)o.ldy, (double)o.nf,
                (double)o.n_ref, (double)o.m_ref, (double)o.neq_ref, (double)o.fixed_rows.size(),
@@ -1850,6 +1884,11 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "g_step") { tmp.assign(o.g_step.begin(), o.g_step.end()); v = &tmp; }
     else if (n == "g_kind") { tmp.assign(o.g_kind.begin(), o.g_kind.end()); v = &tmp; }
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }
+    else if (n == "slo") v = &o.slo; else if (n == "shi") v = &o.shi;
+    else if (n == "ws_limit") {           // most rows a working set may hold, the lists' capacity, doubles of a wavefront's large-working-set slot
+        tmp = {(double)mpcx::ws_limit(o.nz, o.mg, o.n_soft), (double)mpcx::ws_capacity(mpcx::ws_limit(o.nz, o.mg, o.n_soft)), (double)mpcx::lmpc_slot_len(h->dev)};
+        v = &tmp;
+    }
     else if (n == "fallback") {           // the failure queue: served in the last step that had failures, capacity, fallback wavefronts
         tmp.assign(3, 0.0);
         if (out && !h->host_only) {

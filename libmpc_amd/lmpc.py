@@ -546,6 +546,21 @@ class LMPC(_LoopFrontEnd):
         return self._bounds(DUMin, DUMax, self.nu, self.ph, self._lib.mpcx_lmpc_set_input_rate_bounds,
                             self._lib.mpcx_lmpc_set_input_rate_bounds_slice, slice)
 
+    def setSoftConstraintWeights(self, xw, yw, sw, slice=None):
+        """extension: soft state / output / scalar rows.  A weight rho in (0, inf] per state component (xw[nx]), per output component
+        (yw[ny]) and for the scalar row (sw); inf keeps the row hard, a finite weight replaces it by 0.5 rho dist^2(row value, [lo, hi]) in
+        the cost.  None leaves that kind of row as it is.  Without a slice the whole horizon (steps 0 .. ph) is set; a slice works as
+        setStateBounds' does, so that the weight lands on the rows the same slice bounds.  Input and input-rate bounds stay hard.
+        False for NaN, zero or a negative weight and for a bad slice.  The reference's LMPC has no counterpart."""
+        x = None if xw is None else _vec(np.broadcast_to(np.asarray(xw, dtype=np.float64), (self.nx,)) if np.ndim(xw) == 0 else xw, self.nx)
+        y = None if yw is None else _vec(np.broadcast_to(np.asarray(yw, dtype=np.float64), (self.ny,)) if np.ndim(yw) == 0 else yw, self.ny)
+        s = None if sw is None else _vec([float(sw)], 1)
+        px, py, ps = (None if a is None else _p(a) for a in (x, y, s))
+        if slice is None:
+            return self._ok(self._lib.mpcx_lmpc_set_soft_constraint_weights(self._h, px, py, ps))
+        sl = _slice(slice)
+        return self._ok(self._lib.mpcx_lmpc_set_soft_constraint_weights_slice(self._h, px, py, ps, sl.start, sl.end))
+
     def setScalarConstraint(self, *args):
         """(min, max, X, U, slice) as LMPC.hpp:355 or (index, min, max, X, U) as LMPC.hpp:409."""
         if len(args) != 5:
