@@ -164,6 +164,17 @@ int mpcx_lmpc_set_input_rate_bounds_slice(mpcx_lmpc_t h, const double *dumin, co
  * MPCX_E_INVALID: NaN, zero or a negative weight; a slice out of bounds. */
 int mpcx_lmpc_set_soft_constraint_weights(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw);
 int mpcx_lmpc_set_soft_constraint_weights_slice(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw, int start, int end);
+/* Terminal cost: the term 0.5 (x_ph - x_T)' P (x_ph - x_T) on the last predicted state, with
+ *     x_T = xT + Tr yref(., ph - 1) + Td dmeas(., ph - 1),   Tx = [Tr | Td]  [nx x (ny + ndu)] column-major.
+ * P [nx x nx] column-major, symmetric positive semidefinite -- with the cost-to-go of the unconstrained problem (mpcx_dare_batch, control form)
+ * a short horizon behaves like an infinite one.  xT [nx] is a constant target; the columns of Tx are the first ny + ndu columns of map_x of
+ * mpcx_target_map_batch, so that the target follows the instance's own output reference (shared, per-instance or per-step: the column step ph
+ * reads) and its own exogenous input -- the disturbance estimate in an offset-free loop.  A null xT or Tx means zeros; a null P removes the term.
+ * x_ph is the state reached with the blocked inputs.  `cost` stays 0.5 z' P z + q' z of the QP: the constant 0.5 x_T' P x_T is dropped, as
+ * 0.5 r' W r of the output term is.  Row numbering, m_ref and active_words do not change.  The reference's LMPC has no counterpart
+ * (DESIGN.md 3.3).  MPCX_E_INVALID, nothing stored: a NaN or infinite entry; |P - P'|_max > 1e-10 |P|_max (below that the symmetrised
+ * matrix is stored); a smallest eigenvalue below -1e-10 |P|_max. */
+int mpcx_lmpc_set_terminal_cost(mpcx_lmpc_t h, const double *P, const double *xT, const double *Tx);
 /* LMPC::setScalarConstraint slice form (LMPC.hpp:355) and index form (LMPC.hpp:409) */
 int mpcx_lmpc_set_scalar_constraint_slice(mpcx_lmpc_t h, double smin, double smax, const double *X, const double *U,
                                           int start, int end);
@@ -748,7 +759,9 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
 /* condensed arrays of the host set-up by name ("H", "Kinv", "Gr", "Gc", "Y", "lw", "uw", "rho_b", "lg0", "ug0", "rho_g", "dims",
  * "dims_maps", "MA0", "MA1", "g_refrow", "g_step", "g_kind", "g_comp", "flags" = [cost from its definition, one-workgroup form
  * available, fused mat-vec form available], "fallback" = [instances the fallback kernel served in the last step that left it any (reading
- * clears it), entries the failure queue holds, wavefronts of the fallback kernel's grid]); out = NULL returns the length                     */
+ * clears it), entries the failure queue holds, wavefronts of the fallback kernel's grid], "terminal" = the stored terminal cost
+ * [P | xT | Tx], P symmetrised, empty without one, "wOutput" / "wU" = the output and input weights as stored, [ny | nu x (ph + 1)] column-major,
+ * user column k in internal column k + 1); out = NULL returns the length                                                                      */
 int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap);
 /* how many full set-ups (condensing + device rebuild) and how many reference-only refreshes have run on this handle */
 int mpcx_lmpc_debug_setup_counts(mpcx_lmpc_t h, int *full, int *refs);

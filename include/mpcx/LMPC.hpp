@@ -219,6 +219,11 @@ public:
     {
         return ok(mpcx_lmpc_set_soft_constraint_weights_slice(h_, xw, yw, sw, s.start, s.end));
     }
+    // extension: the terminal cost 0.5 (x_ph - x_T)' P (x_ph - x_T), x_T = xT + Tx [yref(., ph - 1); dmeas(., ph - 1)] (mpcx_lmpc_set_terminal_cost;
+    // the reference's LMPC has no counterpart).  P symmetric positive semidefinite; the pointer form takes null for zeros, and a null P removes the term
+    bool setTerminalCost(const mat<Tnx, Tnx> &P) { return ok(mpcx_lmpc_set_terminal_cost(h_, P.data(), nullptr, nullptr)); }
+    bool setTerminalCost(const mat<Tnx, Tnx> &P, const cvec<Tnx> &xT) { return ok(mpcx_lmpc_set_terminal_cost(h_, P.data(), xT.data(), nullptr)); }
+    bool setTerminalCost(const double *P, const double *xT, const double *Tx) { return ok(mpcx_lmpc_set_terminal_cost(h_, P, xT, Tx)); }
     bool setScalarConstraint(const double mn, const double mx, const cvec<Tnx> X, const cvec<Tnu> U, const HorizonSlice &s)   // LMPC.hpp:355
     {
         return ok(mpcx_lmpc_set_scalar_constraint_slice(h_, mn, mx, X.data(), U.data(), s.start, s.end));

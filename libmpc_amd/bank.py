@@ -44,6 +44,8 @@ class LMPCBank:
         for c in controllers:
             if (c.nx, c.nu, c.ny, c.ph, c.device) != (c0.nx, c0.nu, c0.ny, c0.ph, c0.device):
                 raise ValueError("the controllers of a bank share their dimensions and their device")
+            if c._has_terminal != c0._has_terminal:
+                raise ValueError("a bank has a terminal cost in every controller or in none (setTerminalCost); P, xT and Tx may differ")
         self.controllers = list(controllers)
         self.nx, self.nu, self.ny, self.ph, self.device = c0.nx, c0.nu, c0.ny, c0.ph, c0.device
         self._streams = [torch.cuda.Stream(device=self.device) for _ in controllers]
@@ -116,6 +118,7 @@ class LMPCHetero(_LoopFrontEnd):
         self._models = [(c._A, c._B, c._Bd) for c in controllers]        # as given to the setters: what plants=(A, None, None) completes
         self._outputs = [c._C for c in controllers]
         self._feedthrough = [c._Dd for c in controllers]
+        self._controllers = list(controllers)                            # (their handles hold the weights: lqr_terminal_costs)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -210,6 +213,19 @@ class LMPCHetero(_LoopFrontEnd):
                    3: "the doubling iteration broke down"}[int(flags[k])]
             raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {k}: {why}")
         return L
+
+    def lqr_terminal_costs(self, step=1):
+        """LMPC.lqr_terminal_cost for every controller of the bank, (P [count, nx, nx], K [count, nu, nx]) on the device, in one batched
+        mpcx_dare_batch call (libmpc_amd.utils.lqr_gains).  A terminal cost is part of a controller: give each its P with setTerminalCost
+        before the bank is created from them.  ValueError where an input weight is not positive; MpcxError naming the first controller whose
+        equation was not solved."""
+        from .utils import lqr_gains
+        A, B, Q, R = (np.stack(m) for m in zip(*[c._lqr_problem(step) for c in self._controllers]))
+        K, X, flags = lqr_gains(A, B, Q, R, device=self.device)
+        bad = torch.nonzero(flags).reshape(-1)
+        if bad.numel():
+            raise _capi.MpcxError(_capi.E_NUMERIC, f"controller {int(bad[0])}: the Riccati equation was not solved (flag {int(flags[int(bad[0])])})")
+        return X, K
 
     def target_maps(self):
         """LMPC.target_map for every controller of the bank, [count, nu, ny+ndu+nu] on the device, in one batched call

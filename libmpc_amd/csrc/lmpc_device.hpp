@@ -40,14 +40,16 @@ struct LmpcDev {
     int strict_infeasible;                       // 1: report INFEASIBLE / NaN; 0: behave as the reference does
     int n_soft;                                  // soft general rows (in what was padding: every other field keeps its offset)
     double alpha, sigma, eps_abs, eps_rel, eps_prim_inf;
-    int adaptive_rho; double rho_user;            // LParameters::adaptive_rho / rho (the ADMM step sizes of the set-up)
+    int adaptive_rho; double rho_user;            // LParameters::adaptive_rho / rho (the ADMM step sizes of the set-up).  adaptive_rho is a flag word: bit 0
+                                                 // the parameter (MPCX_ADAPTIVE_RHO), bit 1 the terminal cost's presence (MPCX_HAS_TERMINAL) -- only the
+                                                 // condensing kernel and the launch of the generic assemble kernel (its template parameter TERM) read it
     // per-wave LDS carve (in doubles)
     int stage_len, arena_len, lds_per_wave;
     int fast_slice;                              // per-wave LDS slice of the lean solve kernels (doubles)
     int wsld;                                    // per-instance workspace record (doubles): f | t0 | gt0 | lg | ug | c0, flag
     // model, column-major
     const double *A, *B, *C, *Bd, *Dd;
-    const double *Wy, *Wu, *Wdu;                 // [(ph+1) x ny], [(ph+1) x nu], [ph x nu]; column = internal step
+    const double *Wy, *Wu, *Wdu;                 // [(ph+1) x ny], [(ph+1) x nu], [ph x nu]; column = internal step.  Wy: then MPCX_TERMINAL, if present
     const double *yref_s, *uref_s, *duref_s, *dmeas_s;   // shared references [ph x n]
     // step-0 feasibility rows
     const double *lo0x, *hi0x, *lo0u, *hi0u, *lo0y, *hi0y, *sX, *sU;
@@ -74,6 +76,12 @@ struct LmpcDev {
 // 1 / weight of a soft general row, 0 for a hard one and the padding, [ldg]: it rides behind the step sizes in rho_g's array.  The struct travels by
 // value in lmpc_solve_group's kernel arguments, sixteen cache lines to the byte (kernarg_touch): it has room for an int, not for a pointer
 #define MPCX_G_SOFT(M) ((M).rho_g + (M).ldg)
+// The terminal cost rides the same way: its presence in bit 1 of the flag word adaptive_rho, its data behind the output weights in
+// Wy's array, [Wy (ph + 1) ny | P nx nx | xT nx | Tx nx (ny + ndu)], all column-major; without the term the array ends with the weights
+#define MPCX_ADAPTIVE_RHO(M) (((M).adaptive_rho & 1) != 0)
+#define MPCX_HAS_TERMINAL(M) (((M).adaptive_rho & 2) != 0)
+#define MPCX_TERMINAL(M) ((M).Wy + ((M).ph + 1) * (M).ny)
+__host__ __device__ inline int lmpc_terminal_len(int nx, int ny, int ndu) { return nx * nx + nx + nx * (ny + ndu); }
 
 struct LmpcBatchDev {
     int batch;
@@ -100,6 +108,8 @@ struct LmpcBatchDev {
     const int32_t *model_index;
     long long *dbg_cycles;       // optional [B x 8] per-phase cycle counts (profiling aid)
 };
+// Both structs travel by value in lmpc_solve_group's kernel arguments, sixteen cache lines to the byte: a field added to either shows here first
+static_assert(sizeof(LmpcDev) == 712 && sizeof(LmpcBatchDev) == 296, "LmpcDev / LmpcBatchDev changed size: see kernarg_touch (lmpc_fast.hip)");
 // doubles of one wavefront's slot of the large-working-set buffer (LmpcScratch::pbuf)
 __host__ __device__ inline size_t lmpc_slot_len(const LmpcDev &m) { const size_t n = (size_t)ws_limit(m.nz, m.mg, m.n_soft); return n * n; }
 // which entry of the model array instance b uses

@@ -4,6 +4,7 @@
 // v_mfma_f64_16x16x4_f64:
 //     S_i = A S_{i-1} + B E_i            prediction matrices ("A^h, B-stack"), rolled over the horizon, never stored whole
 //     H   = sum_i (C S_i)' W_i (C S_i) + weights on the inputs and their increments                       (MFMA, nz x ny x nz per step)
+//           + S_ph' Pt S_ph, the terminal cost, where a controller has one                (MFMA, Pt S_ph and nz x nx x nz)
 //     G   = the rows of S_i / C S_i / sX' S_i the finite bounds select                                     (written as they appear)
 //     H = L L',  Hinv = L^-T L^-1        Cholesky in LDS, triangular inverse one column per thread, product on MFMA
 //     Y   = [Hinv, (G Hinv)'; G Hinv, G Hinv G']                                                          (MFMA)
@@ -108,6 +109,8 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
         double *rb = wv + ((ny + 3) & ~3) + 4, *rg = rb + NP;                  // rho_b [NP], rho_g [NQ]
         const gdp gA = gl(M.A), gB = gl(M.B), gC = gl(M.C), gWy = gl(M.Wy), gWu = gl(M.Wu), gWdu = gl(M.Wdu), gsX = gl(M.sX), gsU = gl(M.sU);
         const gip blk = gl(M.blk), gk = gl(M.g_kind), gs = gl(M.g_step), gc = gl(M.g_comp);
+        const bool term = MPCX_HAS_TERMINAL(M);                                       // terminal cost
+        const gdp gPt = gl(MPCX_TERMINAL(M));                                         // its weight, nx x nx column-major (read only under `term`)
         const gdp gso = gl(MPCX_G_SOFT(M));                                           // 1 / weight of a soft row, 0 for a hard one
         gdw oH = glw(const_cast<double *>(M.H)), oK = glw(const_cast<double *>(M.Kinv)), oGr = glw(const_cast<double *>(M.Gr)),
             oGc = glw(const_cast<double *>(M.Gc)), oY = glw(const_cast<double *>(M.Y)), orb = glw(const_cast<double *>(M.rho_b)),
@@ -194,6 +197,38 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
                     }
             }
             __syncthreads();
+            if (term && i == ph) {
+                // the terminal cost: Pt S_ph into Sp's buffer (S_{ph-1}, which nothing reads any more), then H += S_ph' (Pt S_ph) on the same tiles,
+                // each with the wavefront and the accumulator it has above
+                mfma_product((nx + 15) >> 4, npt, (nx + 3) >> 2,
+                             [&](int row, int k) { return (row < nx && k < nx) ? gPt[row + k * nx] : 0.0; },
+                             [&](int k, int col) { return k < nx ? Sn[k * ld + col] : 0.0; },
+                             [&](int row, int col, double v) { if (row < nx) Sp[row * ld + col] = v; }, wave, lane);
+                __syncthreads();
+                const int j = lane & 15, kq = lane >> 4, k4 = (nx + 3) >> 2;
+                int s = 0, tcount = 0;
+                for (int tm = 0; tm < npt; ++tm)
+                    for (int tn = tm; tn < npt; ++tn, ++tcount) {
+                        if ((tcount & (kCondWaves - 1)) != wave) continue;
+                        v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+                        for (int kb = 0; kb < k4; ++kb) {
+                            const int a = 4 * kb + kq;
+                            acc = mfma4(a < nx ? Sn[a * ld + 16 * tm + j] : 0.0, a < nx ? Sp[a * ld + 16 * tn + j] : 0.0, acc);
+                        }
+                        if constexpr (BIG) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int row = 16 * tm + 4 * r + kq, col = 16 * tn + j;
+                                if (row < nz && col < nz && row <= col) P[row * ld + col] += acc[r];
+                            }
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < MAXS; ++u) if (u == s) hacc[u] += acc;
+                        }
+                        ++s;
+                    }
+                __syncthreads();
+            }
             double *tmp = Sp; Sp = Sn; Sn = tmp;
         }
         if constexpr (BIG) {
@@ -312,14 +347,14 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
                 const double lo = gl(M.lw)[q], hi = gl(M.uw)[q];
                 double r = 0.0;
                 if (lo > -__builtin_huge_val() || hi < __builtin_huge_val()) {
-                    r = M.adaptive_rho ? kappa / fmax(P[q * ld + q], 1e-300) : M.rho_user;
+                    r = MPCX_ADAPTIVE_RHO(M) ? kappa / fmax(P[q * ld + q], 1e-300) : M.rho_user;
                     if (lo == hi) r *= 1e3;
                     r = fmin(fmax(r, rho_min), rho_max);
                 }
                 rb[q] = r; orb[q] = r;
             }
             for (int r0 = t; r0 < mg; r0 += blockDim.x) {
-                double r = M.adaptive_rho ? kappa / fmax(rg[r0], 1e-300) : M.rho_user;
+                double r = MPCX_ADAPTIVE_RHO(M) ? kappa / fmax(rg[r0], 1e-300) : M.rho_user;
                 if (gl(M.lg0)[r0] == gl(M.ug0)[r0]) r *= 1e3;
                 r = fmin(fmax(r, rho_min), rho_max);
                 rg[r0] = r; org[r0] = r;

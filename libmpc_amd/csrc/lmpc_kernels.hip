@@ -54,7 +54,9 @@ __device__ __forceinline__ void put(double *dst, const double (&v)[K], int n, in
     for (int e = lane + 64 * K; e < n; e += 64) dst[e] = at(e);      // shapes past 64 K elements: the slow way
 }
 
-template <int CPZ, int CPG>
+// TERM: the controller has a terminal cost.  A template parameter, chosen by the launch from the controller's flag word: without
+// the term the kernel is the code it has always been
+template <int CPZ, int CPG, bool TERM>
 __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
                              double *stage, double *arena, gdw ws)
 {
@@ -81,6 +83,8 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
     int *blks = reinterpret_cast<int *>(dms + ph * ndu);         // move-blocking map, ph+1 ints
     // the model matrices: the roll-out and the adjoint pass are chains of ph dependent steps that read them in every step
     double *gA = dms + ph * ndu + (ph + 2) / 2, *gB = gA + nx * nx, *gC = gB + nx * nu, *gBd = gC + ny * nx, *gDd = gBd + nx * ndu;
+    // the terminal cost's P (nx x nx), xT (nx: the whole target x_T once the references are in) and Tx (nx x (ny + ndu)); there only with the term
+    [[maybe_unused]] double *tP = gDd + ny * ndu, *txT = tP + nx * nx, *tTx = txT + nx;
 
     // ---- gather: everything this instance reads from global memory, in two groups of loads ----
     const gdp mA = GP(A), mB = GP(B), mC = GP(C), mBd = GP(Bd), mDd = GP(Dd);
@@ -128,10 +132,17 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
     put<KF>(ey, rR, ney, lane, atR);
     put<KF>(wur, rU, nuu, lane, atU);
     put<KF>(dur, rD, nuu, lane, atD);
-    if (has_dist) {
-        for (int e = lane; e < nx * ndu; e += 64) gBd[e] = mBd[e];
-        for (int e = lane; e < ny * ndu; e += 64) gDd[e] = mDd[e];
+    if (has_dist || TERM) {                       // (the terminal target follows the exogenous input whether or not the model has a disturbance channel)
+        if (has_dist) {
+            for (int e = lane; e < nx * ndu; e += 64) gBd[e] = mBd[e];
+            for (int e = lane; e < ny * ndu; e += 64) gDd[e] = mDd[e];
+        }
         for (int e = lane; e < ph * ndu; e += 64) { const int k = e / ndu; dms[e] = ref_at(gdm, Bt.dmeas_bs, Bt.dmeas_ks, b, k, e - k * ndu); }
+    }
+    if constexpr (TERM) {
+        const gdp gT = gl(MPCX_TERMINAL(M));
+        const int nterm = lmpc_terminal_len(nx, ny, ndu);
+        for (int e = lane; e < nterm; e += 64) tP[e] = gT[e];
     }
     for (int e = lane; e < ldz; e += 64) stage[e] = 0.0;
     wave_sync();
@@ -153,6 +164,14 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
         for (int c = 0; c < nx; ++c) s0 = fma(sxu[c], xb[c], s0);
         for (int c = 0; c < nu; ++c) s0 = fma(sxu[nx + c], u0s[c], s0);
         bad |= violates(s0, M.s0lo, M.s0hi, ea, er);
+    }
+
+    // terminal target x_T = xT + Tr yref(., ph - 1) + Td dmeas(., ph - 1): the last reference column is still in ey (the roll-out's barriers publish it)
+    if (TERM && lane < nx) {
+        double s = txT[lane];
+        for (int a = 0; a < ny; ++a) s = fma(tTx[lane + a * nx], ey[ph * ny + a], s);
+        for (int dd = 0; dd < ndu; ++dd) s = fma(tTx[lane + (ny + dd) * nx], dm(ph - 1, dd), s);
+        txT[lane] = s;
     }
 
     // horizon roll-out of the free response
@@ -183,6 +202,16 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
         const double u = u0v;
         c0 += wu0 * (0.5 * u * u - ur0 * u);
         c0 += wdu0 * (0.5 * u * u + dr0 * u);
+    }
+    // terminal cost: e_T = P (xbar_ph - x_T) seeds the adjoint of step ph; 0.5 xbar' P xbar - x_T' P xbar joins the constant (0.5 x_T' P x_T is dropped)
+    [[maybe_unused]] double eT = 0.0;
+    if (TERM && lane < nx) {
+        const double *xp = xb + ph * nx;
+        double px = 0, pt = 0;
+#pragma unroll 4
+        for (int c = 0; c < nx; ++c) { px = fma(tP[lane + c * nx], xp[c], px); pt = fma(tP[lane + c * nx], txT[c], pt); }
+        eT = px - pt;
+        c0 += (0.5 * px - pt) * xp[lane];
     }
     c0 = wave_sum(c0);
 
@@ -240,6 +269,7 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
         if (lane < nx) {
             const double *pin = pall + (i + 1) * nx;
             double s = pall[i * nx + lane];
+            if (TERM && i == ph) s += eT;         // the terminal cost's seed: p_ph = C' ey_ph + e_T (the slot behind step ph holds zeros)
 #pragma unroll 4
             for (int a = 0; a < nx; ++a) s = fma(gA[a + lane * nx], pin[a], s);
             pall[i * nx + lane] = s;
@@ -365,7 +395,7 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
     wave_sync();
 }
 
-template <int CPZ, int CPG>
+template <int CPZ, int CPG, bool TERM>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_assemble_generic(const LmpcDev *__restrict__ Mp, const LmpcBatchDev Bt, double *wsbase)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -375,7 +405,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_assemble_generic(con
     double *arena = stage + M0.stage_len + M0.ldy;
     const int b = blockIdx.x * (blockDim.x >> 6) + wave;             // one instance per wavefront; the grid covers the batch
     if (b < Bt.batch)
-        assemble_one<CPZ, CPG>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, arena, glw(wsbase) + (size_t)b * M0.wsld);
+        assemble_one<CPZ, CPG, TERM>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, arena, glw(wsbase) + (size_t)b * M0.wsld);
 }
 
 
@@ -1511,10 +1541,12 @@ int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b
     double *const ws = sc.ws;
     const size_t lds = (size_t)kWavesPerBlock * m.lds_per_wave * sizeof(double);
     if (lds > lmpc_lds_limit()) return -2;
-    auto k1 = lmpc_assemble_generic<CPZ, CPG>;
+    // (a bank has the term in every controller or in none: model 0's flag speaks for the launch)
+    auto k1 = MPCX_HAS_TERMINAL(m) ? lmpc_assemble_generic<CPZ, CPG, true> : lmpc_assemble_generic<CPZ, CPG, false>;
     auto k3 = lmpc_solve_admm<CPZ, CPG>;
     static LmpcLdsCache configured;
-    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(k1), reinterpret_cast<const void *>(k3)}, lds) != 0) return -3;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, false>), reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, true>),
+                                            reinterpret_cast<const void *>(k3)}, lds) != 0) return -3;
     int blocks = (b.batch + kWavesPerBlock - 1) / kWavesPerBlock;
     const int cap = 256 * 8;
     if (blocks > cap) blocks = cap;
@@ -1591,6 +1623,7 @@ int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len)
     st = (st + 1) / 2 * 2;
     int a1 = (m.ph + 1) * (m.nx + 2 * m.ny) + (m.ph + 2) * m.nx + 2 * m.ph * m.nu + m.nu + (m.nx + m.nu) + m.ph * m.ndu + (m.ph + 2) / 2 + 8 +
              m.nx * m.nx + m.nx * m.nu + m.ny * m.nx + m.nx * m.ndu + m.ny * m.ndu;      // assemble_one's plan, model matrices last
+    if (MPCX_HAS_TERMINAL(m)) a1 += lmpc_terminal_len(m.nx, m.ny, m.ndu);                // ... and the terminal cost's P, xT, Tx behind them
     const int wcap = ws_capacity(ws_limit(m.nz, m.mg, m.n_soft));
     int a2 = kMaxActive * kSld + 3 * wcap + (wcap + 1) / 2;      // S, lam, wsb, dg0, wsidx (ints)
     int ar = a1 > a2 ? a1 : a2;

@@ -193,6 +193,72 @@ void LmpcController::set_scalar_idx(int idx, double smin, double smax, const dou
     sX.assign(X, X + d.nx); sU.assign(U, U + d.nu);   // the multiplier is shared by all steps
 }
 
+// smallest eigenvalue of a symmetric matrix by cyclic Jacobi rotations (nx <= 64: a set-up step)
+static double min_eigenvalue_sym(Mat S)
+{
+    const int n = S.r;
+    for (int sweep = 0; sweep < 60; sweep++) {
+        double off = 0, dia = 0;
+        for (int j = 0; j < n; j++)
+            for (int i = 0; i < n; i++) (i == j ? dia : off) += S(i, j) * S(i, j);
+        if (!(off > 1e-30 * dia)) break;
+        for (int p = 0; p < n - 1; p++)
+            for (int q = p + 1; q < n; q++) {
+                const double apq = S(p, q);
+                if (apq == 0.0) continue;
+                const double theta = (S(q, q) - S(p, p)) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; k++) { const double kp = S(k, p), kq = S(k, q); S(k, p) = c * kp - s * kq; S(k, q) = s * kp + c * kq; }
+                for (int k = 0; k < n; k++) { const double pk = S(p, k), qk = S(q, k); S(p, k) = c * pk - s * qk; S(q, k) = s * pk + c * qk; }
+            }
+    }
+    double lo = kInf;
+    for (int i = 0; i < n; i++) lo = std::min(lo, S(i, i));
+    return lo;
+}
+
+std::string LmpcController::set_terminal_cost(const double *P, const double *xT, const double *Tx)
+{
+    const int nx = d.nx, nt = d.ny + d.ndu;
+    if (!P) {
+        have_terminal = false;
+        termP = Mat(); termTx = Mat(); termXT.clear();
+        return std::string();
+    }
+    for (int e = 0; e < nx * nx; e++) if (!std::isfinite(P[e])) return "terminal cost: P has a NaN or infinite entry";
+    for (int e = 0; xT && e < nx; e++) if (!std::isfinite(xT[e])) return "terminal cost: xT has a NaN or infinite entry";
+    for (int e = 0; Tx && e < nx * nt; e++) if (!std::isfinite(Tx[e])) return "terminal cost: Tx has a NaN or infinite entry";
+    double pmax = 0, asym = 0;
+    for (int j = 0; j < nx; j++)
+        for (int i = 0; i < nx; i++) {
+            pmax = std::max(pmax, std::fabs(P[i + (size_t)j * nx]));
+            asym = std::max(asym, std::fabs(P[i + (size_t)j * nx] - P[j + (size_t)i * nx]));
+        }
+    if (asym > 1e-10 * pmax) return "terminal cost: P is not symmetric";
+    Mat S(nx, nx);
+    for (int j = 0; j < nx; j++)
+        for (int i = 0; i < nx; i++) S(i, j) = 0.5 * (P[i + (size_t)j * nx] + P[j + (size_t)i * nx]);
+    if (min_eigenvalue_sym(S) < -1e-10 * pmax) return "terminal cost: P is not positive semidefinite";
+    termP = S;
+    termXT.assign(nx, 0.0);
+    if (xT) termXT.assign(xT, xT + nx);
+    termTx = Mat(nx, nt);
+    if (Tx) std::memcpy(termTx.a.data(), Tx, sizeof(double) * nx * nt);
+    have_terminal = true;
+    return std::string();
+}
+
+std::vector<double> LmpcController::terminal_block() const
+{
+    std::vector<double> v;
+    if (!have_terminal) return v;
+    v.insert(v.end(), termP.a.begin(), termP.a.end());
+    v.insert(v.end(), termXT.begin(), termXT.end());
+    v.insert(v.end(), termTx.a.begin(), termTx.a.end());
+    return v;
+}
+
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 std::string LmpcController::condense(Condensed &o, const Condensed *like) const
@@ -247,6 +313,17 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
             }
         for (int j = 0; j < nu; j++) H(o.blk[i] * nu + j, o.blk[i] * nu + j) += wU(j, i);
         o.flops_setup += 2.0 * ny * nx * nz + 1.0 * ny * nz * nz;
+    }
+    if (have_terminal && !light) {
+        // terminal cost: H += Sx_ph' P Sx_ph, the state reached with the blocked inputs
+        Mat PS = matmul(termP, Sx[ph]);                  // nx x nz
+        for (int q = 0; q < nz; q++)
+            for (int p = 0; p <= q; p++) {
+                double s = 0;
+                for (int a = 0; a < nx; a++) s += Sx[ph](a, p) * PS(a, q);
+                H(p, q) += s;
+            }
+        o.flops_setup += 2.0 * nx * nx * nz + 1.0 * nx * nz * nz;
     }
     for (int i = 0; i < ph; i++) {
         // delta_i = v_{i+1} - v_i (v_0 = u0 is data)
@@ -541,6 +618,22 @@ void LmpcController::assemble_host(const Condensed &o, const double *x0, const d
         c0 += wU(j, 0) * (0.5 * u * u - uR(j, 0) * u);
         c0 += wDeltaU(j, 0) * (0.5 * u * u + dR(j, 0) * u);
     }
+    // terminal cost: e_T = P (xbar_ph - x_T) seeds the adjoint at step ph; the constant 0.5 x_T' P x_T is dropped, as 0.5 r' W r is
+    std::vector<double> eT(nx, 0.0);
+    if (have_terminal) {
+        std::vector<double> xT(termXT), Px(nx, 0.0), PxT(nx, 0.0);
+        for (int a = 0; a < nx; a++) {
+            for (int c = 0; c < ny; c++) xT[a] += termTx(a, c) * yR(c, ph - 1);
+            for (int dd = 0; dd < ndu; dd++) xT[a] += termTx(a, ny + dd) * dM(dd, ph - 1);
+        }
+        const double *xp = &xb[(size_t)ph * nx];
+        for (int a = 0; a < nx; a++)
+            for (int c = 0; c < nx; c++) { Px[a] += termP(a, c) * xp[c]; PxT[a] += termP(a, c) * xT[c]; }
+        for (int a = 0; a < nx; a++) {
+            eT[a] = Px[a] - PxT[a];
+            c0 += (0.5 * Px[a] - PxT[a]) * xp[a];
+        }
+    }
     out.c0 = c0;
     auto rowval = [&](int kind, int st, int cp) {
         double v = 0;
@@ -583,6 +676,7 @@ void LmpcController::assemble_host(const Condensed &o, const double *x0, const d
             double s = 0;
             for (int a = 0; a < ny; a++) s += C(a, b) * ey[(size_t)i * ny + a];
             for (int a = 0; a < nx; a++) s += A(a, b) * p[a];
+            if (i == ph && have_terminal) s += eT[b];
             pn[b] = s;
         }
         p = pn;

@@ -115,6 +115,11 @@ struct LmpcController {
     Mat softX, softY;
     std::vector<double> softS;
     std::vector<double> sMin, sMax, sX, sU;
+    // terminal cost 0.5 (x_ph - x_T)' P (x_ph - x_T), x_T = xT + Tx [yref(., ph - 1); dmeas(., ph - 1)] (no counterpart in the
+    // reference's LMPC).  termP [nx x nx] symmetric positive semidefinite, termXT [nx], termTx [nx x (ny + ndu)]; empty without the term
+    bool have_terminal = false;
+    Mat termP, termTx;
+    std::vector<double> termXT;
     // LOptimizer state
     Mat yRef, uRef, duRef, dMeas;
     mpcx_lparams prm{};
@@ -140,6 +145,10 @@ struct LmpcController {
     // LMPC); a null pointer leaves that kind as it is.  idx form: the column shift of set_state_bounds_idx
     void set_soft_weights(const double *xw, const double *yw, const double *sw);
     void set_soft_weights_idx(int idx, const double *xw, const double *yw, const double *sw);
+    // empty string, or why the term is refused (nothing is stored then).  P null: the term is removed; xT / Tx null: zeros
+    std::string set_terminal_cost(const double *P, const double *xT, const double *Tx);
+    // what the device reads behind the output weights (MPCX_TERMINAL in lmpc_device.hpp): [P | xT | Tx], empty without the term
+    std::vector<double> terminal_block() const;
     void set_scalar_vec(const double *smin, const double *smax, const double *X, const double *U);
     void set_scalar_idx(int idx, double smin, double smax, const double *X, const double *U);
 

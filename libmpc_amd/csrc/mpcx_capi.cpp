@@ -117,7 +117,7 @@ static void fill_dev_scalars(const mpcx_lmpc *h, const mpcx::LmpcController &c, 
     D.cost_direct = (o.h_regularised || o.inverse_residual > 1e-9) ? 1 : 0;
     D.check_every = h->dbg_check_every; D.polish_rounds0 = h->dbg_rounds0; D.polish_rounds = 10;
     D.alpha = c.prm.alpha; D.sigma = 1e-6;
-    D.adaptive_rho = c.prm.adaptive_rho ? 1 : 0; D.rho_user = c.prm.rho;
+    D.adaptive_rho = (c.prm.adaptive_rho ? 1 : 0) | (c.have_terminal ? 2 : 0); D.rho_user = c.prm.rho;      // (a flag word: MPCX_HAS_TERMINAL, before lmpc_lds_per_wave)
     D.eps_abs = c.prm.eps_abs; D.eps_rel = c.prm.eps_rel; D.eps_prim_inf = c.prm.eps_prim_inf;
     D.lds_per_wave = mpcx::lmpc_lds_per_wave(D, &D.stage_len, &D.arena_len);
     D.wsld = D.ldz + D.ldy + 2 * D.ldg + 2;
@@ -132,7 +132,14 @@ static void fill_dev_arrays(const mpcx_lmpc *h, const mpcx::LmpcController &c, c
 {
     D.A = U.up(c.A.a, rc); D.B = U.up(c.B.a, rc); D.C = U.up(c.C.a, rc);
     D.Bd = U.up(c.Bd.a, rc); D.Dd = U.up(c.Dd.a, rc);
-    D.Wy = U.up(c.wOutput.a, rc); D.Wu = U.up(c.wU.a, rc); D.Wdu = U.up(c.wDeltaU.a, rc);
+    {
+        // the terminal cost's [P | xT | Tx] rides behind the output weights (MPCX_TERMINAL)
+        std::vector<double> wy(c.wOutput.a);
+        const std::vector<double> term = c.terminal_block();
+        wy.insert(wy.end(), term.begin(), term.end());
+        D.Wy = U.up(wy, rc);
+    }
+    D.Wu = U.up(c.wU.a, rc); D.Wdu = U.up(c.wDeltaU.a, rc);
     D.yref_s = U.up(c.yRef.a, rc); D.uref_s = U.up(c.uRef.a, rc);
     D.duref_s = U.up(c.duRef.a, rc); D.dmeas_s = U.up(c.dMeas.a, rc);
     {
@@ -512,6 +519,16 @@ int mpcx_lmpc_set_soft_constraint_weights_slice(mpcx_lmpc_t h, const double *xw,
 int mpcx_lmpc_set_soft_constraint_weights(mpcx_lmpc_t h, const double *xw, const double *yw, const double *sw)
 {
     return mpcx_lmpc_set_soft_constraint_weights_slice(h, xw, yw, sw, -1, -1);
+}
+
+// Terminal cost 0.5 (x_ph - x_T)' P (x_ph - x_T) (include/mpcx.h).  No counterpart in the reference's LMPC
+int mpcx_lmpc_set_terminal_cost(mpcx_lmpc_t h, const double *P, const double *xT, const double *Tx)
+{
+    CHECK_H(h);
+    const std::string msg = h->ctl.set_terminal_cost(P, xT, Tx);
+    if (!msg.empty()) return fail(MPCX_E_INVALID, msg);
+    h->dirty = true;
+    return MPCX_OK;
 }
 
 int mpcx_lmpc_set_scalar_constraint_slice(mpcx_lmpc_t h, double smin, double smax, const double *X, const double *U, int start, int end)
@@ -1585,6 +1602,9 @@ int mpcx_lmpc_hetero_create_ex(const mpcx_lmpc_t *controllers, int count, int de
         for (size_t r = 0; r < o0.g_soft.size(); ++r)
             if ((ok.g_soft[r] > 0.0) != (o0.g_soft[r] > 0.0))
                 return fail(MPCX_E_INVALID, "controller " + std::to_string(k) + " differs from controller 0 in which constraint rows are soft");
+        // ... and a terminal cost in every controller or in none (the wavefronts' LDS plan is controller 0's); P, xT and Tx may differ
+        if (ck.have_terminal != c0.have_terminal)
+            return fail(MPCX_E_INVALID, "controller " + std::to_string(k) + " differs from controller 0 in whether it has a terminal cost");
     }
     std::unique_ptr<mpcx_lmpc_hetero> f(new mpcx_lmpc_hetero);
     f->device = device; f->count = count; f->d = c0.d; f->active_words = o0.active_words; f->m_ref = o0.m_ref;
@@ -1885,6 +1905,8 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "g_kind") { tmp.assign(o.g_kind.begin(), o.g_kind.end()); v = &tmp; }
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }
     else if (n == "slo") v = &o.slo; else if (n == "shi") v = &o.shi;
+    else if (n == "wOutput") v = &h->ctl.wOutput.a; else if (n == "wU") v = &h->ctl.wU.a;      // the weights as stored, [ny | nu x (ph + 1)] internal columns
+    else if (n == "terminal") { tmp = h->ctl.terminal_block(); v = &tmp; }      // [P | xT | Tx] as stored (P symmetrised); empty without the term
     else if (n == "ws_limit") {           // most rows a working set may hold, the lists' capacity, doubles of a wavefront's large-working-set slot
         tmp = {(double)mpcx::ws_limit(o.nz, o.mg, o.n_soft), (double)mpcx::ws_capacity(mpcx::ws_limit(o.nz, o.mg, o.n_soft)), (double)mpcx::lmpc_slot_len(h->dev)};
         v = &tmp;

@@ -448,6 +448,7 @@ class LMPC(_LoopFrontEnd):
         self._A = self._B = None                                 # the model as given, for loops whose plants default to it
         self._Bd = np.zeros((self.nx, self.ndu))
         self._C, self._Dd = None, np.zeros((self.ny, self.ndu))               # the outputs as given: what an observed loop measures with
+        self._has_terminal = False                               # a terminal cost is set (a bank takes it in every controller or in none)
         self._last = Result(cmd=np.zeros(self.nu))
         self._stats = SolutionStats()
         self._last_u0 = np.zeros(self.nu)
@@ -560,6 +561,50 @@ class LMPC(_LoopFrontEnd):
             return self._ok(self._lib.mpcx_lmpc_set_soft_constraint_weights(self._h, px, py, ps))
         sl = _slice(slice)
         return self._ok(self._lib.mpcx_lmpc_set_soft_constraint_weights_slice(self._h, px, py, ps, sl.start, sl.end))
+
+    def setTerminalCost(self, P, xT=None, Tx=None):
+        """extension: the terminal cost 0.5 (x_ph - x_T)' P (x_ph - x_T) with x_T = xT + Tx [yref(., ph - 1); dmeas(., ph - 1)].  P [nx x nx]
+        symmetric positive semidefinite (lqr_terminal_cost gives the cost-to-go of the unconstrained problem), xT [nx] and Tx [nx x (ny + ndu)]
+        default to zero; the columns of Tx are the first ny + ndu columns of target_map(want_x=True)'s map_x.  P = None removes the term.  The
+        constant 0.5 x_T' P x_T is not part of `cost`.  False for NaN / inf, an asymmetric P or one with a negative eigenvalue (nothing is
+        stored then).  The reference's LMPC has no counterpart."""
+        if P is None:
+            self._has_terminal = False
+            return self._ok(self._lib.mpcx_lmpc_set_terminal_cost(self._h, None, None, None))
+        Pm = _cm(P, self.nx, self.nx)
+        x = None if xT is None else _vec(xT, self.nx)
+        T = None if Tx is None else _cm(Tx, self.nx, self.ny + self.ndu)
+        ok = self._ok(self._lib.mpcx_lmpc_set_terminal_cost(self._h, _p(Pm), None if x is None else _p(x), None if T is None else _p(T)))
+        self._has_terminal = self._has_terminal or ok             # (a refused call stores nothing: what was there stays)
+        return ok
+
+    def _lqr_problem(self, step):
+        """(A, B, Q, R) of the unconstrained problem whose cost-to-go is the terminal weight: the weights of user column `step`"""
+        if self._A is None:
+            raise MpcxError(_capi.E_STATE, "state-space model not set")
+        if not 0 <= int(step) < self.ph:
+            raise ValueError(f"step {step} is not a column of the weights, 0 .. {self.ph - 1}")
+        # the weights as the handle stores them (user column k is internal column k + 1): one source of truth
+        ow = self.debug_get("wOutput").reshape(self.ph + 1, self.ny)[int(step) + 1]
+        r = self.debug_get("wU").reshape(self.ph + 1, self.nu)[int(step) + 1]
+        if not (r > 0).all():
+            raise ValueError("lqr_terminal_cost needs a positive input weight (UWeight) in every component: R = diag(UW[:, step]) must be positive definite")
+        return self._A, self._B, self._C.T @ np.diag(ow) @ self._C, np.diag(r)
+
+    def lqr_terminal_cost(self, step=1):
+        """(P [nx, nx], K [nu, nx]): the cost-to-go and the gain u = -K x of the infinite-horizon problem with Q = C' diag(OW[:, step]) C and
+        R = diag(UW[:, step]) -- the weights of user column `step` as the handle stores them -- through libmpc_amd.utils.lqr_gains (one
+        mpcx_dare_batch call on the device).  setTerminalCost(P) then makes the horizon's cost the infinite one wherever no constraint is
+        active behind it.  The weight on the input increments (DeltaUWeight) is ignored: with one, P is not the exact cost-to-go.  ValueError
+        where an input weight is not positive; MpcxError where the equation was not solved."""
+        from .utils import lqr_gains
+        A, B, Q, R = self._lqr_problem(step)
+        K, X, flags = lqr_gains(A, B, Q, R, device=max(self.device, 0))
+        if int(flags[0]):
+            why = {1: "R is not positive definite", 2: "the doubling iteration has not converged",
+                   3: "the doubling iteration broke down: is (A, B) stabilisable?"}[int(flags[0])]
+            raise MpcxError(_capi.E_NUMERIC, why)
+        return X[0].cpu().numpy().copy(), K[0].cpu().numpy().copy()
 
     def setScalarConstraint(self, *args):
         """(min, max, X, U, slice) as LMPC.hpp:355 or (index, min, max, X, U) as LMPC.hpp:409."""
