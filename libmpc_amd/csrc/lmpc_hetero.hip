@@ -11,7 +11,10 @@
 //     K   = H + sigma I + diag(rho_b) + G' diag(rho_g) G,  Kinv                                           (MFMA, Cholesky, MFMA)
 // The O(n) parts of a controller (bounds, references, row maps) are laid out by the host; this kernel fills the O(n^3) arrays of
 // every model's device struct in place.  Same arithmetic as LmpcController::condense (lmpc_model.cpp), which remains the set-up of
-// a single controller and the check of this kernel (tests/test_lmpc_hetero.py compares the two banks).
+// a single controller.  The check of this kernel -- and of the host set-up -- is a 60-digit truth of every array above from its definition
+// (tests/golden/make_condense_golden.py), held element-wise within a bound that a numpy restatement of this algorithm sets
+// (tests/condense_ref.py): on the device in tests/test_lmpc_condense_gpu.py, this file stepped through on the host in
+// tests/test_emu_condense.py, the host set-up in tests/test_lmpc_condense.py.  tests/test_lmpc_hetero.py still compares the two banks.
 #include "lmpc_kernel_common.hpp"
 
 namespace mpcx {
@@ -19,6 +22,14 @@ namespace mpcx {
 namespace {
 
 constexpr int kCondWaves = 4;
+// the most workgroups a launch has in the LDS form and in the scratch form: a bank of more controllers is walked by a grid-stride loop
+// (tests/emu/run_condense.cpp builds this file with smaller ones, so that one workgroup of the interpreter condenses two controllers)
+#ifndef MPCX_CONDENSE_GRID_LDS
+#define MPCX_CONDENSE_GRID_LDS 1024
+#endif
+#ifndef MPCX_CONDENSE_GRID_BIG
+#define MPCX_CONDENSE_GRID_BIG 512
+#endif
 
 __device__ __forceinline__ v4d mfma4(double a, double b, v4d acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
 
@@ -429,14 +440,14 @@ int lmpc_condense_launch(LmpcDev *models_d, const LmpcDev &m0, int count, void *
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (!big) {
-        const int blocks = count < 1024 ? count : 1024;
+        const int blocks = count < MPCX_CONDENSE_GRID_LDS ? count : MPCX_CONDENSE_GRID_LDS;
         hipLaunchKernelGGL(lmpc_condense_models<false>, dim3(blocks), dim3(kCondWaves * 64), lds, s, models_d, count, NP, NQ, nullptr, 0);
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     // the BIG form: a scratch block per workgroup, two workgroups per CU's worth of them; released when the kernel has finished
     // (a set-up path: the bank is being created, the caller synchronises right behind this call.  On a device short of memory the scratch shrinks --
     // fewer workgroups walk the bank -- before the launch gives up)
-    int blocks = count < 512 ? count : 512;
+    int blocks = count < MPCX_CONDENSE_GRID_BIG ? count : MPCX_CONDENSE_GRID_BIG;
     double *scratch = nullptr;
     while (hipMalloc(reinterpret_cast<void **>(&scratch), (size_t)blocks * big * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();

@@ -39,6 +39,31 @@ typedef struct ihipStream_t *hipStream_t;
 typedef int hipError_t;
 constexpr hipError_t hipSuccess = 0;
 inline hipError_t hipGetLastError() { return hipSuccess; }
+inline hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+// device memory is host memory; every block carries a guard behind it that hipFree checks: a kernel that wrote past its scratch block aborts the run
+constexpr size_t hipemu_guard_doubles = 64;
+constexpr double hipemu_guard_value = -7.25e300;
+inline hipError_t hipMalloc(void **p, size_t bytes)
+{
+    const size_t body = (bytes + 7) / 8;
+    double *b = static_cast<double *>(malloc((2 + body + hipemu_guard_doubles) * sizeof(double)));
+    if (!b) return 2;
+    memcpy(b, &body, sizeof(body));
+    for (size_t i = 0; i < hipemu_guard_doubles; ++i) b[2 + body + i] = hipemu_guard_value;
+    *p = b + 2;
+    return hipSuccess;
+}
+inline hipError_t hipFree(void *p)
+{
+    if (!p) return hipSuccess;
+    double *b = static_cast<double *>(p) - 2;
+    size_t body; memcpy(&body, b, sizeof(body));
+    for (size_t i = 0; i < hipemu_guard_doubles; ++i)
+        if (b[2 + body + i] != hipemu_guard_value) { fprintf(stderr, "hipemu: the guard behind a hipMalloc block of %zu doubles was written (double %zu)\n", body, i); abort(); }
+    free(b);
+    return hipSuccess;
+}
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 inline hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
 template <class K> inline hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int *n, K, int, size_t) { *n = 0; return hipSuccess; }
@@ -224,6 +249,10 @@ template <class A0, class... R> inline size_t first_arg_bytes(const A0 &, const 
 
 inline void __syncthreads() { hipemu::sync_block(); }
 inline double atomicAdd(double *p, double v) { const double o = *p; *p = o + v; return o; }     // (fibres run one at a time)
+inline int atomicAdd(int *p, int v) { const int o = *p; *p = o + v; return o; }
+inline int atomicOr(int *p, int v) { const int o = *p; *p = o | v; return o; }
+struct double2 { double x, y; };
+inline double2 make_double2(double x, double y) { return double2{x, y}; }
 
 using std::max;
 using std::min;
@@ -246,9 +275,21 @@ inline unsigned long long __builtin_amdgcn_read_exec() { return ~0ull; }
 inline void *__builtin_amdgcn_kernarg_segment_ptr() { return const_cast<void *>(hipemu::st().kernarg); }
 // the implicit arguments follow the explicit ones (here: one struct) at the next multiple of eight bytes
 inline void *__builtin_amdgcn_implicitarg_ptr() { return (char *)const_cast<void *>(hipemu::st().kernarg) + ((hipemu::st().kernarg_bytes + 7) & ~(size_t)7); }
+#ifndef __clang__          // (a builtin of clang's on every target)
 inline long long __builtin_readcyclecounter() { return 0; }
+#endif
 // v_rsq_f64: about 2^-26 relative -- the emulation truncates to float precision so that the Newton steps after it have something to do
 inline double __builtin_amdgcn_rsq(double x) { return (double)(float)(1.0 / std::sqrt(x)); }
+// v_rcp_f64: the same precision as the estimate above
+inline double __builtin_amdgcn_rcp(double x) { return (double)(float)(1.0 / x); }
+// ds_swizzle_b32 in bit-mask mode (offset bit 15 clear): within each half of the wavefront lane l reads lane ((l & and_mask) | or_mask) ^ xor_mask
+inline int __builtin_amdgcn_ds_swizzle(int v, int pattern)
+{
+    if (pattern & 0x8000) { fprintf(stderr, "hipemu: ds_swizzle pattern 0x%x is not modelled\n", pattern); abort(); }
+    const int lane = hipemu::tid() % hipemu::kWave, l = lane & 31;
+    const int from = (lane & 32) | ((((l & (pattern & 31)) | ((pattern >> 5) & 31)) ^ ((pattern >> 10) & 31)) & 31);
+    return (int)(uint32_t)hipemu::exchange((uint32_t)v, from, "ds_swizzle");
+}
 inline int __builtin_amdgcn_readlane(int v, int l) { return (int)(uint32_t)hipemu::exchange((uint32_t)v, l, "v_readlane"); }
 inline int __builtin_amdgcn_readfirstlane(int v) { return (int)(uint32_t)hipemu::exchange((uint32_t)v, 0, "v_readfirstlane"); }
 inline int __builtin_amdgcn_update_dpp(int, int src, int ctrl, int, int, bool)
@@ -264,8 +305,11 @@ inline int __builtin_amdgcn_update_dpp(int, int src, int ctrl, int, int, bool)
 }
 inline unsigned long long __ballot(int p) { return hipemu::ballot(p != 0); }
 // v_mfma_f64_16x16x4_f64: D = C + A B with A[m = lane & 15][k = lane >> 4], B[k = lane >> 4][n = lane & 15] one double per lane, C / D
-// four per lane: row (lane >> 4) + 4 r, column lane & 15 in element r.  (clang's ext_vector_type spelled for g++.)
+// four per lane: row (lane >> 4) + 4 r, column lane & 15 in element r.  (clang's ext_vector_type spelled for g++; a program whose kernels name
+// the components of such a vector, v.x, is compiled with clang++, which knows the attribute -- and address_space, which g++ ignores.)
+#ifndef __clang__
 #define ext_vector_type(N) vector_size(8 * (N))
+#endif
 typedef double hipemu_v4d __attribute__((vector_size(32)));
 inline hipemu_v4d __builtin_amdgcn_mfma_f64_16x16x4f64(double a, double b, hipemu_v4d c, int, int, int)
 {
@@ -289,4 +333,4 @@ template <class T> inline T __shfl(T v, int src)
     b = hipemu::exchange(b, src, "__shfl");
     T r; memcpy(&r, &b, sizeof(T)); return r;
 }
-template <class T> inline T __shfl_xor(T v, int mask) { return __shfl(v, (hipemu::tid() % hipemu::kWave) ^ mask); }
+template <class T> inline T __shfl_xor(T v, int mask, int = hipemu::kWave) { return __shfl(v, (hipemu::tid() % hipemu::kWave) ^ mask); }

@@ -23,11 +23,9 @@
 #include <vector>
 
 #if !defined(__HIPCC__)
-// what the driver and mpcx/nlmpc_hooks.hpp's device-pointer path (ErasedHooks, not used here) name and the interpreter's runtime lacks: host memory
+// what the driver and mpcx/nlmpc_hooks.hpp's device-pointer path (ErasedHooks, not used here) name and the interpreter's runtime lacks (hipMalloc and hipFree it has): host memory
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
-inline hipError_t hipMalloc(void **p, size_t n) { *p = std::malloc(n); return *p ? hipSuccess : 1; }
 inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
-inline hipError_t hipFree(void *p) { std::free(p); return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 #endif
 
