@@ -180,6 +180,33 @@ int mpcx_lmpc_set_scalar_constraint_slice(mpcx_lmpc_t h, double smin, double sma
                                           int start, int end);
 int mpcx_lmpc_set_scalar_constraint_index(mpcx_lmpc_t h, int index, double smin, double smax,
                                           const double *X, const double *U);
+/* Linear constraints: nc rows with coefficients shared by all steps and bounds per step,
+ *     lo[c, i] <= Fx[c, :] x_i + Fu[c, :] v_i <= hi[c, i],   i = 0 .. ph,   v_i = x_u(i) = u_{i-1}, v_0 = lastU
+ * -- the scalar row's convention for nc rows: half-plane sets on the state, limits on combinations of actuators, rows that couple state and input,
+ * and with bounds at the last step only a polytopic terminal set.  The reference's LMPC has no counterpart.  Fx [nc x nx],
+ * Fu [nc x nu] column-major.  An infinite side is absent, a row with both sides infinite does not exist, lo == hi is an equality.  Default: no rows.
+ * The first form sets the whole horizon, lo and hi [nc x (ph + 1)] column-major, column i = step i; nc = 0 removes the rows (the other arguments
+ * are then not read).  The slice form takes lo[nc], hi[nc] and has the slice semantics and the column shift of
+ * mpcx_lmpc_set_scalar_constraint_slice: slice index i bounds step i + 1, index 0 also step 0, (-1, -1) every step; the slice (ph - 1, ph) is the
+ * terminal set.  The coefficients it brings replace the stored ones at every step.  A step-0 row sees no decision variable: a hard one is a
+ * feasibility condition on (x0, lastU).
+ * Row numbering: the rows are appended behind the reference's own, step i row c at m_ref(reference) + i nc + c; m_ref and active_words grow by
+ * (ph + 1) nc for a controller that has such a row with a finite bound, and for no other.
+ * nc <= MPCX_MAX_LINEAR_ROWS.  The cap is the LDS the coefficient block takes in lmpc_assemble_generic: nc (nx + nu) doubles in every
+ * wavefront's slice, next to the roll-out's arrays -- 16 KB per wavefront at the largest model the kernels take (nx = nu = 64), a tenth of a
+ * compute unit's LDS, and 2 KB at the quadrotor's nx = 12, nu = 4.
+ * MPCX_E_INVALID, nothing stored: a null pointer with nc > 0; a NaN entry; an infinite coefficient; lo > hi; nc < 0 or above the cap; a slice
+ * out of bounds or with nc = 0; a slice whose nc differs from the stored one while a step outside the slice holds a finite bound. */
+#define MPCX_MAX_LINEAR_ROWS 16
+int mpcx_lmpc_set_linear_constraints(mpcx_lmpc_t h, int nc, const double *Fx, const double *Fu, const double *lo, const double *hi);
+int mpcx_lmpc_set_linear_constraints_slice(mpcx_lmpc_t h, int nc, const double *Fx, const double *Fu, const double *lo, const double *hi,
+                                           int start, int end);
+/* Soft weights of the linear rows, w[nc] with the stored nc, under the rules of mpcx_lmpc_set_soft_constraint_weights: rho in (0, +inf], +inf (the
+ * default) keeps the row hard, a finite weight replaces the row by 0.5 rho dist^2 in the cost.  The first form sets steps 0 .. ph, the slice
+ * form has the slice semantics of mpcx_lmpc_set_linear_constraints_slice.  The weights stay with the rows while calls of the bounds setters keep
+ * nc; a call that changes nc makes every row hard again.  MPCX_E_INVALID: null pointer, NaN, zero or a negative weight; a slice out of bounds. */
+int mpcx_lmpc_set_linear_constraint_weights(mpcx_lmpc_t h, const double *w);
+int mpcx_lmpc_set_linear_constraint_weights_slice(mpcx_lmpc_t h, const double *w, int start, int end);
 /* LMPC::setReferences matrix form (LMPC.hpp:596) / vector+slice form (LMPC.hpp:616) */
 int mpcx_lmpc_set_references(mpcx_lmpc_t h, const double *yref, const double *uref, const double *duref);
 int mpcx_lmpc_set_references_slice(mpcx_lmpc_t h, const double *yref, const double *uref, const double *duref,

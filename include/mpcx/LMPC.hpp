@@ -224,6 +224,16 @@ public:
     bool setTerminalCost(const mat<Tnx, Tnx> &P) { return ok(mpcx_lmpc_set_terminal_cost(h_, P.data(), nullptr, nullptr)); }
     bool setTerminalCost(const mat<Tnx, Tnx> &P, const cvec<Tnx> &xT) { return ok(mpcx_lmpc_set_terminal_cost(h_, P.data(), xT.data(), nullptr)); }
     bool setTerminalCost(const double *P, const double *xT, const double *Tx) { return ok(mpcx_lmpc_set_terminal_cost(h_, P, xT, Tx)); }
+    // extension: nc linear rows lo(c, i) <= Fx(c, :) x_i + Fu(c, :) v_i <= hi(c, i), the scalar row's convention for several rows with shared
+    // coefficients (mpcx_lmpc_set_linear_constraints; the reference's LMPC has no counterpart).  Fx [nc x nx], Fu [nc x nu] column-major; the first form
+    // takes lo, hi [nc x (ph + 1)] for the steps 0 .. ph (nc = 0 removes the rows), the second lo[nc], hi[nc] and a slice as setScalarConstraint's --
+    // HorizonSlice{ph - 1, ph} is a terminal set.  The weights w[nc] soften the rows as setSoftConstraintWeights does the others
+    bool setLinearConstraints(const int nc, const double *Fx, const double *Fu, const double *lo, const double *hi) { return ok(mpcx_lmpc_set_linear_constraints(h_, nc, Fx, Fu, lo, hi)); }
+    bool setLinearConstraints(const int nc, const double *Fx, const double *Fu, const double *lo, const double *hi, const HorizonSlice &s)
+    {
+        return ok(mpcx_lmpc_set_linear_constraints_slice(h_, nc, Fx, Fu, lo, hi, s.start, s.end));
+    }
+    bool setLinearConstraintWeights(const double *w, const HorizonSlice &s = HorizonSlice::all()) { return ok(mpcx_lmpc_set_linear_constraint_weights_slice(h_, w, s.start, s.end)); }
     bool setScalarConstraint(const double mn, const double mx, const cvec<Tnx> X, const cvec<Tnu> U, const HorizonSlice &s)   // LMPC.hpp:355
     {
         return ok(mpcx_lmpc_set_scalar_constraint_slice(h_, mn, mx, X.data(), U.data(), s.start, s.end));

@@ -94,6 +94,8 @@ EXPORTS = [
     "mpcx_lmpc_set_input_rate_bounds", "mpcx_lmpc_set_input_rate_bounds_slice",
     "mpcx_lmpc_set_soft_constraint_weights", "mpcx_lmpc_set_soft_constraint_weights_slice",
     "mpcx_lmpc_set_terminal_cost",
+    "mpcx_lmpc_set_linear_constraints", "mpcx_lmpc_set_linear_constraints_slice",
+    "mpcx_lmpc_set_linear_constraint_weights", "mpcx_lmpc_set_linear_constraint_weights_slice",
     "mpcx_lmpc_set_scalar_constraint_slice", "mpcx_lmpc_set_scalar_constraint_index",
     "mpcx_lmpc_set_references", "mpcx_lmpc_set_references_slice",
     "mpcx_lmpc_set_exogenous_inputs", "mpcx_lmpc_set_exogenous_inputs_slice",
@@ -192,6 +194,10 @@ def lib():
         _lib.mpcx_lmpc_set_soft_constraint_weights.argtypes = [C.c_void_p] * 4
         _lib.mpcx_lmpc_set_soft_constraint_weights_slice.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int]
         _lib.mpcx_lmpc_set_terminal_cost.argtypes = [C.c_void_p] * 4
+        _lib.mpcx_lmpc_set_linear_constraints.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _lib.mpcx_lmpc_set_linear_constraints_slice.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int]
+        _lib.mpcx_lmpc_set_linear_constraint_weights.argtypes = [C.c_void_p] * 2
+        _lib.mpcx_lmpc_set_linear_constraint_weights_slice.argtypes = [C.c_void_p] * 2 + [C.c_int, C.c_int]
         _lib.mpcx_nlmpc_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _lib.mpcx_nlmpc_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_graph_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -41,8 +41,9 @@ struct LmpcDev {
     int n_soft;                                  // soft general rows (in what was padding: every other field keeps its offset)
     double alpha, sigma, eps_abs, eps_rel, eps_prim_inf;
     int adaptive_rho; double rho_user;            // LParameters::adaptive_rho / rho (the ADMM step sizes of the set-up).  adaptive_rho is a flag word: bit 0
-                                                 // the parameter (MPCX_ADAPTIVE_RHO), bit 1 the terminal cost's presence (MPCX_HAS_TERMINAL) -- only the
-                                                 // condensing kernel and the launch of the generic assemble kernel (its template parameter TERM) read it
+                                                 // the parameter (MPCX_ADAPTIVE_RHO), bit 1 the terminal cost's presence (MPCX_HAS_TERMINAL), bits 2 .. 7 the number of
+                                                 // linear rows (MPCX_LINEAR_NC) -- only the condensing kernel and the launch of the generic assemble kernel
+                                                 // (its template parameters TERM and LIN) read those
     // per-wave LDS carve (in doubles)
     int stage_len, arena_len, lds_per_wave;
     int fast_slice;                              // per-wave LDS slice of the lean solve kernels (doubles)
@@ -52,7 +53,7 @@ struct LmpcDev {
     const double *Wy, *Wu, *Wdu;                 // [(ph+1) x ny], [(ph+1) x nu], [ph x nu]; column = internal step.  Wy: then MPCX_TERMINAL, if present
     const double *yref_s, *uref_s, *duref_s, *dmeas_s;   // shared references [ph x n]
     // step-0 feasibility rows
-    const double *lo0x, *hi0x, *lo0u, *hi0u, *lo0y, *hi0y, *sX, *sU;
+    const double *lo0x, *hi0x, *lo0u, *hi0u, *lo0y, *hi0y, *sX, *sU;      // sX: then MPCX_LINEAR_F, if present
     double s0lo, s0hi;
     // condensed QP
     const double *H, *Kinv, *Gr, *Gc, *Y;
@@ -81,6 +82,11 @@ struct LmpcDev {
 #define MPCX_ADAPTIVE_RHO(M) (((M).adaptive_rho & 1) != 0)
 #define MPCX_HAS_TERMINAL(M) (((M).adaptive_rho & 2) != 0)
 #define MPCX_TERMINAL(M) ((M).Wy + ((M).ph + 1) * (M).ny)
+// The linear rows likewise: their number in bits 2 .. 7 of the flag word, their coefficients behind the scalar row's in sX's array,
+// [sX nx | row c: Fx(c, :) nx, Fu(c, :) nu]; a zero-initialised struct has none.  Read by the condensing kernel and by the generic assemble kernel
+// (its template parameter LIN, chosen by the launch)
+#define MPCX_LINEAR_NC(M) (((M).adaptive_rho >> 2) & 63)
+#define MPCX_LINEAR_F(M) ((M).sX + (M).nx)
 __host__ __device__ inline int lmpc_terminal_len(int nx, int ny, int ndu) { return nx * nx + nx + nx * (ny + ndu); }
 
 struct LmpcBatchDev {

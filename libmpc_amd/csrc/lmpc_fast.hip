@@ -858,7 +858,8 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
             if (rr < b_out) return rr + na < b_out ? rr + na : rr;
             if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
             if (rr < b_sc) return rr + M.nu < b_sc ? rr + M.nu : rr;
-            return rr + 1 < M.m_ref ? rr + 1 : rr;
+            const int sh = rr < b_sc + n1 ? 1 : MPCX_LINEAR_NC(M);      // (a linear row, DESIGN.md 3.4: the same row one step later is nc rows on)
+            return rr + sh < M.m_ref ? rr + sh : rr;
         };
 #pragma unroll
         for (int s = 0; s < NZS; ++s) {

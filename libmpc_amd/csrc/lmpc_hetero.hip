@@ -5,7 +5,7 @@
 //     S_i = A S_{i-1} + B E_i            prediction matrices ("A^h, B-stack"), rolled over the horizon, never stored whole
 //     H   = sum_i (C S_i)' W_i (C S_i) + weights on the inputs and their increments                       (MFMA, nz x ny x nz per step)
 //           + S_ph' Pt S_ph, the terminal cost, where a controller has one                (MFMA, Pt S_ph and nz x nx x nz)
-//     G   = the rows of S_i / C S_i / sX' S_i the finite bounds select                                     (written as they appear)
+//     G   = the rows of S_i / C S_i / sX' S_i / Fx S_i the finite bounds select                                    (written as they appear)
 //     H = L L',  Hinv = L^-T L^-1        Cholesky in LDS, triangular inverse one column per thread, product on MFMA
 //     Y   = [Hinv, (G Hinv)'; G Hinv, G Hinv G']                                                          (MFMA)
 //     K   = H + sigma I + diag(rho_b) + G' diag(rho_g) G,  Kinv                                           (MFMA, Cholesky, MFMA)
@@ -171,6 +171,13 @@ __global__ __launch_bounds__(kCondWaves * 64) void lmpc_condense_models(LmpcDev 
                     for (int c = 0; c < nx; ++c) v = fma(gsX[c], Sn[c * ld + q], v);
                     const int bq = q / nu, jq = q - bq * nu;
                     if (bq == blk[i]) v += gsU[jq];
+                } else if (kind == 4) {
+                    // a linear row: Fx(cp, :) S_i + Fu(cp, :) at the step's block
+                    const gdp fr = gl(MPCX_LINEAR_F(M)) + cp * (nx + nu);
+                    v = 0.0;
+                    for (int c = 0; c < nx; ++c) v = fma(fr[c], Sn[c * ld + q], v);
+                    const int bq = q / nu, jq = q - bq * nu;
+                    if (bq == blk[i]) v += fr[nx + jq];
                 } else {
                     // an input-rate row: delta_{i-1} = v_i - v_{i-1}, the two in different blocks (a free move); v_0 is data
                     const int bq = q / nu, jq = q - bq * nu;

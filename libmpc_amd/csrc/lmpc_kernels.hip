@@ -55,8 +55,8 @@ __device__ __forceinline__ void put(double *dst, const double (&v)[K], int n, in
 }
 
 // TERM: the controller has a terminal cost.  A template parameter, chosen by the launch from the controller's flag word: without
-// the term the kernel is the code it has always been
-template <int CPZ, int CPG, bool TERM>
+// the term the kernel is the code it has always been.  LIN: the controller has linear rows, under the same rule
+template <int CPZ, int CPG, bool TERM, bool LIN>
 __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
                              double *stage, double *arena, gdw ws)
 {
@@ -85,6 +85,9 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
     double *gA = dms + ph * ndu + (ph + 2) / 2, *gB = gA + nx * nx, *gC = gB + nx * nu, *gBd = gC + ny * nx, *gDd = gBd + nx * ndu;
     // the terminal cost's P (nx x nx), xT (nx: the whole target x_T once the references are in) and Tx (nx x (ny + ndu)); there only with the term
     [[maybe_unused]] double *tP = gDd + ny * ndu, *txT = tP + nx * nx, *tTx = txT + nx;
+    // the linear rows' coefficients, row c: Fx(c, :) nx, Fu(c, :) nu; there only with such rows, behind whatever the terminal cost takes
+    [[maybe_unused]] double *lF = gDd + ny * ndu + (TERM ? lmpc_terminal_len(nx, ny, ndu) : 0);
+    [[maybe_unused]] const int nlin = LIN ? MPCX_LINEAR_NC(M) : 0, nxu = nx + nu;
 
     // ---- gather: everything this instance reads from global memory, in two groups of loads ----
     const gdp mA = GP(A), mB = GP(B), mC = GP(C), mBd = GP(Bd), mDd = GP(Dd);
@@ -143,6 +146,10 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
         const gdp gT = gl(MPCX_TERMINAL(M));
         const int nterm = lmpc_terminal_len(nx, ny, ndu);
         for (int e = lane; e < nterm; e += 64) tP[e] = gT[e];
+    }
+    if constexpr (LIN) {
+        const gdp gF = gl(MPCX_LINEAR_F(M));
+        for (int e = lane; e < nlin * nxu; e += 64) lF[e] = gF[e];
     }
     for (int e = lane; e < ldz; e += 64) stage[e] = 0.0;
     wave_sync();
@@ -234,6 +241,11 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
                 off = 0;
                 for (int c = 0; c < nx; ++c) off = fma(sxu[c], xb[st * nx + c], off);
                 if (st == 0) for (int c = 0; c < nu; ++c) off = fma(sxu[nx + c], u0s[c], off);      // (a soft step-0 row, as s0 above: lastU is data there)
+            } else if (LIN && kind == 4) {
+                const double *fr = lF + cp * nxu;
+                off = 0;
+                for (int c = 0; c < nx; ++c) off = fma(fr[c], xb[st * nx + c], off);
+                if (st == 0) for (int c = 0; c < nu; ++c) off = fma(fr[nx + c], u0s[c], off);       // (a soft step-0 row)
             } else {
                 off = st == 1 ? -u0s[cp] : 0.0;   // an input-rate row: delta_0 = v_1 - lastU, the later ones see decision variables only
             }
@@ -247,6 +259,11 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
         else if (kind == 1) {
             for (int c = 0; c < nx; ++c) v = fma(gC[cp + c * ny], xb[st * nx + c], v);
             if (has_dist) for (int dd = 0; dd < ndu; ++dd) v = fma(gDd[cp + dd * ny], dm(st - 1, dd), v);
+        } else if (LIN && kind == 4) {
+            // a hard linear row that sees no decision variable; at step 0 (the feasibility check of the linear rows on (x0, lastU)) lastU is data
+            const double *fr = lF + cp * nxu;
+            for (int c = 0; c < nx; ++c) v = fma(fr[c], xb[st * nx + c], v);
+            if (st == 0) for (int c = 0; c < nu; ++c) v = fma(fr[nx + c], u0s[c], v);
         } else {
             for (int c = 0; c < nx; ++c) v = fma(sxu[c], xb[st * nx + c], v);
         }
@@ -347,6 +364,10 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
                 } else if (kind == 2) {
                     for (int c = 0; c < nx; ++c) v = fma(sxu[c], xb[st * nx + c], v);
                     if (st > 0) for (int j = 0; j < nu; ++j) v = fma(sxu[nx + j], stage[blks[st] * nu + j], v);
+                } else if (LIN && kind == 4) {
+                    const double *fr = lF + cp * nxu;
+                    for (int c = 0; c < nx; ++c) v = fma(fr[c], xb[st * nx + c], v);
+                    if (st > 0) for (int j = 0; j < nu; ++j) v = fma(fr[nx + j], stage[blks[st] * nu + j], v);
                 } else {
                     v = stage[blks[st] * nu + cp];
                     if (st > 1) v -= stage[blks[st - 1] * nu + cp];
@@ -395,7 +416,7 @@ __device__ void assemble_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int
     wave_sync();
 }
 
-template <int CPZ, int CPG, bool TERM>
+template <int CPZ, int CPG, bool TERM, bool LIN>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_assemble_generic(const LmpcDev *__restrict__ Mp, const LmpcBatchDev Bt, double *wsbase)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -405,7 +426,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void lmpc_assemble_generic(con
     double *arena = stage + M0.stage_len + M0.ldy;
     const int b = blockIdx.x * (blockDim.x >> 6) + wave;             // one instance per wavefront; the grid covers the batch
     if (b < Bt.batch)
-        assemble_one<CPZ, CPG, TERM>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, arena, glw(wsbase) + (size_t)b * M0.wsld);
+        assemble_one<CPZ, CPG, TERM, LIN>(Mp[lmpc_model_of(Bt, b)], Bt, b, lane, stage, arena, glw(wsbase) + (size_t)b * M0.wsld);
 }
 
 
@@ -645,7 +666,8 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
             if (rr < b_out) return rr + na < b_out ? rr + na : rr;
             if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
             if (rr < b_sc) return rr + M.nu < b_sc ? rr + M.nu : rr;
-            return rr + 1 < M.m_ref ? rr + 1 : rr;
+            const int sh = rr < b_sc + n1 ? 1 : MPCX_LINEAR_NC(M);      // (a linear row, DESIGN.md 3.4: the same row one step later is nc rows on)
+            return rr + sh < M.m_ref ? rr + sh : rr;
         };
 #pragma unroll
         for (int s = 0; s < NZS; ++s) {
@@ -1541,11 +1563,14 @@ int launch_variant(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b
     double *const ws = sc.ws;
     const size_t lds = (size_t)kWavesPerBlock * m.lds_per_wave * sizeof(double);
     if (lds > lmpc_lds_limit()) return -2;
-    // (a bank has the term in every controller or in none: model 0's flag speaks for the launch)
-    auto k1 = MPCX_HAS_TERMINAL(m) ? lmpc_assemble_generic<CPZ, CPG, true> : lmpc_assemble_generic<CPZ, CPG, false>;
+    // (a bank has the term, and linear rows, in every controller or in none: model 0's flag word speaks for the launch)
+    const bool lin = MPCX_LINEAR_NC(m) > 0;
+    auto k1 = MPCX_HAS_TERMINAL(m) ? (lin ? lmpc_assemble_generic<CPZ, CPG, true, true> : lmpc_assemble_generic<CPZ, CPG, true, false>)
+                                   : (lin ? lmpc_assemble_generic<CPZ, CPG, false, true> : lmpc_assemble_generic<CPZ, CPG, false, false>);
     auto k3 = lmpc_solve_admm<CPZ, CPG>;
     static LmpcLdsCache configured;
-    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, false>), reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, true>),
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, false, false>), reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, true, false>),
+                                            reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, false, true>), reinterpret_cast<const void *>(lmpc_assemble_generic<CPZ, CPG, true, true>),
                                             reinterpret_cast<const void *>(k3)}, lds) != 0) return -3;
     int blocks = (b.batch + kWavesPerBlock - 1) / kWavesPerBlock;
     const int cap = 256 * 8;
@@ -1624,6 +1649,7 @@ int lmpc_lds_per_wave(const LmpcDev &m, int *stage_len, int *arena_len)
     int a1 = (m.ph + 1) * (m.nx + 2 * m.ny) + (m.ph + 2) * m.nx + 2 * m.ph * m.nu + m.nu + (m.nx + m.nu) + m.ph * m.ndu + (m.ph + 2) / 2 + 8 +
              m.nx * m.nx + m.nx * m.nu + m.ny * m.nx + m.nx * m.ndu + m.ny * m.ndu;      // assemble_one's plan, model matrices last
     if (MPCX_HAS_TERMINAL(m)) a1 += lmpc_terminal_len(m.nx, m.ny, m.ndu);                // ... and the terminal cost's P, xT, Tx behind them
+    a1 += MPCX_LINEAR_NC(m) * (m.nx + m.nu);                                             // ... and the linear rows' coefficients behind those
     const int wcap = ws_capacity(ws_limit(m.nz, m.mg, m.n_soft));
     int a2 = kMaxActive * kSld + 3 * wcap + (wcap + 1) / 2;      // S, lam, wsb, dg0, wsidx (ints)
     int ar = a1 > a2 ? a1 : a2;

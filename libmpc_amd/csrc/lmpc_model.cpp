@@ -193,6 +193,86 @@ void LmpcController::set_scalar_idx(int idx, double smin, double smax, const dou
     sX.assign(X, X + d.nx); sU.assign(U, U + d.nu);   // the multiplier is shared by all steps
 }
 
+
+// ---- linear rows ----------------------------------------------------------------------------------------------------
+static std::string linear_args_ok(int nc, int nx, int nu, const double *Fx, const double *Fu, const double *lo, const double *hi, int ncol)
+{
+    if (nc < 0 || nc > MPCX_MAX_LINEAR_ROWS) return "linear constraints: nc must be 0 .. " + std::to_string(MPCX_MAX_LINEAR_ROWS);
+    if (nc == 0) return std::string();
+    if (!Fx || !Fu || !lo || !hi) return "linear constraints: null argument";
+    for (int e = 0; e < nc * nx; e++) if (!std::isfinite(Fx[e])) return "linear constraints: Fx has a NaN or infinite entry";
+    for (int e = 0; e < nc * nu; e++) if (!std::isfinite(Fu[e])) return "linear constraints: Fu has a NaN or infinite entry";
+    for (int e = 0; e < nc * ncol; e++) {
+        if (std::isnan(lo[e]) || std::isnan(hi[e])) return "linear constraints: a bound is NaN";
+        if (lo[e] > hi[e]) return "linear constraints: lo > hi";
+    }
+    return std::string();
+}
+static void linear_store_f(LmpcController &c, int nc, const double *Fx, const double *Fu)
+{
+    c.linFx = Mat(nc, c.d.nx); c.linFu = Mat(nc, c.d.nu);
+    if (nc) { std::memcpy(c.linFx.a.data(), Fx, sizeof(double) * nc * c.d.nx); std::memcpy(c.linFu.a.data(), Fu, sizeof(double) * nc * c.d.nu); }
+}
+std::string LmpcController::set_linear(int nc, const double *Fx, const double *Fu, const double *lo, const double *hi)
+{
+    const std::string msg = linear_args_ok(nc, d.nx, d.nu, Fx, Fu, lo, hi, d.ph + 1);
+    if (!msg.empty()) return msg;
+    // (the soft weights belong to the rows: a new set of rows starts hard unless it has as many rows as the old one)
+    if (nc != nlin) linSoft = Mat(nc, d.ph + 1, kInf);
+    nlin = nc;
+    linear_store_f(*this, nc, Fx, Fu);
+    linLo = Mat(nc, d.ph + 1, -kInf); linHi = Mat(nc, d.ph + 1, kInf);
+    if (nc) { std::memcpy(linLo.a.data(), lo, sizeof(double) * nc * (d.ph + 1)); std::memcpy(linHi.a.data(), hi, sizeof(double) * nc * (d.ph + 1)); }
+    return std::string();
+}
+std::string LmpcController::set_linear_slice(int nc, const double *Fx, const double *Fu, const double *lo, const double *hi, int s, int e)
+{
+    if (nc == 0) return "linear constraints: a slice needs nc >= 1 (the whole-horizon form with nc = 0 removes the rows)";
+    const std::string msg = linear_args_ok(nc, d.nx, d.nu, Fx, Fu, lo, hi, 1);
+    if (!msg.empty()) return msg;
+    // internal columns the slice writes: i + 1, and 0 with i = 0 (set_scalar_idx)
+    auto in_slice = [&](int col) { return col == 0 ? s == 0 : (col - 1 >= s && col - 1 < e); };
+    if (nc != nlin) {
+        for (int col = 0; col <= d.ph && nlin > 0; col++)
+            for (int c = 0; c < nlin && !in_slice(col); c++)
+                if (std::isfinite(linLo(c, col)) || std::isfinite(linHi(c, col)))
+                    return "linear constraints: nc differs from the stored rows, which hold bounds at other steps";
+        nlin = nc;
+        linLo = Mat(nc, d.ph + 1, -kInf); linHi = Mat(nc, d.ph + 1, kInf); linSoft = Mat(nc, d.ph + 1, kInf);
+    }
+    linear_store_f(*this, nc, Fx, Fu);         // the coefficients are shared by all steps
+    for (int col = 0; col <= d.ph; col++)
+        if (in_slice(col))
+            for (int c = 0; c < nc; c++) { linLo(c, col) = lo[c]; linHi(c, col) = hi[c]; }
+    return std::string();
+}
+std::string LmpcController::set_linear_weights(const double *w, int s, int e)
+{
+    if (nlin == 0) return std::string();
+    if (!w) return "linear constraint weights: null argument";
+    for (int c = 0; c < nlin; c++) if (!(w[c] > 0.0)) return "linear constraint weights: NaN, zero or negative";
+    const bool all = s == -1 && e == -1;
+    for (int col = 0; col <= d.ph; col++)
+        if (all || (col == 0 ? s == 0 : (col - 1 >= s && col - 1 < e)))
+            for (int c = 0; c < nlin; c++) linSoft(c, col) = w[c];
+    return std::string();
+}
+std::vector<double> LmpcController::scalar_linear_block() const
+{
+    std::vector<double> v(sX);
+    for (int c = 0, nc = linear_rows_live(); c < nc; c++) {
+        for (int a = 0; a < d.nx; a++) v.push_back(linFx(c, a));
+        for (int j = 0; j < d.nu; j++) v.push_back(linFu(c, j));
+    }
+    return v;
+}
+int LmpcController::linear_rows_live() const
+{
+    for (int e = 0; e < nlin * (d.ph + 1); e++)
+        if (std::isfinite(linLo.a[e]) || std::isfinite(linHi.a[e])) return nlin;
+    return 0;
+}
+
 // smallest eigenvalue of a symmetric matrix by cyclic Jacobi rotations (nx <= 64: a set-up step)
 static double min_eigenvalue_sym(Mat S)
 {
@@ -272,7 +352,9 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
     o.n_ref = (ph + 1) * na + ph * nu;
     o.neq_ref = (ph + 1) * na;
     const int nineq = (ph + 1) * na + (ph + 1) * ny + ph * nu + (ph + 1);
-    o.m_ref = o.neq_ref + nineq;
+    // linear rows are appended behind the reference's own, (ph + 1) nc of them, for a controller that has any
+    const int nc = linear_rows_live(), off_lin = nineq;
+    o.m_ref = o.neq_ref + nineq + (ph + 1) * nc;
     o.active_words = (o.m_ref + 31) / 32;
     const int off_y = (ph + 1) * na, off_du = off_y + (ph + 1) * ny, off_s = off_du + ph * nu;
 
@@ -365,6 +447,12 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
         rows.push_back({G_SCALAR, 0, 0, o.neq_ref + off_s, sMin[0], sMax[0], inv_weight(softS[0])});
         grow.emplace_back(nz, 0.0);
     }
+    // (a hard step-0 linear row has no slot of its own among the feasibility rows: the filter below files it under fixed_rows)
+    for (int c = 0; c < nc; c++)
+        if (finite_any(linLo(c, 0), linHi(c, 0))) {
+            rows.push_back({G_LINEAR, 0, c, o.neq_ref + off_lin + c, linLo(c, 0), linHi(c, 0), inv_weight(linSoft(c, 0))});
+            grow.emplace_back(nz, 0.0);
+        }
     for (int i = 1; i <= ph; i++) {
         int k = std::min(i, ph - 1);           // x_u(i) takes input-bound column min(i, ph-1) (:735-749)
         for (int j = 0; j < nx; j++) {
@@ -404,6 +492,18 @@ std::string LmpcController::condense(Condensed &o, const Condensed *like) const
             }
             for (int j = 0; j < nu; j++) g[o.blk[i] * nu + j] += sU[j];
             rows.push_back({G_SCALAR, i, 0, o.neq_ref + off_s + i, sMin[i], sMax[i], inv_weight(softS[i])});
+            grow.push_back(std::move(g));
+        }
+        for (int c = 0; c < nc; c++) {
+            if (!finite_any(linLo(c, i), linHi(c, i))) continue;
+            std::vector<double> g(nz, 0.0);
+            for (int q = 0; q < nz && !light; q++) {
+                double s = 0;
+                for (int a = 0; a < nx; a++) s += linFx(c, a) * Sx[i](a, q);
+                g[q] = s;
+            }
+            for (int j = 0; j < nu; j++) g[o.blk[i] * nu + j] += linFu(c, j);
+            rows.push_back({G_LINEAR, i, c, o.neq_ref + off_lin + i * nc + c, linLo(c, i), linHi(c, i), inv_weight(linSoft(c, i))});
             grow.push_back(std::move(g));
         }
         // delta_{i-1} = v_i - v_{i-1}: bounded for the free moves (i - 1 <= ch, :782-793); v_0 = lastU is data and goes into the offset.
@@ -644,6 +744,9 @@ void LmpcController::assemble_host(const Condensed &o, const double *x0, const d
         } else if (kind == G_SCALAR) {
             for (int c = 0; c < nx; c++) v += sX[c] * xb[(size_t)st * nx + c];
             if (st == 0) for (int j = 0; j < nu; j++) v += sU[j] * u0[j];      // (a soft step-0 row: lastU is data there)
+        } else if (kind == G_LINEAR) {
+            for (int c = 0; c < nx; c++) v += linFx(cp, c) * xb[(size_t)st * nx + c];
+            if (st == 0) for (int j = 0; j < nu; j++) v += linFu(cp, j) * u0[j];  // (a step-0 row, hard or soft: lastU is data there)
         } else {
             v = st == 1 ? -u0[cp] : 0.0;        // G_RATE: delta_0 = v_1 - lastU; no free response, no disturbance
         }

@@ -41,7 +41,8 @@ double cholesky_lower(Mat &A);
 Mat spd_inverse_from_chol(const Mat &L);
 
 // G_RATE: a bound on the input increment delta_i = v_{i+1} - v_i (the reference's delta-u rows, ProblemBuilder.hpp:768-793); step = i + 1
-enum GKind : int { G_STATE = 0, G_OUTPUT = 1, G_SCALAR = 2, G_RATE = 3 };
+// G_LINEAR: row comp of the linear rows lo <= Fx x_i + Fu v_i <= hi (no counterpart in the reference), the scalar row's convention
+enum GKind : int { G_STATE = 0, G_OUTPUT = 1, G_SCALAR = 2, G_RATE = 3, G_LINEAR = 4 };
 
 struct GeneralRow {
     int kind, step, comp;   // which functional of the predicted trajectory
@@ -120,6 +121,10 @@ struct LmpcController {
     bool have_terminal = false;
     Mat termP, termTx;
     std::vector<double> termXT;
+    // linear rows linLo(c, i) <= linFx(c, :) x_i + linFu(c, :) v_i <= linHi(c, i), i = 0 .. ph internal columns as sMin / sMax (no
+    // counterpart in the reference's LMPC).  linFx [nlin x nx], linFu [nlin x nu] shared by all steps; linSoft [nlin x (ph + 1)]: +inf, the row is hard
+    int nlin = 0;
+    Mat linFx, linFu, linLo, linHi, linSoft;
     // LOptimizer state
     Mat yRef, uRef, duRef, dMeas;
     mpcx_lparams prm{};
@@ -151,6 +156,17 @@ struct LmpcController {
     std::vector<double> terminal_block() const;
     void set_scalar_vec(const double *smin, const double *smax, const double *X, const double *U);
     void set_scalar_idx(int idx, double smin, double smax, const double *X, const double *U);
+
+    // linear rows: empty string, or why the call is refused (nothing is stored then).  Whole horizon: lo, hi [nc x (ph + 1)] column-major, column =
+    // step; nc = 0 removes the rows.  Slice [s, e) of the prediction horizon (resolved and checked by the caller): lo, hi [nc], column shift of
+    // set_scalar_idx; an nc other than the stored one only while no step outside the slice holds a finite bound
+    std::string set_linear(int nc, const double *Fx, const double *Fu, const double *lo, const double *hi);
+    std::string set_linear_slice(int nc, const double *Fx, const double *Fu, const double *lo, const double *hi, int s, int e);
+    std::string set_linear_weights(const double *w, int s, int e);       // w [nlin]; s = e = -1: steps 0 .. ph
+    // what the device reads behind sX (MPCX_LINEAR_F in lmpc_device.hpp): [sX | row c: Fx(c, :) Fu(c, :)]
+    std::vector<double> scalar_linear_block() const;
+    // linear rows with a finite bound somewhere: zero means the controller condenses as one that never had any
+    int linear_rows_live() const;
 
     // returns empty string on success, message otherwise
     // like != nullptr: the structure and the O(n) arrays only, rows classified as in `like` (see lmpc_model.cpp)

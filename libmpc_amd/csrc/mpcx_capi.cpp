@@ -117,7 +117,7 @@ static void fill_dev_scalars(const mpcx_lmpc *h, const mpcx::LmpcController &c, 
     D.cost_direct = (o.h_regularised || o.inverse_residual > 1e-9) ? 1 : 0;
     D.check_every = h->dbg_check_every; D.polish_rounds0 = h->dbg_rounds0; D.polish_rounds = 10;
     D.alpha = c.prm.alpha; D.sigma = 1e-6;
-    D.adaptive_rho = (c.prm.adaptive_rho ? 1 : 0) | (c.have_terminal ? 2 : 0); D.rho_user = c.prm.rho;      // (a flag word: MPCX_HAS_TERMINAL, before lmpc_lds_per_wave)
+    D.adaptive_rho = (c.prm.adaptive_rho ? 1 : 0) | (c.have_terminal ? 2 : 0) | (c.linear_rows_live() << 2); D.rho_user = c.prm.rho;      // (a flag word: MPCX_HAS_TERMINAL, MPCX_LINEAR_NC, before lmpc_lds_per_wave)
     D.eps_abs = c.prm.eps_abs; D.eps_rel = c.prm.eps_rel; D.eps_prim_inf = c.prm.eps_prim_inf;
     D.lds_per_wave = mpcx::lmpc_lds_per_wave(D, &D.stage_len, &D.arena_len);
     D.wsld = D.ldz + D.ldy + 2 * D.ldg + 2;
@@ -149,7 +149,7 @@ static void fill_dev_arrays(const mpcx_lmpc *h, const mpcx::LmpcController &c, c
         for (int j = 0; j < c.d.ny; j++) { const bool soft = std::isfinite(c.softY(j, 0)); lo0y[j] = soft ? -mpcx::kInf : c.minY(j, 0); hi0y[j] = soft ? mpcx::kInf : c.maxY(j, 0); }
         D.lo0x = U.up(lo0x, rc); D.hi0x = U.up(hi0x, rc); D.lo0u = U.up(lo0u, rc); D.hi0u = U.up(hi0u, rc);
         D.lo0y = U.up(lo0y, rc); D.hi0y = U.up(hi0y, rc);
-        D.sX = U.up(c.sX, rc); D.sU = U.up(c.sU, rc);
+        D.sX = U.up(c.scalar_linear_block(), rc); D.sU = U.up(c.sU, rc);      // (the linear rows' coefficients ride behind sX: MPCX_LINEAR_F)
     }
     if (o.big_n[0]) {          // structure-only condensing: room for what the device kernel computes
         D.H = U.reserve_big(o.big_n[0]); D.Kinv = U.reserve_big(o.big_n[1]); D.Gr = U.reserve_big(o.big_n[2]); D.Gc = U.reserve_big(o.big_n[3]); D.Y = U.reserve_big(o.big_n[4]);
@@ -554,6 +554,42 @@ int mpcx_lmpc_set_scalar_constraint_index(mpcx_lmpc_t h, int index, double smin,
     h->ctl.set_scalar_idx(index, smin, smax, X, U);
     h->dirty = true;
     return MPCX_OK;
+}
+
+// Linear rows lo <= Fx x_i + Fu v_i <= hi (include/mpcx.h).  No counterpart in the reference's LMPC
+int mpcx_lmpc_set_linear_constraints(mpcx_lmpc_t h, int nc, const double *Fx, const double *Fu, const double *lo, const double *hi)
+{
+    CHECK_H(h);
+    const std::string msg = h->ctl.set_linear(nc, Fx, Fu, lo, hi);
+    if (!msg.empty()) return fail(MPCX_E_INVALID, msg);
+    h->dirty = true;
+    return MPCX_OK;
+}
+int mpcx_lmpc_set_linear_constraints_slice(mpcx_lmpc_t h, int nc, const double *Fx, const double *Fu, const double *lo, const double *hi, int start, int end)
+{
+    CHECK_H(h);
+    auto &c = h->ctl;
+    int s = start, e = end;
+    if (start == -1 && end == -1) { s = 0; e = c.d.ph; }
+    else if (!c.pred_slice_valid(start, end)) return fail(MPCX_E_INVALID, "The prediction horizon slice is out of bounds");
+    const std::string msg = c.set_linear_slice(nc, Fx, Fu, lo, hi, s, e);
+    if (!msg.empty()) return fail(MPCX_E_INVALID, msg);
+    h->dirty = true;
+    return MPCX_OK;
+}
+int mpcx_lmpc_set_linear_constraint_weights_slice(mpcx_lmpc_t h, const double *w, int start, int end)
+{
+    CHECK_H(h);
+    auto &c = h->ctl;
+    if (!(start == -1 && end == -1) && !c.pred_slice_valid(start, end)) return fail(MPCX_E_INVALID, "The prediction horizon slice is out of bounds");
+    const std::string msg = c.set_linear_weights(w, start, end);
+    if (!msg.empty()) return fail(MPCX_E_INVALID, msg);
+    h->dirty = true;
+    return MPCX_OK;
+}
+int mpcx_lmpc_set_linear_constraint_weights(mpcx_lmpc_t h, const double *w)
+{
+    return mpcx_lmpc_set_linear_constraint_weights_slice(h, w, -1, -1);
 }
 
 int mpcx_lmpc_set_references(mpcx_lmpc_t h, const double *yref, const double *uref, const double *duref)
@@ -1605,6 +1641,9 @@ int mpcx_lmpc_hetero_create_ex(const mpcx_lmpc_t *controllers, int count, int de
         // ... and a terminal cost in every controller or in none (the wavefronts' LDS plan is controller 0's); P, xT and Tx may differ
         if (ck.have_terminal != c0.have_terminal)
             return fail(MPCX_E_INVALID, "controller " + std::to_string(k) + " differs from controller 0 in whether it has a terminal cost");
+        // ... and as many linear rows (the LDS plan again, and the row numbering); Fx, Fu and the bounds may differ
+        if (ck.linear_rows_live() != c0.linear_rows_live())
+            return fail(MPCX_E_INVALID, "controller " + std::to_string(k) + " differs from controller 0 in the number of its linear rows");
     }
     std::unique_ptr<mpcx_lmpc_hetero> f(new mpcx_lmpc_hetero);
     f->device = device; f->count = count; f->d = c0.d; f->active_words = o0.active_words; f->m_ref = o0.m_ref;
@@ -1906,6 +1945,16 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }
     else if (n == "slo") v = &o.slo; else if (n == "shi") v = &o.shi;
     else if (n == "wOutput") v = &h->ctl.wOutput.a; else if (n == "wU") v = &h->ctl.wU.a;      // the weights as stored, [ny | nu x (ph + 1)] internal columns
+    else if (n == "linear") {             // the linear rows as stored: [nc | Fx | Fu | lo | hi | weights], the matrices column-major; [0] without any
+        const auto &c = h->ctl;
+        tmp = {(double)c.nlin};
+        for (const mpcx::Mat *m : {&c.linFx, &c.linFu, &c.linLo, &c.linHi, &c.linSoft}) tmp.insert(tmp.end(), m->a.begin(), m->a.end());
+        v = &tmp;
+    }
+    else if (n == "fixed_rows") {         // [kind, step, comp, refrow, lo, hi] of every row that sees no decision variable
+        for (const auto &r : o.fixed_rows) tmp.insert(tmp.end(), {(double)r.kind, (double)r.step, (double)r.comp, (double)r.refrow, r.lo, r.hi});
+        v = &tmp;
+    }
     else if (n == "terminal") { tmp = h->ctl.terminal_block(); v = &tmp; }      // [P | xT | Tx] as stored (P symmetrised); empty without the term
     else if (n == "ws_limit") {           // most rows a working set may hold, the lists' capacity, doubles of a wavefront's large-working-set slot
         tmp = {(double)mpcx::ws_limit(o.nz, o.mg, o.n_soft), (double)mpcx::ws_capacity(mpcx::ws_limit(o.nz, o.mg, o.n_soft)), (double)mpcx::lmpc_slot_len(h->dev)};

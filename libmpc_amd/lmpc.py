@@ -449,6 +449,7 @@ class LMPC(_LoopFrontEnd):
         self._Bd = np.zeros((self.nx, self.ndu))
         self._C, self._Dd = None, np.zeros((self.ny, self.ndu))               # the outputs as given: what an observed loop measures with
         self._has_terminal = False                               # a terminal cost is set (a bank takes it in every controller or in none)
+        self._nlin = 0                                           # linear rows stored (setLinearConstraints)
         self._last = Result(cmd=np.zeros(self.nu))
         self._stats = SolutionStats()
         self._last_u0 = np.zeros(self.nu)
@@ -577,6 +578,43 @@ class LMPC(_LoopFrontEnd):
         ok = self._ok(self._lib.mpcx_lmpc_set_terminal_cost(self._h, _p(Pm), None if x is None else _p(x), None if T is None else _p(T)))
         self._has_terminal = self._has_terminal or ok             # (a refused call stores nothing: what was there stays)
         return ok
+
+    def setLinearConstraints(self, Fx, Fu, lo, hi, slice=None):
+        """extension: nc linear rows lo[c, i] <= Fx[c, :] x_i + Fu[c, :] v_i <= hi[c, i] for the steps i = 0 .. ph, with v_i = u_{i-1} and
+        v_0 = lastU -- the scalar row's convention for nc rows whose coefficients Fx [nc x nx], Fu [nc x nu] all steps share.  Without a
+        slice lo and hi are [nc x (ph + 1)], column i bounding step i (a vector [nc] is taken for every step); with a slice they are vectors
+        [nc] and the slice works as setScalarConstraint's does -- (ph - 1, ph) is a terminal set F x_ph <= g.  An infinite side is absent;
+        Fx = None (or no rows) removes the rows.  False, with nothing stored, for NaN, an infinite coefficient, lo > hi, more than
+        MPCX_MAX_LINEAR_ROWS rows, or a slice whose nc differs from the stored rows' while other steps hold bounds.  The reference's LMPC
+        has no counterpart; the rows' active bits sit behind the reference's, at m_ref(reference) + i nc + c."""
+        if Fx is None or np.asarray(Fx).size + np.asarray(Fu).size == 0:
+            ok = self._ok(self._lib.mpcx_lmpc_set_linear_constraints(self._h, 0, None, None, None, None))
+            self._nlin = 0 if ok else self._nlin
+            return ok
+        Fx = np.atleast_2d(np.asarray(Fx, dtype=np.float64))
+        nc = Fx.shape[0]
+        Fxm, Fum = _cm(Fx, nc, self.nx), _cm(np.atleast_2d(np.asarray(Fu, dtype=np.float64)), nc, self.nu)
+        if slice is None:
+            L, H = (np.asarray(a, dtype=np.float64) for a in (lo, hi))
+            L, H = (np.repeat(a.reshape(nc, 1), self.ph + 1, axis=1) if a.ndim < 2 else a for a in (L, H))
+            L, H = _cm(L, nc, self.ph + 1), _cm(H, nc, self.ph + 1)
+            ok = self._ok(self._lib.mpcx_lmpc_set_linear_constraints(self._h, nc, _p(Fxm), _p(Fum), _p(L), _p(H)))
+        else:
+            sl = _slice(slice)
+            L, H = _vec(lo, nc), _vec(hi, nc)
+            ok = self._ok(self._lib.mpcx_lmpc_set_linear_constraints_slice(self._h, nc, _p(Fxm), _p(Fum), _p(L), _p(H), sl.start, sl.end))
+        self._nlin = nc if ok else self._nlin                     # (a refused call stores nothing: what was there stays)
+        return ok
+
+    def setLinearConstraintWeights(self, w, slice=None):
+        """extension: soft linear rows.  A weight rho in (0, inf] per row (w[nc], or one number for all), inf keeping the row hard, under
+        the rules of setSoftConstraintWeights; without a slice the steps 0 .. ph, a slice as setLinearConstraints' does."""
+        nc = self._nlin
+        wv = _vec(np.broadcast_to(np.asarray(w, dtype=np.float64), (nc,)) if np.ndim(w) == 0 else w, nc)
+        if slice is None:
+            return self._ok(self._lib.mpcx_lmpc_set_linear_constraint_weights(self._h, _p(wv)))
+        sl = _slice(slice)
+        return self._ok(self._lib.mpcx_lmpc_set_linear_constraint_weights_slice(self._h, _p(wv), sl.start, sl.end))
 
     def _lqr_problem(self, step):
         """(A, B, Q, R) of the unconstrained problem whose cost-to-go is the terminal weight: the weights of user column `step`"""
