@@ -247,6 +247,41 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
  * back-to-back launches; returns the mean kernel time in milliseconds. */
 int mpcx_lmpc_time_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream, int repeats, float *ms_mean);
 
+/* Sensitivities of a solved batch: the slope of the solution on each instance's active set.  On the working set a
+ * solve ended with, the decision vector is affine in (x0, lastU, yref); one launch evaluates the transpose of that map per instance.
+ *   MPCX_SENS_JACOBIAN  the local feedback law cmd ~ cmd* + d_x0 (x - x0) + d_u0 (lastU - u0) + d_yref (yref - yref0):
+ *                       d_x0 [B x nu x nx], d_u0 [B x nu x nu], d_yref [B x nu x ny], row-major, rows = components of cmd
+ *   MPCX_SENS_VJP       one cotangent per instance: seed_cmd [B x nu] on cmd and / or seed_input [B x (ph + 1) x nu] on the input sequence
+ *                       as the solve writes it (row i = the input of step min(i + 1, ph); row 0 is cmd); d_x0 [B x nx], d_u0 [B x nu],
+ *                       d_yref [B x ny] are the gradients of sum(seed * output)
+ * active_lower / active_upper are the words a solve of this handle wrote (required); which side a row is active on does not enter.  All
+ * pointers are device pointers; every output may be NULL.  status (optional): an instance whose status is not MPCX_STATUS_SUCCESS gets
+ * flag 1.  flags (optional): 0 fine; 1 not solved; 2 the working set is linearly dependent (the derivative does not exist there);
+ * 3 the working set has more rows than the kernel's LDS plan holds.  The outputs of an instance with a non-zero flag are NaN.
+ * d_x0 and d_u0 hold for every reference mode of the solve that produced the active sets: the linear part of the maps does not depend on
+ * references or exogenous inputs.  d_yref is the derivative with respect to a shift of the output reference common to all steps: the
+ * exact Jacobian for MPCX_REF_PER_INSTANCE, a directional derivative for the other modes.
+ * Asynchronous on `stream`, like the solve; allocates nothing.  Banks (mpcx_lmpc_hetero_*) have no such call. */
+#define MPCX_SENS_JACOBIAN 0
+#define MPCX_SENS_VJP      1
+typedef struct mpcx_lmpc_sens {
+    int batch;
+    const uint32_t *active_lower, *active_upper;  /* [B x active_words], device, as a solve wrote them */
+    const int32_t *status;       /* optional [B] */
+    int mode;                    /* MPCX_SENS_JACOBIAN | MPCX_SENS_VJP */
+    const double *seed_cmd;      /* VJP: [B x nu], may be NULL */
+    const double *seed_input;    /* VJP: [B x (ph+1) x nu], may be NULL (not both) */
+    double *d_x0, *d_u0, *d_yref;
+    int32_t *flags;              /* optional [B] */
+} mpcx_lmpc_sens;
+int mpcx_lmpc_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_sens *s, void *stream);
+int mpcx_lmpc_sens_size(void);   /* sizeof(mpcx_lmpc_sens), for bindings that mirror the struct */
+/* Host-array form for callers without a device allocator (mpc::LMPC<>::sensitivities): the Jacobians of the batch the last
+ * mpcx_lmpc_solve_host of this handle solved, on the active sets and status that call left on the device; d_x0 [B x nu x nx],
+ * d_u0 [B x nu x nu], d_yref [B x nu x ny] row-major and flags [B] on the host, each may be NULL.  Synchronous.  MPCX_E_STATE without
+ * such a solve, or after a change of the controller. */
+int mpcx_lmpc_sensitivity_host(mpcx_lmpc_t h, double *d_x0, double *d_u0, double *d_yref, int32_t *flags);
+
 /* One step as a HIP graph.  A control loop solves the same-sized batch from the same buffers every tick: the launches of
  * one mpcx_lmpc_solve_batch (dispatch-queue reset, assemble, solve, fallback) are captured once for a batch descriptor and
  * replayed with a single hipGraphLaunch.  The descriptor's pointers are baked into the graph; what they point to may change
@@ -788,7 +823,9 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
  * available, fused mat-vec form available], "fallback" = [instances the fallback kernel served in the last step that left it any (reading
  * clears it), entries the failure queue holds, wavefronts of the fallback kernel's grid], "terminal" = the stored terminal cost
  * [P | xT | Tx], P symmetrised, empty without one, "wOutput" / "wU" = the output and input weights as stored, [ny | nu x (ph + 1)] column-major,
- * user column k in internal column k + 1); out = NULL returns the length                                                                      */
+ * user column k in internal column k + 1, "MF1" = the composed map [rowsF x kin] column-major, "dims_fused" = [rowsF, nsp, kin, nxp, nup,
+ * nyp, ione], "boxrow_ptr" / "boxrow_ref" = the CSR table variable -> reference rows, "blk" = the condensed block of every step);
+ * out = NULL returns the length                                                                                                               */
 int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap);
 /* how many full set-ups (condensing + device rebuild) and how many reference-only refreshes have run on this handle */
 int mpcx_lmpc_debug_setup_counts(mpcx_lmpc_t h, int *full, int *refs);

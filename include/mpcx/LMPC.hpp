@@ -278,6 +278,31 @@ public:
         return r;
     }
     Result<Tnu> getLastResult() { return last_; }
+
+    // ---- extension: the local feedback law of the instance optimize() just solved (mpcx.h: sensitivities of a solved batch) ----------
+    // cmd ~ cmd* + Kx (x - x0) + Ku (lastU - u0) + Ky (yref - yref0) while the active set holds.  flag: 0 fine, 1 not solved, 2 dependent
+    // working set, 3 working set beyond the kernel's plan (the matrices are NaN then)
+    struct Sensitivities {
+        mat<Tnu, Tnx> Kx;
+        mat<Tnu, Tnu> Ku;
+        mat<Tnu, Tny> Ky;
+        int flag = 0;
+    };
+    Sensitivities sensitivities()
+    {
+        std::vector<double> kx((size_t)d_.nu * d_.nx), ku((size_t)d_.nu * d_.nu), ky((size_t)d_.nu * d_.ny);
+        int32_t flag = 0;
+        detail::check(mpcx_lmpc_sensitivity_host(h_, kx.data(), ku.data(), ky.data(), &flag), "sensitivities");
+        Sensitivities s;
+        s.Kx.resize(d_.nu, d_.nx); s.Ku.resize(d_.nu, d_.nu); s.Ky.resize(d_.nu, d_.ny);
+        for (int i = 0; i < d_.nu; ++i) {       // row-major from the device -> column-major matrices
+            for (int j = 0; j < d_.nx; ++j) s.Kx(i, j) = kx[(size_t)i * d_.nx + j];
+            for (int j = 0; j < d_.nu; ++j) s.Ku(i, j) = ku[(size_t)i * d_.nu + j];
+            for (int j = 0; j < d_.ny; ++j) s.Ky(i, j) = ky[(size_t)i * d_.ny + j];
+        }
+        s.flag = flag;
+        return s;
+    }
     OptSequence<Tnx, Tny, Tnu, detail::dimp1(Tph)> getOptimalSequence() { return seq_; }
     const SolutionStats &getExecutionStats() { return stats_; }
     void resetStats() { stats_ = SolutionStats{}; }

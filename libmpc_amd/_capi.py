@@ -77,6 +77,16 @@ class TargetDesc(C.Structure):
     _fields_ = [("map", C.c_void_p), ("map_batch", C.c_void_p), ("traj_us", C.c_void_p)]
 
 
+class Sens(C.Structure):
+    """mpcx_lmpc_sens: sensitivities of a solved batch (device pointers throughout)"""
+    _fields_ = [("batch", C.c_int), ("active_lower", C.c_void_p), ("active_upper", C.c_void_p), ("status", C.c_void_p),
+                ("mode", C.c_int), ("seed_cmd", C.c_void_p), ("seed_input", C.c_void_p),
+                ("d_x0", C.c_void_p), ("d_u0", C.c_void_p), ("d_yref", C.c_void_p), ("flags", C.c_void_p)]
+
+
+SENS_JACOBIAN, SENS_VJP = 0, 1
+
+
 class Info(C.Structure):
     _fields_ = [("n_ref", C.c_int), ("m_ref", C.c_int), ("neq_ref", C.c_int), ("nz", C.c_int), ("mg", C.c_int),
                 ("active_words", C.c_int), ("kernel_variant", C.c_int),
@@ -100,7 +110,7 @@ EXPORTS = [
     "mpcx_lmpc_set_references", "mpcx_lmpc_set_references_slice",
     "mpcx_lmpc_set_exogenous_inputs", "mpcx_lmpc_set_exogenous_inputs_slice",
     "mpcx_lmpc_set_optimizer_parameters", "mpcx_lmpc_set_strict_infeasibility", "mpcx_lmpc_setup", "mpcx_lmpc_solve_batch",
-    "mpcx_lmpc_time_solve_batch", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
+    "mpcx_lmpc_time_solve_batch", "mpcx_lmpc_sensitivity_batch", "mpcx_lmpc_sens_size", "mpcx_lmpc_sensitivity_host", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
     "mpcx_lmpc_graph_create", "mpcx_lmpc_graph_launch", "mpcx_lmpc_graph_destroy",
     "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
     "mpcx_lmpc_loop_create_observed", "mpcx_lmpc_hetero_loop_create_observed", "mpcx_lmpc_observer_desc_size", "mpcx_lmpc_kalman_gain",
@@ -200,6 +210,8 @@ def lib():
         _lib.mpcx_lmpc_set_linear_constraint_weights_slice.argtypes = [C.c_void_p] * 2 + [C.c_int, C.c_int]
         _lib.mpcx_nlmpc_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _lib.mpcx_nlmpc_destroy.argtypes = [C.c_void_p]
+        _lib.mpcx_lmpc_sensitivity_batch.argtypes = [C.c_void_p] * 3
+        _lib.mpcx_lmpc_sensitivity_host.argtypes = [C.c_void_p] * 5
         _lib.mpcx_lmpc_graph_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_destroy.argtypes = [C.c_void_p]

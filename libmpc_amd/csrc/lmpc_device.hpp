@@ -183,7 +183,22 @@ int lmpc_raise_dynamic_lds(LmpcLdsCache &cache, std::initializer_list<const void
 size_t lmpc_condense_lds(const LmpcDev &m, int *NP_out, int *NQ_out, size_t *big_out = nullptr);
 int lmpc_condense_launch(LmpcDev *models_d, const LmpcDev &m0, int count, void *stream);
 
-// The closed loop around the solve (lmpc_loop.hip): everything the advance kernel touches.  All device pointers; the same struct at every tick.
+// Sensitivities of a solved batch (lmpc_sens.hip).  All device pointers, laid out as mpcx_lmpc_sens documents them
+struct LmpcSensArgs {
+    int batch;
+    bool jacobian;                                // the nu unit seeds on cmd; otherwise one seed per instance from seed_cmd / seed_input
+    const uint32_t *active_lower, *active_upper;
+    const int32_t *status;
+    const double *seed_cmd, *seed_input;
+    double *d_x0, *d_u0, *d_yref;
+    int32_t *flags;
+};
+// the kernel's shared MFMA operand, the transpose of MF1's t0 rows packed by lmpc_pack_mfma_tiles: its length in doubles (out null), or filled in
+size_t lmpc_sens_operand(int nz, int kin, int rowsF, const double *MF1, double *out);
+// 0; -2: not even a working set of one row fits the LDS plan; -3: a launch or its configuration failed
+int lmpc_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double *T0p, const LmpcSensArgs &a, void *stream);
+
+// The closed loop around the solve (lmpc_loop.hip): everything the advance kernel touches. All device pointers; the same struct at every tick.
 // The packed blocks: per-instance coefficients in the order the advance kernels read them (lmpc_loop.hip, DESIGN 4.3b has the table)
 enum LoopBlock : int {
     kPlantBlock,                                  // [A_p | B_p | Bd_p] of the instance's plant

@@ -65,6 +65,9 @@ struct mpcx_lmpc {
     int warm_batch = 0;                 // batch size whose active sets are in stage_act (0: none)
     int n_full_setups = 0, n_ref_refreshes = 0;      // how often each kind of set-up ran (mpcx_lmpc_debug_setup_counts)
     mpcx::LmpcScratch scratch{};        // workspace, failure queue, large-working-set slots, persistent kernel's counters (lmpc_device.hpp)
+    const double *sens_t0p = nullptr;   // the sensitivity kernel's shared MFMA operand (lmpc_sens_operand), uploaded with the model
+    double *sens_stage = nullptr; size_t sens_stage_cap = 0;      // outputs of mpcx_lmpc_sensitivity_host on the device (kept between calls), instances
+    int sens_batch = 0;                 // batch size of the last mpcx_lmpc_solve_host whose active sets and status are still in the staging buffers (0: none)
     explicit mpcx_lmpc(const mpcx_dims &d) : ctl(d) {}
 
     void release()
@@ -73,13 +76,16 @@ struct mpcx_lmpc {
         allocs.clear();
         mpcx::lmpc_scratch_release(scratch);
         warm_batch = 0;                 // row numbering may have changed with the model
+        sens_batch = 0;
     }
     void release_staging()
     {
         if (stage_d) (void)hipFree(stage_d);
         if (stage_i) (void)hipFree(stage_i);
         if (stage_act) (void)hipFree(stage_act);
+        if (sens_stage) (void)hipFree(sens_stage);
         stage_d = nullptr; stage_i = nullptr; stage_act = nullptr; stage_cap = 0; warm_batch = 0;
+        sens_stage = nullptr; sens_stage_cap = 0; sens_batch = 0;
     }
     // copy into a buffer this handle already owns on the device (same size as at set-up)
     template <typename T>
@@ -716,6 +722,13 @@ int mpcx_lmpc_setup(mpcx_lmpc_t h)
     fill_dev_arrays(h, c, o, D, *h, rc);
     if (rc != MPCX_OK) return fail(rc, "device upload failed");
     {
+        // (the linear part of MF1 does not depend on references or exogenous inputs: a reference refresh leaves this operand as it is)
+        std::vector<double> t0p(mpcx::lmpc_sens_operand(o.nz, o.kin, o.rowsF, nullptr, nullptr));
+        mpcx::lmpc_sens_operand(o.nz, o.kin, o.rowsF, o.MF[1].data(), t0p.data());
+        h->sens_t0p = h->up(t0p, rc);
+        if (rc != MPCX_OK) return fail(rc, "device upload failed");
+    }
+    {
         void *p = nullptr;
         if (hipMalloc(&p, sizeof(mpcx::LmpcDev)) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMalloc failed");
         h->allocs.push_back(p);
@@ -809,6 +822,31 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
     if (mpcx::lmpc_scratch_reserve(h->scratch, h->dev, b->batch, true, stream) != 0) return fail(MPCX_E_DEVICE, "workspace allocation failed");
     const int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->scratch, stream, 7, lmpc_plan(h, b));
     return lr == 0 ? MPCX_OK : launch_failed(lr, h->scratch, stream);
+}
+
+int mpcx_lmpc_sens_size(void) { return (int)sizeof(mpcx_lmpc_sens); }
+
+int mpcx_lmpc_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_sens *s, void *stream)
+{
+    CHECK_H(h);
+    if (!s) return fail(MPCX_E_INVALID, "null sensitivity descriptor");
+    if (s->mode != MPCX_SENS_JACOBIAN && s->mode != MPCX_SENS_VJP) return fail(MPCX_E_INVALID, "unknown sensitivity mode");
+    if (s->batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (s->batch > 0 && (!s->active_lower || !s->active_upper)) return fail(MPCX_E_INVALID, "active_lower and active_upper are required");
+    if (s->batch > 0 && s->mode == MPCX_SENS_VJP && !s->seed_cmd && !s->seed_input) return fail(MPCX_E_INVALID, "a vector-Jacobian product needs seed_cmd or seed_input");
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the sensitivity kernel needs a HIP device, there is no CPU fallback");
+    int rc = mpcx_lmpc_setup(h);
+    if (rc != MPCX_OK) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (s->batch == 0) return MPCX_OK;
+    mpcx::LmpcSensArgs a{};
+    a.batch = s->batch; a.jacobian = s->mode == MPCX_SENS_JACOBIAN;
+    a.active_lower = s->active_lower; a.active_upper = s->active_upper; a.status = s->status;
+    a.seed_cmd = a.jacobian ? nullptr : s->seed_cmd; a.seed_input = a.jacobian ? nullptr : s->seed_input;
+    a.d_x0 = s->d_x0; a.d_u0 = s->d_u0; a.d_yref = s->d_yref; a.flags = s->flags;
+    const int lr = mpcx::lmpc_sens_launch(h->dev, h->dev_d, h->sens_t0p, a, stream);
+    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the sensitivity kernel's LDS budget");
+    return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
 }
 
 struct mpcx_lmpc_graph {
@@ -1517,11 +1555,14 @@ int mpcx_lmpc_solve_host(mpcx_lmpc_t h, int batch, const double *x0, const doubl
                 return fail(MPCX_E_DEVICE, "device copy failed");
             b.warm_active_lower = prev; b.warm_active_upper = prev + B * aw; b.warm_shift = 1;
         }
-        b.active_lower = cur; b.active_upper = cur + B * aw;
     }
+    // the active sets of this call stay on the device: the next call's warm start reads them, and so does mpcx_lmpc_sensitivity_host
+    b.active_lower = h->stage_act; b.active_upper = h->stage_act + B * aw;
+    h->sens_batch = 0;
     rc = mpcx_lmpc_solve_batch(h, &b, nullptr);
     if (rc == MPCX_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MPCX_E_DEVICE, "kernel execution failed");
     h->warm_batch = (rc == MPCX_OK && h->ctl.prm.enable_warm_start) ? batch : 0;
+    h->sens_batch = rc == MPCX_OK ? batch : 0;
     if (rc == MPCX_OK) {
         bool ok = true;
         auto back = [&](void *dst, const void *src, size_t bytes) { if (dst) ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
@@ -1532,6 +1573,36 @@ int mpcx_lmpc_solve_host(mpcx_lmpc_t h, int batch, const double *x0, const doubl
         if (!ok) rc = fail(MPCX_E_DEVICE, "copy of the results to the host failed");
     }
     return rc;
+}
+
+int mpcx_lmpc_sensitivity_host(mpcx_lmpc_t h, double *d_x0, double *d_u0, double *d_yref, int32_t *flags)
+{
+    CHECK_H(h);
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the sensitivity kernel needs a HIP device, there is no CPU fallback");
+    if (h->sens_batch <= 0 || h->dirty) return fail(MPCX_E_STATE, "no solve to differentiate: call mpcx_lmpc_solve_host first (and after any change of the controller)");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    const auto &d = h->ctl.d;
+    const size_t B = (size_t)h->sens_batch, aw = (size_t)h->dev.active_words, nin = (size_t)d.nx + d.nu + d.ny;
+    const size_t per = (size_t)d.nu * nin + 1;           // the three Jacobians, and room for the flag
+    if (B > h->sens_stage_cap) {
+        if (h->sens_stage) (void)hipFree(h->sens_stage);
+        h->sens_stage = nullptr; h->sens_stage_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&h->sens_stage), B * per * sizeof(double)) != hipSuccess) return fail(MPCX_E_DEVICE, "staging allocation failed");
+        h->sens_stage_cap = B;
+    }
+    double *kx = h->sens_stage, *ku = kx + B * d.nu * d.nx, *ky = ku + B * d.nu * d.nu;
+    int32_t *fl = reinterpret_cast<int32_t *>(ky + B * d.nu * d.ny);
+    mpcx_lmpc_sens s{};
+    s.batch = h->sens_batch; s.active_lower = h->stage_act; s.active_upper = h->stage_act + B * aw; s.status = h->stage_i;
+    s.mode = MPCX_SENS_JACOBIAN; s.d_x0 = kx; s.d_u0 = ku; s.d_yref = ky; s.flags = fl;
+    int rc = mpcx_lmpc_sensitivity_batch(h, &s, nullptr);
+    if (rc == MPCX_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MPCX_E_DEVICE, "kernel execution failed");
+    if (rc != MPCX_OK) return rc;
+    bool ok = true;
+    auto back = [&](void *dst, const void *src, size_t bytes) { if (dst) ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    back(d_x0, kx, B * d.nu * d.nx * sizeof(double)); back(d_u0, ku, B * d.nu * d.nu * sizeof(double)); back(d_yref, ky, B * d.nu * d.ny * sizeof(double));
+    back(flags, fl, B * sizeof(int32_t));
+    return ok ? MPCX_OK : fail(MPCX_E_DEVICE, "copy of the results to the host failed");
 }
 
 int mpcx_lmpc_time_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream, int repeats, float *ms_mean)
@@ -1940,6 +2011,11 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
                (double)o.ns, (double)o.ns16, (double)o.kq16, (double)o.rowsA, (double)o.ldy16};
         v = &tmp;
     } else if (n == "g_refrow") { tmp.assign(o.g_refrow.begin(), o.g_refrow.end()); v = &tmp; }
+    else if (n == "MF1") v = &o.MF[1];
+    else if (n == "dims_fused") { tmp = {(double)o.rowsF, (double)o.nsp, (double)o.kin, (double)o.nxp, (double)o.nup, (double)o.nyp, (double)o.ione}; v = &tmp; }
+    else if (n == "boxrow_ptr") { tmp.assign(o.boxrow_ptr.begin(), o.boxrow_ptr.end()); v = &tmp; }
+    else if (n == "boxrow_ref") { tmp.assign(o.boxrow_ref.begin(), o.boxrow_ref.end()); v = &tmp; }
+    else if (n == "blk") { tmp.assign(o.blk.begin(), o.blk.end()); v = &tmp; }
     else if (n == "g_step") { tmp.assign(o.g_step.begin(), o.g_step.end()); v = &tmp; }
     else if (n == "g_kind") { tmp.assign(o.g_kind.begin(), o.g_kind.end()); v = &tmp; }
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }

@@ -117,6 +117,20 @@ class BatchResult:
     seq_input: "object" = None
     polish_rounds: "object" = None
     active_count: "object" = None
+    sensitivities: "object" = None      # a SensitivityResult (optimizeBatch(..., sensitivities=True))
+
+
+@dataclass
+class SensitivityResult:
+    """The slope of a solved batch on each instance's active set (mpcx_lmpc_sensitivity_batch), device tensors.
+    Jacobian mode: d_x0 [B, nu, nx], d_u0 [B, nu, nu], d_yref [B, nu, ny] -- the local feedback law
+    cmd ~ cmd* + d_x0 (x - x0) + d_u0 (lastU - u0) + d_yref (yref - yref0).  With seeds: the gradients [B, nx], [B, nu], [B, ny] of
+    sum(seed * output).  d_yref is with respect to a shift of the output reference common to all steps.  flags [B]: 0 fine, 1 not solved,
+    2 dependent working set, 3 working set larger than the kernel's plan; the rows of an instance with a non-zero flag are NaN."""
+    d_x0: "object"
+    d_u0: "object"
+    d_yref: "object"
+    flags: "object"
 
 
 @dataclass
@@ -910,14 +924,72 @@ class LMPC(_LoopFrontEnd):
         return ms.value
 
     def optimizeBatch(self, x0, lastU, yref=None, uref=None, duref=None, dmeas=None,
-                      want_active=False, want_sequence=False, stream=None, warm=None, warm_shift=False) -> BatchResult:
+                      want_active=False, want_sequence=False, stream=None, warm=None, warm_shift=False, sensitivities=False) -> BatchResult:
         """B independent LOptimizer::run calls (LOptimizer.hpp:189) in one launch.  `warm`: the BatchResult of the
         previous control tick (solved with want_active=True) -- its active sets seed the working sets; warm_shift=True
-        looks each row up one horizon step later (receding horizon)."""
-        b, res, keep = self.make_batch(x0, lastU, yref, uref, duref, dmeas, want_active or warm is not None, want_sequence, warm, warm_shift)
+        looks each row up one horizon step later (receding horizon).  sensitivities=True: the Jacobians of cmd on the active
+        sets this solve wrote, as `result.sensitivities` (one more launch on the same stream)."""
+        b, res, keep = self.make_batch(x0, lastU, yref, uref, duref, dmeas, want_active or sensitivities or warm is not None, want_sequence, warm, warm_shift)
         self.launch(b, stream, keep)
         res._inputs = keep                     # the inputs live as long as the result that was computed from them
+        if sensitivities:
+            res.sensitivities = self.sensitivityBatch(res.active_lower, res.active_upper, status=res.status, stream=stream)
         return res
+
+    def make_sensitivity(self, active_lower, active_upper, status=None, seed_cmd=None, seed_input=None, want=("x0", "u0", "yref")):
+        """Allocate outputs and fill the mpcx_lmpc_sens descriptor.  Returns (Sens, SensitivityResult, keepalive)."""
+        torch, dev = self._torch()
+        words = self.info()["active_words"]
+        al = active_lower.to(dev).contiguous(); au = active_upper.to(dev).contiguous()
+        B = int(al.shape[0])
+        if tuple(al.shape) != (B, words) or tuple(au.shape) != (B, words) or al.dtype != torch.int32 or au.dtype != torch.int32:
+            raise ValueError(f"active sets must be int32 [B, {words}]")
+        st = None if status is None else status.to(device=dev, dtype=torch.int32).contiguous()
+        if st is not None and tuple(st.shape) != (B,):
+            raise ValueError("status must be [B]")
+        sc = self._dev(torch, dev, seed_cmd, (B, self.nu))
+        si = self._dev(torch, dev, seed_input, (B, self.ph + 1, self.nu))
+        jac = sc is None and si is None
+        lead = (B, self.nu) if jac else (B,)
+        f64 = torch.float64
+        out = SensitivityResult(
+            d_x0=torch.empty(lead + (self.nx,), dtype=f64, device=dev) if "x0" in want else None,
+            d_u0=torch.empty(lead + (self.nu,), dtype=f64, device=dev) if "u0" in want else None,
+            d_yref=torch.empty(lead + (self.ny,), dtype=f64, device=dev) if "yref" in want else None,
+            flags=torch.empty((B,), dtype=torch.int32, device=dev))
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        d = _capi.Sens()
+        d.batch = B
+        d.active_lower, d.active_upper, d.status = ptr(al), ptr(au), ptr(st)
+        d.mode = _capi.SENS_JACOBIAN if jac else _capi.SENS_VJP
+        d.seed_cmd, d.seed_input = ptr(sc), ptr(si)
+        d.d_x0, d.d_u0, d.d_yref, d.flags = ptr(out.d_x0), ptr(out.d_u0), ptr(out.d_yref), ptr(out.flags)
+        return d, out, (al, au, st, sc, si, out.d_x0, out.d_u0, out.d_yref, out.flags)
+
+    def launch_sensitivity(self, desc, stream=None, keep=None):
+        """One asynchronous launch for a descriptor built by make_sensitivity(); streams as in launch()."""
+        torch, _ = self._torch()
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+            for t in (keep or ()):
+                if t is not None:
+                    t.record_stream(s)
+        check(self._lib.mpcx_lmpc_sensitivity_batch(self._h, C.byref(desc), C.c_void_p(s.cuda_stream)))
+
+    def sensitivityBatch(self, active_lower, active_upper, status=None, seed_cmd=None, seed_input=None, stream=None,
+                         want=("x0", "u0", "yref")) -> SensitivityResult:
+        """The slope of solved instances on their active sets (mpcx_lmpc_sensitivity_batch): one launch.  active_lower / active_upper
+        [B, active_words] as optimizeBatch(want_active=True) wrote them; status [B] (optional) marks the instances that were not
+        solved.  Without seeds: the Jacobians of cmd.  seed_cmd [B, nu] and / or seed_input [B, ph + 1, nu] (a cotangent on the input
+        sequence as the solve writes it: row 0 is cmd): the vector-Jacobian products.  want: which outputs to compute."""
+        d, out, keep = self.make_sensitivity(active_lower, active_upper, status, seed_cmd, seed_input, want)
+        self.launch_sensitivity(d, stream, keep)
+        out._inputs = keep[:5]
+        return out
 
     def optimize(self, x0, lastU) -> Result:
         """IMPC::optimize (IMPC.hpp:149-166) for one instance, through the batched path."""
