@@ -282,6 +282,44 @@ int mpcx_lmpc_sens_size(void);   /* sizeof(mpcx_lmpc_sens), for bindings that mi
  * such a solve, or after a change of the controller. */
 int mpcx_lmpc_sensitivity_host(mpcx_lmpc_t h, double *d_x0, double *d_u0, double *d_yref, int32_t *flags);
 
+/* Parameter sensitivities of a solved batch: the gradient of sum(seed * output) -- seeds on cmd and / or on the input sequence,
+ * exactly as MPCX_SENS_VJP takes them, one per instance -- with respect to the three weight matrices of mpcx_lmpc_set_objective_weights and to
+ * every bound of the QP, on the active set each instance was solved on.  One launch after the solve; a second small one adds up the batch.
+ *   solved      the batch descriptor a solve of this handle filled, unchanged since: x0, u0, the references in their modes, seq_output,
+ *               seq_input, active_lower, active_upper (all required) and status (optional: an unsolved instance gets flag 1)
+ *   reduce      0: an output set per instance, d_oweight [B x (ny x ph)], d_uweight, d_duweight [B x (nu x ph)], each matrix column-major as
+ *               the setter takes it (column = user step), d_lower, d_upper [B x m_ref]; 1: one set, the sum over the instances whose flag is 0,
+ *               added in a fixed order without floating-point atomics (two launches give the same bits), and n_used [1] = how many those were.
+ *               reduce = 1 takes its partial sums from a buffer of the handle: mpcx_lmpc_param_sens_reserve(h, batch) once, outside any
+ *               capture, for the largest batch (MPCX_E_STATE otherwise); the launch itself allocates nothing
+ *   d_lower / d_upper   one entry per row the active words name (mpcx_lmpc_info.m_ref, the linear rows included), in that numbering: the
+ *               multiplier of the adjoint system on the side whose bit is set (the upper one where both are), zero for every other row and
+ *               for rows without decision variables (the step-0 box rows).  A condensed variable bounded by several reference rows (move
+ *               blocking) files the whole value under the lowest-numbered row whose bit is set
+ * flags: the codes of mpcx_lmpc_sens -- 0 fine, 1 not solved, 2 dependent working set, 3 beyond the LDS plan; with reduce = 0 the outputs of a flagged
+ * instance are NaN.  All pointers are device pointers, every output may be NULL.  MPCX_E_STATE when the controller changed, or was set up
+ * again, since this handle's last mpcx_lmpc_solve_batch: the batch must be the one that call solved.  Not differentiated: the model, the terminal weight, soft weights, the coefficients of scalar and linear rows.
+ * Asynchronous on `stream`; neither form allocates or copies at launch: the kernel's operand Cq is uploaded by the set-up, the partial sums of
+ * reduce = 1 by mpcx_lmpc_param_sens_reserve.  With reduce = 1 and both d_lower and d_upper NULL the bound rows are not computed at all.
+ * Banks have no such call. */
+typedef struct mpcx_lmpc_param_sens {
+    const mpcx_lmpc_batch *solved;
+    const double *seed_cmd, *seed_input;          /* [B x nu], [B x (ph+1) x nu]; at least one */
+    int reduce;
+    double *d_oweight, *d_uweight, *d_duweight;
+    double *d_lower, *d_upper;
+    int32_t *flags;                               /* optional [B] */
+    int32_t *n_used;                              /* optional [1], reduce = 1 only */
+} mpcx_lmpc_param_sens;
+int mpcx_lmpc_param_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_param_sens *s, void *stream);
+int mpcx_lmpc_param_sens_size(void);   /* sizeof(mpcx_lmpc_param_sens) */
+int mpcx_lmpc_param_sens_reserve(mpcx_lmpc_t h, int batch);      /* the partial sums of reduce = 1 for batches up to `batch` (grow-only) */
+/* Host-array form over the batch the last mpcx_lmpc_solve_host of this handle solved with its sequences asked for (mpc::LMPC<>::
+ * parameterSensitivities): seeds and outputs on the host, laid out as above; synchronous.  MPCX_E_STATE without such a solve. */
+int mpcx_lmpc_param_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, const double *seed_input, int reduce,
+                                     double *d_oweight, double *d_uweight, double *d_duweight, double *d_lower, double *d_upper,
+                                     int32_t *flags, int32_t *n_used);
+
 /* One step as a HIP graph.  A control loop solves the same-sized batch from the same buffers every tick: the launches of
  * one mpcx_lmpc_solve_batch (dispatch-queue reset, assemble, solve, fallback) are captured once for a batch descriptor and
  * replayed with a single hipGraphLaunch.  The descriptor's pointers are baked into the graph; what they point to may change
@@ -824,7 +862,9 @@ int mpcx_lmpc_debug_time_kernels(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *
  * clears it), entries the failure queue holds, wavefronts of the fallback kernel's grid], "terminal" = the stored terminal cost
  * [P | xT | Tx], P symmetrised, empty without one, "wOutput" / "wU" = the output and input weights as stored, [ny | nu x (ph + 1)] column-major,
  * user column k in internal column k + 1, "MF1" = the composed map [rowsF x kin] column-major, "dims_fused" = [rowsF, nsp, kin, nxp, nup,
- * nyp, ione], "boxrow_ptr" / "boxrow_ref" = the CSR table variable -> reference rows, "blk" = the condensed block of every step);
+ * nyp, ione], "boxrow_ptr" / "boxrow_ref" = the CSR table variable -> reference rows, "blk" = the condensed block of every step,
+ * "Cq" = the derivative of the outputs of the steps 1 .. ph with respect to the decision vector, [rows16 x nz] column-major, rows16 = ny ph
+ * rounded up to 16, row (i - 1) ny + a = output a of step i);
  * out = NULL returns the length                                                                                                               */
 int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap);
 /* how many full set-ups (condensing + device rebuild) and how many reference-only refreshes have run on this handle */

@@ -303,6 +303,29 @@ public:
         s.flag = flag;
         return s;
     }
+    // ---- extension: gradients with respect to the weights and bounds of the instance optimize() just solved (mpcx.h: parameter sensitivities
+    // of a solved batch).  For a cotangent seed on cmd: the gradient of seed' cmd with respect to the matrices setObjectiveWeights takes (same
+    // indexing) and to every bound of the QP, in the row numbering of the active sets (mpcx_lmpc_info.m_ref entries a side).  flag as above
+    struct ParameterSensitivities {
+        mat<Tny, Tph> dOWeight;
+        mat<Tnu, Tph> dUWeight, dDeltaUWeight;
+        std::vector<double> dLower, dUpper;
+        int flag = 0;
+    };
+    ParameterSensitivities parameterSensitivities(const cvec<Tnu> &seed_cmd)
+    {
+        mpcx_lmpc_info info{};
+        detail::check(mpcx_lmpc_get_info(h_, &info), "parameterSensitivities");
+        ParameterSensitivities s;
+        s.dOWeight.resize(d_.ny, d_.ph); s.dUWeight.resize(d_.nu, d_.ph); s.dDeltaUWeight.resize(d_.nu, d_.ph);
+        s.dLower.assign((size_t)info.m_ref, 0.0); s.dUpper.assign((size_t)info.m_ref, 0.0);
+        int32_t flag = 0;
+        // (the device writes the matrices column-major, as these are stored)
+        detail::check(mpcx_lmpc_param_sensitivity_host(h_, seed_cmd.data(), nullptr, 0, s.dOWeight.data(), s.dUWeight.data(), s.dDeltaUWeight.data(),
+                                                       s.dLower.data(), s.dUpper.data(), &flag, nullptr), "parameterSensitivities");
+        s.flag = flag;
+        return s;
+    }
     OptSequence<Tnx, Tny, Tnu, detail::dimp1(Tph)> getOptimalSequence() { return seq_; }
     const SolutionStats &getExecutionStats() { return stats_; }
     void resetStats() { stats_ = SolutionStats{}; }

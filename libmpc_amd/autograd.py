@@ -6,7 +6,18 @@
 The gradient is that of the solution on the active set the solve ended with: exact wherever the active set does not change
 under an infinitesimal perturbation, NaN for an instance that was not solved or whose working set is linearly dependent (the flags of
 mpcx_lmpc_sensitivity_batch).  yref is a per-instance constant reference [B, ny]; a per-step reference can be passed but not differentiated.
-Torch is imported on first use, as elsewhere in the package."""
+Torch is imported on first use, as elsewhere in the package.
+
+    cmd = lmpc_cmd_params(controller, x0, u0, yref, OWeight, UWeight, DeltaUWeight)
+
+is the same first move, differentiable with respect to the three weight matrices of setObjectiveWeights as well: what a tuning loop needs that
+descends on a closed-loop or imitation loss over many instances.  Forward sets the weights, sets the controller up and solves; backward is
+one launch of the vector-Jacobian product above and one of LMPC.paramSensitivityBatch with reduce=True -- the weights are
+shared by the batch, so their gradient is the sum over the instances, added in a fixed order; an instance that was not solved or whose working
+set is dependent contributes nothing to it.  Gradients with respect to the bounds are not part of this function: paramSensitivityBatch returns
+them, in the row numbering of the active sets.  The backward pass differentiates the batch the controller solved last, under the set-up of that solve:
+call backward before the controller is changed, set up again or given another forward pass of this function (mpcx_lmpc_param_sensitivity_batch
+answers MPCX_E_STATE after a change or a new set-up); keep one controller per graph that is kept."""
 from __future__ import annotations
 
 _FUNCTION = None
@@ -37,6 +48,62 @@ def _function():
 
     _FUNCTION = LmpcCmd
     return _FUNCTION
+
+
+_PARAM_FUNCTION = None
+
+
+def _param_function():
+    global _PARAM_FUNCTION
+    if _PARAM_FUNCTION is not None:
+        return _PARAM_FUNCTION
+    import torch
+
+    class LmpcCmdParams(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, controller, x0, u0, yref, ow, uw, dw):
+            if not controller.setObjectiveWeights(ow.detach().cpu().numpy(), uw.detach().cpu().numpy(), dw.detach().cpu().numpy()):
+                raise ValueError("lmpc_cmd_params: the controller refused the weights")
+            controller.setup()
+            res = controller.optimizeBatch(x0.detach(), u0.detach(), None if yref is None else yref.detach(), want_active=True, want_sequence=True)
+            ctx.controller, ctx.res = controller, res
+            ctx.has_yref = yref is not None
+            ctx.mark_non_differentiable(res.status)
+            return res.cmd, res.status
+
+        @staticmethod
+        def backward(ctx, grad_cmd, _grad_status):
+            c, res = ctx.controller, ctx.res
+            seed = grad_cmd.contiguous()
+            need = ctx.needs_input_grad
+            g = [None] * 7
+            want = tuple(n for n, k in zip(("x0", "u0", "yref"), need[1:4]) if k)
+            if want:
+                s = c.sensitivityBatch(res.active_lower, res.active_upper, status=res.status, seed_cmd=seed, want=want)
+                g[1], g[2], g[3] = s.d_x0, s.d_u0, (s.d_yref if ctx.has_yref else None)
+            wantp = tuple(n for n, k in zip(("oweight", "uweight", "duweight"), need[4:7]) if k)
+            if wantp:
+                p = c.paramSensitivityBatch(res, seed_cmd=seed, reduce=True, want=wantp)
+                g[4], g[5], g[6] = p.d_oweight, p.d_uweight, p.d_duweight
+            return tuple(g)
+
+    _PARAM_FUNCTION = LmpcCmdParams
+    return _PARAM_FUNCTION
+
+
+def lmpc_cmd_params(controller, x0, u0, yref, OWeight, UWeight, DeltaUWeight, return_status=False):
+    """cmd [B, nu] of `controller` (a libmpc_amd.LMPC) with the objective weights OWeight [ny, ph], UWeight [nu, ph], DeltaUWeight [nu, ph] (the
+    matrices of setObjectiveWeights, torch tensors on any device) at x0 [B, nx], u0 [B, nu] and the per-instance output reference yref [B, ny]
+    (None: the controller's own), differentiable with respect to all six.  The controller keeps the weights afterwards.  The gradients of the
+    weights are sums over the batch; those of the bounds come from LMPC.paramSensitivityBatch.  return_status: (cmd, status) instead."""
+    import torch
+    _, dev = controller._torch()
+    as_t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64)).to(device=dev, dtype=torch.float64)
+    x0, u0, yref = as_t(x0), as_t(u0), as_t(yref)
+    if yref is not None and yref.dim() != 2 and yref.requires_grad:
+        raise ValueError("lmpc_cmd_params differentiates a per-instance output reference [B, ny]; a per-step reference has no gradient here")
+    cmd, status = _param_function().apply(controller, x0, u0, yref, as_t(OWeight), as_t(UWeight), as_t(DeltaUWeight))
+    return (cmd, status) if return_status else cmd
 
 
 def lmpc_cmd(controller, x0, u0, yref=None, return_status=False):

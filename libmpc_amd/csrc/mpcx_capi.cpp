@@ -68,6 +68,13 @@ struct mpcx_lmpc {
     const double *sens_t0p = nullptr;   // the sensitivity kernel's shared MFMA operand (lmpc_sens_operand), uploaded with the model
     double *sens_stage = nullptr; size_t sens_stage_cap = 0;      // outputs of mpcx_lmpc_sensitivity_host on the device (kept between calls), instances
     int sens_batch = 0;                 // batch size of the last mpcx_lmpc_solve_host whose active sets and status are still in the staging buffers (0: none)
+    // parameter sensitivities (lmpc_param_sens.hip): Cq on the host and packed on the device, built at first use after a set-up; the partials of the
+    // batch reduction (mpcx_lmpc_param_sens_reserve; grow-only); the host form's outputs on the device; whether the last mpcx_lmpc_solve_host kept its sequences
+    std::vector<double> param_cq; const double *param_cqp = nullptr;
+    double *param_part = nullptr; size_t param_part_cap = 0;
+    double *param_stage = nullptr; size_t param_stage_cap = 0;      // (capacity in doubles: a set-up may change m_ref, and with it the length per instance)
+    bool sens_has_seq = false;
+    int solved_full = -1, solved_refs = -1;          // n_full_setups / n_ref_refreshes when mpcx_lmpc_solve_batch last launched: the set-up a solved batch belongs to
     explicit mpcx_lmpc(const mpcx_dims &d) : ctl(d) {}
 
     void release()
@@ -77,6 +84,7 @@ struct mpcx_lmpc {
         mpcx::lmpc_scratch_release(scratch);
         warm_batch = 0;                 // row numbering may have changed with the model
         sens_batch = 0;
+        param_cqp = nullptr;            // (it was one of allocs)
     }
     void release_staging()
     {
@@ -84,6 +92,9 @@ struct mpcx_lmpc {
         if (stage_i) (void)hipFree(stage_i);
         if (stage_act) (void)hipFree(stage_act);
         if (sens_stage) (void)hipFree(sens_stage);
+        if (param_stage) (void)hipFree(param_stage);
+        if (param_part) (void)hipFree(param_part);
+        param_stage = nullptr; param_stage_cap = 0; param_part = nullptr; param_part_cap = 0;
         stage_d = nullptr; stage_i = nullptr; stage_act = nullptr; stage_cap = 0; warm_batch = 0;
         sens_stage = nullptr; sens_stage_cap = 0; sens_batch = 0;
     }
@@ -700,6 +711,8 @@ static int refresh_references(mpcx_lmpc_t h)
     return ok ? MPCX_OK : fail(MPCX_E_DEVICE, "device upload failed");
 }
 
+static int param_operand(mpcx_lmpc_t h, bool device);
+
 int mpcx_lmpc_setup(mpcx_lmpc_t h)
 {
     CHECK_H(h);
@@ -714,6 +727,7 @@ int mpcx_lmpc_setup(mpcx_lmpc_t h)
         return fail(MPCX_E_UNSUPPORTED, "condensed problem larger than 512 variables / rows");
     mpcx::LmpcDev &D = h->dev;
     fill_dev_scalars(h, c, o, D);
+    h->param_cq.clear();
     if (h->host_only) { h->dirty = false; return MPCX_OK; }
 
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
@@ -728,6 +742,8 @@ int mpcx_lmpc_setup(mpcx_lmpc_t h)
         h->sens_t0p = h->up(t0p, rc);
         if (rc != MPCX_OK) return fail(rc, "device upload failed");
     }
+    // the parameter-sensitivity kernel's operand beside it (Cq depends on the model and the blocking alone): its launch allocates and copies nothing
+    if (param_operand(h, true) != MPCX_OK) return MPCX_E_DEVICE;
     {
         void *p = nullptr;
         if (hipMalloc(&p, sizeof(mpcx::LmpcDev)) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMalloc failed");
@@ -821,6 +837,8 @@ int mpcx_lmpc_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream)
     if (rc != MPCX_OK) return rc;
     if (mpcx::lmpc_scratch_reserve(h->scratch, h->dev, b->batch, true, stream) != 0) return fail(MPCX_E_DEVICE, "workspace allocation failed");
     const int lr = mpcx::lmpc_launch(h->dev, h->dev_d, B, h->scratch, stream, 7, lmpc_plan(h, b));
+    if (lr == 0) { h->solved_full = h->n_full_setups; h->solved_refs = h->n_ref_refreshes; }
+    else h->solved_full = h->solved_refs = -1;
     return lr == 0 ? MPCX_OK : launch_failed(lr, h->scratch, stream);
 }
 
@@ -846,6 +864,90 @@ int mpcx_lmpc_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_sens *s, void *st
     a.d_x0 = s->d_x0; a.d_u0 = s->d_u0; a.d_yref = s->d_yref; a.flags = s->flags;
     const int lr = mpcx::lmpc_sens_launch(h->dev, h->dev_d, h->sens_t0p, a, stream);
     if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the sensitivity kernel's LDS budget");
+    return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+}
+
+// Cq of the current set-up on the host (a host-only handle: at first use) and, with a device, packed in HBM (by the set-up)
+static int param_operand(mpcx_lmpc_t h, bool device)
+{
+    const auto &c = h->ctl;
+    const auto &o = h->cond;
+    if (h->param_cq.empty()) {
+        h->param_cq.resize(mpcx::lmpc_param_sens_cq(c.d.nx, c.d.nu, c.d.ny, c.d.ph, o.nz, nullptr, nullptr, nullptr, nullptr, nullptr));
+        mpcx::lmpc_param_sens_cq(c.d.nx, c.d.nu, c.d.ny, c.d.ph, o.nz, c.A.a.data(), c.B.a.data(), c.C.a.data(), o.blk.data(), h->param_cq.data());
+    }
+    if (device && !h->param_cqp) {
+        const int rows16 = (c.d.ny * c.d.ph + 15) / 16 * 16;
+        std::vector<double> pk(mpcx::lmpc_packed_len(rows16, o.nz));
+        mpcx::lmpc_pack_mfma_tiles(h->param_cq.data(), rows16, o.nz, pk.data());
+        int rc = MPCX_OK;
+        h->param_cqp = h->up(pk, rc);
+        if (rc != MPCX_OK) { h->param_cqp = nullptr; return fail(rc, "device upload failed"); }
+    }
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_param_sens_size(void) { return (int)sizeof(mpcx_lmpc_param_sens); }
+
+int mpcx_lmpc_param_sens_reserve(mpcx_lmpc_t h, int batch)
+{
+    CHECK_H(h);
+    if (batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the parameter-sensitivity kernel needs a HIP device, there is no CPU fallback");
+    int rc = mpcx_lmpc_setup(h);
+    if (rc != MPCX_OK) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    const size_t need = mpcx::lmpc_param_sens_partials(h->dev, batch);
+    if (need > h->param_part_cap) {
+        if (h->param_part) (void)hipFree(h->param_part);
+        h->param_part = nullptr; h->param_part_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&h->param_part), need * sizeof(double)) != hipSuccess) return fail(MPCX_E_DEVICE, "allocation of the partial sums failed");
+        h->param_part_cap = need;
+    }
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_param_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_param_sens *s, void *stream)
+{
+    CHECK_H(h);
+    if (!s) return fail(MPCX_E_INVALID, "null parameter-sensitivity descriptor");
+    const mpcx_lmpc_batch *b = s->solved;
+    if (!b) return fail(MPCX_E_INVALID, "the solved batch is required");
+    if (b->batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (s->reduce != 0 && s->reduce != 1) return fail(MPCX_E_INVALID, "reduce must be 0 or 1");
+    if (b->batch > 0 && (!b->active_lower || !b->active_upper)) return fail(MPCX_E_INVALID, "active_lower and active_upper of the solved batch are required");
+    if (b->batch > 0 && (!b->seq_output || !b->seq_input)) return fail(MPCX_E_INVALID, "seq_output and seq_input of the solved batch are required");
+    if (b->batch > 0 && (!b->x0 || !b->u0)) return fail(MPCX_E_INVALID, "x0 and u0 of the solved batch are required");
+    if (b->batch > 0 && !s->seed_cmd && !s->seed_input) return fail(MPCX_E_INVALID, "a parameter sensitivity needs seed_cmd or seed_input");
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the parameter-sensitivity kernel needs a HIP device, there is no CPU fallback");
+    // (a set-up that ran since the handle's last solve -- any call sets a changed controller up -- has replaced what that solve's active sets refer to)
+    if (h->dirty || h->refs_dirty || !h->dev_d || h->solved_full != h->n_full_setups || h->solved_refs != h->n_ref_refreshes)
+        return fail(MPCX_E_STATE, "the controller changed since the set-up that solved this batch (or nothing was solved): solve again first");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (b->batch == 0) return MPCX_OK;
+    mpcx::LmpcBatchDev B;
+    {
+        // (cmd is not read here; the solve's own check of it does not apply)
+        const auto &D = h->dev;
+        const double *const shared[4] = {D.yref_s, D.uref_s, D.duref_s, D.dmeas_s};
+        const int rc = make_batch(h->ctl.d, b, shared, B);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (s->reduce && mpcx::lmpc_param_sens_partials(h->dev, b->batch) > h->param_part_cap)
+        return fail(MPCX_E_STATE, "reduce = 1 needs mpcx_lmpc_param_sens_reserve for this batch size first: the launch allocates nothing");
+    if (!h->param_cqp) return fail(MPCX_E_STATE, "the controller was never set up on the device");
+    mpcx::LmpcParamSensArgs a{};
+    a.batch = b->batch; a.reduce = s->reduce != 0;
+    a.active_lower = b->active_lower; a.active_upper = b->active_upper; a.status = b->status;
+    a.seed_cmd = s->seed_cmd; a.seed_input = s->seed_input;
+    a.u0 = b->u0; a.seq_output = b->seq_output; a.seq_input = b->seq_input;
+    a.yref = B.yref; a.yref_bs = B.yref_bs; a.yref_ks = B.yref_ks;
+    a.uref = B.uref; a.uref_bs = B.uref_bs; a.uref_ks = B.uref_ks;
+    a.duref = B.duref; a.duref_bs = B.duref_bs; a.duref_ks = B.duref_ks;
+    a.d_oweight = s->d_oweight; a.d_uweight = s->d_uweight; a.d_duweight = s->d_duweight; a.d_lower = s->d_lower; a.d_upper = s->d_upper;
+    a.flags = s->flags; a.n_used = s->n_used; a.partials = s->reduce ? h->param_part : nullptr;
+    const int lr = mpcx::lmpc_param_sens_launch(h->dev, h->dev_d, h->param_cqp, a, stream);
+    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the parameter-sensitivity kernel's LDS budget");
     return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
 }
 
@@ -1563,6 +1665,7 @@ int mpcx_lmpc_solve_host(mpcx_lmpc_t h, int batch, const double *x0, const doubl
     if (rc == MPCX_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MPCX_E_DEVICE, "kernel execution failed");
     h->warm_batch = (rc == MPCX_OK && h->ctl.prm.enable_warm_start) ? batch : 0;
     h->sens_batch = rc == MPCX_OK ? batch : 0;
+    h->sens_has_seq = want_seq;
     if (rc == MPCX_OK) {
         bool ok = true;
         auto back = [&](void *dst, const void *src, size_t bytes) { if (dst) ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
@@ -1602,6 +1705,56 @@ int mpcx_lmpc_sensitivity_host(mpcx_lmpc_t h, double *d_x0, double *d_u0, double
     auto back = [&](void *dst, const void *src, size_t bytes) { if (dst) ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
     back(d_x0, kx, B * d.nu * d.nx * sizeof(double)); back(d_u0, ku, B * d.nu * d.nu * sizeof(double)); back(d_yref, ky, B * d.nu * d.ny * sizeof(double));
     back(flags, fl, B * sizeof(int32_t));
+    return ok ? MPCX_OK : fail(MPCX_E_DEVICE, "copy of the results to the host failed");
+}
+
+int mpcx_lmpc_param_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, const double *seed_input, int reduce,
+                                     double *d_oweight, double *d_uweight, double *d_duweight, double *d_lower, double *d_upper, int32_t *flags, int32_t *n_used)
+{
+    CHECK_H(h);
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the parameter-sensitivity kernel needs a HIP device, there is no CPU fallback");
+    if (h->sens_batch <= 0 || h->dirty || h->refs_dirty || !h->sens_has_seq || h->solved_full != h->n_full_setups || h->solved_refs != h->n_ref_refreshes)
+        return fail(MPCX_E_STATE, "no solve to differentiate: call mpcx_lmpc_solve_host with its sequences first (and after any change of the controller)");
+    if (!seed_cmd && !seed_input) return fail(MPCX_E_INVALID, "a parameter sensitivity needs seed_cmd or seed_input");
+    if (reduce != 0 && reduce != 1) return fail(MPCX_E_INVALID, "reduce must be 0 or 1");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    const auto &d = h->ctl.d;
+    const size_t B = (size_t)h->sens_batch, aw = (size_t)h->dev.active_words, n1 = (size_t)d.ph + 1, mr = (size_t)h->dev.m_ref;
+    const size_t nw = (size_t)(d.ny + 2 * d.nu) * d.ph, nseed = (size_t)d.nu + n1 * d.nu;
+    const size_t per = nseed + nw + 2 * mr + 2;           // seeds, the five outputs, and room for flag and count
+    if (B * per > h->param_stage_cap) {
+        if (h->param_stage) (void)hipFree(h->param_stage);
+        h->param_stage = nullptr; h->param_stage_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&h->param_stage), B * per * sizeof(double)) != hipSuccess) return fail(MPCX_E_DEVICE, "staging allocation failed");
+        h->param_stage_cap = B * per;
+    }
+    int rc = reduce ? mpcx_lmpc_param_sens_reserve(h, h->sens_batch) : MPCX_OK;
+    if (rc != MPCX_OK) return rc;
+    double *sc = h->param_stage, *si = sc + B * d.nu, *gow = si + B * n1 * d.nu, *guw = gow + B * d.ny * d.ph, *gdw = guw + B * d.nu * d.ph;
+    double *glo = gdw + B * d.nu * d.ph, *gup = glo + B * mr;
+    int32_t *fl = reinterpret_cast<int32_t *>(gup + B * mr), *nu_ = fl + B;
+    if ((seed_cmd && hipMemcpy(sc, seed_cmd, B * d.nu * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) ||
+        (seed_input && hipMemcpy(si, seed_input, B * n1 * d.nu * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
+        return fail(MPCX_E_DEVICE, "copy of the seeds to the device failed");
+    // the batch mpcx_lmpc_solve_host solved, where it left it: the staging buffers' layout of that function
+    double *dx0 = h->stage_d, *du0 = dx0 + B * d.nx, *dcmd = du0 + B * d.nu, *dcost = dcmd + B * d.nu;
+    double *dss = dcost + B, *dso = dss + B * n1 * d.nx, *dsi = dso + B * n1 * d.ny;
+    mpcx_lmpc_batch b{};
+    b.batch = h->sens_batch; b.x0 = dx0; b.u0 = du0; b.cmd = dcmd; b.status = h->stage_i;
+    b.active_lower = h->stage_act; b.active_upper = h->stage_act + B * aw; b.seq_output = dso; b.seq_input = dsi;
+    mpcx_lmpc_param_sens s{};
+    s.solved = &b; s.seed_cmd = seed_cmd ? sc : nullptr; s.seed_input = seed_input ? si : nullptr; s.reduce = reduce;
+    s.d_oweight = gow; s.d_uweight = guw; s.d_duweight = gdw; s.d_lower = glo; s.d_upper = gup; s.flags = fl; s.n_used = nu_;
+    rc = mpcx_lmpc_param_sensitivity_batch(h, &s, nullptr);
+    if (rc == MPCX_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MPCX_E_DEVICE, "kernel execution failed");
+    if (rc != MPCX_OK) return rc;
+    const size_t lead = reduce ? 1 : B;
+    bool ok = true;
+    auto back = [&](void *dst, const void *src, size_t bytes) { if (dst) ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    back(d_oweight, gow, lead * d.ny * d.ph * sizeof(double)); back(d_uweight, guw, lead * d.nu * d.ph * sizeof(double));
+    back(d_duweight, gdw, lead * d.nu * d.ph * sizeof(double)); back(d_lower, glo, lead * mr * sizeof(double)); back(d_upper, gup, lead * mr * sizeof(double));
+    back(flags, fl, B * sizeof(int32_t));
+    if (reduce) back(n_used, nu_, sizeof(int32_t));
     return ok ? MPCX_OK : fail(MPCX_E_DEVICE, "copy of the results to the host failed");
 }
 
@@ -2016,6 +2169,7 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "boxrow_ptr") { tmp.assign(o.boxrow_ptr.begin(), o.boxrow_ptr.end()); v = &tmp; }
     else if (n == "boxrow_ref") { tmp.assign(o.boxrow_ref.begin(), o.boxrow_ref.end()); v = &tmp; }
     else if (n == "blk") { tmp.assign(o.blk.begin(), o.blk.end()); v = &tmp; }
+    else if (n == "Cq") { if (param_operand(h, false) != MPCX_OK) return MPCX_E_DEVICE; v = &h->param_cq; }
     else if (n == "g_step") { tmp.assign(o.g_step.begin(), o.g_step.end()); v = &tmp; }
     else if (n == "g_kind") { tmp.assign(o.g_kind.begin(), o.g_kind.end()); v = &tmp; }
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }

@@ -121,6 +121,22 @@ class BatchResult:
 
 
 @dataclass
+class ParamSensitivityResult:
+    """Gradients of sum(seed * output) of a solved batch with respect to the controller's weights and bounds (mpcx_lmpc_param_sensitivity_batch,
+    DESIGN.md 4.9), device tensors.  Per instance: d_oweight [B, ny, ph], d_uweight, d_duweight [B, nu, ph] -- indexed as the matrices
+    setObjectiveWeights takes --, d_lower, d_upper [B, m_ref] in the row numbering of the active sets; reduced: the same without the leading
+    B, summed over the instances whose flag is 0, and n_used [1] how many those were.  flags [B] as SensitivityResult's; per instance, the
+    rows of a flagged instance are NaN."""
+    d_oweight: "object"
+    d_uweight: "object"
+    d_duweight: "object"
+    d_lower: "object"
+    d_upper: "object"
+    flags: "object"
+    n_used: "object" = None
+
+
+@dataclass
 class SensitivityResult:
     """The slope of a solved batch on each instance's active set (mpcx_lmpc_sensitivity_batch), device tensors.
     Jacobian mode: d_x0 [B, nu, nx], d_u0 [B, nu, nu], d_yref [B, nu, ny] -- the local feedback law
@@ -932,6 +948,7 @@ class LMPC(_LoopFrontEnd):
         b, res, keep = self.make_batch(x0, lastU, yref, uref, duref, dmeas, want_active or sensitivities or warm is not None, want_sequence, warm, warm_shift)
         self.launch(b, stream, keep)
         res._inputs = keep                     # the inputs live as long as the result that was computed from them
+        res._batch = b                         # ... and the descriptor: paramSensitivityBatch differentiates the batch it describes
         if sensitivities:
             res.sensitivities = self.sensitivityBatch(res.active_lower, res.active_upper, status=res.status, stream=stream)
         return res
@@ -989,6 +1006,70 @@ class LMPC(_LoopFrontEnd):
         d, out, keep = self.make_sensitivity(active_lower, active_upper, status, seed_cmd, seed_input, want)
         self.launch_sensitivity(d, stream, keep)
         out._inputs = keep[:5]
+        return out
+
+    def make_param_sensitivity(self, solved, seed_cmd=None, seed_input=None, reduce=False,
+                               want=("oweight", "uweight", "duweight", "lower", "upper")):
+        """Allocate outputs and fill the mpcx_lmpc_param_sens descriptor for `solved`: a BatchResult of optimizeBatch(..., want_active=True,
+        want_sequence=True), or the Batch descriptor of make_batch (whose tensors the caller keeps alive).  With reduce the handle's partial
+        sums are sized here, so that the launch allocates nothing.  Returns (ParamSens, ParamSensitivityResult, keepalive)."""
+        torch, dev = self._torch()
+        b = getattr(solved, "_batch", solved)
+        if not isinstance(b, _capi.Batch):
+            raise ValueError("paramSensitivityBatch needs the result of optimizeBatch(want_active=True, want_sequence=True) or a Batch descriptor")
+        if not (b.active_lower and b.active_upper and b.seq_output and b.seq_input):
+            raise ValueError("the batch must have been solved with want_active=True and want_sequence=True")
+        B = int(b.batch)
+        sc = self._dev(torch, dev, seed_cmd, (B, self.nu))
+        si = self._dev(torch, dev, seed_input, (B, self.ph + 1, self.nu))
+        if sc is None and si is None:
+            raise ValueError("a parameter sensitivity needs seed_cmd or seed_input")
+        m = self.info()["m_ref"]
+        lead = () if reduce else (B,)
+        f64 = torch.float64
+        # (the kernel writes each weight matrix column-major, as the setter reads it: allocated [ph, rows], handed out transposed)
+        mat = lambda rows, name: torch.empty(lead + (self.ph, rows), dtype=f64, device=dev) if name in want else None
+        ow, uw, dw = mat(self.ny, "oweight"), mat(self.nu, "uweight"), mat(self.nu, "duweight")
+        lo = torch.empty(lead + (m,), dtype=f64, device=dev) if "lower" in want else None
+        up = torch.empty(lead + (m,), dtype=f64, device=dev) if "upper" in want else None
+        flags = torch.empty((B,), dtype=torch.int32, device=dev)
+        n_used = torch.zeros((1,), dtype=torch.int32, device=dev) if reduce else None
+        tr = lambda t: None if t is None else t.transpose(-1, -2)
+        out = ParamSensitivityResult(tr(ow), tr(uw), tr(dw), lo, up, flags, n_used)
+        if reduce:
+            check(self._lib.mpcx_lmpc_param_sens_reserve(self._h, B))
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        d = _capi.ParamSens()
+        d.solved = C.cast(C.pointer(b), C.c_void_p)
+        d.seed_cmd, d.seed_input, d.reduce = ptr(sc), ptr(si), int(bool(reduce))
+        d.d_oweight, d.d_uweight, d.d_duweight, d.d_lower, d.d_upper = ptr(ow), ptr(uw), ptr(dw), ptr(lo), ptr(up)
+        d.flags, d.n_used = ptr(flags), ptr(n_used)
+        return d, out, (b, solved, sc, si, ow, uw, dw, lo, up, flags, n_used)
+
+    def launch_param_sensitivity(self, desc, stream=None, keep=None):
+        """One asynchronous launch (two kernels with reduce) for a descriptor built by make_param_sensitivity(); streams as in launch()."""
+        torch, _ = self._torch()
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+            for t in (keep or ()):
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(s)
+        check(self._lib.mpcx_lmpc_param_sensitivity_batch(self._h, C.byref(desc), C.c_void_p(s.cuda_stream)))
+
+    def paramSensitivityBatch(self, solved, seed_cmd=None, seed_input=None, reduce=False, stream=None,
+                              want=("oweight", "uweight", "duweight", "lower", "upper")) -> ParamSensitivityResult:
+        """The gradient of sum(seed_cmd * cmd) + sum(seed_input * input sequence) of a solved batch with respect to OWeight, UWeight,
+        DeltaUWeight and to every bound of the QP (mpcx_lmpc_param_sensitivity_batch): one launch after the solve, on each instance's
+        active set.  solved: the result of optimizeBatch(..., want_active=True, want_sequence=True) of this controller, unchanged since.
+        reduce: the sum over the batch (in a fixed order: the same bits every time) instead of one set per instance.  Bounds come in the
+        row numbering of the active sets (info()["m_ref"] rows)."""
+        d, out, keep = self.make_param_sensitivity(solved, seed_cmd, seed_input, reduce, want)
+        self.launch_param_sensitivity(d, stream, keep)
+        out._inputs = keep[:4]
         return out
 
     def optimize(self, x0, lastU) -> Result:
