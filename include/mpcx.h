@@ -298,7 +298,7 @@ int mpcx_lmpc_sensitivity_host(mpcx_lmpc_t h, double *d_x0, double *d_u0, double
  *               blocking) files the whole value under the lowest-numbered row whose bit is set
  * flags: the codes of mpcx_lmpc_sens -- 0 fine, 1 not solved, 2 dependent working set, 3 beyond the LDS plan; with reduce = 0 the outputs of a flagged
  * instance are NaN.  All pointers are device pointers, every output may be NULL.  MPCX_E_STATE when the controller changed, or was set up
- * again, since this handle's last mpcx_lmpc_solve_batch: the batch must be the one that call solved.  Not differentiated: the model, the terminal weight, soft weights, the coefficients of scalar and linear rows.
+ * again, since this handle's last mpcx_lmpc_solve_batch: the batch must be the one that call solved.  Not differentiated here: the model (mpcx_lmpc_model_sensitivity_batch has it), the terminal weight, soft weights, the coefficients of scalar and linear rows.
  * Asynchronous on `stream`; neither form allocates or copies at launch: the kernel's operand Cq is uploaded by the set-up, the partial sums of
  * reduce = 1 by mpcx_lmpc_param_sens_reserve.  With reduce = 1 and both d_lower and d_upper NULL the bound rows are not computed at all.
  * Banks have no such call. */
@@ -319,6 +319,35 @@ int mpcx_lmpc_param_sens_reserve(mpcx_lmpc_t h, int batch);      /* the partial 
 int mpcx_lmpc_param_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, const double *seed_input, int reduce,
                                      double *d_oweight, double *d_uweight, double *d_duweight, double *d_lower, double *d_upper,
                                      int32_t *flags, int32_t *n_used);
+
+/* Model sensitivities of a solved batch: the gradient of sum(seed * output) -- seeds as mpcx_lmpc_param_sens takes them -- with
+ * respect to every entry of the model's matrices A [nx x nx], B [nx x nu], C [ny x nx], Bd [nx x ndu] and Dd [ny x ndu], on the active set each
+ * instance was solved on.  One launch after the solve; a second small one adds up the batch.
+ *   solved      as for mpcx_lmpc_param_sens, and seq_state as well; the exogenous inputs in their mode
+ *   reduce      0: a set per instance, [B x ..], each matrix column-major as mpcx_lmpc_set_state_space_model / _set_disturbances take it;
+ *               1: one set, the sum over the instances whose flag is 0 in a fixed order (two launches give the same bits), n_used [1] = how
+ *               many those were.  reduce = 1 needs mpcx_lmpc_model_sens_reserve(h, batch) once, outside any capture (MPCX_E_STATE otherwise)
+ * flags as in mpcx_lmpc_param_sens; with reduce = 0 the outputs of a flagged instance are NaN.  All pointers are device pointers, every output
+ * may be NULL; d_Bd / d_Dd are ignored without exogenous inputs.  MPCX_E_STATE under the rules of mpcx_lmpc_param_sensitivity_batch.
+ * The multipliers of the optimum are recomputed from its own sequences, so every reference mode of the solved batch is served.
+ * Not differentiated: soft weights, the terminal weight, its target and target map, the coefficients of scalar and linear rows; step 0.
+ * Asynchronous on `stream`; the launch allocates nothing: the kernel's operand Xq is built and uploaded by mpcx_lmpc_model_sens_reserve or by
+ * the first launch outside a capture after a set-up (a launch under capture without either: MPCX_E_STATE).  Banks have no such call. */
+typedef struct mpcx_lmpc_model_sens {
+    const mpcx_lmpc_batch *solved;
+    const double *seed_cmd, *seed_input;          /* [B x nu], [B x (ph+1) x nu]; at least one */
+    int reduce;
+    double *d_A, *d_B, *d_C, *d_Bd, *d_Dd;
+    int32_t *flags;                               /* optional [B] */
+    int32_t *n_used;                              /* optional [1], reduce = 1 only */
+} mpcx_lmpc_model_sens;
+int mpcx_lmpc_model_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_model_sens *s, void *stream);
+int mpcx_lmpc_model_sens_size(void);   /* sizeof(mpcx_lmpc_model_sens) */
+int mpcx_lmpc_model_sens_reserve(mpcx_lmpc_t h, int batch);      /* Xq of the current set-up, and the partial sums of reduce = 1 for batches up to `batch` (grow-only; 0: Xq alone) */
+/* Host-array form over the batch the last mpcx_lmpc_solve_host of this handle solved with its sequences asked for (mpc::LMPC<>::
+ * modelSensitivities): seeds and outputs on the host, laid out as above; synchronous.  MPCX_E_STATE without such a solve. */
+int mpcx_lmpc_model_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, const double *seed_input, int reduce,
+                                     double *d_A, double *d_B, double *d_C, double *d_Bd, double *d_Dd, int32_t *flags, int32_t *n_used);
 
 /* One step as a HIP graph.  A control loop solves the same-sized batch from the same buffers every tick: the launches of
  * one mpcx_lmpc_solve_batch (dispatch-queue reset, assemble, solve, fallback) are captured once for a batch descriptor and

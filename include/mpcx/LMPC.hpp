@@ -326,6 +326,28 @@ public:
         s.flag = flag;
         return s;
     }
+    // ---- extension: gradients with respect to the model of the instance optimize() just solved (mpcx.h: model sensitivities of a solved batch).
+    // For a cotangent seed on cmd: the gradient of seed' cmd with respect to the matrices setStateSpaceModel and setDisturbances take (same
+    // indexing; dBd, dDd are empty without exogenous inputs).  flag as above
+    struct ModelSensitivities {
+        mat<Tnx, Tnx> dA;
+        mat<Tnx, Tnu> dB;
+        mat<Tny, Tnx> dC;
+        mat<Tnx, Tndu> dBd;
+        mat<Tny, Tndu> dDd;
+        int flag = 0;
+    };
+    ModelSensitivities modelSensitivities(const cvec<Tnu> &seed_cmd)
+    {
+        ModelSensitivities s;
+        s.dA.resize(d_.nx, d_.nx); s.dB.resize(d_.nx, d_.nu); s.dC.resize(d_.ny, d_.nx); s.dBd.resize(d_.nx, d_.ndu); s.dDd.resize(d_.ny, d_.ndu);
+        int32_t flag = 0;
+        // (the device writes the matrices column-major, as these are stored)
+        detail::check(mpcx_lmpc_model_sensitivity_host(h_, seed_cmd.data(), nullptr, 0, s.dA.data(), s.dB.data(), s.dC.data(),
+                                                       d_.ndu > 0 ? s.dBd.data() : nullptr, d_.ndu > 0 ? s.dDd.data() : nullptr, &flag, nullptr), "modelSensitivities");
+        s.flag = flag;
+        return s;
+    }
     OptSequence<Tnx, Tny, Tnu, detail::dimp1(Tph)> getOptimalSequence() { return seq_; }
     const SolutionStats &getExecutionStats() { return stats_; }
     void resetStats() { stats_ = SolutionStats{}; }

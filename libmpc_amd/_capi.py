@@ -94,6 +94,13 @@ class ParamSens(C.Structure):
                 ("d_lower", C.c_void_p), ("d_upper", C.c_void_p), ("flags", C.c_void_p), ("n_used", C.c_void_p)]
 
 
+class ModelSens(C.Structure):
+    """mpcx_lmpc_model_sens: model sensitivities of a solved batch (device pointers; `solved` points to a Batch)"""
+    _fields_ = [("solved", C.c_void_p), ("seed_cmd", C.c_void_p), ("seed_input", C.c_void_p), ("reduce", C.c_int),
+                ("d_A", C.c_void_p), ("d_B", C.c_void_p), ("d_C", C.c_void_p), ("d_Bd", C.c_void_p), ("d_Dd", C.c_void_p),
+                ("flags", C.c_void_p), ("n_used", C.c_void_p)]
+
+
 class Info(C.Structure):
     _fields_ = [("n_ref", C.c_int), ("m_ref", C.c_int), ("neq_ref", C.c_int), ("nz", C.c_int), ("mg", C.c_int),
                 ("active_words", C.c_int), ("kernel_variant", C.c_int),
@@ -118,7 +125,8 @@ EXPORTS = [
     "mpcx_lmpc_set_exogenous_inputs", "mpcx_lmpc_set_exogenous_inputs_slice",
     "mpcx_lmpc_set_optimizer_parameters", "mpcx_lmpc_set_strict_infeasibility", "mpcx_lmpc_setup", "mpcx_lmpc_solve_batch",
     "mpcx_lmpc_time_solve_batch", "mpcx_lmpc_sensitivity_batch", "mpcx_lmpc_sens_size", "mpcx_lmpc_sensitivity_host",
-    "mpcx_lmpc_param_sensitivity_batch", "mpcx_lmpc_param_sens_size", "mpcx_lmpc_param_sens_reserve", "mpcx_lmpc_param_sensitivity_host", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
+    "mpcx_lmpc_param_sensitivity_batch", "mpcx_lmpc_param_sens_size", "mpcx_lmpc_param_sens_reserve", "mpcx_lmpc_param_sensitivity_host",
+    "mpcx_lmpc_model_sensitivity_batch", "mpcx_lmpc_model_sens_size", "mpcx_lmpc_model_sens_reserve", "mpcx_lmpc_model_sensitivity_host", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
     "mpcx_lmpc_graph_create", "mpcx_lmpc_graph_launch", "mpcx_lmpc_graph_destroy",
     "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
     "mpcx_lmpc_loop_create_observed", "mpcx_lmpc_hetero_loop_create_observed", "mpcx_lmpc_observer_desc_size", "mpcx_lmpc_kalman_gain",
@@ -223,6 +231,9 @@ def lib():
         _lib.mpcx_lmpc_param_sensitivity_batch.argtypes = [C.c_void_p] * 3
         _lib.mpcx_lmpc_param_sens_reserve.argtypes = [C.c_void_p, C.c_int]
         _lib.mpcx_lmpc_param_sensitivity_host.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7
+        _lib.mpcx_lmpc_model_sensitivity_batch.argtypes = [C.c_void_p] * 3
+        _lib.mpcx_lmpc_model_sens_reserve.argtypes = [C.c_void_p, C.c_int]
+        _lib.mpcx_lmpc_model_sensitivity_host.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7
         _lib.mpcx_lmpc_graph_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_graph_destroy.argtypes = [C.c_void_p]

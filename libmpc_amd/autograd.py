@@ -17,7 +17,14 @@ shared by the batch, so their gradient is the sum over the instances, added in a
 set is dependent contributes nothing to it.  Gradients with respect to the bounds are not part of this function: paramSensitivityBatch returns
 them, in the row numbering of the active sets.  The backward pass differentiates the batch the controller solved last, under the set-up of that solve:
 call backward before the controller is changed, set up again or given another forward pass of this function (mpcx_lmpc_param_sensitivity_batch
-answers MPCX_E_STATE after a change or a new set-up); keep one controller per graph that is kept."""
+answers MPCX_E_STATE after a change or a new set-up); keep one controller per graph that is kept.
+
+    cmd = lmpc_cmd_model(controller, x0, u0, yref, A, B, C, Bd=None, Dd=None)
+
+differentiates the same first move with respect to the model: what fitting A, B, C of a fleet's controller to logged or expert closed-loop
+behaviour needs.  Forward sets the model (and the disturbance matrices, where given), sets the controller up and solves; backward is one launch of
+the vector-Jacobian product and one of LMPC.modelSensitivityBatch with reduce=True (DESIGN.md 4.10).  The controller keeps every other setting;
+the rules of lmpc_cmd_params hold."""
 from __future__ import annotations
 
 _FUNCTION = None
@@ -103,6 +110,68 @@ def lmpc_cmd_params(controller, x0, u0, yref, OWeight, UWeight, DeltaUWeight, re
     if yref is not None and yref.dim() != 2 and yref.requires_grad:
         raise ValueError("lmpc_cmd_params differentiates a per-instance output reference [B, ny]; a per-step reference has no gradient here")
     cmd, status = _param_function().apply(controller, x0, u0, yref, as_t(OWeight), as_t(UWeight), as_t(DeltaUWeight))
+    return (cmd, status) if return_status else cmd
+
+
+_MODEL_FUNCTION = None
+
+
+def _model_function():
+    global _MODEL_FUNCTION
+    if _MODEL_FUNCTION is not None:
+        return _MODEL_FUNCTION
+    import torch
+
+    class LmpcCmdModel(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, controller, x0, u0, yref, A, B, Cm, Bd, Dd):
+            host = lambda t: t.detach().cpu().numpy()
+            if not controller.setStateSpaceModel(host(A), host(B), host(Cm)):
+                raise ValueError("lmpc_cmd_model: the controller refused the model")
+            if Bd is not None and not controller.setDisturbances(host(Bd), host(Dd)):
+                raise ValueError("lmpc_cmd_model: the controller refused the disturbance matrices")
+            controller.setup()
+            res = controller.optimizeBatch(x0.detach(), u0.detach(), None if yref is None else yref.detach(), want_active=True, want_sequence=True)
+            ctx.controller, ctx.res = controller, res
+            ctx.has_yref = yref is not None
+            ctx.mark_non_differentiable(res.status)
+            return res.cmd, res.status
+
+        @staticmethod
+        def backward(ctx, grad_cmd, _grad_status):
+            c, res = ctx.controller, ctx.res
+            seed = grad_cmd.contiguous()
+            need = ctx.needs_input_grad
+            g = [None] * 9
+            want = tuple(n for n, k in zip(("x0", "u0", "yref"), need[1:4]) if k)
+            if want:
+                s = c.sensitivityBatch(res.active_lower, res.active_upper, status=res.status, seed_cmd=seed, want=want)
+                g[1], g[2], g[3] = s.d_x0, s.d_u0, (s.d_yref if ctx.has_yref else None)
+            wantm = tuple(n for n, k in zip(("A", "B", "C", "Bd", "Dd"), need[4:9]) if k)
+            if wantm:
+                m = c.modelSensitivityBatch(res, seed_cmd=seed, reduce=True, want=wantm)
+                g[4], g[5], g[6], g[7], g[8] = m.d_A, m.d_B, m.d_C, m.d_Bd, m.d_Dd
+            return tuple(g)
+
+    _MODEL_FUNCTION = LmpcCmdModel
+    return _MODEL_FUNCTION
+
+
+def lmpc_cmd_model(controller, x0, u0, yref, A, B, C, Bd=None, Dd=None, return_status=False):
+    """cmd [B, nu] of `controller` (a libmpc_amd.LMPC) with the model A [nx, nx], B [nx, nu], C [ny, nx] and, where given, the disturbance
+    matrices Bd [nx, ndu], Dd [ny, ndu] (the matrices of setStateSpaceModel / setDisturbances, torch tensors on any device) at x0 [B, nx],
+    u0 [B, nu] and the per-instance output reference yref [B, ny] (None: the controller's own), differentiable with respect to all of them.  The
+    controller keeps the model afterwards, and every other setting.  The gradients of the model are sums over the batch.  return_status:
+    (cmd, status) instead."""
+    import torch
+    _, dev = controller._torch()
+    as_t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64)).to(device=dev, dtype=torch.float64)
+    x0, u0, yref = as_t(x0), as_t(u0), as_t(yref)
+    if yref is not None and yref.dim() != 2 and yref.requires_grad:
+        raise ValueError("lmpc_cmd_model differentiates a per-instance output reference [B, ny]; a per-step reference has no gradient here")
+    if (Bd is None) != (Dd is None):
+        raise ValueError("lmpc_cmd_model: Bd and Dd go together")
+    cmd, status = _model_function().apply(controller, x0, u0, yref, as_t(A), as_t(B), as_t(C), as_t(Bd), as_t(Dd))
     return (cmd, status) if return_status else cmd
 
 

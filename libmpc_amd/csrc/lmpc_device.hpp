@@ -220,6 +220,29 @@ size_t lmpc_param_sens_partials(const LmpcDev &m, int batch);
 // 0; -2: not even a working set of one row fits the LDS plan; -3: a launch or its configuration failed (reduce without partials among them)
 int lmpc_param_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double *Cqp, const LmpcParamSensArgs &a, void *stream);
 
+// Model sensitivities of a solved batch (lmpc_model_sens.hip).  All device pointers; the references as LmpcBatchDev's accessors
+struct LmpcModelSensArgs {
+    int batch;
+    bool reduce;                                  // the outputs summed over the batch (through `partials`) instead of one set per instance
+    const uint32_t *active_lower, *active_upper;
+    const int32_t *status;
+    const double *seed_cmd, *seed_input;
+    const double *u0, *seq_state, *seq_output, *seq_input;      // of the solved batch
+    const double *yref; long yref_bs, yref_ks;
+    const double *uref; long uref_bs, uref_ks;
+    const double *duref; long duref_bs, duref_ks;
+    const double *dmeas; long dmeas_bs, dmeas_ks;
+    double *d_A, *d_B, *d_C, *d_Bd, *d_Dd;        // column-major, [B x ..] or one set (reduce); d_Bd / d_Dd are ignored without exogenous inputs
+    int32_t *flags, *n_used;
+    double *partials;                             // reduce: lmpc_model_sens_partials(m, batch) doubles
+};
+// Xq, the derivative of the states of the steps 1 .. ph with respect to the decision vector, [rows16 x nz] column-major (rows16 = nx ph rounded up to
+// the MFMA row tile; what lmpc_pack_mfma_tiles takes): its length in doubles (out null), or filled in.  A, B column-major on the host
+size_t lmpc_model_sens_xq(int nx, int nu, int ph, int nz, const double *A, const double *B, const int *blk, double *out);
+size_t lmpc_model_sens_partials(const LmpcDev &m, int batch);
+// 0; -2: not even a working set of one row fits the LDS plan; -3: a launch or its configuration failed (reduce without partials among them)
+int lmpc_model_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double *Xqp, const LmpcModelSensArgs &a, void *stream);
+
 // The closed loop around the solve (lmpc_loop.hip): everything the advance kernel touches. All device pointers; the same struct at every tick.
 // The packed blocks: per-instance coefficients in the order the advance kernels read them (lmpc_loop.hip, DESIGN 4.3b has the table)
 enum LoopBlock : int {

@@ -74,6 +74,11 @@ struct mpcx_lmpc {
     double *param_part = nullptr; size_t param_part_cap = 0;
     double *param_stage = nullptr; size_t param_stage_cap = 0;      // (capacity in doubles: a set-up may change m_ref, and with it the length per instance)
     bool sens_has_seq = false;
+    // model sensitivities (lmpc_model_sens.hip): Xq likewise, built by mpcx_lmpc_model_sens_reserve or the first launch after a set-up -- a controller
+    // that never asks pays nothing; its partials and the host form's staging
+    std::vector<double> model_xq; const double *model_xqp = nullptr;
+    double *model_part = nullptr; size_t model_part_cap = 0;
+    double *model_stage = nullptr; size_t model_stage_cap = 0;
     int solved_full = -1, solved_refs = -1;          // n_full_setups / n_ref_refreshes when mpcx_lmpc_solve_batch last launched: the set-up a solved batch belongs to
     explicit mpcx_lmpc(const mpcx_dims &d) : ctl(d) {}
 
@@ -85,6 +90,7 @@ struct mpcx_lmpc {
         warm_batch = 0;                 // row numbering may have changed with the model
         sens_batch = 0;
         param_cqp = nullptr;            // (it was one of allocs)
+        model_xqp = nullptr;
     }
     void release_staging()
     {
@@ -95,6 +101,9 @@ struct mpcx_lmpc {
         if (param_stage) (void)hipFree(param_stage);
         if (param_part) (void)hipFree(param_part);
         param_stage = nullptr; param_stage_cap = 0; param_part = nullptr; param_part_cap = 0;
+        if (model_stage) (void)hipFree(model_stage);
+        if (model_part) (void)hipFree(model_part);
+        model_stage = nullptr; model_stage_cap = 0; model_part = nullptr; model_part_cap = 0;
         stage_d = nullptr; stage_i = nullptr; stage_act = nullptr; stage_cap = 0; warm_batch = 0;
         sens_stage = nullptr; sens_stage_cap = 0; sens_batch = 0;
     }
@@ -728,6 +737,7 @@ int mpcx_lmpc_setup(mpcx_lmpc_t h)
     mpcx::LmpcDev &D = h->dev;
     fill_dev_scalars(h, c, o, D);
     h->param_cq.clear();
+    h->model_xq.clear();                 // (built again when somebody asks: model_operand)
     if (h->host_only) { h->dirty = false; return MPCX_OK; }
 
     if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
@@ -948,6 +958,98 @@ int mpcx_lmpc_param_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_param_sens 
     a.flags = s->flags; a.n_used = s->n_used; a.partials = s->reduce ? h->param_part : nullptr;
     const int lr = mpcx::lmpc_param_sens_launch(h->dev, h->dev_d, h->param_cqp, a, stream);
     if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the parameter-sensitivity kernel's LDS budget");
+    return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+}
+
+// Xq of the current set-up on the host (at first use) and, with a device, packed in HBM
+static int model_operand(mpcx_lmpc_t h, bool device)
+{
+    const auto &c = h->ctl;
+    const auto &o = h->cond;
+    if (h->model_xq.empty()) {
+        h->model_xq.resize(mpcx::lmpc_model_sens_xq(c.d.nx, c.d.nu, c.d.ph, o.nz, nullptr, nullptr, nullptr, nullptr));
+        mpcx::lmpc_model_sens_xq(c.d.nx, c.d.nu, c.d.ph, o.nz, c.A.a.data(), c.B.a.data(), o.blk.data(), h->model_xq.data());
+    }
+    if (device && !h->model_xqp) {
+        const int rows16 = (c.d.nx * c.d.ph + 15) / 16 * 16;
+        std::vector<double> pk(mpcx::lmpc_packed_len(rows16, o.nz));
+        mpcx::lmpc_pack_mfma_tiles(h->model_xq.data(), rows16, o.nz, pk.data());
+        int rc = MPCX_OK;
+        h->model_xqp = h->up(pk, rc);
+        if (rc != MPCX_OK) { h->model_xqp = nullptr; return fail(rc, "device upload failed"); }
+    }
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_model_sens_size(void) { return (int)sizeof(mpcx_lmpc_model_sens); }
+
+int mpcx_lmpc_model_sens_reserve(mpcx_lmpc_t h, int batch)
+{
+    CHECK_H(h);
+    if (batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the model-sensitivity kernel needs a HIP device, there is no CPU fallback");
+    int rc = mpcx_lmpc_setup(h);
+    if (rc != MPCX_OK) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    rc = model_operand(h, true);
+    if (rc != MPCX_OK) return rc;
+    const size_t need = mpcx::lmpc_model_sens_partials(h->dev, batch);
+    if (need > h->model_part_cap) {
+        if (h->model_part) (void)hipFree(h->model_part);
+        h->model_part = nullptr; h->model_part_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&h->model_part), need * sizeof(double)) != hipSuccess) return fail(MPCX_E_DEVICE, "allocation of the partial sums failed");
+        h->model_part_cap = need;
+    }
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_model_sensitivity_batch(mpcx_lmpc_t h, const mpcx_lmpc_model_sens *s, void *stream)
+{
+    CHECK_H(h);
+    if (!s) return fail(MPCX_E_INVALID, "null model-sensitivity descriptor");
+    const mpcx_lmpc_batch *b = s->solved;
+    if (!b) return fail(MPCX_E_INVALID, "the solved batch is required");
+    if (b->batch < 0) return fail(MPCX_E_INVALID, "negative batch");
+    if (s->reduce != 0 && s->reduce != 1) return fail(MPCX_E_INVALID, "reduce must be 0 or 1");
+    if (b->batch > 0 && (!b->active_lower || !b->active_upper)) return fail(MPCX_E_INVALID, "active_lower and active_upper of the solved batch are required");
+    if (b->batch > 0 && (!b->x0 || !b->u0)) return fail(MPCX_E_INVALID, "x0 and u0 of the solved batch are required");
+    if (b->batch > 0 && !s->seed_cmd && !s->seed_input) return fail(MPCX_E_INVALID, "a model sensitivity needs seed_cmd or seed_input");
+    if (b->batch > 0 && (!b->seq_state || !b->seq_output || !b->seq_input)) return fail(MPCX_E_STATE, "the solved batch carries no sequences: seq_state, seq_output and seq_input are required");
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the model-sensitivity kernel needs a HIP device, there is no CPU fallback");
+    if (h->dirty || h->refs_dirty || !h->dev_d || h->solved_full != h->n_full_setups || h->solved_refs != h->n_ref_refreshes)
+        return fail(MPCX_E_STATE, "the controller changed since the set-up that solved this batch (or nothing was solved): solve again first");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (b->batch == 0) return MPCX_OK;
+    mpcx::LmpcBatchDev B;
+    {
+        const auto &D = h->dev;
+        const double *const shared[4] = {D.yref_s, D.uref_s, D.duref_s, D.dmeas_s};
+        const int rc = make_batch(h->ctl.d, b, shared, B);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (s->reduce && mpcx::lmpc_model_sens_partials(h->dev, b->batch) > h->model_part_cap)
+        return fail(MPCX_E_STATE, "reduce = 1 needs mpcx_lmpc_model_sens_reserve for this batch size first: the launch allocates nothing");
+    if (!h->model_xqp) {
+        // the first launch after a set-up builds and uploads Xq, unless a capture is under way: then mpcx_lmpc_model_sens_reserve comes first
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return fail(MPCX_E_STATE, "a captured launch needs mpcx_lmpc_model_sens_reserve after the set-up first: the launch allocates nothing");
+        const int rc = model_operand(h, true);
+        if (rc != MPCX_OK) return rc;
+    }
+    mpcx::LmpcModelSensArgs a{};
+    a.batch = b->batch; a.reduce = s->reduce != 0;
+    a.active_lower = b->active_lower; a.active_upper = b->active_upper; a.status = b->status;
+    a.seed_cmd = s->seed_cmd; a.seed_input = s->seed_input;
+    a.u0 = b->u0; a.seq_state = b->seq_state; a.seq_output = b->seq_output; a.seq_input = b->seq_input;
+    a.yref = B.yref; a.yref_bs = B.yref_bs; a.yref_ks = B.yref_ks;
+    a.uref = B.uref; a.uref_bs = B.uref_bs; a.uref_ks = B.uref_ks;
+    a.duref = B.duref; a.duref_bs = B.duref_bs; a.duref_ks = B.duref_ks;
+    a.dmeas = B.dmeas; a.dmeas_bs = B.dmeas_bs; a.dmeas_ks = B.dmeas_ks;
+    a.d_A = s->d_A; a.d_B = s->d_B; a.d_C = s->d_C; a.d_Bd = s->d_Bd; a.d_Dd = s->d_Dd;
+    a.flags = s->flags; a.n_used = s->n_used; a.partials = s->reduce ? h->model_part : nullptr;
+    const int lr = mpcx::lmpc_model_sens_launch(h->dev, h->dev_d, h->model_xqp, a, stream);
+    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the model-sensitivity kernel's LDS budget");
     return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
 }
 
@@ -1758,6 +1860,56 @@ int mpcx_lmpc_param_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, cons
     return ok ? MPCX_OK : fail(MPCX_E_DEVICE, "copy of the results to the host failed");
 }
 
+int mpcx_lmpc_model_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, const double *seed_input, int reduce,
+                                     double *d_A, double *d_B, double *d_C, double *d_Bd, double *d_Dd, int32_t *flags, int32_t *n_used)
+{
+    CHECK_H(h);
+    if (h->host_only) return fail(MPCX_E_DEVICE, "host-only handle: the model-sensitivity kernel needs a HIP device, there is no CPU fallback");
+    if (h->sens_batch <= 0 || h->dirty || h->refs_dirty || !h->sens_has_seq || h->solved_full != h->n_full_setups || h->solved_refs != h->n_ref_refreshes)
+        return fail(MPCX_E_STATE, "no solve to differentiate: call mpcx_lmpc_solve_host with its sequences first (and after any change of the controller)");
+    if (!seed_cmd && !seed_input) return fail(MPCX_E_INVALID, "a model sensitivity needs seed_cmd or seed_input");
+    if (reduce != 0 && reduce != 1) return fail(MPCX_E_INVALID, "reduce must be 0 or 1");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    const auto &d = h->ctl.d;
+    const size_t B = (size_t)h->sens_batch, aw = (size_t)h->dev.active_words, n1 = (size_t)d.ph + 1;
+    const size_t nA = (size_t)d.nx * d.nx, nB = (size_t)d.nx * d.nu, nC = (size_t)d.ny * d.nx, nBd = (size_t)d.nx * d.ndu, nDd = (size_t)d.ny * d.ndu;
+    const size_t nseed = (size_t)d.nu + n1 * d.nu;
+    const size_t per = nseed + nA + nB + nC + nBd + nDd + 2;           // seeds, the five outputs, and room for flag and count
+    if (B * per > h->model_stage_cap) {
+        if (h->model_stage) (void)hipFree(h->model_stage);
+        h->model_stage = nullptr; h->model_stage_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&h->model_stage), B * per * sizeof(double)) != hipSuccess) return fail(MPCX_E_DEVICE, "staging allocation failed");
+        h->model_stage_cap = B * per;
+    }
+    int rc = mpcx_lmpc_model_sens_reserve(h, reduce ? h->sens_batch : 0);
+    if (rc != MPCX_OK) return rc;
+    double *sc = h->model_stage, *si = sc + B * d.nu, *gA = si + B * n1 * d.nu, *gB = gA + B * nA, *gC = gB + B * nB, *gBd = gC + B * nC, *gDd = gBd + B * nBd;
+    int32_t *fl = reinterpret_cast<int32_t *>(gDd + B * nDd), *nu_ = fl + B;
+    if ((seed_cmd && hipMemcpy(sc, seed_cmd, B * d.nu * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) ||
+        (seed_input && hipMemcpy(si, seed_input, B * n1 * d.nu * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
+        return fail(MPCX_E_DEVICE, "copy of the seeds to the device failed");
+    // the batch mpcx_lmpc_solve_host solved, where it left it: the staging buffers' layout of that function
+    double *dx0 = h->stage_d, *du0 = dx0 + B * d.nx, *dcmd = du0 + B * d.nu, *dcost = dcmd + B * d.nu;
+    double *dss = dcost + B, *dso = dss + B * n1 * d.nx, *dsi = dso + B * n1 * d.ny;
+    mpcx_lmpc_batch b{};
+    b.batch = h->sens_batch; b.x0 = dx0; b.u0 = du0; b.cmd = dcmd; b.status = h->stage_i;
+    b.active_lower = h->stage_act; b.active_upper = h->stage_act + B * aw; b.seq_state = dss; b.seq_output = dso; b.seq_input = dsi;
+    mpcx_lmpc_model_sens s{};
+    s.solved = &b; s.seed_cmd = seed_cmd ? sc : nullptr; s.seed_input = seed_input ? si : nullptr; s.reduce = reduce;
+    s.d_A = gA; s.d_B = gB; s.d_C = gC; s.d_Bd = gBd; s.d_Dd = gDd; s.flags = fl; s.n_used = nu_;
+    rc = mpcx_lmpc_model_sensitivity_batch(h, &s, nullptr);
+    if (rc == MPCX_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MPCX_E_DEVICE, "kernel execution failed");
+    if (rc != MPCX_OK) return rc;
+    const size_t lead = reduce ? 1 : B;
+    bool ok = true;
+    auto back = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    back(d_A, gA, lead * nA * sizeof(double)); back(d_B, gB, lead * nB * sizeof(double)); back(d_C, gC, lead * nC * sizeof(double));
+    back(d_Bd, gBd, lead * nBd * sizeof(double)); back(d_Dd, gDd, lead * nDd * sizeof(double));
+    back(flags, fl, B * sizeof(int32_t));
+    if (reduce) back(n_used, nu_, sizeof(int32_t));
+    return ok ? MPCX_OK : fail(MPCX_E_DEVICE, "copy of the results to the host failed");
+}
+
 int mpcx_lmpc_time_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *stream, int repeats, float *ms_mean)
 {
     CHECK_H(h);
@@ -2170,6 +2322,14 @@ int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)
     else if (n == "boxrow_ref") { tmp.assign(o.boxrow_ref.begin(), o.boxrow_ref.end()); v = &tmp; }
     else if (n == "blk") { tmp.assign(o.blk.begin(), o.blk.end()); v = &tmp; }
     else if (n == "Cq") { if (param_operand(h, false) != MPCX_OK) return MPCX_E_DEVICE; v = &h->param_cq; }
+    else if (n == "Xq") { if (model_operand(h, false) != MPCX_OK) return MPCX_E_DEVICE; v = &h->model_xq; }
+    else if (n == "model") {              // A | B | C | Bd | Dd as stored, column-major
+        for (const mpcx::Mat *m : {&h->ctl.A, &h->ctl.B, &h->ctl.C, &h->ctl.Bd, &h->ctl.Dd}) tmp.insert(tmp.end(), m->a.begin(), m->a.end());
+        v = &tmp;
+    }
+    else if (n == "wDeltaU") v = &h->ctl.wDeltaU.a;
+    else if (n == "scalar") { tmp = h->ctl.scalar_linear_block(); v = &tmp; }      // sX | row c: Fx(c, :), Fu(c, :) of the live linear rows
+    else if (n == "sU") v = &h->ctl.sU;
     else if (n == "g_step") { tmp.assign(o.g_step.begin(), o.g_step.end()); v = &tmp; }
     else if (n == "g_kind") { tmp.assign(o.g_kind.begin(), o.g_kind.end()); v = &tmp; }
     else if (n == "g_comp") { tmp.assign(o.g_comp.begin(), o.g_comp.end()); v = &tmp; }

@@ -137,6 +137,22 @@ class ParamSensitivityResult:
 
 
 @dataclass
+class ModelSensitivityResult:
+    """Gradients of sum(seed * output) of a solved batch with respect to the model (mpcx_lmpc_model_sensitivity_batch), device
+    tensors.  Per instance: d_A [B, nx, nx], d_B [B, nx, nu], d_C [B, ny, nx], d_Bd [B, nx, ndu], d_Dd [B, ny, ndu] -- indexed as the matrices
+    setStateSpaceModel / setDisturbances take (d_Bd, d_Dd None without exogenous inputs) --; reduced: the same without the leading B, summed
+    over the instances whose flag is 0, and n_used [1] how many those were.  flags [B] as SensitivityResult's; per instance, the entries of a
+    flagged instance are NaN."""
+    d_A: "object"
+    d_B: "object"
+    d_C: "object"
+    d_Bd: "object"
+    d_Dd: "object"
+    flags: "object"
+    n_used: "object" = None
+
+
+@dataclass
 class SensitivityResult:
     """The slope of a solved batch on each instance's active set (mpcx_lmpc_sensitivity_batch), device tensors.
     Jacobian mode: d_x0 [B, nu, nx], d_u0 [B, nu, nu], d_yref [B, nu, ny] -- the local feedback law
@@ -1069,6 +1085,66 @@ class LMPC(_LoopFrontEnd):
         row numbering of the active sets (info()["m_ref"] rows)."""
         d, out, keep = self.make_param_sensitivity(solved, seed_cmd, seed_input, reduce, want)
         self.launch_param_sensitivity(d, stream, keep)
+        out._inputs = keep[:4]
+        return out
+
+    def make_model_sensitivity(self, solved, seed_cmd=None, seed_input=None, reduce=False, want=("A", "B", "C", "Bd", "Dd")):
+        """Allocate outputs and fill the mpcx_lmpc_model_sens descriptor for `solved`: a BatchResult of optimizeBatch(..., want_active=True,
+        want_sequence=True), or the Batch descriptor of make_batch (whose tensors the caller keeps alive).  The kernel's operand and, with
+        reduce, the handle's partial sums are sized here, so that the launch allocates nothing.  Returns (ModelSens, ModelSensitivityResult,
+        keepalive)."""
+        torch, dev = self._torch()
+        b = getattr(solved, "_batch", solved)
+        if not isinstance(b, _capi.Batch):
+            raise ValueError("modelSensitivityBatch needs the result of optimizeBatch(want_active=True, want_sequence=True) or a Batch descriptor")
+        if not (b.active_lower and b.active_upper and b.seq_state and b.seq_output and b.seq_input):
+            raise ValueError("the batch must have been solved with want_active=True and want_sequence=True")
+        B = int(b.batch)
+        sc = self._dev(torch, dev, seed_cmd, (B, self.nu))
+        si = self._dev(torch, dev, seed_input, (B, self.ph + 1, self.nu))
+        if sc is None and si is None:
+            raise ValueError("a model sensitivity needs seed_cmd or seed_input")
+        lead = () if reduce else (B,)
+        f64 = torch.float64
+        # (the kernel writes each matrix column-major, as the setter reads it: allocated [columns, rows], handed out transposed)
+        mat = lambda rows, cols, name: torch.empty(lead + (cols, rows), dtype=f64, device=dev) if (name in want and rows * cols > 0) else None
+        gA, gB, gC = mat(self.nx, self.nx, "A"), mat(self.nx, self.nu, "B"), mat(self.ny, self.nx, "C")
+        gBd, gDd = mat(self.nx, self.ndu, "Bd"), mat(self.ny, self.ndu, "Dd")
+        flags = torch.empty((B,), dtype=torch.int32, device=dev)
+        n_used = torch.zeros((1,), dtype=torch.int32, device=dev) if reduce else None
+        tr = lambda t: None if t is None else t.transpose(-1, -2)
+        out = ModelSensitivityResult(tr(gA), tr(gB), tr(gC), tr(gBd), tr(gDd), flags, n_used)
+        check(self._lib.mpcx_lmpc_model_sens_reserve(self._h, B if reduce else 0))
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        d = _capi.ModelSens()
+        d.solved = C.cast(C.pointer(b), C.c_void_p)
+        d.seed_cmd, d.seed_input, d.reduce = ptr(sc), ptr(si), int(bool(reduce))
+        d.d_A, d.d_B, d.d_C, d.d_Bd, d.d_Dd = ptr(gA), ptr(gB), ptr(gC), ptr(gBd), ptr(gDd)
+        d.flags, d.n_used = ptr(flags), ptr(n_used)
+        return d, out, (b, solved, sc, si, gA, gB, gC, gBd, gDd, flags, n_used)
+
+    def launch_model_sensitivity(self, desc, stream=None, keep=None):
+        """One asynchronous launch (two kernels with reduce) for a descriptor built by make_model_sensitivity(); streams as in launch()."""
+        torch, _ = self._torch()
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+            for t in (keep or ()):
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(s)
+        check(self._lib.mpcx_lmpc_model_sensitivity_batch(self._h, C.byref(desc), C.c_void_p(s.cuda_stream)))
+
+    def modelSensitivityBatch(self, solved, seed_cmd=None, seed_input=None, reduce=False, stream=None,
+                              want=("A", "B", "C", "Bd", "Dd")) -> ModelSensitivityResult:
+        """The gradient of sum(seed_cmd * cmd) + sum(seed_input * input sequence) of a solved batch with respect to every entry of A, B, C, Bd
+        and Dd (mpcx_lmpc_model_sensitivity_batch): one launch after the solve, on each instance's active set.  solved: the result of
+        optimizeBatch(..., want_active=True, want_sequence=True) of this controller, unchanged since.  reduce: the sum over the batch (in a
+        fixed order: the same bits every time) instead of one set per instance."""
+        d, out, keep = self.make_model_sensitivity(solved, seed_cmd, seed_input, reduce, want)
+        self.launch_model_sensitivity(d, stream, keep)
         out._inputs = keep[:4]
         return out
 
