@@ -261,7 +261,7 @@ int mpcx_lmpc_time_solve_batch(mpcx_lmpc_t h, const mpcx_lmpc_batch *b, void *st
  * d_x0 and d_u0 hold for every reference mode of the solve that produced the active sets: the linear part of the maps does not depend on
  * references or exogenous inputs.  d_yref is the derivative with respect to a shift of the output reference common to all steps: the
  * exact Jacobian for MPCX_REF_PER_INSTANCE, a directional derivative for the other modes.
- * Asynchronous on `stream`, like the solve; allocates nothing.  Banks (mpcx_lmpc_hetero_*) have no such call. */
+ * Asynchronous on `stream`, like the solve; allocates nothing.  Banks (mpcx_lmpc_hetero_*): mpcx_lmpc_hetero_sensitivity_batch. */
 #define MPCX_SENS_JACOBIAN 0
 #define MPCX_SENS_VJP      1
 typedef struct mpcx_lmpc_sens {
@@ -852,6 +852,15 @@ int mpcx_lmpc_hetero_get_info(mpcx_lmpc_hetero_t f, int *count, int *active_word
 int mpcx_lmpc_hetero_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream);
 int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream,
                                       int repeats, float *ms_mean);
+/* Sensitivities of a solved batch of a bank: what mpcx_lmpc_sensitivity_batch gives for one controller, every instance on its
+ * own.  Replaces no call of the reference: the reference has no derivative.  The descriptor is mpcx_lmpc_sens unchanged -- modes, layouts, flags
+ * and the NaN rule as documented there; active_lower / active_upper are the words mpcx_lmpc_hetero_solve_batch wrote.  model_index as in
+ * mpcx_lmpc_hetero_solve_batch (device, [B]; NULL: instance b is controller b, batch = K); an index outside [0, K) gets flag 1.  d_yref is the
+ * derivative with respect to a shift, common to all steps, of the output reference the instance was solved with -- the controller's own, per
+ * instance or per step.  Asynchronous on `stream`; allocates nothing.  MPCX_E_INVALID: null bank or descriptor, batch below 1, missing active
+ * words, unknown mode, a vector-Jacobian product without a seed, no model_index and a batch that is not the bank; MPCX_E_UNSUPPORTED: not even a
+ * working set of one row fits the kernel's LDS plan. */
+int mpcx_lmpc_hetero_sensitivity_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_sens *s, const int32_t *model_index, void *stream);
 /* The closed loop of a bank: a tick is mpcx_lmpc_hetero_solve_batch on the loop's own buffers followed by the advance kernel, captured as for a
  * controller (two graphs with carry_working_set).  The loop is the type mpcx_lmpc_loop_create returns: mpcx_lmpc_loop_run, _destroy, _debug_replay
  * and _debug_tick serve both.  The descriptor's rules are mpcx_lmpc_loop_create's; without a model_index the batch must be the bank.  model_index

@@ -142,6 +142,7 @@ EXPORTS = [
     "mpcx_comm_get_unique_id", "mpcx_comm_create", "mpcx_comm_destroy", "mpcx_comm_rank", "mpcx_comm_world", "mpcx_allgather_u",
     "mpcx_lmpc_hetero_create", "mpcx_lmpc_hetero_destroy", "mpcx_lmpc_hetero_get_info", "mpcx_lmpc_hetero_solve_batch",
     "mpcx_lmpc_hetero_time_solve_batch", "mpcx_lmpc_hetero_create_ex", "mpcx_lmpc_hetero_debug_get", "mpcx_lmpc_hetero_loop_create",
+    "mpcx_lmpc_hetero_sensitivity_batch",
     # profiling and testing aids (declared in include/mpcx.h under that heading)
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
     "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer",
@@ -228,6 +229,7 @@ def lib():
         _lib.mpcx_nlmpc_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_sensitivity_batch.argtypes = [C.c_void_p] * 3
         _lib.mpcx_lmpc_sensitivity_host.argtypes = [C.c_void_p] * 5
+        _lib.mpcx_lmpc_hetero_sensitivity_batch.argtypes = [C.c_void_p] * 4
         _lib.mpcx_lmpc_param_sensitivity_batch.argtypes = [C.c_void_p] * 3
         _lib.mpcx_lmpc_param_sens_reserve.argtypes = [C.c_void_p, C.c_int]
         _lib.mpcx_lmpc_param_sensitivity_host.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7

@@ -38,9 +38,11 @@ def _function():
 
     class LmpcCmd(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, controller, x0, u0, yref):
-            res = controller.optimizeBatch(x0.detach(), u0.detach(), None if yref is None else yref.detach(), want_active=True)
-            ctx.controller = controller
+        def forward(ctx, controller, x0, u0, yref, bank_model=None):
+            # a bank (LMPCHetero) takes the instance -> controller map in the solve and in the backward launch; a controller has none
+            kw = {} if bank_model is None else {"model": bank_model[0]}
+            res = controller.optimizeBatch(x0.detach(), u0.detach(), yref=None if yref is None else yref.detach(), want_active=True, **kw)
+            ctx.controller, ctx.kw = controller, kw
             ctx.has_yref = yref is not None
             ctx.save_for_backward(res.active_lower, res.active_upper, res.status)
             ctx.mark_non_differentiable(res.status)
@@ -49,9 +51,9 @@ def _function():
         @staticmethod
         def backward(ctx, grad_cmd, _grad_status):
             al, au, status = ctx.saved_tensors
-            want = tuple(n for n, need in zip(("x0", "u0", "yref"), ctx.needs_input_grad[1:]) if need)
-            s = ctx.controller.sensitivityBatch(al, au, status=status, seed_cmd=grad_cmd.contiguous(), want=want)
-            return None, s.d_x0, s.d_u0, (s.d_yref if ctx.has_yref else None)
+            want = tuple(n for n, need in zip(("x0", "u0", "yref"), ctx.needs_input_grad[1:4]) if need)
+            s = ctx.controller.sensitivityBatch(al, au, status=status, seed_cmd=grad_cmd.contiguous(), want=want, **ctx.kw)
+            return None, s.d_x0, s.d_u0, (s.d_yref if ctx.has_yref else None), None
 
     _FUNCTION = LmpcCmd
     return _FUNCTION
@@ -175,14 +177,20 @@ def lmpc_cmd_model(controller, x0, u0, yref, A, B, C, Bd=None, Dd=None, return_s
     return (cmd, status) if return_status else cmd
 
 
-def lmpc_cmd(controller, x0, u0, yref=None, return_status=False):
+def lmpc_cmd(controller, x0, u0, yref=None, return_status=False, model=None):
     """cmd [B, nu] of `controller` (a libmpc_amd.LMPC) at x0 [B, nx], u0 [B, nu] and the per-instance output reference yref [B, ny] (None:
-    the controller's own), differentiable with respect to the three.  return_status: (cmd, status) instead."""
+    the controller's own), differentiable with respect to the three.  return_status: (cmd, status) instead.  `controller` may be a bank
+    (libmpc_amd.LMPCHetero): model [B] is then the controller of every instance (None: instance b = controller b), passed to the solve and
+    to the backward launch (LMPCHetero.sensitivityBatch); None is then each controller's own reference."""
     import torch
     _, dev = controller._torch()
+    from .bank import LMPCHetero
+    is_bank = isinstance(controller, LMPCHetero)
+    if model is not None and not is_bank:
+        raise ValueError("lmpc_cmd: model= is the instance -> controller map of a bank (LMPCHetero)")
     as_t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64)).to(device=dev, dtype=torch.float64)
     x0, u0, yref = as_t(x0), as_t(u0), as_t(yref)
     if yref is not None and yref.dim() != 2 and yref.requires_grad:
         raise ValueError("lmpc_cmd differentiates a per-instance output reference [B, ny]; a per-step reference has no gradient here")
-    cmd, status = _function().apply(controller, x0, u0, yref)
+    cmd, status = _function().apply(controller, x0, u0, yref, (model,) if is_bank else None)      # (a tuple: the map passes through apply as it is)
     return (cmd, status) if return_status else cmd

@@ -19,7 +19,7 @@ import ctypes as C
 
 from . import _capi
 from ._capi import check
-from .lmpc import LMPC, BatchResult, ClosedLoopResult, Loop, _LoopFrontEnd
+from .lmpc import LMPC, BatchResult, ClosedLoopResult, Loop, SensitivityResult, _LoopFrontEnd
 
 
 def group_by_model(model, n_models: int):
@@ -157,15 +157,60 @@ class LMPCHetero(_LoopFrontEnd):
         return ms.value
 
     def optimizeBatch(self, x0, lastU, model=None, yref=None, uref=None, duref=None, dmeas=None, want_active=False, want_sequence=False,
-                      stream=None, warm=None, warm_shift=False) -> BatchResult:
+                      stream=None, warm=None, warm_shift=False, sensitivities=False) -> BatchResult:
         """x0 [B, nx], lastU [B, nu]; model [B] controller index per instance (None: instance b = controller b); references None
         (each controller's own) | [B, n] | [B, ph, n]; warm / warm_shift: a previous result's active sets as the first working sets, as
-        LMPC.optimizeBatch takes them"""
-        b, res, keep, mi = self.make_batch(x0, lastU, model, yref=yref, uref=uref, duref=duref, dmeas=dmeas, want_active=want_active,
+        LMPC.optimizeBatch takes them.  sensitivities=True: the Jacobians of cmd on the active sets this solve wrote, as
+        `result.sensitivities` (one more launch on the same stream)"""
+        b, res, keep, mi = self.make_batch(x0, lastU, model, yref=yref, uref=uref, duref=duref, dmeas=dmeas, want_active=want_active or sensitivities,
                                            want_sequence=want_sequence, warm=warm, warm_shift=warm_shift)
         self.launch(b, mi, stream)
         res._inputs = keep
+        if sensitivities:
+            res.sensitivities = self.sensitivityBatch(res.active_lower, res.active_upper, model=mi, status=res.status, stream=stream)
         return res
+
+    # -- sensitivities of a solved batch (mpcx_lmpc_hetero_sensitivity_batch, DESIGN.md 4.8b) ----------------------------------
+    def _model_index(self, model, B):
+        """model as make_batch validates it: None, or one controller index in [0, count) per instance, int32 on the device"""
+        if model is None:
+            if B != self.count:
+                raise ValueError("model: without it the batch must be the bank (instance b = controller b)")
+            return None
+        mi = torch.as_tensor(model).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
+        if mi.numel() != B or (mi.numel() and (int(mi.min()) < 0 or int(mi.max()) >= self.count)):
+            raise ValueError("model: one controller index in [0, %d) per instance" % self.count)
+        return mi
+
+    def make_sensitivity(self, active_lower, active_upper, model=None, status=None, seed_cmd=None, seed_input=None, want=("x0", "u0", "yref")):
+        """Allocate outputs and fill the mpcx_lmpc_sens descriptor, which is the single-controller one.  Returns (Sens, SensitivityResult,
+        keepalive, model index on the device | None)."""
+        d, out, keep = LMPC.make_sensitivity(self, active_lower, active_upper, status, seed_cmd, seed_input, want)
+        mi = self._model_index(model, d.batch)
+        return d, out, keep + (mi,), mi
+
+    def launch_sensitivity(self, desc, mi=None, stream=None, keep=None):
+        """One asynchronous launch for a descriptor built by make_sensitivity(); streams as in LMPC.launch()."""
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+            for t in (keep or ()):
+                if t is not None:
+                    t.record_stream(s)
+        check(self._lib.mpcx_lmpc_hetero_sensitivity_batch(self._h, C.byref(desc), None if mi is None else C.c_void_p(mi.data_ptr()),
+                                                           C.c_void_p(s.cuda_stream)))
+
+    def sensitivityBatch(self, active_lower, active_upper, model=None, status=None, seed_cmd=None, seed_input=None, stream=None,
+                         want=("x0", "u0", "yref")) -> SensitivityResult:
+        """LMPC.sensitivityBatch for a bank: the slope of solved instances on their active sets, instance b differentiated on controller
+        model[b] (None: controller b) -- one launch.  active_lower / active_upper [B, active_words] as optimizeBatch(want_active=True)
+        wrote them; status [B] (optional) marks the instances that were not solved.  Without seeds: the Jacobians of cmd.  seed_cmd
+        [B, nu] and / or seed_input [B, ph + 1, nu]: the vector-Jacobian products.  want: which outputs to compute."""
+        d, out, keep, mi = self.make_sensitivity(active_lower, active_upper, model, status, seed_cmd, seed_input, want)
+        self.launch_sensitivity(d, mi, stream, keep)
+        out._inputs = keep[:5] + (mi,)
+        return out
 
     # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create*; the loop itself is _LoopFrontEnd's) ---------------------
     _loop_entry = "mpcx_lmpc_hetero_loop_create"

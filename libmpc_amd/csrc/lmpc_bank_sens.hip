@@ -1,0 +1,348 @@
+// Sensitivities of a solved batch of a bank: vector-Jacobian products of the decision vector w with respect to
+// vin = [x0 | lastU | yref], every instance on its own controller.
+//
+// A bank's controllers carry no composed affine maps (MF1), so 4.8's formula is restated without them.  On the working set A, with
+// S = Y[A, A] and a cotangent p on w,
+//     mu = S^-1 Y[A, 0:nz] p,     q = Y[0:nz, 0:nz] p - Y[0:nz, A] mu,     g = -F' q - OFF[A, :]' mu
+// F = df/dvin is the linear term's dependence on the data and OFF = d(offset of a general row)/dvin (its bounds are lg0 - off, ug0 - off).  Both
+// are the linear part of the roll-out in lmpc_assemble_generic, so both products are its adjoint and need no matrix of the condensed problem:
+//     dv_i = q[blk[i] nu + .],  dx_0 = 0,  dx_i = A dx_{i-1} + B dv_i                                       i = 1 .. ph
+//     do_i  = Wy_i C dx_i                                                  (d_yref sums these, and Tx' P dx_ph of the terminal target)
+//     gam_i = C' (do_i + output rows' mu_r e_comp) + state rows' mu_r e_comp + scalar / linear rows' mu_r sX / Fx[c, :] + [i = ph] P dx_ph
+//     eta_ph = gam_ph,  eta_i = gam_i + A' eta_{i+1},      d_x0 = -A' eta_1 - gam_0
+//     d_u0 = Wdu[:, 0] dv_1 + (rate rows of step 1) mu_r e_comp - (scalar / linear rows of step 0) mu_r sU / Fu[c, :]
+// gam_0 and the last term of d_u0 belong to rows of step 0, which are in the condensed problem only where a slack variable makes them soft.
+//
+// One wavefront per instance, the whole kernel without a workgroup barrier.  Every matrix differs from instance to instance: there is no shared
+// operand for the matrix pipe.  The seeds of an instance (nu unit seeds in Jacobian mode) are served one after another on one factor of S.
+// lmpc_sens.hip's working-set decode and Cholesky are restated here; that file is untouched.
+#include "lmpc_kernel_common.hpp"
+
+namespace mpcx {
+
+namespace {
+
+// a pivot below this fraction of the row's own diagonal entry of S: the working set is dependent (flag 2)
+constexpr double kBankPivotTol = 1e-11;
+constexpr int kBankState = 0, kBankOutput = 1, kBankScalar = 2, kBankRate = 3, kBankLinear = 4;      // GKind of lmpc_model.hpp
+
+struct LmpcBankSensDev {
+    LmpcBankSensArgs a;
+    int nx, nu, ny, ph, nz, mg, ldz, ldy, aw, term;      // controller 0's: the same for every controller of a bank
+    int R;                                               // seeds per instance
+    int cap;                                             // rows of S a wavefront's LDS slice holds
+};
+
+__host__ __device__ inline int bank_even(int n) { return (n + 1) & ~1; }
+// a wavefront's slice: S (packed lower triangle) | its original diagonal | one right-hand side | the working set's unified indices and the kind,
+// step and component of its general rows (ints) | blk (ints) | A, B, C | p, q | dx [(ph + 1) x nx] and P dx_ph | do [ph x ny] | gam [(ph + 1) x nx] |
+// the sums of d_u0.  Nothing a recursion over the horizon reads lies in HBM: a step of it costs LDS latency, not a trip to memory
+__host__ __device__ inline size_t bank_wave_len(int cap, int nx, int nu, int ny, int ph, int nz)
+{
+    return (size_t)cap * (cap + 1) / 2 + 2 * (size_t)cap + 2 * (size_t)cap + (size_t)(ph + 2) / 2 + (size_t)nx * (nx + nu) + (size_t)ny * nx +
+           2 * (size_t)bank_even(nz) + (size_t)(ph + 2) * nx + (size_t)ph * ny + (size_t)(ph + 1) * nx + nu;
+}
+
+// ---- the phases, one wavefront each; the parameter and model gradients of a bank need the first three as they are -------------------------------
+
+// the working set of instance b from its active bits by ballot compaction: a variable is in A when any of its reference rows has a bit, a general
+// row when bit g_refrow[r] is set.  Returns the number of rows; only the first `cap` are stored
+__device__ inline int bank_working_set(const LmpcDev &M, const uint32_t MPCX_GAS *wl, const uint32_t MPCX_GAS *wu, int aw, int nz, int mg, int ldz,
+                                       int cap, int lane, int *idx)
+{
+    auto bit = [&](int rr) -> bool { return rr >= 0 && (rr >> 5) < aw && (((wl[rr >> 5] | wu[rr >> 5]) >> (rr & 31)) & 1u) != 0u; };
+    int n = 0;
+    for (int base = 0; base < nz + mg; base += 64) {
+        const int e = base + lane;
+        bool in = false;
+        if (e < nz) { for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) in = in || bit(GP(boxrow_ref)[p]); }
+        else if (e < nz + mg) in = bit(GP(g_refrow)[e - nz]);
+        const unsigned long long mask = __ballot(in);
+        const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
+        if (in && pos < cap) idx[pos] = e < nz ? e : ldz + (e - nz);
+        n += __popcll(mask);
+    }
+    return n;
+}
+
+// S = Y[A, A] gathered as a packed lower triangle and factored in place by a left-looking Cholesky, a row per lane.  false: a pivot at or below
+// kBankPivotTol of the row's own diagonal entry
+__device__ inline bool bank_factor(gdp Y, int ldy, const int *idx, int n, int lane, double *S, double *dg)
+{
+    for (int t = lane; t < n * n; t += 64) {              // (the square is walked and its lower triangle kept: independent loads, all in flight)
+        const int i = t / n, j = t - i * n;
+        if (j > i) continue;
+        const double v = Y[(size_t)idx[j] * ldy + idx[i]];
+        if (j == i) dg[i] = v;
+        S[(size_t)i * (i + 1) / 2 + j] = v;
+    }
+    wave_sync();
+    for (int k = 0; k < n; ++k) {
+        const double *Lk = S + (size_t)k * (k + 1) / 2;
+        for (int i = k + lane; i < n; i += 64) {
+            double *Li = S + (size_t)i * (i + 1) / 2;
+            double s = Li[k];
+#pragma unroll 4
+            for (int j = 0; j < k; ++j) s = fma(-Li[j], Lk[j], s);
+            Li[k] = s;
+        }
+        wave_sync();
+        const double d = Lk[k];
+        if (!(d > kBankPivotTol * dg[k])) return false;
+        const double sd = sqrt(d), rd = 1.0 / sd;
+        wave_sync();
+        for (int i = k + lane; i < n; i += 64) { double *Li = S + (size_t)i * (i + 1) / 2; Li[k] = i == k ? sd : Li[k] * rd; }
+        wave_sync();
+    }
+    return true;
+}
+
+// L L' x = v on the factor in S, in place
+__device__ inline void bank_chol_solve(const double *S, double *V, int n, int lane)
+{
+    for (int k = 0; k < n; ++k) {
+        if (lane == 0) V[k] /= S[(size_t)k * (k + 1) / 2 + k];
+        wave_sync();
+        for (int i = k + 1 + lane; i < n; i += 64) V[i] = fma(-S[(size_t)i * (i + 1) / 2 + k], V[k], V[i]);
+        wave_sync();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        const double *Lk = S + (size_t)k * (k + 1) / 2;
+        if (lane == 0) V[k] /= Lk[k];
+        wave_sync();
+        for (int i = lane; i < k; i += 64) V[i] = fma(-Lk[i], V[k], V[i]);
+        wave_sync();
+    }
+}
+
+// the direction's roll-out through the instance's own model (As, Bs, Cs column-major and blk in LDS): dx [(ph + 1) x nx] by the chain of ph steps,
+// then the outputs of every step at once, do[(i - 1) ny + j] = Wy_i (C dx_i)[j] for i = 1 .. ph
+__device__ inline void bank_rollout(const double *As, const double *Bs, const double *Cs, gdp Wy, const int *blk, const double *q, int nx, int nu, int ny,
+                                    int ph, int lane, double *dx, double *dov)
+{
+    for (int a = lane; a < nx; a += 64) dx[a] = 0.0;
+    wave_sync();
+    for (int i = 1; i <= ph; ++i) {
+        const double *dv = q + blk[i] * nu, *xp = dx + (size_t)(i - 1) * nx;
+        for (int a = lane; a < nx; a += 64) {
+            double s = 0.0;
+#pragma unroll 4
+            for (int c = 0; c < nx; ++c) s = fma(As[a + (size_t)c * nx], xp[c], s);
+#pragma unroll 4
+            for (int j = 0; j < nu; ++j) s = fma(Bs[a + (size_t)j * nx], dv[j], s);
+            dx[(size_t)i * nx + a] = s;
+        }
+        wave_sync();
+    }
+    for (int t = lane; t < ph * ny; t += 64) {
+        const int i = t / ny + 1, j = t - (i - 1) * ny;
+        const double *xi = dx + (size_t)i * nx;
+        double s = 0.0;
+#pragma unroll 4
+        for (int c = 0; c < nx; ++c) s = fma(Cs[j + (size_t)c * ny], xi[c], s);
+        dov[t] = Wy[j + (size_t)i * ny] * s;
+    }
+    wave_sync();
+}
+
+__global__ __launch_bounds__(256) void lmpc_bank_sensitivity(const LmpcBankSensDev Sd)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int b = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;       // one instance per wavefront; the grid covers the batch
+    if (b >= Sd.a.s.batch) return;                                        // (a whole wavefront: the kernel has no workgroup barrier)
+    const LmpcSensArgs &Ar = Sd.a.s;
+    const int nx = Sd.nx, nu = Sd.nu, ny = Sd.ny, ph = Sd.ph, nz = Sd.nz, mg = Sd.mg, ldz = Sd.ldz, ldy = Sd.ldy, aw = Sd.aw;
+    const int cap = Sd.cap, R = Sd.R, nzp = bank_even(nz);
+    const bool jac = Ar.jacobian, term = Sd.term != 0;
+    const double qnan = __builtin_nan("");
+
+    double *S = smem + (size_t)wave * bank_wave_len(cap, nx, nu, ny, ph, nz);
+    double *dg = S + (size_t)cap * (cap + 1) / 2, *V = dg + cap;
+    int *idx = reinterpret_cast<int *>(V + cap), *rkind = idx + cap, *rstep = rkind + cap, *rcomp = rstep + cap;
+    int *blk = reinterpret_cast<int *>(V + 3 * (size_t)cap);
+    double *As = V + 3 * (size_t)cap + (size_t)(ph + 2) / 2, *Bs = As + (size_t)nx * nx, *Cs = Bs + (size_t)nx * nu;
+    double *pv = Cs + (size_t)ny * nx, *qv = pv + nzp;
+    double *dx = qv + nzp, *pdx = dx + (size_t)(ph + 1) * nx;
+    double *dov = pdx + nx, *gam = dov + (size_t)ph * ny, *du = gam + (size_t)(ph + 1) * nx;
+
+    // the instance's controller; an index outside the bank is answered like an instance that was not solved
+    const int km = __builtin_amdgcn_readfirstlane(Sd.a.n_models <= 0 ? 0 : (Sd.a.model_index ? (int)gl(Sd.a.model_index)[b] : b));
+    const bool known = km >= 0 && km < (Sd.a.n_models > 0 ? Sd.a.n_models : 1);
+    const LmpcDev &M = Sd.a.models[known ? km : 0];
+    int flag = (!known || (Ar.status && gl(Ar.status)[b] != 0)) ? 1 : 0;
+    int n = 0;
+    if (!flag) {
+        n = bank_working_set(M, gl(Ar.active_lower) + (size_t)b * aw, gl(Ar.active_upper) + (size_t)b * aw, aw, nz, mg, ldz, cap, lane, idx);
+        if (n > cap) flag = 3;
+    }
+    wave_sync();
+    const gdp Y = GP(Y);
+    if (!flag) {
+        const int nA = nx * nx, nB = nx * nu, nC = ny * nx;
+        for (int t = lane; t < nA + nB + nC; t += 64) As[t] = t < nA ? GP(A)[t] : (t < nA + nB ? GP(B)[t - nA] : GP(C)[t - nA - nB]);
+        for (int i = lane; i <= ph; i += 64) blk[i] = GP(blk)[i];
+        for (int k = lane; k < n; k += 64) {
+            const int rr = idx[k] - ldz;
+            rkind[k] = rr >= 0 ? GP(g_kind)[rr] : -1; rstep[k] = rr >= 0 ? GP(g_step)[rr] : 0; rcomp[k] = rr >= 0 ? GP(g_comp)[rr] : 0;
+        }
+        wave_sync();
+        if (n > 0 && !bank_factor(Y, ldy, idx, n, lane, S, dg)) flag = 2;
+    }
+    wave_sync();
+
+    for (int r = 0; r < R; ++r) {
+        const size_t row = (size_t)b * R + r;
+        if (flag) {
+            for (int a = lane; a < nx; a += 64) if (Ar.d_x0) glw(Ar.d_x0)[row * nx + a] = qnan;
+            for (int j = lane; j < nu; j += 64) if (Ar.d_u0) glw(Ar.d_u0)[row * nu + j] = qnan;
+            for (int j = lane; j < ny; j += 64) if (Ar.d_yref) glw(Ar.d_yref)[row * ny + j] = qnan;
+            continue;
+        }
+        // ---- the cotangent on w: a unit vector on the first move (then Y p is a column of Y), or the seeds scattered through blk
+        const int col = blk[1] * nu + r;
+        if (!jac) {
+            for (int t = lane; t < nzp; t += 64) {
+                double v = 0.0;
+                if (t < nz) {
+                    const int bq = t / nu, jq = t - bq * nu;
+                    if (Ar.seed_cmd && bq == blk[1]) v = gl(Ar.seed_cmd)[(size_t)b * nu + jq];
+                    if (Ar.seed_input)              // row i of the sequence is v_{min(i + 1, ph)} (OptSequence)
+                        for (int i = 0; i <= ph; ++i)
+                            if (blk[i + 1 <= ph ? i + 1 : ph] == bq) v += gl(Ar.seed_input)[((size_t)b * (ph + 1) + i) * nu + jq];
+                }
+                pv[t] = v;
+            }
+            wave_sync();
+        }
+        // ---- mu = S^-1 Y[A, 0:nz] p, a row per lane (Y is symmetric: row idx[i] of a column)
+        for (int i = lane; i < n; i += 64) {
+            const int qi = idx[i];
+            double s = 0.0;
+            if (jac) s = Y[(size_t)col * ldy + qi];
+            else
+                for (int q = 0; q < nz; ++q) {
+                    const double p = pv[q];
+                    if (p != 0.0) s = fma(Y[(size_t)q * ldy + qi], p, s);
+                }
+            V[i] = s;
+        }
+        wave_sync();
+        bank_chol_solve(S, V, n, lane);
+        // ---- q = Y[0:nz, 0:nz] p - Y[0:nz, A] mu: a lane owns element pairs of the contiguous columns, one 16-byte load each (ldy is even)
+        for (int e = 2 * lane; e < nz; e += 128) {
+            double s0 = 0.0, s1 = 0.0;
+            if (jac) { const d2 y = ld2(Y + (size_t)col * ldy + e); s0 = y.x; s1 = y.y; }
+            else
+                for (int q = 0; q < nz; ++q) {
+                    const double p = pv[q];
+                    if (p != 0.0) { const d2 y = ld2(Y + (size_t)q * ldy + e); s0 = fma(y.x, p, s0); s1 = fma(y.y, p, s1); }
+                }
+            for (int i = 0; i < n; ++i) {
+                const d2 y = ld2(Y + (size_t)idx[i] * ldy + e);
+                s0 = fma(-y.x, V[i], s0); s1 = fma(-y.y, V[i], s1);
+            }
+            qv[e] = s0; qv[e + 1] = e + 1 < nz ? s1 : 0.0;
+        }
+        wave_sync();
+        // ---- forward: the direction through the instance's model
+        bank_rollout(As, Bs, Cs, GP(Wy), blk, qv, nx, nu, ny, ph, lane, dx, dov);
+        const double *dxph = dx + (size_t)ph * nx;
+        const gdp tP = gl(MPCX_TERMINAL(M)), tTx = tP + (size_t)nx * nx + nx;
+        for (int a = lane; a < nx; a += 64) {
+            double s = 0.0;
+            if (term) for (int c = 0; c < nx; ++c) s = fma(tP[a + (size_t)c * nx], dxph[c], s);
+            pdx[a] = s;
+        }
+        for (int t = lane; t < (ph + 1) * nx; t += 64) gam[t] = 0.0;
+        for (int j = lane; j < nu; j += 64) du[j] = GP(Wdu)[j] * qv[blk[1] * nu + j];
+        wave_sync();
+        // d_yref: the cost's part of do_i alone, and the terminal target's Tx-columns of yref
+        for (int j = lane; j < ny; j += 64) {
+            double s = 0.0;
+            for (int i = 0; i < ph; ++i) s += dov[i * ny + j];
+            if (term) for (int a = 0; a < nx; ++a) s = fma(tTx[a + (size_t)j * nx], pdx[a], s);
+            if (Ar.d_yref) glw(Ar.d_yref)[row * ny + j] = s;
+        }
+        for (int a = lane; a < nx; a += 64) gam[(size_t)ph * nx + a] = pdx[a];
+        // ---- the working rows one after the other; an entry is always touched by the same lane
+        for (int k = 0; k < n; ++k) {
+            const int kind = rkind[k], st = rstep[k], cpn = rcomp[k];
+            if (kind < 0) continue;
+            const double mu = V[k];
+            if (kind == kBankOutput) {
+                if (st >= 1) { if (lane == (cpn & 63)) dov[(st - 1) * ny + cpn] += mu; }
+                else for (int c = lane; c < nx; c += 64) gam[c] = fma(mu, Cs[cpn + (size_t)c * ny], gam[c]);
+            } else if (kind == kBankState) {
+                if (lane == (cpn & 63)) gam[(size_t)st * nx + cpn] += mu;
+            } else if (kind == kBankScalar || kind == kBankLinear) {
+                const gdp Fx = kind == kBankScalar ? GP(sX) : gl(MPCX_LINEAR_F(M)) + (size_t)cpn * (nx + nu);
+                const gdp Fu = kind == kBankScalar ? GP(sU) : Fx + nx;
+                for (int c = lane; c < nx; c += 64) gam[(size_t)st * nx + c] = fma(mu, Fx[c], gam[(size_t)st * nx + c]);
+                if (st == 0) for (int j = lane; j < nu; j += 64) du[j] = fma(-mu, Fu[j], du[j]);
+            } else if (kind == kBankRate && st == 1) {
+                if (lane == (cpn & 63)) du[cpn] += mu;
+            }
+        }
+        wave_sync();
+        // ---- backward: eta_i = gam_i + C' do_i + A' eta_{i+1}, in place: the output terms of every step at once, then the chain
+        for (int t = lane; t < ph * nx; t += 64) {
+            const int i = t / nx + 1, a = t - (i - 1) * nx;
+            const double *dc = dov + (size_t)(i - 1) * ny;
+            double s = gam[(size_t)i * nx + a];
+#pragma unroll 4
+            for (int j = 0; j < ny; ++j) s = fma(Cs[j + (size_t)a * ny], dc[j], s);
+            gam[(size_t)i * nx + a] = s;
+        }
+        wave_sync();
+        for (int i = ph - 1; i >= 1; --i) {
+            double *gc = gam + (size_t)i * nx;
+            for (int a = lane; a < nx; a += 64) {
+                double s = gc[a];
+#pragma unroll 4
+                for (int c = 0; c < nx; ++c) s = fma(As[c + (size_t)a * nx], gc[nx + c], s);
+                gc[a] = s;
+            }
+            wave_sync();
+        }
+        for (int a = lane; a < nx; a += 64) {
+            double s = gam[a];
+#pragma unroll 4
+            for (int c = 0; c < nx; ++c) s = fma(As[c + (size_t)a * nx], gam[nx + c], s);
+            if (Ar.d_x0) glw(Ar.d_x0)[row * nx + a] = -s;
+        }
+        for (int j = lane; j < nu; j += 64) if (Ar.d_u0) glw(Ar.d_u0)[row * nu + j] = du[j];
+        wave_sync();
+    }
+    if (Ar.flags && lane == 0) glw(Ar.flags)[b] = flag;
+}
+
+}  // namespace
+
+int lmpc_bank_sens_launch(const LmpcDev &m, const LmpcBankSensArgs &a, void *stream)
+{
+    LmpcBankSensDev s{};
+    s.a = a;
+    s.nx = m.nx; s.nu = m.nu; s.ny = m.ny; s.ph = m.ph; s.nz = m.nz; s.mg = m.mg; s.ldz = m.ldz; s.ldy = m.ldy; s.aw = m.active_words;
+    s.term = MPCX_HAS_TERMINAL(m) ? 1 : 0;
+    s.R = a.s.jacobian ? m.nu : 1;
+    // every wavefront's slice holds the largest working set there can be (ws_limit) where four, two or one of them fit in a CU's LDS; otherwise one
+    // wavefront with the largest slice that fits, and larger sets get flag 3
+    const size_t limit = lmpc_lds_limit() / sizeof(double);
+    auto len = [&](int cap) { return bank_wave_len(cap, m.nx, m.nu, m.ny, m.ph, m.nz); };
+    const int want = ws_limit(m.nz, m.mg, m.n_soft) > 1 ? ws_limit(m.nz, m.mg, m.n_soft) : 1;
+    int waves = 4;
+    while (waves > 1 && waves * len(want) > limit) waves >>= 1;
+    s.cap = want;
+    while (s.cap > 0 && waves * len(s.cap) > limit) --s.cap;
+    if (s.cap <= 0) return -2;
+    const size_t bytes = waves * len(s.cap) * sizeof(double);
+    static LmpcLdsCache configured;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_bank_sensitivity)}, bytes) != 0) return -3;
+    const int blocks = (a.s.batch + waves - 1) / waves;
+    hipLaunchKernelGGL(lmpc_bank_sensitivity, dim3(blocks), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream), s);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace mpcx

@@ -198,6 +198,17 @@ size_t lmpc_sens_operand(int nz, int kin, int rowsF, const double *MF1, double *
 // 0; -2: not even a working set of one row fits the LDS plan; -3: a launch or its configuration failed
 int lmpc_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double *T0p, const LmpcSensArgs &a, void *stream);
 
+// The same for a bank (lmpc_bank_sens.hip): instance b on models[model_index[b]] (null map: entry b), as lmpc_model_of reads a batch
+struct LmpcBankSensArgs {
+    LmpcSensArgs s;
+    const LmpcDev *models;                        // the bank's model structs (device array)
+    const int32_t *model_index;
+    int n_models;
+};
+// m: controller 0 (dimensions; the same for every controller of a bank).  0; -2: not even a working set of one row fits the LDS plan; -3: a launch
+// or its configuration failed
+int lmpc_bank_sens_launch(const LmpcDev &m, const LmpcBankSensArgs &a, void *stream);
+
 // Parameter sensitivities of a solved batch (lmpc_param_sens.hip).  All device pointers; the references as LmpcBatchDev's accessors
 struct LmpcParamSensArgs {
     int batch;

@@ -2161,6 +2161,27 @@ int mpcx_lmpc_hetero_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b,
     return lr == 0 ? MPCX_OK : launch_failed(lr, f->scratch, stream);
 }
 
+int mpcx_lmpc_hetero_sensitivity_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_sens *s, const int32_t *model_index, void *stream)
+{
+    if (!f) return fail(MPCX_E_INVALID, "null bank");
+    if (!s) return fail(MPCX_E_INVALID, "null sensitivity descriptor");
+    if (s->mode != MPCX_SENS_JACOBIAN && s->mode != MPCX_SENS_VJP) return fail(MPCX_E_INVALID, "unknown sensitivity mode");
+    if (s->batch < 1) return fail(MPCX_E_INVALID, "batch below 1");
+    if (!s->active_lower || !s->active_upper) return fail(MPCX_E_INVALID, "active_lower and active_upper are required");
+    if (s->mode == MPCX_SENS_VJP && !s->seed_cmd && !s->seed_input) return fail(MPCX_E_INVALID, "a vector-Jacobian product needs seed_cmd or seed_input");
+    if (!model_index && s->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    mpcx::LmpcBankSensArgs a{};
+    a.s.batch = s->batch; a.s.jacobian = s->mode == MPCX_SENS_JACOBIAN;
+    a.s.active_lower = s->active_lower; a.s.active_upper = s->active_upper; a.s.status = s->status;
+    a.s.seed_cmd = a.s.jacobian ? nullptr : s->seed_cmd; a.s.seed_input = a.s.jacobian ? nullptr : s->seed_input;
+    a.s.d_x0 = s->d_x0; a.s.d_u0 = s->d_u0; a.s.d_yref = s->d_yref; a.s.flags = s->flags;
+    a.models = f->models_d; a.model_index = model_index; a.n_models = f->count;
+    const int lr = mpcx::lmpc_bank_sens_launch(f->dev0, a, stream);
+    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the bank sensitivity kernel's LDS budget");
+    return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+}
+
 int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream, int repeats, float *ms_mean)
 {
     if (!f || !b || !ms_mean || repeats < 1) return fail(MPCX_E_INVALID, "bad argument");
