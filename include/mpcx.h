@@ -918,6 +918,10 @@ int mpcx_lmpc_debug_force_generic(mpcx_lmpc_t h, int on);
 int mpcx_lmpc_debug_set_rounds(mpcx_lmpc_t h, int rounds0, int check_every);
 /* device buffer [B x 8] of int64 receiving per-instance cycle stamps of the solve kernel (NULL: off) */
 int mpcx_lmpc_debug_set_cycle_buffer(mpcx_lmpc_t h, void *dev_ptr);
+/* the wave-wide sums of the lean LMPC kernels side by side, one wavefront per vector: in [nvec][64] doubles -> out [nvec][4][64] = every lane of
+ * (0) the six-level butterfly sum, (1) its lane-swap / DPP form, (2) the two-level sum over lanes l, l ^ 16, l ^ 32, l ^ 48 by shuffles, (3) the same
+ * by lane swaps.  Device pointers; asynchronous on `stream` */
+int mpcx_lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream);
 /* one more replay of a loop's tick graph behind a finished run, without the reset: the tick counter stands at `ticks`, so the replay writes no
  * trajectory, state or counter / the tick counter as it stands on the device, after synchronising the device */
 int mpcx_lmpc_loop_debug_replay(mpcx_lmpc_loop_t l, void *stream);

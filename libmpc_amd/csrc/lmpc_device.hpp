@@ -173,6 +173,9 @@ int lmpc_fast_slice(const LmpcDev &m);          // needs wsld, kin, nx
 size_t lmpc_group_lds_bytes(const LmpcDev &m);  // LDS block of lmpc_solve_group (0: no group form for the variant); needs fast_slice, kin, nz16, nu
 // implemented in lmpc_fast.hip: the polish-first kernel of `form` on `stream`
 int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, LmpcForm form);
+// testing aid (lmpc_fast.hip): in [nvec][64] -> out [nvec][4][64] = every lane of wave_sum, of wave_sum_full, and of the two-level sum (lanes l, l ^ 16,
+// l ^ 32, l ^ 48) by __shfl_xor and by lane swaps; device pointers
+int lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream);
 // hipFuncAttributeMaxDynamicSharedMemorySize of `kernels` raised to `bytes` on the current device unless `cache` says it has been: one cache per
 // set of kernels that are raised together, grow-only, an atomic per device (two host threads or two handles on different GPUs can neither skip
 // nor tear the update).  0, or -3

@@ -58,6 +58,15 @@ namespace {
 //     from 0.0346 to 0.0386 ms with every class on it (fewer vector instructions, but it is the slowest chain that ends the launch, and that chain is latency).
 //     The elimination's steps are instances of one lambda over the step number either way (the crossbar's lane is an immediate).  No floating-point operation
 //     changed; profiles/r10_round_ab.txt, r10_round_isa_census.txt.
+//   * round 11: what a step runs outside the rounds.  The wave-wide sums there still went through the ds_bpermute butterfly of wave_sum -- the cost's sum in
+//     fast_finish (the last thing the slowest instance does), the cost constant's two levels in front of the barrier between lmpc_solve_group's products, the
+//     deal's key and rank: 42 ds_bpermute_b32 in lmpc_solve_group<1, 1>, sixteen dependent LDS round trips on every step's critical path.  They are lane swaps
+//     (v_permlane32_swap / v_permlane16_swap) and DPP moves now, wave_sum_full below: the butterfly's own pairing tree, so the cost keeps its bits; the deal's
+//     key, whose bits reach no result, takes the cheapest tree.  Against the same source with MPCX_FAST_DPP_SUMS 0, whole step, three runs each: 0.03396 ->
+//     0.03334 ms, 0.03242 -> 0.03180 ms at --steps 2000, every run below every run of the other.  Tried with it and not kept, each level with "off" on the
+//     GPU: the sixteen-term sums of the cost constants on the last wavefront instead of wavefront 0 (which has a tile of the second product); the fallback
+//     launch's queue pointer as a preloaded kernel argument (one trip to memory for the idle exit test instead of two).  profiles/r13_head_ab.txt,
+//     r13_head_isa_census.txt.
 // Working sets of more than kFastCap rows are left to the fallback kernel (none in 32768 instances of config 2, none in 8192 of
 // config 4).
 // How deep a round reaches into memory ahead of its arithmetic (ws_solve_reg).  Rows of Y requested with the Schur entries, ahead of the elimination:
@@ -139,6 +148,105 @@ __device__ __forceinline__ double wave_max_dpp(double v)
     v = fmax(v, dpp_mov_d<0x142>(v));    // row_bcast:15
     v = fmax(v, dpp_mov_d<0x143>(v));    // row_bcast:31
     return readlane_d(v, 63);
+}
+// Round 11: the sums on the critical path outside the rounds -- the cost in fast_finish, the cost constant, the deal's key and rank in lmpc_solve_group --
+// without the ds_bpermute butterfly of wave_sum (kernel_common), behind one switch for the A/B builds (profiles/r13_head_ab.txt).
+#ifndef MPCX_FAST_DPP_SUMS
+#define MPCX_FAST_DPP_SUMS 1
+#endif
+// v[l] + v[l ^ 32] (ROW16 false) or v[l] + v[l ^ 16] (ROW16 true) in every lane, by gfx950's lane swaps: the instruction exchanges the upper half (the odd
+// rows of sixteen) of its first operand with the lower half (the even rows) of its second, so with v in both the first comes back as the lower partner in
+// every lane and the second as the upper one.  The lanes of the upper half add their pair in the other order than the butterfly did: IEEE addition is
+// commutative, signed zeros included, so the bits are the butterfly's (a NaN stays a NaN).  Every lane has to be active.
+template <bool ROW16>
+__device__ __forceinline__ double lane_swap_pair_sum(double v)
+{
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    if constexpr (ROW16) {
+        const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+    } else {
+        const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+    }
+}
+template <bool ROW16>
+__device__ __forceinline__ int lane_swap_pair_sum(int v)
+{
+    if constexpr (ROW16) { const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false); return (int)(r[0] + r[1]); }
+    else { const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false); return (int)(r[0] + r[1]); }
+}
+// Sum over the wavefront, the same in every lane and bit for bit wave_sum's: the same pairing tree in the same order (xor 32, 16, 8, 4, 2, 1), each level a
+// lane swap or DPP moves instead of two ds_bpermute_b32 -- no LDS round trip on the chain.  xor 8 is a rotation of the row by eight; xor 4 is a rotation by
+// twelve for the banks 0 and 2 of a row and by four for the banks 1 and 3, two moves into one register under complementary bank masks; xor 2 and xor 1 are
+// quad permutations.  EVERY LANE HAS TO BE ACTIVE (a DPP move or a lane swap reads an inactive lane's register as it stands, or 0): it is called from
+// wave-uniform code only -- fast_finish, lmpc_solve_group's head, the debug kernel below.  Everything else keeps wave_sum.
+__device__ __forceinline__ double wave_sum_full(double v)
+{
+    v = lane_swap_pair_sum<false>(v);
+    v = lane_swap_pair_sum<true>(v);
+    v += dpp_mov_d<0x128>(v);            // row_ror:8
+    {
+        int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x12C, 0xF, 0x5, true);      // row_ror:12, banks 0 and 2
+        int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x12C, 0xF, 0x5, true);
+        lo = __builtin_amdgcn_update_dpp(lo, __double2loint(v), 0x124, 0xF, 0xA, false);  // row_ror:4, banks 1 and 3
+        hi = __builtin_amdgcn_update_dpp(hi, __double2hiint(v), 0x124, 0xF, 0xA, false);
+        v += __hiloint2double(hi, lo);
+    }
+    v += dpp_mov_d<0x4E>(v);             // quad_perm [2,3,0,1]
+    v += dpp_mov_d<0xB1>(v);             // quad_perm [1,0,3,2]
+    return v;
+}
+// the two-level form of lmpc_solve_group's head: the sum over the four lanes l, l ^ 16, l ^ 32, l ^ 48, paired as the two __shfl_xor levels paired them
+// (16, then 32).  Every lane active.
+template <typename T>
+__device__ __forceinline__ T wave_sum_rows_swap(T v)
+{
+    v = lane_swap_pair_sum<true>(v);
+    return lane_swap_pair_sum<false>(v);
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum_rows_shfl(T v)
+{
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum_rows(T v)
+{
+#if MPCX_FAST_DPP_SUMS
+    return wave_sum_rows_swap(v);
+#else
+    return wave_sum_rows_shfl(v);
+#endif
+}
+// a sum over the wavefront whose bits need not be wave_sum's (another tree: within the rows as wave_max_dpp's maximum, across them towards lane 63, a row
+// without a source takes in a 0), the same in every lane and the same from run to run.  Every lane active.
+__device__ __forceinline__ double wave_sum_any(double v)
+{
+#if MPCX_FAST_DPP_SUMS
+    v += dpp_mov_d<0xB1>(v);
+    v += dpp_mov_d<0x4E>(v);
+    v += dpp_mov_d<0x141>(v);
+    v += dpp_mov_d<0x140>(v);
+    v += dpp_mov_d<0x142>(v);
+    v += dpp_mov_d<0x143>(v);
+    return readlane_d(v, 63);
+#else
+    return wave_sum(v);
+#endif
+}
+// the sums of fast_finish: the cost's bits are the result's
+__device__ __forceinline__ double wave_sum_cost(double v)
+{
+#if MPCX_FAST_DPP_SUMS
+    return wave_sum_full(v);
+#else
+    return wave_sum(v);
+#endif
 }
 
 // One solve of the working-set system and the update of the primal point, working set of at most CAP (<= 16) rows.
@@ -584,7 +692,7 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
 #pragma unroll
         for (int s = 0; s < NZS; ++s) j = fma(f[s], w[s], j);
         if (lane < na_last) j = fma(-lam[lane], wsb[lane], j);
-        cost = 0.5 * wave_sum(j) + c0;
+        cost = 0.5 * wave_sum_cost(j) + c0;
     } else if (!FUSED && Bt.n_models <= 0) {
         // cost from its definition by lmpc_cost_mfma: the solution goes to the workspace in t0's place
 #pragma unroll
@@ -593,10 +701,15 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
             if (e < ldz) st2(ws + ldz + e, w[2 * c], w[2 * c + 1]);
         }
         if (M.n_soft > 0) {                         // lmpc_cost_mfma adds the record's constant: the penalty rides in it
-            const double pen = wave_sum(soft_penalty());
+            const double pen = wave_sum_cost(soft_penalty());
             if (lane == 0) ws[ldz + ldy + 2 * ldg] = c0 + pen;
         }
         cost = 0.0;
+        cost_pending = true;
+    } else if (SRC == 2 && CPZ == 2 && Bt.n_models <= 0) {
+        // lmpc_solve_group<2, 2>: the workgroup takes these costs from their definition together, behind its solves, by lmpc_cost_mfma's own
+        // arithmetic (group_cost_mfma) -- the two-kernel form's bits.  Here only what that kernel reads from the record: the constant, with the penalty in it
+        cost = M.n_soft > 0 ? c0 + wave_sum_cost(soft_penalty()) : c0;
         cost_pending = true;
     } else {
         double hw[NZS];
@@ -607,7 +720,7 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
 #pragma unroll
         for (int s = 0; s < NZS; ++s) j += w[s] * (0.5 * hw[s] + f[s]);
         if constexpr (SRC != 1) { if (M.n_soft > 0) j += soft_penalty(); }      // (the fused mat-vec form is never taken with cost_direct: fused_ok)
-        cost = wave_sum(j) + c0;
+        cost = wave_sum_cost(j) + c0;
     }
 #pragma unroll
     for (int s = 0; s < NZS; ++s) {
@@ -617,7 +730,7 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
     if (outs) {
         if (lane == 0) {
             outs[0] = cost; outs[1] = solver_status == 1 ? 0 : (solver_status == -2 ? 1 : 2); outs[2] = solver_status;
-            outs[3] = solver_status == -3 ? 0 : 1; outs[4] = 0; outs[5] = rounds_total; outs[6] = infeasible ? 0 : na_last; outs[7] = 2.0;
+            outs[3] = solver_status == -3 ? 0 : 1; outs[4] = cost_pending ? 1.0 : 0.0; outs[5] = rounds_total; outs[6] = infeasible ? 0 : na_last; outs[7] = 2.0;
         }
     } else if (lane == 0) {
         if (Bt.cost && !cost_pending) glw(Bt.cost)[b] = cost;
@@ -1195,7 +1308,9 @@ __global__ __launch_bounds__(kPersistWaves * 64) void lmpc_solve_persistent(cons
 // one workgroup deep.  A workgroup moves on when its slowest instance is done, so long batches use the two-kernel path instead.
 // Round 5: the two-chunk variant too (CPZ = CPG = 2: up to 256 condensed variables -- config 4's N = 50).  Its slices are 10.9 KB, so a workgroup
 // holds EIGHT instances on eight wavefronts (eight of the sixteen MFMA columns carry an instance, the others repeat the last one and store
-// nothing); such a controller's cost comes from its definition, one product with H per instance inside solve_fast (SRC = 2 is a fused form).
+// nothing); such a controller's cost comes from its definition: behind the solves, H times the workgroup's solutions on the matrix pipe, by the arithmetic of
+// lmpc_cost_mfma step for step, so that the cost is the two-kernel form's bit for bit (round 11; it was one product with H per instance inside solve_fast, whose
+// summation agreed with the other form's to 6e-12 only).
 // The kernel arguments are a kilobyte here (the model struct by value) and the compiler fetches each field where it is first used: a dozen scalar
 // loads on different cache lines, each a miss, one after the other.  Touch every 64-byte line of the segment at once instead (one dword each, all
 // requested before the one wait), after which the compiler's own loads hit the scalar cache.
@@ -1397,8 +1512,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
         for (int t = wave + kGroupWaves; t < ntile1; t += kGroupWaves) tile1.template operator()<false>(t);
         if (badl && jlive) atomicOr(&bad[j], 1u);
         // this wavefront's share of the cost constant of instance j (no atomics: the sum must not depend on arrival order)
-        c0p += __shfl_xor(c0p, 16, 64);
-        c0p += __shfl_xor(c0p, 32, 64);
+        c0p = wave_sum_rows(c0p);
         if (kq == 0) c0s[wave * 16 + j] = c0p;
         __syncthreads();
         gstamp(5);
@@ -1439,6 +1553,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
             }
             eqb[lane] = bits;
         }
+        // (round 11 moved this section to the last wavefront, which has no tile of the second product at the benchmark's sizes: no gain, not kept)
         if (threadIdx.x < kGroupWaves) {
             double *tl = slices + (size_t)threadIdx.x * M.fast_slice + 2 * ZP + 3 * GPD;
             double c0 = 0.0;
@@ -1474,7 +1589,9 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
                 const double2 l = *reinterpret_cast<const double2 *>(lgm + r), u = *reinterpret_cast<const double2 *>(ugm + r), t = *reinterpret_cast<const double2 *>(gt0m + r);
                 sv += over(t.x, l.x, u.x) + over(t.y, l.y, u.y);
             }
-            sv = wave_sum(sv);
+            // (the key's bits reach no result: a changed key can only change which wavefront solves which instance, never what the solve of an instance
+            // computes -- so the cheapest deterministic sum serves, not wave_sum's tree)
+            sv = wave_sum_any(sv);
             double *keys = reinterpret_cast<double *>(bad);      // (the flags were read before the barrier above; sixteen doubles are theirs)
             if (lane == 0) keys[wave] = sv;
             __syncthreads();
@@ -1489,8 +1606,7 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
                 const double kj = keys[jj];
                 rank += (kj > ki || (kj == ki && jj < me)) ? 1 : 0;
             }
-            rank += __shfl_xor(rank, 16, 64);
-            rank += __shfl_xor(rank, 32, 64);
+            rank = wave_sum_rows(rank);
             const int q = rank >> 2, sd = (q & 1) ? 3 - (rank & 3) : (rank & 3);
             inst = (int)__builtin_ctzll(__ballot(lane < kGroupWaves && 4 * q + sd == wave));      // (a permutation: exactly one lane answers)
         }
@@ -1503,6 +1619,66 @@ __global__ __launch_bounds__(kGroupWavesOf<CPZ> * 64) void lmpc_solve_group(cons
 #endif
         if (b < Bt.batch) solve_fast<CPZ, CPG, 2>(M, Bt, b, lane, slice_i, lwuw, glw(wsbase) + (size_t)b * M.wsld, nullptr, outs + inst * outld, eqbits);
         __syncthreads();
+        if constexpr (CPZ == 2) {
+            // The two-chunk controller's cost comes from its definition.  The solves left the constant in their result records and marked them; the products
+            // with H are taken here for the workgroup's instances together, on the matrix pipe, by the arithmetic of lmpc_cost_mfma (lmpc_kernels.hip) step for
+            // step -- its four wavefronts' shares of the row tiles, its order within a share, its two-level sum over a column's four lanes, its pairing of the
+            // four shares -- so that the group form and the two-kernel form return the same bits (tests/test_lmpc_group_head_gpu.py).  A column is an instance
+            // and no product mixes columns: what another column holds (an open instance's linear term, an infeasible one's NaNs) reaches nobody's cost.
+            // Operands: the solution from the instance's slice (fast_finish put it in f's place, zero from nz on), f from the first product's staging block Bf,
+            // which nothing has written since (lane (j, kq) of k-step 4 t + r holds f[16 t + 4 r + kq] of instance j: the layout this sum walks).
+            if (M.cost_direct && Bt.n_models <= 0) {
+                double *cs = c0s;                    // [4 shares][16 instances]: the head's partials were read in front of its last barrier
+                if (wave < 4) {
+                    const int ntile = M.nz16 >> 4;
+                    const gdp H = GP(H), Hp = GP(Hp);
+                    constexpr int kCostGB = 4;
+                    double part = 0.0;
+                    for (int tl = wave; tl < ntile; tl += 4) {
+                        v4d acc = {0.0, 0.0, 0.0, 0.0};
+                        auto wop = [&](const int kb) { const int k = 4 * kb + kq; return k < M.nz ? fj[k] : 0.0; };
+                        if (Hp) {
+                            for (int g0 = 0; g0 < G2; g0 += kCostGB) {
+                                v4d a[kCostGB];
+#pragma unroll
+                                for (int g = 0; g < kCostGB; ++g) if (g0 + g < G2) a[g] = ld4(Hp + (((size_t)tl * G2 + g0 + g) * 64 + lane) * 4);
+#pragma unroll
+                                for (int g = 0; g < kCostGB; ++g)
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e) {
+                                        const int kb = 4 * (g0 + g) + e;
+                                        if (kb < nz4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[g][e], wop(kb), acc, 0, 0, 0);
+                                    }
+                            }
+                        } else {
+                            const int rowa = 16 * tl + j;
+                            const gdp Ht = H + (rowa < ldz ? rowa : 0);
+                            for (int kb = 0; kb < nz4; ++kb) {
+                                const int col = 4 * kb + kq;
+                                const double a = (col < M.nz && rowa < ldz) ? Ht[(size_t)col * ldz] : 0.0;
+                                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, wop(kb), acc, 0, 0, 0);
+                            }
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = 16 * tl + 4 * r + kq;
+                            const double w = wop(4 * tl + r);
+                            const double fr = row < M.nz ? Bf[(4 * tl + r) * 64 + lane] : 0.0;
+                            part = fma(w, 0.5 * acc[r] + fr, part);
+                        }
+                    }
+                    part = wave_sum_rows(part);
+                    if (kq == 0) cs[wave * 16 + j] = part;      // one slot per share, added up in a fixed order
+                }
+                __syncthreads();
+                if (threadIdx.x < kGroupWaves) {
+                    double *o = outs + threadIdx.x * outld;
+                    const int t = threadIdx.x;
+                    if (o[7] == 2.0 && o[4] == 1.0) o[0] = ((cs[t] + cs[16 + t]) + (cs[32 + t] + cs[48 + t])) + o[0];
+                }
+                __syncthreads();
+            }
+        }
         // the sixteen instances' results, written by neighbouring lanes: one transaction per array and workgroup instead of sixteen
         {
             const int t = threadIdx.x;
@@ -1612,6 +1788,27 @@ size_t lmpc_group_lds_bytes(const LmpcDev &m)
     if (cp != 1 && cp != 2) return 0;
     const int nw = cp == 1 ? 16 : 8;
     return ((size_t)2 * 128 * cp + (size_t)nw * m.fast_slice + (size_t)(m.kin / 4 + m.nz16 / 4) * 64 + (size_t)nw * 16 + 16 + (size_t)nw * (8 + ((m.nu + 1) & ~1)) + 32) * sizeof(double);
+}
+
+namespace {
+// testing aid: one wavefront per vector of 64 values; all 64 lanes of the butterfly's sum, of wave_sum_full's, and of the two forms of the two-level sum
+__global__ __launch_bounds__(64) void lmpc_wave_reduce_probe(const double *in, double *out)
+{
+    const int lane = threadIdx.x;
+    const double x = in[(size_t)blockIdx.x * 64 + lane];
+    double *o = out + (size_t)blockIdx.x * 256;
+    o[lane] = wave_sum(x);
+    o[64 + lane] = wave_sum_full(x);
+    o[128 + lane] = wave_sum_rows_shfl(x);
+    o[192 + lane] = wave_sum_rows_swap(x);
+}
+}  // namespace
+
+int lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream)
+{
+    if (nvec <= 0) return 0;
+    hipLaunchKernelGGL(lmpc_wave_reduce_probe, dim3(nvec), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), in, out);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev &b, double *ws, void *stream, LmpcForm form)

@@ -2303,6 +2303,14 @@ int mpcx_lmpc_debug_set_cycle_buffer(mpcx_lmpc_t h, void *dev_ptr)
     return MPCX_OK;
 }
 
+/* testing aid: the wave-wide sums of the lean LMPC kernels on nvec vectors of 64 doubles, every lane of the old and of the new form
+ * (include/mpcx.h) */
+int mpcx_lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream)
+{
+    if (!in || !out || nvec < 0) return fail(MPCX_E_INVALID, "mpcx_lmpc_debug_wave_reduce: null buffer or negative count");
+    return mpcx::lmpc_debug_wave_reduce(in, out, nvec, stream) == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, "mpcx_lmpc_debug_wave_reduce: launch failed");
+}
+
 /* ---- testing aid (not part of the reference-facing surface): copy a condensed array to
  * the host so that CPU-only tests can check the set-up without a GPU. ------------------ */
 int mpcx_lmpc_debug_get(mpcx_lmpc_t h, const char *name, double *out, int cap)

@@ -11,8 +11,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
         name = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
     except OSError:
         pass
-    name = re.sub(r"\(.*$", "", name)
     name = name.replace("mpcx::engine::", "").replace("mpcx::models::", "").replace("mpcx::(anonymous namespace)::", "").replace("mpcx::", "")
+    name = re.sub(r"\(.*$", "", name)      # (after the namespaces are gone: "(anonymous namespace)" has a parenthesis of its own)
     name = re.sub(r"Oscillators<(\d+)>", r"Oscillators<\1>", name)
 
     def g(key):
