@@ -15,16 +15,12 @@
 //
 // One wavefront per instance, the whole kernel without a workgroup barrier.  Every matrix differs from instance to instance: there is no shared
 // operand for the matrix pipe.  The seeds of an instance (nu unit seeds in Jacobian mode) are served one after another on one factor of S.
-// lmpc_sens.hip's working-set decode and Cholesky are restated here; that file is untouched.
-#include "lmpc_kernel_common.hpp"
+// The working-set decode, the factor of S, the solve on it and the seed scatter are lmpc_sens_common.hpp's, shared with the other sensitivity kernels.
+#include "lmpc_sens_common.hpp"
 
 namespace mpcx {
 
 namespace {
-
-// a pivot below this fraction of the row's own diagonal entry of S: the working set is dependent (flag 2)
-constexpr double kBankPivotTol = 1e-11;
-constexpr int kBankState = 0, kBankOutput = 1, kBankScalar = 2, kBankRate = 3, kBankLinear = 4;      // GKind of lmpc_model.hpp
 
 struct LmpcBankSensDev {
     LmpcBankSensArgs a;
@@ -41,78 +37,6 @@ __host__ __device__ inline size_t bank_wave_len(int cap, int nx, int nu, int ny,
 {
     return (size_t)cap * (cap + 1) / 2 + 2 * (size_t)cap + 2 * (size_t)cap + (size_t)(ph + 2) / 2 + (size_t)nx * (nx + nu) + (size_t)ny * nx +
            2 * (size_t)bank_even(nz) + (size_t)(ph + 2) * nx + (size_t)ph * ny + (size_t)(ph + 1) * nx + nu;
-}
-
-// ---- the phases, one wavefront each; the parameter and model gradients of a bank need the first three as they are -------------------------------
-
-// the working set of instance b from its active bits by ballot compaction: a variable is in A when any of its reference rows has a bit, a general
-// row when bit g_refrow[r] is set.  Returns the number of rows; only the first `cap` are stored
-__device__ inline int bank_working_set(const LmpcDev &M, const uint32_t MPCX_GAS *wl, const uint32_t MPCX_GAS *wu, int aw, int nz, int mg, int ldz,
-                                       int cap, int lane, int *idx)
-{
-    auto bit = [&](int rr) -> bool { return rr >= 0 && (rr >> 5) < aw && (((wl[rr >> 5] | wu[rr >> 5]) >> (rr & 31)) & 1u) != 0u; };
-    int n = 0;
-    for (int base = 0; base < nz + mg; base += 64) {
-        const int e = base + lane;
-        bool in = false;
-        if (e < nz) { for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) in = in || bit(GP(boxrow_ref)[p]); }
-        else if (e < nz + mg) in = bit(GP(g_refrow)[e - nz]);
-        const unsigned long long mask = __ballot(in);
-        const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
-        if (in && pos < cap) idx[pos] = e < nz ? e : ldz + (e - nz);
-        n += __popcll(mask);
-    }
-    return n;
-}
-
-// S = Y[A, A] gathered as a packed lower triangle and factored in place by a left-looking Cholesky, a row per lane.  false: a pivot at or below
-// kBankPivotTol of the row's own diagonal entry
-__device__ inline bool bank_factor(gdp Y, int ldy, const int *idx, int n, int lane, double *S, double *dg)
-{
-    for (int t = lane; t < n * n; t += 64) {              // (the square is walked and its lower triangle kept: independent loads, all in flight)
-        const int i = t / n, j = t - i * n;
-        if (j > i) continue;
-        const double v = Y[(size_t)idx[j] * ldy + idx[i]];
-        if (j == i) dg[i] = v;
-        S[(size_t)i * (i + 1) / 2 + j] = v;
-    }
-    wave_sync();
-    for (int k = 0; k < n; ++k) {
-        const double *Lk = S + (size_t)k * (k + 1) / 2;
-        for (int i = k + lane; i < n; i += 64) {
-            double *Li = S + (size_t)i * (i + 1) / 2;
-            double s = Li[k];
-#pragma unroll 4
-            for (int j = 0; j < k; ++j) s = fma(-Li[j], Lk[j], s);
-            Li[k] = s;
-        }
-        wave_sync();
-        const double d = Lk[k];
-        if (!(d > kBankPivotTol * dg[k])) return false;
-        const double sd = sqrt(d), rd = 1.0 / sd;
-        wave_sync();
-        for (int i = k + lane; i < n; i += 64) { double *Li = S + (size_t)i * (i + 1) / 2; Li[k] = i == k ? sd : Li[k] * rd; }
-        wave_sync();
-    }
-    return true;
-}
-
-// L L' x = v on the factor in S, in place
-__device__ inline void bank_chol_solve(const double *S, double *V, int n, int lane)
-{
-    for (int k = 0; k < n; ++k) {
-        if (lane == 0) V[k] /= S[(size_t)k * (k + 1) / 2 + k];
-        wave_sync();
-        for (int i = k + 1 + lane; i < n; i += 64) V[i] = fma(-S[(size_t)i * (i + 1) / 2 + k], V[k], V[i]);
-        wave_sync();
-    }
-    for (int k = n - 1; k >= 0; --k) {
-        const double *Lk = S + (size_t)k * (k + 1) / 2;
-        if (lane == 0) V[k] /= Lk[k];
-        wave_sync();
-        for (int i = lane; i < k; i += 64) V[i] = fma(-Lk[i], V[k], V[i]);
-        wave_sync();
-    }
 }
 
 // the direction's roll-out through the instance's own model (As, Bs, Cs column-major and blk in LDS): dx [(ph + 1) x nx] by the chain of ph steps,
@@ -174,7 +98,7 @@ __global__ __launch_bounds__(256) void lmpc_bank_sensitivity(const LmpcBankSensD
     int flag = (!known || (Ar.status && gl(Ar.status)[b] != 0)) ? 1 : 0;
     int n = 0;
     if (!flag) {
-        n = bank_working_set(M, gl(Ar.active_lower) + (size_t)b * aw, gl(Ar.active_upper) + (size_t)b * aw, aw, nz, mg, ldz, cap, lane, idx);
+        n = sens_working_set(M, gl(Ar.active_lower) + (size_t)b * aw, gl(Ar.active_upper) + (size_t)b * aw, aw, nz, mg, ldz, cap, lane, idx, nullptr);
         if (n > cap) flag = 3;
     }
     wave_sync();
@@ -188,7 +112,7 @@ __global__ __launch_bounds__(256) void lmpc_bank_sensitivity(const LmpcBankSensD
             rkind[k] = rr >= 0 ? GP(g_kind)[rr] : -1; rstep[k] = rr >= 0 ? GP(g_step)[rr] : 0; rcomp[k] = rr >= 0 ? GP(g_comp)[rr] : 0;
         }
         wave_sync();
-        if (n > 0 && !bank_factor(Y, ldy, idx, n, lane, S, dg)) flag = 2;
+        if (n > 0 && !sens_factor(Y, ldy, idx, n, lane, S, dg)) flag = 2;
     }
     wave_sync();
 
@@ -203,33 +127,16 @@ __global__ __launch_bounds__(256) void lmpc_bank_sensitivity(const LmpcBankSensD
         // ---- the cotangent on w: a unit vector on the first move (then Y p is a column of Y), or the seeds scattered through blk
         const int col = blk[1] * nu + r;
         if (!jac) {
-            for (int t = lane; t < nzp; t += 64) {
-                double v = 0.0;
-                if (t < nz) {
-                    const int bq = t / nu, jq = t - bq * nu;
-                    if (Ar.seed_cmd && bq == blk[1]) v = gl(Ar.seed_cmd)[(size_t)b * nu + jq];
-                    if (Ar.seed_input)              // row i of the sequence is v_{min(i + 1, ph)} (OptSequence)
-                        for (int i = 0; i <= ph; ++i)
-                            if (blk[i + 1 <= ph ? i + 1 : ph] == bq) v += gl(Ar.seed_input)[((size_t)b * (ph + 1) + i) * nu + jq];
-                }
-                pv[t] = v;
-            }
+            for (int t = lane; t < nzp; t += 64) pv[t] = t < nz ? sens_seed(Ar.seed_cmd, Ar.seed_input, blk, nu, ph, b, t) : 0.0;
             wave_sync();
         }
         // ---- mu = S^-1 Y[A, 0:nz] p, a row per lane (Y is symmetric: row idx[i] of a column)
         for (int i = lane; i < n; i += 64) {
             const int qi = idx[i];
-            double s = 0.0;
-            if (jac) s = Y[(size_t)col * ldy + qi];
-            else
-                for (int q = 0; q < nz; ++q) {
-                    const double p = pv[q];
-                    if (p != 0.0) s = fma(Y[(size_t)q * ldy + qi], p, s);
-                }
-            V[i] = s;
+            V[i] = jac ? Y[(size_t)col * ldy + qi] : sens_rhs(Y, ldy, nz, qi, [&](int q) { return pv[q]; });
         }
         wave_sync();
-        bank_chol_solve(S, V, n, lane);
+        sens_chol_solve(S, V, n, lane);
         // ---- q = Y[0:nz, 0:nz] p - Y[0:nz, A] mu: a lane owns element pairs of the contiguous columns, one 16-byte load each (ldy is even)
         for (int e = 2 * lane; e < nz; e += 128) {
             double s0 = 0.0, s1 = 0.0;
@@ -271,17 +178,17 @@ __global__ __launch_bounds__(256) void lmpc_bank_sensitivity(const LmpcBankSensD
             const int kind = rkind[k], st = rstep[k], cpn = rcomp[k];
             if (kind < 0) continue;
             const double mu = V[k];
-            if (kind == kBankOutput) {
+            if (kind == G_OUTPUT) {
                 if (st >= 1) { if (lane == (cpn & 63)) dov[(st - 1) * ny + cpn] += mu; }
                 else for (int c = lane; c < nx; c += 64) gam[c] = fma(mu, Cs[cpn + (size_t)c * ny], gam[c]);
-            } else if (kind == kBankState) {
+            } else if (kind == G_STATE) {
                 if (lane == (cpn & 63)) gam[(size_t)st * nx + cpn] += mu;
-            } else if (kind == kBankScalar || kind == kBankLinear) {
-                const gdp Fx = kind == kBankScalar ? GP(sX) : gl(MPCX_LINEAR_F(M)) + (size_t)cpn * (nx + nu);
-                const gdp Fu = kind == kBankScalar ? GP(sU) : Fx + nx;
+            } else if (kind == G_SCALAR || kind == G_LINEAR) {
+                const gdp Fx = kind == G_SCALAR ? GP(sX) : gl(MPCX_LINEAR_F(M)) + (size_t)cpn * (nx + nu);
+                const gdp Fu = kind == G_SCALAR ? GP(sU) : Fx + nx;
                 for (int c = lane; c < nx; c += 64) gam[(size_t)st * nx + c] = fma(mu, Fx[c], gam[(size_t)st * nx + c]);
                 if (st == 0) for (int j = lane; j < nu; j += 64) du[j] = fma(-mu, Fu[j], du[j]);
-            } else if (kind == kBankRate && st == 1) {
+            } else if (kind == G_RATE && st == 1) {
                 if (lane == (cpn & 63)) du[cpn] += mu;
             }
         }
@@ -327,21 +234,13 @@ int lmpc_bank_sens_launch(const LmpcDev &m, const LmpcBankSensArgs &a, void *str
     s.nx = m.nx; s.nu = m.nu; s.ny = m.ny; s.ph = m.ph; s.nz = m.nz; s.mg = m.mg; s.ldz = m.ldz; s.ldy = m.ldy; s.aw = m.active_words;
     s.term = MPCX_HAS_TERMINAL(m) ? 1 : 0;
     s.R = a.s.jacobian ? m.nu : 1;
-    // every wavefront's slice holds the largest working set there can be (ws_limit) where four, two or one of them fit in a CU's LDS; otherwise one
-    // wavefront with the largest slice that fits, and larger sets get flag 3
-    const size_t limit = lmpc_lds_limit() / sizeof(double);
-    auto len = [&](int cap) { return bank_wave_len(cap, m.nx, m.nu, m.ny, m.ph, m.nz); };
-    const int want = ws_limit(m.nz, m.mg, m.n_soft) > 1 ? ws_limit(m.nz, m.mg, m.n_soft) : 1;
-    int waves = 4;
-    while (waves > 1 && waves * len(want) > limit) waves >>= 1;
-    s.cap = want;
-    while (s.cap > 0 && waves * len(s.cap) > limit) --s.cap;
-    if (s.cap <= 0) return -2;
-    const size_t bytes = waves * len(s.cap) * sizeof(double);
+    const SensLdsPlan plan = sens_lds_plan(m, 4, [&](int waves, int cap) { return waves * bank_wave_len(cap, m.nx, m.nu, m.ny, m.ph, m.nz); });
+    if (plan.cap <= 0) return -2;
+    s.cap = plan.cap;
     static LmpcLdsCache configured;
-    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_bank_sensitivity)}, bytes) != 0) return -3;
-    const int blocks = (a.s.batch + waves - 1) / waves;
-    hipLaunchKernelGGL(lmpc_bank_sensitivity, dim3(blocks), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream), s);
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_bank_sensitivity)}, plan.bytes) != 0) return -3;
+    const int blocks = (a.s.batch + plan.waves - 1) / plan.waves;
+    hipLaunchKernelGGL(lmpc_bank_sensitivity, dim3(blocks), dim3(64 * plan.waves), plan.bytes, static_cast<hipStream_t>(stream), s);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

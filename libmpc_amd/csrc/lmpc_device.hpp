@@ -26,6 +26,11 @@ __host__ __device__ inline int ws_limit(int nz, int mg, int n_soft) { return nz 
 // kMaxActive rows goes to a device buffer of one limit x limit slot per wavefront.  Without soft rows: nz, as it has always been
 __host__ __device__ inline int ws_capacity(int limit) { return limit > kMaxActive ? limit : kMaxActive; }
 
+// what a general row bounds (g_kind, f_kind; step and comp say where along the predicted trajectory)
+// G_RATE: a bound on the input increment delta_i = v_{i+1} - v_i (the reference's delta-u rows, ProblemBuilder.hpp:768-793); step = i + 1
+// G_LINEAR: row comp of the linear rows lo <= Fx x_i + Fu v_i <= hi (no counterpart in the reference), the scalar row's convention
+enum GKind : int { G_STATE = 0, G_OUTPUT = 1, G_SCALAR = 2, G_RATE = 3, G_LINEAR = 4 };
+
 struct LmpcDev {
     int nx, nu, ndu, ny, ph, ch, nf, nz, mg;
     int ldz, ldg, ldy;

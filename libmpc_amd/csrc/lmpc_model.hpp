@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mpcx.h"
+#include "lmpc_device.hpp"
 
 namespace mpcx {
 
@@ -40,12 +41,8 @@ double cholesky_lower(Mat &A);
 // inverse of SPD matrix from its Cholesky factor
 Mat spd_inverse_from_chol(const Mat &L);
 
-// G_RATE: a bound on the input increment delta_i = v_{i+1} - v_i (the reference's delta-u rows, ProblemBuilder.hpp:768-793); step = i + 1
-// G_LINEAR: row comp of the linear rows lo <= Fx x_i + Fu v_i <= hi (no counterpart in the reference), the scalar row's convention
-enum GKind : int { G_STATE = 0, G_OUTPUT = 1, G_SCALAR = 2, G_RATE = 3, G_LINEAR = 4 };
-
 struct GeneralRow {
-    int kind, step, comp;   // which functional of the predicted trajectory
+    int kind, step, comp;   // which functional of the predicted trajectory (GKind, lmpc_device.hpp)
     int refrow;             // row in the reference QP's inequality block numbering + neq offset applied later
     double lo, hi;          // bounds before the per-instance free-response offset
     double soft = 0.0;      // 1 / weight of a soft row, 0: hard

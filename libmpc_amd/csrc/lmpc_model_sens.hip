@@ -17,21 +17,17 @@
 // The plan is lmpc_param_sensitivity's: a workgroup takes sixteen instances; one wavefront per instance decodes the working set, factors S in LDS
 // and leaves (rows, mu, lambda) in the instance's record and q as a column of an MFMA B operand; Xq Q goes through the f64 matrix pipe; then one
 // wavefront per instance forms the stage gradients and the two costates, and the workgroup sums the outer products, an output entry per thread.
-// reduce: the instances are added in instance order into the workgroup's row of a partials buffer, lmpc_model_reduce adds the rows in workgroup
+// reduce: the instances are added in instance order into the workgroup's row of a partials buffer, lmpc_sens_reduce adds the rows in workgroup
 // order -- no floating-point atomics, the same bits on every launch.
-// (The working set, the factor and q restate lmpc_param_sensitivity's: that kernel's code is left as it was.)
-#include "lmpc_kernel_common.hpp"
-
-#include <vector>
+// The working set, the factor, the solve on it, q, the tile product and the reduce kernel are lmpc_sens_common.hpp's, shared with the other
+// sensitivity kernels.
+#include "lmpc_sens_common.hpp"
 
 namespace mpcx {
 
 namespace {
 
-// a pivot below this fraction of the row's own diagonal entry of S: the working set is dependent (flag 2)
-constexpr double kModelPivotTol = 1e-11;
 constexpr int kModelIpg = 16;      // instances of a workgroup: one MFMA column tile
-constexpr int kKindState = 0, kKindOutput = 1, kKindScalar = 2, kKindLinear = 4;      // GKind of lmpc_model.hpp (rate rows carry no state coefficient)
 
 struct LmpcModelDev {
     int batch, reduce;
@@ -91,7 +87,9 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
     auto slice_of = [&](int w) -> double * { return slices + (size_t)w * model_wave_len(cap, nz, nx, ny, ph); };
     auto pi_of = [&](int w) -> double * { return slice_of(w) + (size_t)cap * (cap + 1) / 2 + cap + (size_t)(cap + 1) / 2 + nz + 3 * (size_t)nx + ny; };
     double *S = slice_of(wave), *dg = S + (size_t)cap * (cap + 1) / 2;
-    int *sdv = reinterpret_cast<int *>(dg + cap);                 // 1: the row's upper bound is the working one
+    // the working rows' slots 2 row + (upper ? 1 : 0) as sens_working_set leaves them; bit 0 is read on general rows only, which have one reference
+    // row each: there it says that the row's upper bound is the working one
+    int *sdv = reinterpret_cast<int *>(dg + cap);
     double *grad = dg + cap + (size_t)(cap + 1) / 2, *c0 = grad + nz, *c1 = c0 + nx, *xt = c1 + nx, *ey = xt + nx;
     double *pi = ey + ny, *eta = pi + (size_t)ph * nx, *ov = eta + (size_t)ph * nx, *dov = ov + (size_t)ph * ny;
     const gdp Y = GP(Y);
@@ -101,8 +99,6 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
     const gdp tP = gl(MPCX_TERMINAL(M)), tXT = tP + nA, tTx = tXT + nx;
     const gdp Flin = gl(MPCX_LINEAR_F(M));
     const double qnan = __builtin_nan("");
-    auto ld4 = [](gdp p) -> v4d { return *reinterpret_cast<const v4d MPCX_GAS *>(p); };
-    auto opnd = [&](double *P, int c, int q) -> double & { return P[(size_t)(q >> 2) * 64 + 16 * (q & 3) + c]; };
     const gdp yr = gl(Pd.yref), ur = gl(Pd.uref), dr = gl(Pd.duref), dm = gl(Pd.dmeas);
     const gdp sqx = gl(Pd.seq_state), sqy = gl(Pd.seq_output), sqv = gl(Pd.seq_input), u0p = gl(Pd.u0);
     // v_i of instance b: v_0 = lastU, v_i = row i - 1 of the sequence
@@ -110,22 +106,6 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
     // the rate term of the increment delta_i = v_{i+1} - v_i, i = 0 .. ph - 1
     auto rate = [&](int b, int i, int j) -> double {
         return Wdu[j + (size_t)i * nu] * (vin(b, i + 1, j) - vin(b, i, j) - ref_at(dr, Pd.duref_bs, Pd.duref_ks, b, i > 0 ? i - 1 : 0, j));
-    };
-    // L L' x = v on the factor in S, in place
-    auto chol_solve = [&](double *V, int n) {
-        for (int k = 0; k < n; ++k) {
-            if (lane == 0) V[k] /= S[(size_t)k * (k + 1) / 2 + k];
-            wave_sync();
-            for (int i = k + 1 + lane; i < n; i += 64) V[i] = fma(-S[(size_t)i * (i + 1) / 2 + k], V[k], V[i]);
-            wave_sync();
-        }
-        for (int k = n - 1; k >= 0; --k) {
-            const double *Lk = S + (size_t)k * (k + 1) / 2;
-            if (lane == 0) V[k] /= Lk[k];
-            wave_sync();
-            for (int i = lane; i < k; i += 64) V[i] = fma(-Lk[i], V[k], V[i]);
-            wave_sync();
-        }
     };
 
     for (int t = tid; t < nA + nB + nC; t += blockDim.x) As[t] = t < nA ? GP(A)[t] : (t < nA + nB ? GP(B)[t - nA] : GP(C)[t - nA - nB]);
@@ -140,13 +120,7 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
         for (int t = tid; t < kModelIpg * nz; t += blockDim.x) {
             const int il = t / nz, q = t - il * nz, b = b0 + il;
             if (b >= Pd.batch) continue;
-            const int bq = q / nu, jq = q - bq * nu;
-            double v = 0.0;
-            if (Pd.seed_cmd && bq == blk[1]) v = gl(Pd.seed_cmd)[(size_t)b * nu + jq];
-            if (Pd.seed_input)              // row i of the sequence is v_{min(i + 1, ph)} (OptSequence)
-                for (int i = 0; i <= ph; ++i)
-                    if (blk[i + 1 <= ph ? i + 1 : ph] == bq) v += gl(Pd.seed_input)[((size_t)b * n1 + i) * nu + jq];
-            opnd(Bp, il, q) = v;
+            sens_opnd(Bp, il, q) = sens_seed(Pd.seed_cmd, Pd.seed_input, blk, nu, ph, b, q);
         }
         __syncthreads();
 
@@ -157,82 +131,24 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
             double *V = mu_of(il), *R = V + cap;
             int *idx = idx_of(il);
             int flag = 0, n = 0;
+            auto cot = [&](int q) { return sens_opnd(Bp, il, q); };      // the instance's cotangent
             if (valid) {
                 flag = (Pd.status && gl(Pd.status)[b] != 0) ? 1 : 0;
                 if (!flag) {
-                    const uint32_t MPCX_GAS *wl = gl(Pd.al) + (size_t)b * aw, *wu = gl(Pd.au) + (size_t)b * aw;
-                    // 0: no bit, 1: the lower bound's, 2: the upper bound's
-                    auto side = [&](int rr) -> int {
-                        if (rr < 0 || (rr >> 5) >= aw) return 0;
-                        if ((wu[rr >> 5] >> (rr & 31)) & 1u) return 2;
-                        return (int)((wl[rr >> 5] >> (rr & 31)) & 1u);
-                    };
-                    for (int base = 0; base < nz + mg; base += 64) {
-                        const int e = base + lane;
-                        int sd = 0;
-                        if (e < nz) {
-                            for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) sd |= side(GP(boxrow_ref)[p]);
-                        } else if (e < nz + mg) sd = side(GP(g_refrow)[e - nz]);
-                        const bool in = sd != 0;
-                        const unsigned long long mask = __ballot(in);
-                        const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
-                        if (in && pos < cap) { idx[pos] = e < nz ? e : ldz + (e - nz); sdv[pos] = sd >> 1; }
-                        n += __popcll(mask);
-                    }
+                    n = sens_working_set(M, gl(Pd.al) + (size_t)b * aw, gl(Pd.au) + (size_t)b * aw, aw, nz, mg, ldz, cap, lane, idx, sdv);
                     if (n > cap) flag = 3;
                 }
             }
             wave_sync();
             if (valid && !flag && n > 0) {
-                for (int i = 0; i < n; ++i) {
-                    const int qi = idx[i];
-                    for (int j = lane; j <= i; j += 64) {
-                        double v = Y[(size_t)idx[j] * ldy + qi];
-                        if (j == i) dg[i] = v;
-                        S[(size_t)i * (i + 1) / 2 + j] = v;
-                    }
-                }
                 // right-hand side Y[A, 0:nz] p, a row per lane
-                for (int i = lane; i < n; i += 64) {
-                    const int qi = idx[i];
-                    double s = 0.0;
-                    for (int q = 0; q < nz; ++q) {
-                        const double pv = opnd(Bp, il, q);
-                        if (pv != 0.0) s = fma(Y[(size_t)q * ldy + qi], pv, s);
-                    }
-                    V[i] = s;
-                }
-                wave_sync();
-                // left-looking Cholesky, a row per lane
-                for (int k = 0; k < n && !flag; ++k) {
-                    const double *Lk = S + (size_t)k * (k + 1) / 2;
-                    for (int i = k + lane; i < n; i += 64) {
-                        double *Li = S + (size_t)i * (i + 1) / 2;
-                        double s = Li[k];
-                        for (int j = 0; j < k; ++j) s = fma(-Li[j], Lk[j], s);
-                        Li[k] = s;
-                    }
-                    wave_sync();
-                    const double d = Lk[k];
-                    if (!(d > kModelPivotTol * dg[k])) { flag = 2; break; }
-                    const double sd = sqrt(d), rd = 1.0 / sd;
-                    wave_sync();
-                    for (int i = k + lane; i < n; i += 64) { double *Li = S + (size_t)i * (i + 1) / 2; Li[k] = i == k ? sd : Li[k] * rd; }
-                    wave_sync();
-                }
-                if (!flag) chol_solve(V, n);
+                for (int i = lane; i < n; i += 64) V[i] = sens_rhs(Y, ldy, nz, idx[i], cot);
+                if (!sens_factor(Y, ldy, idx, n, lane, S, dg)) flag = 2;
+                else sens_chol_solve(S, V, n, lane);
             }
             if (valid && !flag) {
                 // q = Y[0:nz, 0:nz] p - Y[0:nz, A] mu, an element per lane (Y is symmetric: column t read along its rows)
-                for (int t = lane; t < nz; t += 64) {
-                    double s = 0.0;
-                    for (int q = 0; q < nz; ++q) {
-                        const double pv = opnd(Bp, il, q);
-                        if (pv != 0.0) s = fma(Y[(size_t)q * ldy + t], pv, s);
-                    }
-                    for (int i = 0; i < n; ++i) s = fma(-Y[(size_t)idx[i] * ldy + t], V[i], s);
-                    opnd(Qp, il, t) = s;
-                }
+                for (int t = lane; t < nz; t += 64) sens_opnd(Qp, il, t) = sens_direction(Y, ldy, nz, t, cot, idx, V, n);
             }
             if (valid && !flag && n > 0) {
                 // the cost's condensed gradient at the optimum: one backward pass over the solve's own sequences
@@ -279,22 +195,22 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
                         const int kind = GP(g_kind)[rr], st = GP(g_step)[rr], cpn = GP(g_comp)[rr];
                         const gdp xs = sqx + ((size_t)b * n1 + st) * nx;
                         double v = 0.0;
-                        if (kind == kKindState) v = xs[cpn];
-                        else if (kind == kKindOutput) v = sqy[((size_t)b * n1 + st) * ny + cpn];
-                        else if (kind == kKindScalar) {
+                        if (kind == G_STATE) v = xs[cpn];
+                        else if (kind == G_OUTPUT) v = sqy[((size_t)b * n1 + st) * ny + cpn];
+                        else if (kind == G_SCALAR) {
                             for (int c = 0; c < nx; ++c) v = fma(sX[c], xs[c], v);
                             for (int j = 0; j < nu; ++j) v = fma(sU[j], vin(b, st, j), v);
-                        } else if (kind == kKindLinear) {
+                        } else if (kind == G_LINEAR) {
                             const gdp F = Flin + (size_t)cpn * (nx + nu);
                             for (int c = 0; c < nx; ++c) v = fma(F[c], xs[c], v);
                             for (int j = 0; j < nu; ++j) v = fma(F[nx + j], vin(b, st, j), v);
                         } else v = vin(b, st, cpn) - vin(b, st - 1, cpn);
-                        s += v - (sdv[k] ? GP(ug0)[rr] : GP(lg0)[rr]);
+                        s += v - ((sdv[k] & 1) ? GP(ug0)[rr] : GP(lg0)[rr]);
                     }
                     R[k] = s;
                 }
                 wave_sync();
-                chol_solve(R, n);
+                sens_chol_solve(S, R, n, lane);
             }
             if (valid && Pd.flags && lane == 0) glw(Pd.flags)[b] = flag;
             if (lane == 0) { flg[il] = valid ? flag : -1; cnt[il] = (valid && !flag) ? n : 0; }
@@ -305,15 +221,7 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
         // ---- Xq Q: the row tiles over the wavefronts
         const int ntile = rows16 >> 4;
         for (int t = wave; t < ntile; t += W) {
-            v4d acc = {0.0, 0.0, 0.0, 0.0};
-            for (int g = 0; g < Pd.G; ++g) {
-                const v4d a = ld4(gl(Pd.Xqp) + (((size_t)t * Pd.G + g) * 64 + lane) * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int kb = 4 * g + e;
-                    if (kb < nz4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[e], Qp[kb * 64 + lane], acc, 0, 0, 0);
-                }
-            }
+            const v4d acc = sens_mfma_tile(gl(Pd.Xqp), t, Pd.G, nz4, Qp, lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) DX[(size_t)j16 * rows16 + 16 * t + 4 * r + kq] = acc[r];
         }
@@ -350,10 +258,10 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
                     const int kind = GP(g_kind)[rr], st = GP(g_step)[rr], cpn = GP(g_comp)[rr];
                     if (st < 1) continue;
                     const double lam = R[k], mu = V[k];
-                    if (kind == kKindOutput) { if (lane == (cpn & 63)) { ov[(st - 1) * ny + cpn] += lam; dov[(st - 1) * ny + cpn] += mu; } }
-                    else if (kind == kKindState) { if (lane == (cpn & 63)) { pi[(st - 1) * nx + cpn] += lam; eta[(st - 1) * nx + cpn] += mu; } }
-                    else if (kind == kKindScalar || kind == kKindLinear) {
-                        const gdp F = kind == kKindScalar ? sX : Flin + (size_t)cpn * (nx + nu);
+                    if (kind == G_OUTPUT) { if (lane == (cpn & 63)) { ov[(st - 1) * ny + cpn] += lam; dov[(st - 1) * ny + cpn] += mu; } }
+                    else if (kind == G_STATE) { if (lane == (cpn & 63)) { pi[(st - 1) * nx + cpn] += lam; eta[(st - 1) * nx + cpn] += mu; } }
+                    else if (kind == G_SCALAR || kind == G_LINEAR) {
+                        const gdp F = kind == G_SCALAR ? sX : Flin + (size_t)cpn * (nx + nu);
                         for (int c = lane; c < nx; c += 64) { pi[(st - 1) * nx + c] = fma(lam, F[c], pi[(st - 1) * nx + c]); eta[(st - 1) * nx + c] = fma(mu, F[c], eta[(st - 1) * nx + c]); }
                     }
                 }
@@ -396,7 +304,7 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
                                 if (i > 1) s = fma(pw[(i - 1) * nx + r], dx[(i - 2) * nx + c], s);
                             } else if (kind == 1) {
                                 s = fma(ew[(i - 1) * nx + r], vin(bw, i, c), s);
-                                s = fma(pw[(i - 1) * nx + r], opnd(Qp, iw, blk[i] * nu + c), s);
+                                s = fma(pw[(i - 1) * nx + r], sens_opnd(Qp, iw, blk[i] * nu + c), s);
                             } else if (kind == 2) {
                                 s = fma(dw[(i - 1) * ny + r], xs[(size_t)i * nx + c], s);
                                 s = fma(ow[(i - 1) * ny + r], dx[(i - 1) * nx + c], s);
@@ -421,30 +329,6 @@ __global__ __launch_bounds__(256) void lmpc_model_sensitivity(const LmpcDev *__r
     }
 }
 
-// the rows of the partials buffer added in workgroup order, an entry per thread
-__global__ __launch_bounds__(256) void lmpc_model_reduce(const LmpcModelDev Pd, int groups, int nx, int nu, int ny, int ndu)
-{
-    const size_t plen = model_glen(nx, nu, ny, ndu) + 1;
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= plen) return;
-    const size_t eA = (size_t)nx * nx, eB = eA + (size_t)nx * nu, eC = eB + (size_t)ny * nx, eBd = eC + (size_t)nx * ndu;
-    double *dst = t < eA ? Pd.d_A : (t < eB ? Pd.d_B : (t < eC ? Pd.d_C : (t < eBd ? Pd.d_Bd : Pd.d_Dd)));
-    const bool count = t == plen - 1;
-    if (count ? !Pd.n_used : !dst) return;
-    double s = 0.0;
-    int g = 0;
-    for (; g + 8 <= groups; g += 8) {           // eight loads in flight, the additions in workgroup order all the same
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = gl(Pd.part)[(size_t)(g + u) * plen + t];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; g < groups; ++g) s += gl(Pd.part)[(size_t)g * plen + t];
-    if (count) glw(Pd.n_used)[0] = (int32_t)s;
-    else glw(dst)[t - (t < eA ? 0 : (t < eB ? eA : (t < eC ? eB : (t < eBd ? eC : eBd))))] = s;
-}
-
 }  // namespace
 
 // Xq = d (states of the steps 1 .. ph) / d w as the kernel's A operand source: [rows16 x nz] column-major, row (i - 1) nx + a = state a of step i,
@@ -454,21 +338,10 @@ size_t lmpc_model_sens_xq(int nx, int nu, int ph, int nz, const double *A, const
     const int rows16 = (nx * ph + 15) / 16 * 16;
     const size_t len = (size_t)rows16 * nz;
     if (!out) return len;
-    std::vector<double> x(nx), xn(nx);
     for (int q = 0; q < nz; ++q) {
         double *col = out + (size_t)q * rows16;
         for (int r = 0; r < rows16; ++r) col[r] = 0.0;
-        x.assign(nx, 0.0);
-        for (int i = 1; i <= ph; ++i) {
-            for (int a = 0; a < nx; ++a) {
-                double s = 0.0;
-                for (int c = 0; c < nx; ++c) s += A[a + (size_t)c * nx] * x[c];
-                if (blk[i] == q / nu) s += B[a + (size_t)(q % nu) * nx];
-                xn[a] = s;
-            }
-            x.swap(xn);
-            for (int a = 0; a < nx; ++a) col[(i - 1) * nx + a] = x[a];
-        }
+        sens_unit_rollout(nx, nu, ph, q, A, B, blk, [&](int i, const double *x) { for (int a = 0; a < nx; ++a) col[(i - 1) * nx + a] = x[a]; });
     }
     return len;
 }
@@ -493,29 +366,22 @@ int lmpc_model_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double 
     s.d_A = a.d_A; s.d_B = a.d_B; s.d_C = a.d_C; s.d_Bd = m.ndu > 0 ? a.d_Bd : nullptr; s.d_Dd = m.ndu > 0 ? a.d_Dd : nullptr;
     s.flags = a.flags; s.n_used = a.n_used; s.part = a.reduce ? a.partials : nullptr; s.Xqp = Xqp;
     if (a.reduce && !a.partials) return -3;
-    // the slices as lmpc_param_sens_launch sizes them: the largest working set there can be where four, two or one wavefront's fit beside the
-    // shared operands and the sixteen records; otherwise one wavefront with the largest capacity that fits, and larger sets get flag 3
-    const size_t limit = lmpc_lds_limit() / sizeof(double);
-    auto total = [&](int waves, int cap) { return model_shared_len(m.nz16, s.rows16, m.nx, m.nu, m.ny, cap) + waves * model_wave_len(cap, m.nz, m.nx, m.ny, m.ph); };
-    const int want = ws_limit(m.nz, m.mg, m.n_soft) > 1 ? ws_limit(m.nz, m.mg, m.n_soft) : 1;
-    int waves = 4;
-    while (waves > 1 && total(waves, want) > limit) waves >>= 1;
-    s.cap = want;
-    while (s.cap > 0 && total(waves, s.cap) > limit) --s.cap;
-    if (s.cap <= 0) return -2;
-    const size_t bytes = total(waves, s.cap) * sizeof(double);
+    // the wavefronts' slices beside the shared operands and the sixteen records, which grow with the capacity as well
+    const SensLdsPlan plan = sens_lds_plan(m, 4, [&](int waves, int cap) {
+        return model_shared_len(m.nz16, s.rows16, m.nx, m.nu, m.ny, cap) + waves * model_wave_len(cap, m.nz, m.nx, m.ny, m.ph);
+    });
+    if (plan.cap <= 0) return -2;
+    s.cap = plan.cap;
     static LmpcLdsCache configured;
-    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_model_sensitivity)}, bytes) != 0) return -3;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_model_sensitivity)}, plan.bytes) != 0) return -3;
     const int groups = (a.batch + kModelIpg - 1) / kModelIpg;
     const int blocks = groups > 65536 ? 65536 : groups;
-    hipLaunchKernelGGL(lmpc_model_sensitivity, dim3(blocks), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream), m_dev, s);
+    hipLaunchKernelGGL(lmpc_model_sensitivity, dim3(blocks), dim3(64 * plan.waves), plan.bytes, static_cast<hipStream_t>(stream), m_dev, s);
     if (hipGetLastError() != hipSuccess) return -3;
-    if (a.reduce) {
-        const size_t plen = model_glen(m.nx, m.nu, m.ny, m.ndu) + 1;
-        hipLaunchKernelGGL(lmpc_model_reduce, dim3((unsigned)((plen + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), s, groups, m.nx, m.nu, m.ny, m.ndu);
-        if (hipGetLastError() != hipSuccess) return -3;
-    }
-    return 0;
+    if (!a.reduce) return 0;
+    const size_t eA = (size_t)m.nx * m.nx, eB = eA + (size_t)m.nx * m.nu, eC = eB + (size_t)m.ny * m.nx, eBd = eC + (size_t)m.nx * m.ndu;      // model_glen's order
+    const size_t glen = model_glen(m.nx, m.nu, m.ny, m.ndu);
+    return sens_reduce_launch(SensReduce{s.part, glen + 1, {eA, eB, eC, eBd, glen}, {s.d_A, s.d_B, s.d_C, s.d_Bd, s.d_Dd}, s.n_used, groups}, stream);
 }
 
 }  // namespace mpcx

@@ -11,19 +11,16 @@
 // with y, v the solve's own seq_output, seq_input (row i of seq_input is v_{min(i + 1, ph)}) and v_0 = lastU.
 // The plan is lmpc_sensitivity's: a workgroup takes sixteen instances, one seed each; one wavefront per instance decodes the working set, factors S
 // in LDS and forms q; then Cq Q, Q the sixteen q as one column tile, goes through the f64 matrix pipe, the wavefronts splitting the row tiles.
-// reduce: a workgroup adds its instances in instance order into its own row of a partials buffer, lmpc_param_reduce adds the rows in workgroup
+// reduce: a workgroup adds its instances in instance order into its own row of a partials buffer, lmpc_sens_reduce adds the rows in workgroup
 // order -- no floating-point atomics, the same bits on every launch.
-// (The per-instance part restates lmpc_sensitivity's for one seed instead of sharing a header with it: that kernel's code is left as it was.)
-#include "lmpc_kernel_common.hpp"
-
-#include <vector>
+// The per-instance part (working set, factor, solve, q), the tile product and the reduce kernel are lmpc_sens_common.hpp's, shared with the other
+// sensitivity kernels.
+#include "lmpc_sens_common.hpp"
 
 namespace mpcx {
 
 namespace {
 
-// a pivot below this fraction of the row's own diagonal entry of S: the working set is dependent (flag 2)
-constexpr double kParamPivotTol = 1e-11;
 constexpr int kParamIpg = 16;      // instances of a workgroup: one MFMA column tile
 
 struct LmpcParamDev {
@@ -76,8 +73,6 @@ __global__ __launch_bounds__(256) void lmpc_param_sensitivity(const LmpcDev *__r
     const gdp Y = GP(Y);
     const gip blk = GP(blk);
     const double qnan = __builtin_nan("");
-    auto ld4 = [](gdp p) -> v4d { return *reinterpret_cast<const v4d MPCX_GAS *>(p); };
-    auto opnd = [&](double *P, int c, int q) -> double & { return P[(size_t)(q >> 2) * 64 + 16 * (q & 3) + c]; };
     const gdp yr = gl(Pd.yref), ur = gl(Pd.uref), dr = gl(Pd.duref);
 
     for (int g0 = blockIdx.x; g0 * kParamIpg < Pd.batch; g0 += gridDim.x) {
@@ -98,13 +93,7 @@ __global__ __launch_bounds__(256) void lmpc_param_sensitivity(const LmpcDev *__r
         for (int t = tid; t < kParamIpg * nz; t += blockDim.x) {
             const int il = t / nz, q = t - il * nz, b = b0 + il;
             if (b >= Pd.batch) continue;
-            const int bq = q / nu, jq = q - bq * nu;
-            double v = 0.0;
-            if (Pd.seed_cmd && bq == blk[1]) v = gl(Pd.seed_cmd)[(size_t)b * nu + jq];
-            if (Pd.seed_input)              // row i of the sequence is v_{min(i + 1, ph)} (OptSequence)
-                for (int i = 0; i <= ph; ++i)
-                    if (blk[i + 1 <= ph ? i + 1 : ph] == bq) v += gl(Pd.seed_input)[((size_t)b * (ph + 1) + i) * nu + jq];
-            opnd(Bp, il, q) = v;
+            sens_opnd(Bp, il, q) = sens_seed(Pd.seed_cmd, Pd.seed_input, blk, nu, ph, b, q);
         }
         __syncthreads();
 
@@ -113,102 +102,25 @@ __global__ __launch_bounds__(256) void lmpc_param_sensitivity(const LmpcDev *__r
             const int il = r0 + wave, b = b0 + il;
             const bool valid = b < Pd.batch;
             int flag = 0, n = 0;
+            auto cot = [&](int q) { return sens_opnd(Bp, il, q); };      // the instance's cotangent
             if (valid) {
                 flag = (Pd.status && gl(Pd.status)[b] != 0) ? 1 : 0;
                 if (!flag) {
-                    const uint32_t MPCX_GAS *wl = gl(Pd.al) + (size_t)b * aw, *wu = gl(Pd.au) + (size_t)b * aw;
-                    // 0: no bit, 1: the lower bound's, 2: the upper bound's (which takes the gradient where both are set)
-                    auto side = [&](int rr) -> int {
-                        if (rr < 0 || (rr >> 5) >= aw) return 0;
-                        if ((wu[rr >> 5] >> (rr & 31)) & 1u) return 2;
-                        return (int)((wl[rr >> 5] >> (rr & 31)) & 1u);
-                    };
-                    for (int base = 0; base < nz + mg; base += 64) {
-                        const int e = base + lane;
-                        int slot = -1;                          // 2 row + (upper ? 1 : 0) of the bound that takes mu
-                        if (e < nz) {                           // (several reference rows on one variable: the lowest-numbered one with a bit)
-                            for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
-                                const int rr = GP(boxrow_ref)[p], sd = side(rr);
-                                if (sd && (slot < 0 || rr < (slot >> 1))) slot = 2 * rr + (sd - 1);
-                            }
-                        } else if (e < nz + mg) {
-                            const int rr = GP(g_refrow)[e - nz], sd = side(rr);
-                            if (sd) slot = 2 * rr + (sd - 1);
-                        }
-                        const bool in = slot >= 0;
-                        const unsigned long long mask = __ballot(in);
-                        const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
-                        if (in && pos < cap) { idx[pos] = e < nz ? e : ldz + (e - nz); tgt[pos] = slot; }
-                        n += __popcll(mask);
-                    }
+                    // (tgt: the bound that takes the row's mu, the upper one where both bits are set)
+                    n = sens_working_set(M, gl(Pd.al) + (size_t)b * aw, gl(Pd.au) + (size_t)b * aw, aw, nz, mg, ldz, cap, lane, idx, tgt);
                     if (n > cap) flag = 3;
                 }
             }
             wave_sync();
             if (valid && !flag && n > 0) {
-                for (int i = 0; i < n; ++i) {
-                    const int qi = idx[i];
-                    for (int j = lane; j <= i; j += 64) {
-                        double v = Y[(size_t)idx[j] * ldy + qi];
-                        if (j == i) dg[i] = v;
-                        S[(size_t)i * (i + 1) / 2 + j] = v;
-                    }
-                }
                 // right-hand side Y[A, 0:nz] p, a row per lane
-                for (int i = lane; i < n; i += 64) {
-                    const int qi = idx[i];
-                    double s = 0.0;
-                    for (int q = 0; q < nz; ++q) {
-                        const double pv = opnd(Bp, il, q);
-                        if (pv != 0.0) s = fma(Y[(size_t)q * ldy + qi], pv, s);
-                    }
-                    V[i] = s;
-                }
-                wave_sync();
-                // left-looking Cholesky, a row per lane
-                for (int k = 0; k < n && !flag; ++k) {
-                    const double *Lk = S + (size_t)k * (k + 1) / 2;
-                    for (int i = k + lane; i < n; i += 64) {
-                        double *Li = S + (size_t)i * (i + 1) / 2;
-                        double s = Li[k];
-                        for (int j = 0; j < k; ++j) s = fma(-Li[j], Lk[j], s);
-                        Li[k] = s;
-                    }
-                    wave_sync();
-                    const double d = Lk[k];
-                    if (!(d > kParamPivotTol * dg[k])) { flag = 2; break; }
-                    const double sd = sqrt(d), rd = 1.0 / sd;
-                    wave_sync();
-                    for (int i = k + lane; i < n; i += 64) { double *Li = S + (size_t)i * (i + 1) / 2; Li[k] = i == k ? sd : Li[k] * rd; }
-                    wave_sync();
-                }
-                if (!flag) {
-                    for (int k = 0; k < n; ++k) {                 // L y = v
-                        if (lane == 0) V[k] /= S[(size_t)k * (k + 1) / 2 + k];
-                        wave_sync();
-                        for (int i = k + 1 + lane; i < n; i += 64) V[i] = fma(-S[(size_t)i * (i + 1) / 2 + k], V[k], V[i]);
-                        wave_sync();
-                    }
-                    for (int k = n - 1; k >= 0; --k) {            // L' mu = y
-                        const double *Lk = S + (size_t)k * (k + 1) / 2;
-                        if (lane == 0) V[k] /= Lk[k];
-                        wave_sync();
-                        for (int i = lane; i < k; i += 64) V[i] = fma(-Lk[i], V[k], V[i]);
-                        wave_sync();
-                    }
-                }
+                for (int i = lane; i < n; i += 64) V[i] = sens_rhs(Y, ldy, nz, idx[i], cot);
+                if (!sens_factor(Y, ldy, idx, n, lane, S, dg)) flag = 2;
+                else sens_chol_solve(S, V, n, lane);
             }
             if (valid && !flag) {
                 // q = Y[0:nz, 0:nz] p - Y[0:nz, A] mu, an element per lane (Y is symmetric: column t read along its rows)
-                for (int t = lane; t < nz; t += 64) {
-                    double s = 0.0;
-                    for (int q = 0; q < nz; ++q) {
-                        const double pv = opnd(Bp, il, q);
-                        if (pv != 0.0) s = fma(Y[(size_t)q * ldy + t], pv, s);
-                    }
-                    for (int i = 0; i < n; ++i) s = fma(-Y[(size_t)idx[i] * ldy + t], V[i], s);
-                    opnd(Qp, il, t) = s;
-                }
+                for (int t = lane; t < nz; t += 64) sens_opnd(Qp, il, t) = sens_direction(Y, ldy, nz, t, cot, idx, V, n);
             }
             if (valid && !reduce) {
                 // the bounds of this instance: mu on the side whose bit is set; NaN everywhere for a flagged one
@@ -244,15 +156,7 @@ __global__ __launch_bounds__(256) void lmpc_param_sensitivity(const LmpcDev *__r
         // ---- Cq Q: the row tiles over the wavefronts
         const int ntile = rows16 >> 4;
         for (int t = wave; t < ntile; t += W) {
-            v4d acc = {0.0, 0.0, 0.0, 0.0};
-            for (int g = 0; g < Pd.G; ++g) {
-                const v4d a = ld4(gl(Pd.Cqp) + (((size_t)t * Pd.G + g) * 64 + lane) * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int kb = 4 * g + e;
-                    if (kb < nz4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[e], Qp[kb * 64 + lane], acc, 0, 0, 0);
-                }
-            }
+            const v4d acc = sens_mfma_tile(gl(Pd.Cqp), t, Pd.G, nz4, Qp, lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) DY[(size_t)j16 * rows16 + 16 * t + 4 * r + kq] = acc[r];
         }
@@ -276,10 +180,10 @@ __global__ __launch_bounds__(256) void lmpc_param_sensitivity(const LmpcDev *__r
                         c = -DY[(size_t)il * rows16 + i * ny + j] * e;
                     } else {
                         const double vn = gl(Pd.seq_input)[((size_t)b * (ph + 1) + i) * nu + j];
-                        if (kind == 1) c = -opnd(Qp, il, qn) * (vn - ref_at(ur, Pd.uref_bs, Pd.uref_ks, b, i, j));
+                        if (kind == 1) c = -sens_opnd(Qp, il, qn) * (vn - ref_at(ur, Pd.uref_bs, Pd.uref_ks, b, i, j));
                         else {
                             const double vp = i > 0 ? gl(Pd.seq_input)[((size_t)b * (ph + 1) + i - 1) * nu + j] : gl(Pd.u0)[(size_t)b * nu + j];
-                            const double dq = opnd(Qp, il, qn) - (qp >= 0 ? opnd(Qp, il, qp) : 0.0);
+                            const double dq = sens_opnd(Qp, il, qn) - (qp >= 0 ? sens_opnd(Qp, il, qp) : 0.0);
                             c = -dq * (vn - vp - ref_at(dr, Pd.duref_bs, Pd.duref_ks, b, i > 0 ? i - 1 : 0, j));
                         }
                     }
@@ -298,31 +202,6 @@ __global__ __launch_bounds__(256) void lmpc_param_sensitivity(const LmpcDev *__r
     }
 }
 
-// the rows of the partials buffer added in workgroup order, an entry per thread
-__global__ __launch_bounds__(256) void lmpc_param_reduce(const LmpcParamDev Pd, int groups, int ny, int nu, int ph)
-{
-    const int m_rows = Pd.m_rows;
-    const size_t plen = param_plen(ny, nu, ph, m_rows);
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= plen) return;
-    const size_t eo = (size_t)ny * ph, eu = eo + (size_t)nu * ph, ed = eu + (size_t)nu * ph;
-    double *dst = t < eo ? Pd.d_ow : (t < eu ? Pd.d_uw : (t < ed ? Pd.d_duw : (t < ed + m_rows ? Pd.d_lo : Pd.d_up)));
-    const bool count = t == plen - 1;
-    if (count ? !Pd.n_used : !dst) return;       // (the bound rows of the partials are not even filled when neither side is asked for)
-    double s = 0.0;
-    int g = 0;
-    for (; g + 8 <= groups; g += 8) {           // eight loads in flight, the additions in workgroup order all the same
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = gl(Pd.part)[(size_t)(g + u) * plen + t];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; g < groups; ++g) s += gl(Pd.part)[(size_t)g * plen + t];
-    if (count) glw(Pd.n_used)[0] = (int32_t)s;
-    else glw(dst)[t - (t < eo ? 0 : (t < eu ? eo : (t < ed ? eu : (t < ed + m_rows ? ed : ed + m_rows))))] = s;
-}
-
 }  // namespace
 
 // Cq = d (outputs of the steps 1 .. ph) / d w as the kernel's A operand source: [rows16 x nz] column-major, row (i - 1) ny + a = output a of step i,
@@ -332,25 +211,16 @@ size_t lmpc_param_sens_cq(int nx, int nu, int ny, int ph, int nz, const double *
     const int rows16 = (ny * ph + 15) / 16 * 16;
     const size_t len = (size_t)rows16 * nz;
     if (!out) return len;
-    std::vector<double> x(nx), xn(nx);
     for (int q = 0; q < nz; ++q) {
         double *col = out + (size_t)q * rows16;
         for (int r = 0; r < rows16; ++r) col[r] = 0.0;
-        x.assign(nx, 0.0);
-        for (int i = 1; i <= ph; ++i) {
-            for (int a = 0; a < nx; ++a) {
-                double s = 0.0;
-                for (int c = 0; c < nx; ++c) s += A[a + (size_t)c * nx] * x[c];
-                if (blk[i] == q / nu) s += B[a + (size_t)(q % nu) * nx];
-                xn[a] = s;
-            }
-            x.swap(xn);
+        sens_unit_rollout(nx, nu, ph, q, A, B, blk, [&](int i, const double *x) {
             for (int a = 0; a < ny; ++a) {
                 double s = 0.0;
                 for (int c = 0; c < nx; ++c) s += C[a + (size_t)c * ny] * x[c];
                 col[(i - 1) * ny + a] = s;
             }
-        }
+        });
     }
     return len;
 }
@@ -374,28 +244,20 @@ int lmpc_param_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double 
     s.d_ow = a.d_oweight; s.d_uw = a.d_uweight; s.d_duw = a.d_duweight; s.d_lo = a.d_lower; s.d_up = a.d_upper;
     s.flags = a.flags; s.n_used = a.n_used; s.part = a.reduce ? a.partials : nullptr; s.Cqp = Cqp;
     if (a.reduce && !a.partials) return -3;
-    // the slices as lmpc_sens_launch sizes them: the largest working set there can be where four, two or one wavefront's fit beside the shared
-    // operands; otherwise one wavefront with the largest slice that fits, and larger sets get flag 3
-    const size_t limit = lmpc_lds_limit() / sizeof(double), shared = param_shared_len(m.nz16, s.rows16);
-    const int want = ws_limit(m.nz, m.mg, m.n_soft) > 1 ? ws_limit(m.nz, m.mg, m.n_soft) : 1;
-    int waves = 4;
-    while (waves > 1 && shared + waves * param_wave_len(want) > limit) waves >>= 1;
-    s.cap = want;
-    while (s.cap > 0 && shared + waves * param_wave_len(s.cap) > limit) --s.cap;
-    if (s.cap <= 0) return -2;
-    const size_t bytes = (shared + waves * param_wave_len(s.cap)) * sizeof(double);
+    // the wavefronts' slices beside the shared operands
+    const size_t shared = param_shared_len(m.nz16, s.rows16);
+    const SensLdsPlan plan = sens_lds_plan(m, 4, [&](int waves, int cap) { return shared + waves * param_wave_len(cap); });
+    if (plan.cap <= 0) return -2;
+    s.cap = plan.cap;
     static LmpcLdsCache configured;
-    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_param_sensitivity)}, bytes) != 0) return -3;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_param_sensitivity)}, plan.bytes) != 0) return -3;
     const int groups = (a.batch + kParamIpg - 1) / kParamIpg;
     const int blocks = groups > 65536 ? 65536 : groups;
-    hipLaunchKernelGGL(lmpc_param_sensitivity, dim3(blocks), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream), m_dev, s);
+    hipLaunchKernelGGL(lmpc_param_sensitivity, dim3(blocks), dim3(64 * plan.waves), plan.bytes, static_cast<hipStream_t>(stream), m_dev, s);
     if (hipGetLastError() != hipSuccess) return -3;
-    if (a.reduce) {
-        const size_t plen = param_plen(m.ny, m.nu, m.ph, m.m_ref);
-        hipLaunchKernelGGL(lmpc_param_reduce, dim3((unsigned)((plen + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), s, groups, m.ny, m.nu, m.ph);
-        if (hipGetLastError() != hipSuccess) return -3;
-    }
-    return 0;
+    if (!a.reduce) return 0;
+    const size_t eo = (size_t)m.ny * m.ph, eu = eo + (size_t)m.nu * m.ph, ed = eu + (size_t)m.nu * m.ph, mr = (size_t)m.m_ref;      // param_plen's order
+    return sens_reduce_launch(SensReduce{s.part, param_plen(m.ny, m.nu, m.ph, m.m_ref), {eo, eu, ed, ed + mr, ed + 2 * mr}, {s.d_ow, s.d_uw, s.d_duw, s.d_lo, s.d_up}, s.n_used, groups}, stream);
 }
 
 }  // namespace mpcx

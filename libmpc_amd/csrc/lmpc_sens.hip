@@ -8,17 +8,13 @@
 // The first product does not depend on the working set: sixteen (instance, seed) columns share the operand T0' and go through the f64 matrix
 // pipe (v_mfma_f64_16x16x4_f64) with the packed operands of lmpc_pack_mfma_tiles, the wavefronts of a workgroup splitting the tiles.  The rest
 // is per instance, one wavefront each: decode the working set from the active bits, gather S into LDS (packed lower triangle), factor it by
-// Cholesky with a relative pivot test, solve for the seeds, gather the rows of MF1.
-#include "lmpc_kernel_common.hpp"
-
-#include <vector>
+// Cholesky with a relative pivot test, solve for the seeds, gather the rows of MF1.  The decode, the factor, the seed scatter and the tile product
+// are lmpc_sens_common.hpp's, shared with the other sensitivity kernels.
+#include "lmpc_sens_common.hpp"
 
 namespace mpcx {
 
 namespace {
-
-// a pivot below this fraction of the row's own diagonal entry of S: the working set is dependent (flag 2)
-constexpr double kSensPivotTol = 1e-11;
 
 struct LmpcSensDev {
     int batch, R, jac;            // seeds per instance; jac: the nu unit seeds on cmd
@@ -55,9 +51,8 @@ __global__ __launch_bounds__(256) void lmpc_sensitivity(const LmpcDev *__restric
     const gdp Y = GP(Y), MF = GP(MF1);
     const gip blk = GP(blk);
     const double qnan = __builtin_nan("");
-    auto ld4 = [](gdp p) -> v4d { return *reinterpret_cast<const v4d MPCX_GAS *>(p); };
     // element q of column c's cotangent, where the B operands keep it
-    auto pcol = [&](int c, int q) -> double & { return Bp[((size_t)(c >> 4) * nz4 + (q >> 2)) * 64 + 16 * (q & 3) + (c & 15)]; };
+    auto pcol = [&](int c, int q) -> double & { return sens_opnd(Bp + (size_t)(c >> 4) * nz4 * 64, c & 15, q); };
 
     for (int g0 = blockIdx.x; g0 * ipg < Sd.batch; g0 += gridDim.x) {
         const int b0 = g0 * ipg;
@@ -67,32 +62,14 @@ __global__ __launch_bounds__(256) void lmpc_sensitivity(const LmpcDev *__restric
         for (int t = threadIdx.x; t < ncol * nz; t += blockDim.x) {
             const int c = t / nz, q = t - c * nz, il = c / R, r = c - il * R, b = b0 + il;
             if (b >= Sd.batch) continue;
-            const int bq = q / nu, jq = q - bq * nu;
-            double v = 0.0;
-            if (Sd.jac) v = (bq == blk[1] && jq == r) ? 1.0 : 0.0;
-            else {
-                if (Sd.seed_cmd && bq == blk[1]) v = gl(Sd.seed_cmd)[(size_t)b * nu + jq];
-                if (Sd.seed_input)              // row i of the sequence is v_{min(i + 1, ph)} (OptSequence)
-                    for (int i = 0; i <= ph; ++i)
-                        if (blk[i + 1 <= ph ? i + 1 : ph] == bq) v += gl(Sd.seed_input)[((size_t)b * (ph + 1) + i) * nu + jq];
-            }
-            pcol(c, q) = v;
+            pcol(c, q) = Sd.jac ? (q == blk[1] * nu + r ? 1.0 : 0.0) : sens_seed(Sd.seed_cmd, Sd.seed_input, blk, nu, ph, b, q);
         }
         __syncthreads();
         // ---- T0' P: row tiles x column tiles over the wavefronts
         const int ntile = kin16 >> 4;
         for (int item = wave; item < ntile * Sd.ctiles; item += W) {
             const int t = item % ntile, ct = item / ntile;
-            const double *Bc = Bp + (size_t)ct * nz4 * 64;
-            v4d acc = {0.0, 0.0, 0.0, 0.0};
-            for (int g = 0; g < Sd.G; ++g) {
-                const v4d a = ld4(gl(Sd.T0p) + (((size_t)t * Sd.G + g) * 64 + lane) * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int kb = 4 * g + e;
-                    if (kb < nz4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[e], Bc[kb * 64 + lane], acc, 0, 0, 0);
-                }
-            }
+            const v4d acc = sens_mfma_tile(gl(Sd.T0p), t, Sd.G, nz4, Bp + (size_t)ct * nz4 * 64, lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) G0[(size_t)(16 * ct + j16) * kin16 + 16 * t + 4 * r + kq] = acc[r];
         }
@@ -105,58 +82,19 @@ __global__ __launch_bounds__(256) void lmpc_sensitivity(const LmpcDev *__restric
             int flag = (Sd.status && gl(Sd.status)[b] != 0) ? 1 : 0;
             int n = 0;
             if (!flag) {
-                const uint32_t MPCX_GAS *wl = gl(Sd.al) + (size_t)b * aw, *wu = gl(Sd.au) + (size_t)b * aw;
-                auto bit = [&](int rr) -> bool { return rr >= 0 && (rr >> 5) < aw && (((wl[rr >> 5] | wu[rr >> 5]) >> (rr & 31)) & 1u) != 0u; };
-                for (int base = 0; base < nz + mg; base += 64) {
-                    const int e = base + lane;
-                    bool in = false;
-                    if (e < nz) { for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) in = in || bit(GP(boxrow_ref)[p]); }
-                    else if (e < nz + mg) in = bit(GP(g_refrow)[e - nz]);
-                    const unsigned long long mask = __ballot(in);
-                    const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
-                    if (in && pos < cap) idx[pos] = e < nz ? e : ldz + (e - nz);
-                    n += __popcll(mask);
-                }
+                n = sens_working_set(M, gl(Sd.al) + (size_t)b * aw, gl(Sd.au) + (size_t)b * aw, aw, nz, mg, ldz, cap, lane, idx, nullptr);
                 if (n > cap) flag = 3;
             }
             wave_sync();
             if (!flag && n > 0) {
-                for (int i = 0; i < n; ++i) {
-                    const int qi = idx[i];
-                    for (int j = lane; j <= i; j += 64) {
-                        double v = Y[(size_t)idx[j] * ldy + qi];
-                        if (j == i) dg[i] = v;
-                        S[(size_t)i * (i + 1) / 2 + j] = v;
-                    }
-                }
                 // right-hand sides Y[A, 0:nz] p, one (seed, row) pair per lane
                 for (int t = lane; t < R * n; t += 64) {
-                    const int r = t / n, i = t - r * n, c = il * R + r, qi = idx[i];
-                    double s = 0.0;
-                    for (int q = 0; q < nz; ++q) {
-                        const double pv = pcol(c, q);
-                        if (pv != 0.0) s = fma(Y[(size_t)q * ldy + qi], pv, s);
-                    }
-                    V[(size_t)r * cap + i] = s;
+                    const int r = t / n, i = t - r * n, c = il * R + r;
+                    V[(size_t)r * cap + i] = sens_rhs(Y, ldy, nz, idx[i], [&](int q) { return pcol(c, q); });
                 }
-                wave_sync();
-                // left-looking Cholesky, a row per lane
-                for (int k = 0; k < n && !flag; ++k) {
-                    const double *Lk = S + (size_t)k * (k + 1) / 2;
-                    for (int i = k + lane; i < n; i += 64) {
-                        double *Li = S + (size_t)i * (i + 1) / 2;
-                        double s = Li[k];
-                        for (int j = 0; j < k; ++j) s = fma(-Li[j], Lk[j], s);
-                        Li[k] = s;
-                    }
-                    wave_sync();
-                    const double d = Lk[k];
-                    if (!(d > kSensPivotTol * dg[k])) { flag = 2; break; }
-                    const double sd = sqrt(d), rd = 1.0 / sd;
-                    wave_sync();
-                    for (int i = k + lane; i < n; i += 64) { double *Li = S + (size_t)i * (i + 1) / 2; Li[k] = i == k ? sd : Li[k] * rd; }
-                    wave_sync();
-                }
+                if (!sens_factor(Y, ldy, idx, n, lane, S, dg)) flag = 2;
+                // the R right-hand sides at once, a column scaled by the pivot's reciprocal: sens_chol_solve divides, and folding this solve into
+                // it would change this kernel's last bits
                 if (!flag) {
                     for (int k = 0; k < n; ++k) {                 // L y = v
                         const double rd = 1.0 / S[(size_t)k * (k + 1) / 2 + k];
@@ -234,21 +172,16 @@ int lmpc_sens_launch(const LmpcDev &m, const LmpcDev *m_dev, const double *T0p, 
     s.al = a.active_lower; s.au = a.active_upper; s.status = a.status;
     s.seed_cmd = a.seed_cmd; s.seed_input = a.seed_input;
     s.d_x0 = a.d_x0; s.d_u0 = a.d_u0; s.d_yref = a.d_yref; s.flags = a.flags; s.T0p = T0p;
-    // every wavefront's slice holds the largest working set there can be (ws_limit) where four, two or one of them fit in a CU's LDS beside the shared
-    // operands; otherwise one wavefront with the largest slice that fits, and larger sets get flag 3
-    const size_t limit = lmpc_lds_limit() / sizeof(double), shared = sens_shared_len(s, m.nz16);
-    const int want = ws_limit(m.nz, m.mg, m.n_soft) > 1 ? ws_limit(m.nz, m.mg, m.n_soft) : 1;
-    int waves = s.ipg < 4 ? (s.ipg < 2 ? 1 : 2) : 4;
-    while (waves > 1 && shared + waves * sens_wave_len(want, s.R) > limit) waves >>= 1;
-    s.cap = want;
-    while (s.cap > 0 && shared + waves * sens_wave_len(s.cap, s.R) > limit) --s.cap;
-    if (s.cap <= 0) return -2;
-    const size_t bytes = (shared + waves * sens_wave_len(s.cap, s.R)) * sizeof(double);
+    // the wavefronts' slices beside the shared operands, no more wavefronts than instances
+    const size_t shared = sens_shared_len(s, m.nz16);
+    const SensLdsPlan plan = sens_lds_plan(m, s.ipg < 4 ? (s.ipg < 2 ? 1 : 2) : 4, [&](int waves, int cap) { return shared + waves * sens_wave_len(cap, s.R); });
+    if (plan.cap <= 0) return -2;
+    s.cap = plan.cap;
     static LmpcLdsCache configured;
-    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_sensitivity)}, bytes) != 0) return -3;
+    if (lmpc_raise_dynamic_lds(configured, {reinterpret_cast<const void *>(lmpc_sensitivity)}, plan.bytes) != 0) return -3;
     int blocks = (a.batch + s.ipg - 1) / s.ipg;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(lmpc_sensitivity, dim3(blocks), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream), m_dev, s);
+    hipLaunchKernelGGL(lmpc_sensitivity, dim3(blocks), dim3(64 * plan.waves), plan.bytes, static_cast<hipStream_t>(stream), m_dev, s);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE -- runs the model-sensitivity kernels (libmpc_amd/csrc/lmpc_model_sens.hip, compiled unchanged: lmpc_model_sens_launch,
-// lmpc_model_sensitivity, lmpc_model_reduce) through the lock-step interpreter of tests/emu/hip/hip_runtime.h on the host: no GPU, nothing of
+// lmpc_model_sensitivity, lmpc_sens_reduce) through the lock-step interpreter of tests/emu/hip/hip_runtime.h on the host: no GPU, nothing of
 // libmpcx.so.  Compiled with clang++ (the kernel's helpers name the components of an ext_vector_type).
 //
 //   run_model_sens <lds_limit bytes> < numbers

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE -- runs the parameter-sensitivity kernels (libmpc_amd/csrc/lmpc_param_sens.hip, compiled unchanged: lmpc_param_sens_launch,
-// lmpc_param_sensitivity, lmpc_param_reduce) through the lock-step interpreter of tests/emu/hip/hip_runtime.h on the host: no GPU, nothing of
+// lmpc_param_sensitivity, lmpc_sens_reduce) through the lock-step interpreter of tests/emu/hip/hip_runtime.h on the host: no GPU, nothing of
 // libmpcx.so.  Compiled with clang++ (the kernel's helpers name the components of an ext_vector_type).
 //
 //   run_param_sens <lds_limit bytes> < numbers

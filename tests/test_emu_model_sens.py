@@ -183,6 +183,8 @@ def test_reduced_form_flags_null_outputs_and_a_small_lds_limit(exe):
     assert part["d_B"].tobytes() == per["d_B"].tobytes() and part["d_Dd"].tobytes() == per["d_Dd"].tobytes()
     part = run(exe, pr, reduce=True, want=(1, 0, 0, 1, 0, 0, 1))
     assert part["n_used"] == used.sum() and part["d_A"].tobytes() == first["d_A"].tobytes() and part["d_Bd"].tobytes() == first["d_Bd"].tobytes()
+    part = run(exe, pr, reduce=True, want=(0, 1, 0, 0, 0, 0, 0))      # d_B alone: null destinations on both sides of it, no count
+    assert part["d_B"].tobytes() == first["d_B"].tobytes()
     # an LDS limit that holds working sets of a few rows only: the larger ones get flag 3 and NaN, the others keep their bits
     small = run(exe, pr, limit=SMALL_LDS)
     assert small["rc"] == 0
