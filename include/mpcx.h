@@ -922,6 +922,15 @@ int mpcx_lmpc_debug_set_cycle_buffer(mpcx_lmpc_t h, void *dev_ptr);
  * (0) the six-level butterfly sum, (1) its lane-swap / DPP form, (2) the two-level sum over lanes l, l ^ 16, l ^ 32, l ^ 48 by shuffles, (3) the same
  * by lane swaps.  Device pointers; asynchronous on `stream` */
 int mpcx_lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream);
+/* one working-set solve of the lean LMPC kernels (the Gauss-Jordan elimination on Y[A, A] and the update w = t0 - Y[:, A] lambda, one-chunk shape) per
+ * wavefront, with the elimination's pivot row by scalar lane reads (form 0) and by DPP row broadcast inside the FMA (form 1).  `count` problems: Y
+ * [count][n][ldy] dense symmetric (indices 0 .. nz - 1 the decision variables, nz .. n - 1 the general rows; nz and n - nz even, 2 .. 128; ldy >= n, even),
+ * wsidx / wsb [count][16] the working set's indices (clamped to 0 .. n - 1) and bound values, na [count] its size (1 .. 16: it selects the size class; a
+ * problem with another na is skipped), t0 [count][n] = [t0 | G t0].  out [count][2][274] per form: dep_at (position of a dependent row, or -1), lmax,
+ * lam [16], w of the 64 lanes [128], G w of the 64 lanes [128]; a solve that ends at a dependent row writes only dep_at and zeros.  Device pointers;
+ * asynchronous on `stream` */
+int mpcx_lmpc_debug_ws_solve(const double *Y, int n, int ldy, int nz, const int *wsidx, const double *wsb, const int *na, const double *t0, double *out,
+                             int count, void *stream);
 /* one more replay of a loop's tick graph behind a finished run, without the reset: the tick counter stands at `ticks`, so the replay writes no
  * trajectory, state or counter / the tick counter as it stands on the device, after synchronising the device */
 int mpcx_lmpc_loop_debug_replay(mpcx_lmpc_loop_t l, void *stream);

@@ -145,7 +145,7 @@ EXPORTS = [
     "mpcx_lmpc_hetero_sensitivity_batch",
     # profiling and testing aids (declared in include/mpcx.h under that heading)
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
-    "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer", "mpcx_lmpc_debug_wave_reduce",
+    "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer", "mpcx_lmpc_debug_wave_reduce", "mpcx_lmpc_debug_ws_solve",
     "mpcx_lmpc_loop_debug_replay", "mpcx_lmpc_loop_debug_tick", "mpcx_nlmpc_loop_debug_replay", "mpcx_nlmpc_loop_debug_tick",
     "mpcx_dare_debug_product", "mpcx_nlmpc_debug_set_tolerances", "mpcx_nlmpc_debug_last_form", "mpcx_nlmpc_last_form", "mpcx_nlmpc_debug_get_ws", "mpcx_nlmpc_debug_generated_source", "mpcx_nlmpc_debug_compile_source",
 ]
@@ -263,6 +263,7 @@ def lib():
         _lib.mpcx_dare_batch.argtypes = [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 5
         _lib.mpcx_dare_debug_product.argtypes = [C.c_int]
         _lib.mpcx_lmpc_debug_wave_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.mpcx_lmpc_debug_ws_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.mpcx_nlmpc_set_optimizer_parameters.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_solve_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_time_solve_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

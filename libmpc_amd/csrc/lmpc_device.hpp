@@ -181,6 +181,11 @@ int lmpc_launch_fast(const LmpcDev &m, const LmpcDev *m_dev, const LmpcBatchDev 
 // testing aid (lmpc_fast.hip): in [nvec][64] -> out [nvec][4][64] = every lane of wave_sum, of wave_sum_full, and of the two-level sum (lanes l, l ^ 16,
 // l ^ 32, l ^ 48) by __shfl_xor and by lane swaps; device pointers
 int lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream);
+// testing aid (lmpc_fast.hip): one working-set solve and update of the lean kernels (ws_solve_reg, one chunk) per wavefront, with the elimination by scalar
+// lane reads and by DPP row broadcast: out [count][2][kWsProbeLen] = dep_at, lmax, lam [16], wv [64 lanes x 2], gw [64 lanes x 2] of each form (mpcx.h)
+constexpr int kWsProbeLen = 2 + 16 + 128 + 128;
+int lmpc_debug_ws_solve(const double *Y, int n, int ldy, int nz, const int *wsidx, const double *wsb, const int *na, const double *t0, double *out, int count,
+                        void *stream);
 // hipFuncAttributeMaxDynamicSharedMemorySize of `kernels` raised to `bytes` on the current device unless `cache` says it has been: one cache per
 // set of kernels that are raised together, grow-only, an atomic per device (two host threads or two handles on different GPUs can neither skip
 // nor tear the update).  0, or -3

@@ -47,8 +47,8 @@ namespace {
 //     The verify phase's multiplier signs are bit arithmetic instead of four exec-mask ladders, the wave maximum's DPP moves no longer copy their source,
 //     and viol()'s contractions are written out.  What is still not straight-line code there: the NaN screen, the "solved" test and the choice between
 //     the two repair rules are wave-uniform branches.  No floating-point operation changed; profiles/r09_round_isa_census.txt.
-//   * round 10: the broadcasts of ws_solve_reg off the vector pipe, behind two switches per size class (MPCX_FAST_XBAR_CLASSES, MPCX_FAST_LDSMULT_CLASSES below),
-//     each kept where it wins on the GPU.  (1) The update's multipliers read back from lam[] in LDS at wave-uniform addresses, two per 16-byte read, each read
+//   * round 10: the broadcasts of ws_solve_reg off the vector pipe, behind a switch per size class (MPCX_FAST_LDSMULT_CLASSES below; the crossbar form of (2)
+//     had one of its own until round 12 removed the form), each kept where it wins on the GPU.  (1) The update's multipliers read back from lam[] in LDS at wave-uniform addresses, two per 16-byte read, each read
 //     travelling with the rows of Y it multiplies, instead of a v_readlane pair per row: on in the 8- and 10-row classes.  Whole step, parent -> this:
 //     0.03414 -> 0.03359 ms, 0.03280 -> 0.03220 ms at --steps 2000.  In the 4- and 6-row classes it is within the noise of the scalar reads; in the 12- to
 //     16-row classes the pairs in flight beside three batches of rows do not fit 128 VGPRs (12 B of scratch) and the step is 0.7 us SLOWER.  (2) The
@@ -67,6 +67,11 @@ namespace {
 //     GPU: the sixteen-term sums of the cost constants on the last wavefront instead of wavefront 0 (which has a tile of the second product); the fallback
 //     launch's queue pointer as a preloaded kernel argument (one trip to memory for the idle exit test instead of two).  profiles/r13_head_ab.txt,
 //     r13_head_isa_census.txt.
+//   * round 12: the elimination's pivot row and right-hand side by DPP row broadcast inside the FMA -- v_fmac_f64_dpp row_newbcast:K, one vector instruction
+//     per eliminated entry where the scalar form has two v_readlane_b32 and the FMA, no SGPR on the dependent chain (fmac_row_bcast, gj_step below: the
+//     latency of a lane read, not of LDS, which is what round 10's crossbar form lacked; that form is gone).  Behind MPCX_FAST_DPP_CLASSES, a bit per size
+//     class; both forms stay compiled in the probe kernel at the end of this file (mpcx_lmpc_debug_ws_solve), which holds them to the same bits.  No
+//     floating-point operation changed; profiles/r14_round_dpp_ab.txt, r14_round_isa_census.txt.
 // Working sets of more than kFastCap rows are left to the fallback kernel (none in 32768 instances of config 2, none in 8192 of
 // config 4).
 // How deep a round reaches into memory ahead of its arithmetic (ws_solve_reg).  Rows of Y requested with the Schur entries, ahead of the elimination:
@@ -95,26 +100,26 @@ namespace {
 #ifndef MPCX_FAST_DEEP_CHUNKS
 #define MPCX_FAST_DEEP_CHUNKS 4
 #endif
-// Which size classes of ws_solve_reg take their broadcasts off the vector pipe (round 10 in the comment above), two switches per class, each decided by
-// measurement (profiles/r10_round_ab.txt), never by round number at run time.  Bit CAP / 2 stands for the class of at most CAP rows (4, 6, ..., 16: bits 2
-// to 8).  MPCX_FAST_XBAR_CLASSES: the elimination's pivot row and right-hand side through the LDS crossbar (its parameter XB).  MPCX_FAST_LDSMULT_CLASSES:
-// the update's multipliers read back from LDS (XL).  Both only in the variants whose lane holds at most MPCX_FAST_XBAR_CHUNKS pairs of a row, and not in
-// the kernels that compute the record themselves (lmpc_solve_fused, lmpc_solve_persistent: they sit at their register budgets, see solve_fast).
-#ifndef MPCX_FAST_XBAR_CLASSES
-#define MPCX_FAST_XBAR_CLASSES 0
+// Which size classes of ws_solve_reg take their broadcasts off the scalar lane reads (rounds 10 and 12 in the comment above), two switches per class, each
+// decided by measurement (profiles/r10_round_ab.txt, r14_round_dpp_ab.txt), never by round number at run time.  Bit CAP / 2 stands for the class of at most
+// CAP rows (4, 6, ..., 16: bits 2 to 8).  MPCX_FAST_DPP_CLASSES: the elimination's pivot row and right-hand side taken by the FMA itself as a DPP row
+// broadcast (its parameter DP; the one- and two-chunk variants -- a lane holds at most MPCX_FAST_DPP_CHUNKS pairs of a row -- of the kernels that read the
+// record: where the resource listing shows more scratch with it, see solve_fast, the scalar reads stay).  MPCX_FAST_LDSMULT_CLASSES: the
+// update's multipliers read back from LDS (XL; not in the kernels that compute the record themselves -- lmpc_solve_fused, lmpc_solve_persistent: they sit at
+// their register budgets, see solve_fast -- and only in the variants whose lane holds at most MPCX_FAST_LDSMULT_CHUNKS pairs of a row, as before).
+#ifndef MPCX_FAST_DPP_CLASSES
+#define MPCX_FAST_DPP_CLASSES 0x1FC
+#endif
+#ifndef MPCX_FAST_DPP_CHUNKS
+#define MPCX_FAST_DPP_CHUNKS 4
 #endif
 #ifndef MPCX_FAST_LDSMULT_CLASSES
 #define MPCX_FAST_LDSMULT_CLASSES 0x30
 #endif
-#ifndef MPCX_FAST_XBAR_CHUNKS
-#define MPCX_FAST_XBAR_CHUNKS 4
+#ifndef MPCX_FAST_LDSMULT_CHUNKS
+#define MPCX_FAST_LDSMULT_CHUNKS 4
 #endif
-// entries of a step's pivot row per chunk (two chunks are in flight), one hexadecimal digit per size class: digit CAP / 2, as the bits above
-#ifndef MPCX_FAST_XBAR_CHUNK
-#define MPCX_FAST_XBAR_CHUNK 0x333442400ull
-#endif
-constexpr int fast_xbar_chunk(int cap) { return (int)((MPCX_FAST_XBAR_CHUNK >> (4 * (cap / 2))) & 15) > 0 ? (int)((MPCX_FAST_XBAR_CHUNK >> (4 * (cap / 2))) & 15) : 1; }
-constexpr bool fast_class_bit(unsigned mask, int cap, int chunks) { return chunks <= MPCX_FAST_XBAR_CHUNKS && ((mask >> (cap / 2)) & 1u) != 0; }
+constexpr bool fast_class_bit(unsigned mask, int cap) { return ((mask >> (cap / 2)) & 1u) != 0; }
 // between the stages of the pipelined update: the instruction scheduler moves nothing across (a batch's loads stay ahead of the wait for the batch before it)
 #ifndef MPCX_FAST_STAGE
 #define MPCX_FAST_STAGE() __builtin_amdgcn_sched_barrier(0)
@@ -266,7 +271,62 @@ __device__ __forceinline__ double wave_sum_cost(double v)
 #define MPCX_PROF_PASS
 #endif
 
-template <int CAP, int NLO, int CPZ, int CPG, bool XB = false, bool XL = false>
+// Round 12: e[i] += nm * (lane K's e[i], of this lane's row of sixteen lanes), i < N, each ONE instruction: gfx950's DP-ALU takes the DPP control
+// row_newbcast:K on 64-bit VOP2, so the FMA reads lane K's entry itself -- no v_readlane pair, no SGPR, no broadcast value held in a register.  A single
+// rounding, as fma(nm, p, e).  EVERY LANE HAS TO BE ACTIVE (a DPP source lane that is switched off delivers nothing).
+// One asm statement for all N entries of an elimination step.  The hazard recogniser does not see into it, so the statement opens with its own wait
+// states: a DPP read of a VGPR needs two after the VALU instruction that wrote it (s_nop 1) -- here nm, or an entry the step before wrote.  The five wait
+// states between a VALU write of EXEC and a DPP instruction are not padded: no v_cmpx stands in the elimination, and every step's nm hangs on the pivot's
+// reciprocal (a v_rcp_f64 and four FMAs behind the step's first instruction).  An entry is read (by DPP) and written by the same instruction only, so
+// nothing inside the statement needs a wait.  N <= 14: an asm statement takes thirty operands, a read-write one counts twice.
+#define MPCX_DPP_L(i) "v_fmac_f64_dpp %[e" #i "], %[e" #i "], %[nm] row_newbcast:%c[k] row_mask:0xf bank_mask:0xf\n\t"
+#define MPCX_DPP_O(i) [e##i] "+v"(e[i])
+#define MPCX_DPP_L1 MPCX_DPP_L(0)
+#define MPCX_DPP_L2 MPCX_DPP_L1 MPCX_DPP_L(1)
+#define MPCX_DPP_L3 MPCX_DPP_L2 MPCX_DPP_L(2)
+#define MPCX_DPP_L4 MPCX_DPP_L3 MPCX_DPP_L(3)
+#define MPCX_DPP_L5 MPCX_DPP_L4 MPCX_DPP_L(4)
+#define MPCX_DPP_L6 MPCX_DPP_L5 MPCX_DPP_L(5)
+#define MPCX_DPP_L7 MPCX_DPP_L6 MPCX_DPP_L(6)
+#define MPCX_DPP_L8 MPCX_DPP_L7 MPCX_DPP_L(7)
+#define MPCX_DPP_L9 MPCX_DPP_L8 MPCX_DPP_L(8)
+#define MPCX_DPP_L10 MPCX_DPP_L9 MPCX_DPP_L(9)
+#define MPCX_DPP_L11 MPCX_DPP_L10 MPCX_DPP_L(10)
+#define MPCX_DPP_L12 MPCX_DPP_L11 MPCX_DPP_L(11)
+#define MPCX_DPP_L13 MPCX_DPP_L12 MPCX_DPP_L(12)
+#define MPCX_DPP_L14 MPCX_DPP_L13 MPCX_DPP_L(13)
+#define MPCX_DPP_O1 MPCX_DPP_O(0)
+#define MPCX_DPP_O2 MPCX_DPP_O1, MPCX_DPP_O(1)
+#define MPCX_DPP_O3 MPCX_DPP_O2, MPCX_DPP_O(2)
+#define MPCX_DPP_O4 MPCX_DPP_O3, MPCX_DPP_O(3)
+#define MPCX_DPP_O5 MPCX_DPP_O4, MPCX_DPP_O(4)
+#define MPCX_DPP_O6 MPCX_DPP_O5, MPCX_DPP_O(5)
+#define MPCX_DPP_O7 MPCX_DPP_O6, MPCX_DPP_O(6)
+#define MPCX_DPP_O8 MPCX_DPP_O7, MPCX_DPP_O(7)
+#define MPCX_DPP_O9 MPCX_DPP_O8, MPCX_DPP_O(8)
+#define MPCX_DPP_O10 MPCX_DPP_O9, MPCX_DPP_O(9)
+#define MPCX_DPP_O11 MPCX_DPP_O10, MPCX_DPP_O(10)
+#define MPCX_DPP_O12 MPCX_DPP_O11, MPCX_DPP_O(11)
+#define MPCX_DPP_O13 MPCX_DPP_O12, MPCX_DPP_O(12)
+#define MPCX_DPP_O14 MPCX_DPP_O13, MPCX_DPP_O(13)
+#define MPCX_DPP_CASE(n) if constexpr (N == n) asm volatile("s_nop 1\n\t" MPCX_DPP_L##n : MPCX_DPP_O##n : [nm] "v"(nm), [k] "i"(K))
+constexpr int kDppBlock = 14;
+template <int K, int N>
+__device__ __forceinline__ void fmac_row_bcast(double (&e)[N], const double nm)
+{
+    static_assert(K >= 0 && K < 16 && N >= 1 && N <= kDppBlock, "a row of sixteen lanes, at most fourteen read-write operands");
+    MPCX_DPP_CASE(1); MPCX_DPP_CASE(2); MPCX_DPP_CASE(3); MPCX_DPP_CASE(4); MPCX_DPP_CASE(5); MPCX_DPP_CASE(6); MPCX_DPP_CASE(7);
+    MPCX_DPP_CASE(8); MPCX_DPP_CASE(9); MPCX_DPP_CASE(10); MPCX_DPP_CASE(11); MPCX_DPP_CASE(12); MPCX_DPP_CASE(13); MPCX_DPP_CASE(14);
+}
+template <int K>
+__device__ __forceinline__ double fmac_row_bcast(double acc, const double nm)
+{
+    double e[1] = {acc};
+    fmac_row_bcast<K, 1>(e, nm);
+    return e[0];
+}
+
+template <int CAP, int NLO, int CPZ, int CPG, bool DP = false, bool XL = false>
 __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const int ldz, const int na, const int lane_in,
                                             const int *wsidx, const double *wsb, const double *t0s, double *lam,
                                             const unsigned (&offz)[CPZ], const unsigned (&offg)[CPG],
@@ -323,44 +383,44 @@ __device__ __forceinline__ int ws_solve_reg(const gdp gY, const int ldy, const i
     double mydinv = 1.0;
     unsigned long long dep = 0ull;
     // Gauss-Jordan on [S | y], lane i = row i; a failed pivot test is recorded and looked at once, after the loop
-    // (the step number is a template argument: the crossbar's lane is an immediate of the instruction)
+    // (the step number is a template argument: the DPP form's source lane is an immediate of the instruction)
     auto gj_step = [&]<int K>() {
         dep |= __ballot(!(Sr[K] > pthr)) & (1ull << K);       // lane K's verdict on its pivot
-        // the pivot itself stays a scalar read in both forms: its reciprocal chain starts at once and runs while the crossbar answers
+        // the pivot itself is a scalar read in both forms: its reciprocal chain runs on a wave-uniform value
         const double rinv = pivot_rcp(readlane_d(Sr[K], K));
-        if constexpr (XB) {
-            // Round 10: the pivot row and the right-hand side through the crossbar.  The step's entries -- columns K + 1 .. CAP - 1, then y -- are consumed
-            // in chunks of XCH, chunk c + 1 requested before chunk c's FMAs: a broadcast value is a pair of VGPRs where v_readlane's was a pair of SGPRs,
-            // and a whole row in flight beside the rows of Y requested ahead spills (MPCX_FAST_XBAR_CHUNK).  The requests run with every lane active --
-            // lane K is the source, and an inactive lane reads as 0 -- so each chunk's FMAs are masked on their own (two scalar instructions per chunk).
-            // The crossbar broadcasts within 32 lanes.  The rows live in lanes 0..15, which receive lane K's values as v_readlane delivered them.  Lanes
-            // 32..63 receive lane 32 + K's instead: a row of the padding, all zero and never a pivot row, so their own m is 0 x rinv and their rows stay
-            // zero (or turn NaN where a pivot is not a positive finite number, as the padding in lanes 16..31 does and did: the dep test ends that solve).
-            // Nothing reads those lanes: the ballot keeps bit K < 16 only, lam[] is written by the lanes below CAP, and the update takes no lane's y.
-            constexpr int NE = CAP - K, XCH = fast_xbar_chunk(CAP), NC = (NE + XCH - 1) / XCH;
-            double pv[2][XCH];
-            auto request = [&](const int c) {
+        if constexpr (DP) {
+            // Round 12: the pivot row and the right-hand side by DPP row broadcast inside the FMA (fmac_row_bcast above), one instruction per entry where the
+            // scalar form has two v_readlane_b32 and the FMA.  A DPP source lane has to be active, so there is NO execution mask around the FMAs -- every lane
+            // is active here: ws_solve_reg is called from wave-uniform code, and the region `if (!real)` above closes before the elimination; keep it so --
+            // and lane K, the source, takes the multiplier +0 instead of being masked off.  Why the bits are those of the scalar form:
+            //   * lanes 0..15 are one DPP row and receive lane K's value, which is what v_readlane delivered, and -m is an exact negation: the operands of
+            //     every FMA on the real lanes and on the identity padding below lane 16 are the old ones, and fma(-m, p, S) is S += (-m) p in one rounding;
+            //   * lane K computes S + (+0) S, which is S for every finite S, both signed zeros included (the product has S's sign; x + (+-0) = x, and
+            //     (+-0) + (+-0) of equal signs keeps the sign) -- tests/test_lmpc_round_dpp_probe_gpu.py holds the sign cases;
+            //   * lanes 16..63 hold zero rows and receive lane 16 r + K's zeros instead of lane K's values.  Their own m is 0 x rinv either way, so their rows
+            //     stay zero (or turn NaN where a pivot is not a positive finite number, as the padding in lanes 16..31 did: the dep test ends that solve).
+            //     Nothing reads them: lam[] is written by the lanes below CAP, the ballot keeps bit K < 16, and the update takes no lane's y;
+            //   * a non-finite entry in the pivot row turns lane K's row into NaN where it stayed +-inf.  Such an instance reaches the NaN screen in both
+            //     forms and goes to the fallback (tests/test_lmpc_round_dpp_gpu.py, test_bad_neighbour_in_the_workgroup).
+            if (lane == K) mydinv = rinv;
+            const double nm = lane == K ? 0.0 : -(Sr[K] * rinv);
+            constexpr int NE = CAP - K;              // the step's entries: columns K + 1 .. CAP - 1, then y
+            auto block = [&]<int J0, int N>() {
+                double e[N];
 #pragma unroll
-                for (int u = 0; u < XCH; ++u) {
-                    const int j = K + 1 + c * XCH + u;
-                    if (j <= CAP) pv[c & 1][u] = swizzle_bcast_d<K>(j < CAP ? Sr[j < CAP ? j : 0] : y);
+                for (int u = 0; u < N; ++u) e[u] = J0 + u < CAP ? Sr[J0 + u < CAP ? J0 + u : 0] : y;
+                fmac_row_bcast<K, N>(e, nm);
+#pragma unroll
+                for (int u = 0; u < N; ++u) {
+                    if (J0 + u < CAP) Sr[J0 + u < CAP ? J0 + u : 0] = e[u];
+                    else y = e[u];
                 }
             };
-            request(0);
-            if (lane == K) mydinv = rinv;
-            asm volatile("" : "+v"(mydinv));       // taken here: sunk to the loop's end, the selects keep every step's mask lane == K alive (spilled SGPRs)
-            const double m = Sr[K] * rinv;         // (lane K's is not used)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if (c + 1 < NC) request(c + 1);
-                if (lane != K) {
-#pragma unroll
-                    for (int u = 0; u < XCH; ++u) {
-                        const int j = K + 1 + c * XCH + u;
-                        if (j < CAP) Sr[j] = fma(-m, pv[c & 1][u], Sr[j]);
-                        else if (j == CAP) y = fma(-m, pv[c & 1][u], y);
-                    }
-                }
+            if constexpr (NE <= kDppBlock) block.template operator()<K + 1, NE>();
+            else {
+                static_assert(NE <= 2 * kDppBlock, "two statements hold a step of the largest class");
+                block.template operator()<K + 1, kDppBlock>();
+                block.template operator()<K + 1 + kDppBlock, NE - kDppBlock>();
             }
         } else {
             double pj[CAP];
@@ -1057,21 +1117,25 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
             MPCX_LAP_WAIT(0);                        // 0: working set built and in LDS
             int dep_at = -1;
             double lmax = 0.0;
-            // (SRC = 1, the kernels that compute the record themselves, keep the scalar reads: at 128 and 168 VGPRs every broadcast value kept in a VGPR spills there)
-            constexpr auto xb = [](int cap) { return SRC != 1 && fast_class_bit(MPCX_FAST_XBAR_CLASSES, cap, CPZ + CPG); };
-            constexpr auto xl = [](int cap) { return SRC != 1 && fast_class_bit(MPCX_FAST_LDSMULT_CLASSES, cap, CPZ + CPG); };
+            // (SRC = 1, the kernels that compute the record themselves, keep the update's scalar reads: at 128 and 168 VGPRs every multiplier kept in a VGPR spills
+            // there.  The elimination's DPP form holds no broadcast value in a register, and the resource listing decides where it goes
+            // (profiles/r14_resource_usage_lmpc.txt): with it lmpc_solve_persistent<1, 1> goes from 188 to 204 B of scratch per lane, and lmpc_solve_fused
+            // -- 124 VGPRs and no scratch either way -- is the same instantiation of this function, so SRC = 1 keeps the scalar reads; the four-chunk
+            // variants go from 132 to 172 B of scratch and keep them too)
+            constexpr auto dp = [](int cap) { return SRC != 1 && CPZ + CPG <= MPCX_FAST_DPP_CHUNKS && fast_class_bit(MPCX_FAST_DPP_CLASSES, cap); };
+            constexpr auto xl = [](int cap) { return SRC != 1 && CPZ + CPG <= MPCX_FAST_LDSMULT_CHUNKS && fast_class_bit(MPCX_FAST_LDSMULT_CLASSES, cap); };
             if (na == 0) {
 #pragma unroll
                 for (int c = 0; c < CPZ; ++c) { const double2 v = *reinterpret_cast<const double2 *>(t0s + 128 * c + 2 * lane); wv[2 * c] = v.x; wv[2 * c + 1] = v.y; }
 #pragma unroll
                 for (int c = 0; c < CPG; ++c) { const double2 v = *reinterpret_cast<const double2 *>(gt0s + 128 * c + 2 * lane); gw[2 * c] = v.x; gw[2 * c + 1] = v.y; }
-            } else if (na <= 4) dep_at = ws_solve_reg<4, 1, CPZ, CPG, xb(4), xl(4)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 6) dep_at = ws_solve_reg<6, 5, CPZ, CPG, xb(6), xl(6)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 8) dep_at = ws_solve_reg<8, 7, CPZ, CPG, xb(8), xl(8)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 10) dep_at = ws_solve_reg<10, 9, CPZ, CPG, xb(10), xl(10)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 12) dep_at = ws_solve_reg<12, 11, CPZ, CPG, xb(12), xl(12)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else if (na <= 14) dep_at = ws_solve_reg<14, 13, CPZ, CPG, xb(14), xl(14)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
-            else dep_at = ws_solve_reg<kFastCap, 15, CPZ, CPG, xb(kFastCap), xl(kFastCap)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            } else if (na <= 4) dep_at = ws_solve_reg<4, 1, CPZ, CPG, dp(4), xl(4)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 6) dep_at = ws_solve_reg<6, 5, CPZ, CPG, dp(6), xl(6)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 8) dep_at = ws_solve_reg<8, 7, CPZ, CPG, dp(8), xl(8)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 10) dep_at = ws_solve_reg<10, 9, CPZ, CPG, dp(10), xl(10)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 12) dep_at = ws_solve_reg<12, 11, CPZ, CPG, dp(12), xl(12)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else if (na <= 14) dep_at = ws_solve_reg<14, 13, CPZ, CPG, dp(14), xl(14)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+            else dep_at = ws_solve_reg<kFastCap, 15, CPZ, CPG, dp(kFastCap), xl(kFastCap)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
             if (dep_at >= 0) {
                 // linearly dependent working set: drop the offending row and try again
                 const int q = wsidx[dep_at];
@@ -1802,7 +1866,71 @@ __global__ __launch_bounds__(64) void lmpc_wave_reduce_probe(const double *in, d
     o[128 + lane] = wave_sum_rows_shfl(x);
     o[192 + lane] = wave_sum_rows_swap(x);
 }
+
+// testing aid: ws_solve_reg<CAP, NLO, 1, 1> of the class that na selects (the update's multipliers as the one-chunk product kernels take them), one
+// wavefront per problem, with the elimination in form DP.  o [kWsProbeLen]: dep_at, lmax, lam [16], wv of the 64 lanes [128], gw [128]; what a solve that
+// ends at a dependent row leaves unwritten stays 0
+template <bool DP>
+__device__ __forceinline__ void ws_probe_form(const gdp gY, const int ldy, const int ldz, const int na, const int lane, const int *wsidx, const double *wsb,
+                                              const double *t0s, double *lam, const unsigned (&boffz)[1], const unsigned (&boffg)[1], double *o)
+{
+    double wv[2] = {0.0, 0.0}, gw[2] = {0.0, 0.0}, lmax = 0.0;
+    int dep_at = -1;
+#ifdef MPCX_PROFILE_ROUNDS
+    long long pacc[6] = {0, 0, 0, 0, 0, 0}, plast = 0;
+#endif
+    if (lane < kFastCap + 2) lam[lane] = 0.0;
+    wave_sync();
+    constexpr auto xl = [](int cap) { return 2 <= MPCX_FAST_LDSMULT_CHUNKS && fast_class_bit(MPCX_FAST_LDSMULT_CLASSES, cap); };
+    if (na <= 4) dep_at = ws_solve_reg<4, 1, 1, 1, DP, xl(4)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    else if (na <= 6) dep_at = ws_solve_reg<6, 5, 1, 1, DP, xl(6)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    else if (na <= 8) dep_at = ws_solve_reg<8, 7, 1, 1, DP, xl(8)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    else if (na <= 10) dep_at = ws_solve_reg<10, 9, 1, 1, DP, xl(10)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    else if (na <= 12) dep_at = ws_solve_reg<12, 11, 1, 1, DP, xl(12)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    else if (na <= 14) dep_at = ws_solve_reg<14, 13, 1, 1, DP, xl(14)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    else dep_at = ws_solve_reg<kFastCap, 15, 1, 1, DP, xl(kFastCap)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
+    wave_sync();
+    if (lane == 0) { o[0] = (double)dep_at; o[1] = lmax; }
+    if (lane < kFastCap) o[2 + lane] = lam[lane];
+    o[2 + kFastCap + 2 * lane] = wv[0]; o[2 + kFastCap + 2 * lane + 1] = wv[1];
+    o[2 + kFastCap + 128 + 2 * lane] = gw[0]; o[2 + kFastCap + 128 + 2 * lane + 1] = gw[1];
+    wave_sync();
+}
+// problem p = blockIdx.x: Y + p n ldy (symmetric, n x n, rows 0 .. nz - 1 the z rows and the rest the general rows of the unified index), wsidx / wsb + 16 p,
+// na[p], t0 + p n = [t0 | G t0] by unified index.  Indices are clamped to the matrix, a problem whose na is not in 1 .. 16 is left alone.
+__global__ __launch_bounds__(64) void lmpc_ws_solve_probe(const double *Y, const int n, const int ldy, const int nz, const int *wsidx_in, const double *wsb_in,
+                                                          const int *na_in, const double *t0_in, double *out)
+{
+    __shared__ double t0s[256], lam[kFastCap + 2], wsb[kFastCap + 2];
+    __shared__ int wsidx[kFastCap + 2];
+    const int lane = threadIdx.x, p = blockIdx.x;
+    const int na = __builtin_amdgcn_readfirstlane(na_in[p]);
+    if (na < 1 || na > kFastCap) return;
+    const int ng = n - nz;
+    for (int e = lane; e < 256; e += 64) t0s[e] = e < nz ? t0_in[(size_t)p * n + e] : (e >= 128 && e - 128 < ng ? t0_in[(size_t)p * n + nz + e - 128] : 0.0);
+    if (lane < kFastCap + 2) {
+        const int q = lane < kFastCap ? wsidx_in[(size_t)p * kFastCap + lane] : 0;
+        wsidx[lane] = q < 0 ? 0 : (q < n ? q : n - 1);
+        wsb[lane] = lane < kFastCap ? wsb_in[(size_t)p * kFastCap + lane] : 0.0;
+    }
+    wave_sync();
+    const unsigned boffz[1] = {(unsigned)(2 * lane < nz ? 2 * lane : 0) * 8u}, boffg[1] = {(unsigned)(nz + (2 * lane < ng ? 2 * lane : 0)) * 8u};
+    const gdp gY = gl(Y + (size_t)p * n * ldy);
+    double *o = out + (size_t)p * 2 * kWsProbeLen;
+    ws_probe_form<false>(gY, ldy, nz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, o);
+    ws_probe_form<true>(gY, ldy, nz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, o + kWsProbeLen);
+}
 }  // namespace
+
+int lmpc_debug_ws_solve(const double *Y, int n, int ldy, int nz, const int *wsidx, const double *wsb, const int *na, const double *t0, double *out, int count,
+                        void *stream)
+{
+    // one chunk: at most 128 z rows and 128 general rows, at least one lane pair of each (a lane without a pair re-reads pair 0), a row of Y in whole pairs
+    if (n < 4 || nz < 2 || n - nz < 2 || nz > 128 || n - nz > 128 || nz % 2 != 0 || (n - nz) % 2 != 0 || ldy < n || ldy % 2 != 0) return -2;
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL(lmpc_ws_solve_probe, dim3(count), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), Y, n, ldy, nz, wsidx, wsb, na, t0, out);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *stream)
 {

@@ -85,18 +85,7 @@ __device__ __forceinline__ double readlane_d(double v, int l)
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
 }
-// broadcast lane K's value (K a compile-time constant) through the LDS crossbar: two ds_swizzle_b32 in broadcast mode.  They issue on the LDS port, touch no
-// LDS memory and take no vector issue slot; the result is a vector register, i.e. it feeds an FMA as a vector operand.  The crossbar works within groups of
-// 32 lanes: lanes 0..31 receive lane K's value, lanes 32..63 lane 32 + K's.  Every lane has to be active where this is called (an inactive source lane
-// reads as 0), and the value is there only after the wait on the LDS counter that the compiler places in front of its first use.
-template <int K>
-__device__ __forceinline__ double swizzle_bcast_d(double v)
-{
-    static_assert(K >= 0 && K < 32, "the crossbar broadcasts within groups of 32 lanes");
-    const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), K << 5);      // bit-mask mode: and_mask 0, or_mask K, xor_mask 0
-    const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), K << 5);
-    return __hiloint2double(hi, lo);
-}
+// (the lean kernels' elimination has a form that takes lane K's value inside the FMA instead, fmac_row_bcast in lmpc_fast.hip: MPCX_FAST_DPP_CLASSES)
 constexpr int kRegCap = 16;      // working sets up to this size are factored in registers
 // 1/d for a positive, well-scaled pivot: hardware estimate + two Newton steps (full precision, a third of the latency of the
 // IEEE division sequence, which sits on the dependent chain of every elimination step)

@@ -2310,6 +2310,14 @@ int mpcx_lmpc_debug_wave_reduce(const double *in, double *out, int nvec, void *s
     if (!in || !out || nvec < 0) return fail(MPCX_E_INVALID, "mpcx_lmpc_debug_wave_reduce: null buffer or negative count");
     return mpcx::lmpc_debug_wave_reduce(in, out, nvec, stream) == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, "mpcx_lmpc_debug_wave_reduce: launch failed");
 }
+int mpcx_lmpc_debug_ws_solve(const double *Y, int n, int ldy, int nz, const int *wsidx, const double *wsb, const int *na, const double *t0, double *out,
+                             int count, void *stream)
+{
+    if (!Y || !wsidx || !wsb || !na || !t0 || !out || count < 0) return fail(MPCX_E_INVALID, "mpcx_lmpc_debug_ws_solve: null buffer or negative count");
+    const int rc = mpcx::lmpc_debug_ws_solve(Y, n, ldy, nz, wsidx, wsb, na, t0, out, count, stream);
+    if (rc == -2) return fail(MPCX_E_INVALID, "mpcx_lmpc_debug_ws_solve: nz and n - nz must be even and in 2 .. 128, ldy even and >= n");
+    return rc == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, "mpcx_lmpc_debug_ws_solve: launch failed");
+}
 
 /* ---- testing aid (not part of the reference-facing surface): copy a condensed array to
  * the host so that CPU-only tests can check the set-up without a GPU. ------------------ */
