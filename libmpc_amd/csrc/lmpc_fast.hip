@@ -1,6 +1,6 @@
 // Lean polish kernels of the batched LMPC solve (see the comment at solve_fast); launched by lmpc_launch (lmpc_kernels.hip)
 // through lmpc_launch_fast.
-#include "lmpc_kernel_common.hpp"
+#include "lmpc_solve_common.hpp"
 #include <cstddef>
 #include <cstdlib>
 #include <utility>
@@ -675,8 +675,7 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
 {
     constexpr int NZS = 2 * CPZ, NGS = 2 * CPG, ZP = 128 * CPZ, GPD = 128 * CPG;
     constexpr bool FUSED = SRC != 0;
-    const int nx = M.nx, nu = M.nu, ny = M.ny, ndu = M.ndu, ph = M.ph;
-    const int nz = M.nz, mg = M.mg, ldz = M.ldz, ldg = M.ldg, ldy = M.ldy;
+    const int nu = M.nu, nz = M.nz, mg = M.mg, ldz = M.ldz, ldg = M.ldg, ldy = M.ldy;
     double *t0s = slice, *gt0s = t0s + ZP, *lgs = gt0s + GPD, *ugs = lgs + GPD, *fs = ugs + GPD, *tail = fs + ZP;
     double *lam = tail + 2, *wsb = lam + (kFastCap + 2);
     double *scratch = wsb + (kFastCap + 2) + (kFastCap + 2) / 2 + 1;
@@ -789,26 +788,16 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
     }
     if (outs) {
         if (lane == 0) {
-            outs[0] = cost; outs[1] = solver_status == 1 ? 0 : (solver_status == -2 ? 1 : 2); outs[2] = solver_status;
-            outs[3] = solver_status == -3 ? 0 : 1; outs[4] = cost_pending ? 1.0 : 0.0; outs[5] = rounds_total; outs[6] = infeasible ? 0 : na_last; outs[7] = 2.0;
+            outs[0] = cost; outs[1] = ref_status(solver_status); outs[2] = solver_status;
+            outs[3] = ref_feasible(solver_status); outs[4] = cost_pending ? 1.0 : 0.0; outs[5] = rounds_total; outs[6] = infeasible ? 0 : na_last; outs[7] = 2.0;
         }
     } else if (lane == 0) {
-        if (Bt.cost && !cost_pending) glw(Bt.cost)[b] = cost;
-        if (Bt.solver_status) glw(Bt.solver_status)[b] = solver_status;
-        if (Bt.status) glw(Bt.status)[b] = solver_status == 1 ? 0 : (solver_status == -2 ? 1 : 2);     // LOptimizer.hpp:386-415
-        if (Bt.is_feasible) glw(Bt.is_feasible)[b] = solver_status == -3 ? 0 : 1;
-        if (Bt.iterations) glw(Bt.iterations)[b] = 0;
-        if (Bt.polish_rounds) glw(Bt.polish_rounds)[b] = rounds_total;
-        if (Bt.active_count) glw(Bt.active_count)[b] = infeasible ? 0 : na_last;
+        store_scalars(Bt, b, !cost_pending, cost, solver_status, 0, rounds_total, infeasible ? 0 : na_last);
     }
 
     if (Bt.active_lower && Bt.active_upper) {
-        // bits assembled in LDS (in t0's place: no longer needed), written out as whole words
-        wave_sync();
-        unsigned *bl = reinterpret_cast<unsigned *>(t0s);
-        unsigned *bu = bl + M.active_words;
-        for (int wd = lane; wd < 2 * M.active_words; wd += 64) bl[wd] = 0u;
-        wave_sync();
+        // a working row is active where its multiplier is not zero; t0's place in LDS is free for the words
+        const ActiveBits bits(M, t0s, lane);
         if (!infeasible) {
 #pragma unroll
             for (int s = 0; s < NZS; ++s) {
@@ -816,13 +805,7 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
                 if (e >= nz || actb[s] == 0) continue;
                 const double l = lam[posb[s]];
                 if (!(fabs(l) > dtol_last)) continue;
-                const int side = l < 0 ? -1 : 1;
-                const double lo = lws[e], hi = uws[e];
-                for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
-                    const int rr = GP(boxrow_ref)[p];
-                    if (side < 0 && GP(boxrow_lo)[p] == lo) atomicOr(&bl[rr >> 5], 1u << (rr & 31));
-                    if (side > 0 && GP(boxrow_hi)[p] == hi) atomicOr(&bu[rr >> 5], 1u << (rr & 31));
-                }
+                bits.mark_box(e, l < 0 ? -1 : 1, lws[e], uws[e]);
             }
 #pragma unroll
             for (int s = 0; s < NGS; ++s) {
@@ -830,53 +813,13 @@ __device__ __forceinline__ void fast_finish(const LmpcDev &M, const LmpcBatchDev
                 if (r >= mg || actg[s] == 0) continue;
                 const double l = lam[posg[s]];
                 if (!(fabs(l) > dtol_last)) continue;
-                const int rr = GP(g_refrow)[r];
-                if (l < 0) atomicOr(&bl[rr >> 5], 1u << (rr & 31));
-                else atomicOr(&bu[rr >> 5], 1u << (rr & 31));
+                bits.mark_row(r, l < 0 ? -1 : 1);
             }
         }
-        wave_sync();
-        for (int wd = lane; wd < M.active_words; wd += 64) {
-            glw(Bt.active_lower)[(size_t)b * M.active_words + wd] = bl[wd];
-            glw(Bt.active_upper)[(size_t)b * M.active_words + wd] = bu[wd];
-        }
-        wave_sync();
+        bits.store(Bt, b, lane);
     }
 
-    if (Bt.seq_state || Bt.seq_input || Bt.seq_output) {
-        // OptSequence (LOptimizer.hpp:305-338): roll the model forward with the optimal inputs
-        wave_sync();
-        const gdp gA = GP(A), gB = GP(B), gC = GP(C), gBd = GP(Bd), gDd = GP(Dd), gdm = gl(Bt.dmeas ? Bt.dmeas : M.dmeas_s);
-        const gip gblk = GP(blk);
-        auto dm = [&](int k, int dd) -> double { return ref_at(gdm, Bt.dmeas_bs, Bt.dmeas_ks, b, k, dd); };
-        double *xs0 = scratch, *xs1 = scratch + nx;      // ping-pong state
-        if (lane < nx) xs0[lane] = infeasible ? qnan : gl(Bt.x0)[(size_t)b * nx + lane];
-        wave_sync();
-        for (int i = 0; i <= ph; ++i) {
-            const double *xc = (i & 1) ? xs1 : xs0;
-            double *xn = (i & 1) ? xs0 : xs1;
-            const int k = i > 0 ? i - 1 : 0;
-            if (Bt.seq_state && lane < nx) glw(Bt.seq_state)[((size_t)b * (ph + 1) + i) * nx + lane] = xc[lane];
-            if (Bt.seq_input && lane < nu) {
-                const int ii = (i + 1 <= ph) ? i + 1 : ph;
-                glw(Bt.seq_input)[((size_t)b * (ph + 1) + i) * nu + lane] = stage[gblk[ii] * nu + lane];
-            }
-            if (Bt.seq_output && lane < ny) {
-                double yv = 0;
-                for (int c = 0; c < nx; ++c) yv = fma(gC[lane + c * ny], xc[c], yv);
-                if (M.has_dist) for (int dd = 0; dd < ndu; ++dd) yv = fma(gDd[lane + dd * ny], dm(k, dd), yv);
-                glw(Bt.seq_output)[((size_t)b * (ph + 1) + i) * ny + lane] = yv;
-            }
-            if (i < ph && lane < nx) {
-                double s = 0;
-                for (int c = 0; c < nx; ++c) s = fma(gA[lane + c * nx], xc[c], s);
-                for (int c = 0; c < nu; ++c) s = fma(gB[lane + c * nx], stage[gblk[i + 1] * nu + c], s);
-                if (M.has_dist) for (int dd = 0; dd < ndu; ++dd) s = fma(gBd[lane + dd * nx], dm(i, dd), s);
-                xn[lane] = s;
-            }
-            wave_sync();
-        }
-    }
+    sequence_rollout(M, Bt, b, lane, stage, scratch, infeasible);
     wave_sync();
     if (lane == 0 && !outs) ws[ldz + ldy + 2 * ldg + 1] = cost_pending ? 3.0 : 2.0;     // 2: done, the fallback kernel skips it; 3: lmpc_cost_mfma first
     stamp(ts3);   // 3: unpacked
@@ -1021,38 +964,17 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
     stamp(ts1);   // 1: loaded
 
     if (Bt.warm_lower) {
-        // warm start: the first working set is the previous solve's active set (see admm_solve_one)
-        const unsigned MPCX_GAS *wl = gl(Bt.warm_lower) + (size_t)b * M.active_words;
-        const unsigned MPCX_GAS *wu = gl(Bt.warm_upper) + (size_t)b * M.active_words;
-        const int na = M.nx + M.nu, n1 = M.ph + 1;
-        const int b_box = M.neq_ref, b_out = b_box + n1 * na, b_du = b_out + n1 * M.ny, b_sc = b_du + M.ph * M.nu;
-        auto look = [&](int rr) {
-            if (!Bt.warm_shift) return rr;
-            if (rr < b_out) return rr + na < b_out ? rr + na : rr;
-            if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
-            if (rr < b_sc) return rr + M.nu < b_sc ? rr + M.nu : rr;
-            const int sh = rr < b_sc + n1 ? 1 : MPCX_LINEAR_NC(M);      // (a linear row, DESIGN.md 3.4: the same row one step later is nc rows on)
-            return rr + sh < M.m_ref ? rr + sh : rr;
-        };
+        // the first working set is the previous solve's active set; an equality row (2) stays in whatever the bits say
+        const WarmStart warm(M, Bt, b);
 #pragma unroll
         for (int s = 0; s < NZS; ++s) {
             const int e = 128 * (s >> 1) + 2 * lane + (s & 1);
-            if (e >= nz || actb[s] == 2) continue;
-            const double lo = lws[e], hi = uws[e];
-            int side = 0;
-            for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
-                const int rr = look(GP(boxrow_ref)[p]);
-                if (((wl[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_lo)[p] == lo) side = -1;
-                if (((wu[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_hi)[p] == hi) side = 1;
-            }
-            actb[s] = side;
+            if (e < nz && actb[s] != 2) actb[s] = warm.box_side(e, lws[e], uws[e]);
         }
 #pragma unroll
         for (int s = 0; s < NGS; ++s) {
             const int r = 128 * (s >> 1) + 2 * lane + (s & 1);
-            if (r >= mg || actg[s] == 2) continue;
-            const int rr = look(GP(g_refrow)[r]);
-            actg[s] = ((wl[rr >> 5] >> (rr & 31)) & 1u) ? -1 : (((wu[rr >> 5] >> (rr & 31)) & 1u) ? 1 : 0);
+            if (r < mg && actg[s] != 2) actg[s] = warm.row_side(r);
         }
     }
 
@@ -1138,13 +1060,7 @@ __device__ __forceinline__ void solve_fast(const LmpcDev &M, const LmpcBatchDev 
             else dep_at = ws_solve_reg<kFastCap, 15, CPZ, CPG, dp(kFastCap), xl(kFastCap)>(gY, ldy, ldz, na, lane, wsidx, wsb, t0s, lam, boffz, boffg, wv, gw, lmax MPCX_PROF_PASS);
             if (dep_at >= 0) {
                 // linearly dependent working set: drop the offending row and try again
-                const int q = wsidx[dep_at];
-#pragma unroll
-                for (int s = 0; s < NZS; ++s)
-                    if (128 * (s >> 1) + 2 * lane + (s & 1) == q) actb[s] = 0;
-#pragma unroll
-                for (int s = 0; s < NGS; ++s)
-                    if (ldz + 128 * (s >> 1) + 2 * lane + (s & 1) == q) actg[s] = 0;
+                row_leaves(wsidx[dep_at], ldz, lane, actb, actg);
                 wave_sync();
                 continue;
             }

@@ -21,7 +21,7 @@
 // through the wave's LDS slice; the shared matrices stream from L2 with 16-byte loads that
 // are coalesced across the wavefront and never predicated (out-of-range lanes re-read
 // element 0), so the compiler keeps many of them in flight.
-#include "lmpc_kernel_common.hpp"
+#include "lmpc_solve_common.hpp"
 
 namespace mpcx {
 
@@ -571,13 +571,139 @@ __global__ __launch_bounds__(256) void lmpc_assemble_mfma(const LmpcDev *__restr
 // =====================================================================================
 // the ADMM fallback's solve: one instance per wavefront
 // =====================================================================================
+// The polish's linear solve on a working set of na rows (wsidx, bound values wsb): S = Y[A, A] factored, lam = S^-1 (t0[A] - b_A) left in lam.
+// Returns -1, or the position of the first row that depends on those before it (lam is then undefined).  Up to kRegCap rows in registers, up to
+// kMaxActive in the wavefront's LDS arena S (dg0: the pivots' scale), beyond that in bigS, its slot of a device buffer.
+__device__ __forceinline__ int ws_factor_solve(const gdp gY, const int ldy, const int *wsidx, const double *wsb, const double *nt0, double *lam, double *S,
+                                               double *dg0, gdw bigS, const int na, const int lane)
+{
+    int dep_at = -1;
+    // ---- Schur complement in registers: lane i owns row i; LDL' with the pivot column broadcast by v_readlane (no LDS round trip on the
+    // dependent chain).  The code is fully unrolled, so it is instantiated for six capacities and the smallest that holds the working set
+    // runs (mean |A| is ~6: the 8-row version does most rounds).
+    auto reg_solve = [&](auto capc) {
+        constexpr int CAPB = decltype(capc)::value;
+        const int qi = wsidx[lane < na ? lane : 0];
+        double Sr[CAPB];
+#pragma unroll
+        for (int c = 0; c < CAPB; ++c) {
+            const int qc = wsidx[c < na ? c : 0];
+            Sr[c] = gY[(size_t)qi * ldy + qc];
+        }
+        double y = nt0[qi] - wsb[lane < na ? lane : 0];
+        double dgi = 1.0, mydinv = 1.0;
+#pragma unroll
+        for (int c = 0; c < CAPB; ++c) if (lane == c) dgi = Sr[c];
+#pragma unroll
+        for (int k = 0; k < CAPB; ++k) {
+            if (k < na && dep_at < 0) {
+                const double dk = readlane_d(Sr[k], k);
+                const double d0 = readlane_d(dgi, k);
+                if (!(dk > 1e-11 * d0)) {
+                    dep_at = k;
+                } else {
+                    const double rinv = pivot_rcp(dk);
+                    if (lane == k) mydinv = rinv;
+                    const double lik = Sr[k] * rinv;
+                    // (columns past na only touch lanes past na: no guard, no branch)
+#pragma unroll
+                    for (int j = k + 1; j < CAPB; ++j) {
+                        const double tjk = readlane_d(Sr[k], j);
+                        if (lane >= j) Sr[j] = fma(-lik, tjk, Sr[j]);
+                    }
+                    if (lane > k) Sr[k] = lik;
+                }
+            }
+        }
+        if (dep_at < 0) {
+#pragma unroll
+            for (int k = 0; k < CAPB; ++k) {
+                const double yk = readlane_d(y, k);
+                if (lane > k && lane < na) y = fma(-Sr[k], yk, y);
+            }
+            y *= mydinv;
+            // transpose L through LDS so that the back-substitution also walks registers
+            double *T = S;
+#pragma unroll
+            for (int c = 0; c < CAPB; ++c)
+                if (c < lane && lane < na) T[lane * CAPB + c] = Sr[c];
+            wave_sync();
+#pragma unroll
+            for (int k = 0; k < CAPB; ++k) {
+                const bool ok = k > lane && k < na;
+                const double v = T[(ok ? k : 0) * CAPB + (ok ? lane : 0)];
+                Sr[k] = ok ? v : 0.0;
+            }
+#pragma unroll
+            for (int k = CAPB - 1; k >= 0; --k) {
+                if (k < na) {
+                    const double xk = readlane_d(y, k);
+                    if (lane < k) y = fma(-Sr[k], xk, y);
+                }
+            }
+            if (lane < na) lam[lane] = y;
+            wave_sync();
+        }
+    };
+    // row-by-row Cholesky S = L L' on the working set's rows of Y, then the two triangular solves for lam (in the device buffer every lane-to-lane
+    // hand-over goes through memory with a workgroup-scope fence: the stores must have landed before another lane reads)
+    auto chol_solve = [&](auto Sp, const int sld, auto sync) {
+        for (int p = lane; p < na * na; p += 64) {
+            const int a = p / na, c = p - a * na;
+            Sp[a * sld + c] = gY[(size_t)wsidx[a] * ldy + wsidx[c]];
+        }
+        for (int a = lane; a < na; a += 64) lam[a] = nt0[wsidx[a]] - wsb[a];
+        sync();
+        for (int a = lane; a < na; a += 64) dg0[a] = Sp[a * sld + a];
+        sync();
+        for (int k = 0; k < na; ++k) {
+            const double d = Sp[k * sld + k];
+            if (!(d > 1e-11 * dg0[k])) { dep_at = k; break; }
+            const double sd = sqrt(d);
+            for (int a = k + 1 + lane; a < na; a += 64) Sp[a * sld + k] /= sd;
+            if (lane == 0) Sp[k * sld + k] = sd;
+            sync();
+            for (int a = k + 1 + lane; a < na; a += 64) {
+                const double lik = Sp[a * sld + k];
+                for (int j = k + 1; j <= a; ++j) Sp[a * sld + j] -= lik * Sp[j * sld + k];
+            }
+            sync();
+        }
+        if (dep_at < 0) {
+            for (int k = 0; k < na; ++k) {
+                const double yk = lam[k] / Sp[k * sld + k];
+                wave_sync();
+                if (lane == 0) lam[k] = yk;
+                for (int a = k + 1 + lane; a < na; a += 64) lam[a] -= Sp[a * sld + k] * yk;
+                wave_sync();
+            }
+            for (int k = na - 1; k >= 0; --k) {
+                const double lk = lam[k] / Sp[k * sld + k];
+                wave_sync();
+                if (lane == 0) lam[k] = lk;
+                for (int a = lane; a < k; a += 64) lam[a] -= Sp[k * sld + a] * lk;
+                wave_sync();
+            }
+        }
+    };
+    if (na == 0) return dep_at;
+    if (na <= 4) reg_solve(std::integral_constant<int, 4>{});
+    else if (na <= 6) reg_solve(std::integral_constant<int, 6>{});
+    else if (na <= 8) reg_solve(std::integral_constant<int, 8>{});
+    else if (na <= 10) reg_solve(std::integral_constant<int, 10>{});
+    else if (na <= 12) reg_solve(std::integral_constant<int, 12>{});      // the slow instances live here: |A| of 9..12
+    else if (na <= kRegCap) reg_solve(std::integral_constant<int, kRegCap>{});
+    else if (na <= kMaxActive) chol_solve(S, kSld, [] { wave_sync(); });
+    else chol_solve(bigS, na, [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); });
+    return dep_at;
+}
+
 template <int CPZ, int CPG>
 __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const int b, const int lane,
                                double *stage, double *nt0, double *arena, gdw ws, gdw bigS)
 {
     constexpr int NZS = 2 * CPZ, NGS = 2 * CPG;
-    const int nx = M.nx, nu = M.nu, ny = M.ny, ndu = M.ndu, ph = M.ph;
-    const int nz = M.nz, mg = M.mg, ldz = M.ldz, ldg = M.ldg, ldy = M.ldy;
+    const int nu = M.nu, nz = M.nz, mg = M.mg, ldz = M.ldz, ldg = M.ldg, ldy = M.ldy;
     const double INF = __builtin_huge_val();
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     const gdp gY = GP(Y);
@@ -654,39 +780,17 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
     }
 
     if (Bt.warm_lower) {
-        // warm start: the first working set is the previous solve's active set (bits over the reference's rows,
-        // ProblemBuilder.hpp:814-822: equalities | box on [x; x_u] | outputs | delta-u | scalar).  With warm_shift the
-        // row looked up is the same constraint one step later: the previous tick's step i+1 is this tick's step i.
-        const unsigned MPCX_GAS *wl = gl(Bt.warm_lower) + (size_t)b * M.active_words;
-        const unsigned MPCX_GAS *wu = gl(Bt.warm_upper) + (size_t)b * M.active_words;
-        const int na = M.nx + M.nu, n1 = M.ph + 1;
-        const int b_box = M.neq_ref, b_out = b_box + n1 * na, b_du = b_out + n1 * M.ny, b_sc = b_du + M.ph * M.nu;
-        auto look = [&](int rr) {
-            if (!Bt.warm_shift) return rr;
-            if (rr < b_out) return rr + na < b_out ? rr + na : rr;
-            if (rr < b_du) return rr + M.ny < b_du ? rr + M.ny : rr;
-            if (rr < b_sc) return rr + M.nu < b_sc ? rr + M.nu : rr;
-            const int sh = rr < b_sc + n1 ? 1 : MPCX_LINEAR_NC(M);      // (a linear row, DESIGN.md 3.4: the same row one step later is nc rows on)
-            return rr + sh < M.m_ref ? rr + sh : rr;
-        };
+        // the first working set is the previous solve's active set; an equality row stays in whatever the bits say
+        const WarmStart warm(M, Bt, b);
 #pragma unroll
         for (int s = 0; s < NZS; ++s) {
             const int e = 128 * (s >> 1) + 2 * lane + (s & 1);
-            if (e >= nz || eqb[s]) continue;
-            int side = 0;
-            for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
-                const int rr = look(GP(boxrow_ref)[p]);
-                if (((wl[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_lo)[p] == lw[s]) side = -1;
-                if (((wu[rr >> 5] >> (rr & 31)) & 1u) && GP(boxrow_hi)[p] == uw[s]) side = 1;
-            }
-            actb[s] = side;
+            if (e < nz && !eqb[s]) actb[s] = warm.box_side(e, lw[s], uw[s]);
         }
 #pragma unroll
         for (int s = 0; s < NGS; ++s) {
             const int r = 128 * (s >> 1) + 2 * lane + (s & 1);
-            if (r >= mg || eqg[s]) continue;
-            const int rr = look(GP(g_refrow)[r]);
-            actg[s] = ((wl[rr >> 5] >> (rr & 31)) & 1u) ? -1 : (((wu[rr >> 5] >> (rr & 31)) & 1u) ? 1 : 0);
+            if (r < mg && !eqg[s]) actg[s] = warm.row_side(r);
         }
     }
 
@@ -759,140 +863,10 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
             seen[0] = hsh;
             na_last = na;
             wave_sync();
-            int dep_at = -1;
-            if (na > 0) {
-                // ---- Schur complement in registers: lane i owns row i; LDL' with the pivot column
-                // broadcast by v_readlane (no LDS round trip on the dependent chain).  The code is
-                // fully unrolled, so it is instantiated for three capacities and the smallest that
-                // holds the working set runs (mean |A| is ~6: the 8-row version does most rounds).
-                auto reg_polish = [&](auto capc) {
-                    constexpr int CAPB = decltype(capc)::value;
-                    // ---- Schur complement in registers: lane i owns row i; LDL' with the pivot
-                    // column broadcast by v_readlane (no LDS round trip on the dependent chain)
-                    const int qi = wsidx[lane < na ? lane : 0];
-                    double Sr[CAPB];
-#pragma unroll
-                    for (int c = 0; c < CAPB; ++c) {
-                        const int qc = wsidx[c < na ? c : 0];
-                        Sr[c] = gY[(size_t)qi * ldy + qc];
-                    }
-                    double y = nt0[qi] - wsb[lane < na ? lane : 0];
-                    double dgi = 1.0, mydinv = 1.0;
-#pragma unroll
-                    for (int c = 0; c < CAPB; ++c) if (lane == c) dgi = Sr[c];
-#pragma unroll
-                    for (int k = 0; k < CAPB; ++k) {
-                        if (k < na && dep_at < 0) {
-                            const double dk = readlane_d(Sr[k], k);
-                            const double d0 = readlane_d(dgi, k);
-                            if (!(dk > 1e-11 * d0)) {
-                                dep_at = k;
-                            } else {
-                                const double rinv = pivot_rcp(dk);
-                                if (lane == k) mydinv = rinv;
-                                const double lik = Sr[k] * rinv;
-                                // (columns past na only touch lanes past na: no guard, no branch)
-#pragma unroll
-                                for (int j = k + 1; j < CAPB; ++j) {
-                                    const double tjk = readlane_d(Sr[k], j);
-                                    if (lane >= j) Sr[j] = fma(-lik, tjk, Sr[j]);
-                                }
-                                if (lane > k) Sr[k] = lik;
-                            }
-                        }
-                    }
-                    if (dep_at < 0) {
-#pragma unroll
-                        for (int k = 0; k < CAPB; ++k) {
-                            const double yk = readlane_d(y, k);
-                            if (lane > k && lane < na) y = fma(-Sr[k], yk, y);
-                        }
-                        y *= mydinv;
-                        // transpose L through LDS so that the back-substitution also walks registers
-                        double *T = S;
-#pragma unroll
-                        for (int c = 0; c < CAPB; ++c)
-                            if (c < lane && lane < na) T[lane * CAPB + c] = Sr[c];
-                        wave_sync();
-#pragma unroll
-                        for (int k = 0; k < CAPB; ++k) {
-                            const bool ok = k > lane && k < na;
-                            const double v = T[(ok ? k : 0) * CAPB + (ok ? lane : 0)];
-                            Sr[k] = ok ? v : 0.0;
-                        }
-#pragma unroll
-                        for (int k = CAPB - 1; k >= 0; --k) {
-                            if (k < na) {
-                                const double xk = readlane_d(y, k);
-                                if (lane < k) y = fma(-Sr[k], xk, y);
-                            }
-                        }
-                        if (lane < na) lam[lane] = y;
-                        wave_sync();
-                    }
-                };
-                if (na <= 4) reg_polish(std::integral_constant<int, 4>{});
-                else if (na <= 6) reg_polish(std::integral_constant<int, 6>{});
-                else if (na <= 8) reg_polish(std::integral_constant<int, 8>{});
-                else if (na <= 10) reg_polish(std::integral_constant<int, 10>{});
-                else if (na <= 12) reg_polish(std::integral_constant<int, 12>{});      // the slow instances live here: |A| of 9..12
-                else if (na <= kRegCap) reg_polish(std::integral_constant<int, kRegCap>{});
-                else {
-                    // row-by-row Cholesky S = L L' on the working set's rows of Y, then the two triangular solves for lam: in this
-                    // wavefront's LDS arena up to kMaxActive rows, in its slot of the device buffer beyond (there every lane-to-lane
-                    // hand-over goes through memory with a workgroup-scope fence: the stores must have landed before another lane reads)
-                    auto chol_solve = [&](auto Sp, const int sld, auto sync) {
-                        for (int p = lane; p < na * na; p += 64) {
-                            const int a = p / na, c = p - a * na;
-                            Sp[a * sld + c] = gY[(size_t)wsidx[a] * ldy + wsidx[c]];
-                        }
-                        for (int a = lane; a < na; a += 64) lam[a] = nt0[wsidx[a]] - wsb[a];
-                        sync();
-                        for (int a = lane; a < na; a += 64) dg0[a] = Sp[a * sld + a];
-                        sync();
-                        for (int k = 0; k < na; ++k) {
-                            const double d = Sp[k * sld + k];
-                            if (!(d > 1e-11 * dg0[k])) { dep_at = k; break; }
-                            const double sd = sqrt(d);
-                            for (int a = k + 1 + lane; a < na; a += 64) Sp[a * sld + k] /= sd;
-                            if (lane == 0) Sp[k * sld + k] = sd;
-                            sync();
-                            for (int a = k + 1 + lane; a < na; a += 64) {
-                                const double lik = Sp[a * sld + k];
-                                for (int j = k + 1; j <= a; ++j) Sp[a * sld + j] -= lik * Sp[j * sld + k];
-                            }
-                            sync();
-                        }
-                        if (dep_at < 0) {
-                            for (int k = 0; k < na; ++k) {
-                                const double yk = lam[k] / Sp[k * sld + k];
-                                wave_sync();
-                                if (lane == 0) lam[k] = yk;
-                                for (int a = k + 1 + lane; a < na; a += 64) lam[a] -= Sp[a * sld + k] * yk;
-                                wave_sync();
-                            }
-                            for (int k = na - 1; k >= 0; --k) {
-                                const double lk = lam[k] / Sp[k * sld + k];
-                                wave_sync();
-                                if (lane == 0) lam[k] = lk;
-                                for (int a = lane; a < k; a += 64) lam[a] -= Sp[k * sld + a] * lk;
-                                wave_sync();
-                            }
-                        }
-                    };
-                    if (na <= kMaxActive) chol_solve(S, kSld, [] { wave_sync(); });
-                    else chol_solve(bigS, na, [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); });
-                }
-            }
+            const int dep_at = ws_factor_solve(gY, ldy, wsidx, wsb, nt0, lam, S, dg0, bigS, na, lane);
             if (dep_at >= 0) {
                 // linearly dependent working set: drop the offending row and try again
-                const int q = wsidx[dep_at];
-#pragma unroll
-                for (int s = 0; s < NZS; ++s)
-                    if (128 * (s >> 1) + 2 * lane + (s & 1) == q) actb[s] = 0;
-#pragma unroll
-                for (int s = 0; s < NGS; ++s)
-                    if (ldz + 128 * (s >> 1) + 2 * lane + (s & 1) == q) actg[s] = 0;
+                row_leaves(wsidx[dep_at], ldz, lane, actb, actg);
                 wave_sync();
                 continue;
             }
@@ -1277,30 +1251,11 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
         const int e = 128 * (s >> 1) + 2 * lane + (s & 1);
         if (e < nu) glw(Bt.cmd)[(size_t)b * nu + e] = w[s];
     }
-    if (lane == 0) {
-        if (Bt.cost) glw(Bt.cost)[b] = cost;
-        if (Bt.solver_status) glw(Bt.solver_status)[b] = solver_status;
-        if (Bt.status) {
-            // LOptimizer.hpp:386-415
-            int st = 4;
-            if (solver_status == 1 || solver_status == 2) st = 0;
-            else if (solver_status == -2) st = 1;
-            else if (solver_status == -3) st = 2;
-            glw(Bt.status)[b] = st;
-        }
-        if (Bt.is_feasible) glw(Bt.is_feasible)[b] = (solver_status == 1 || solver_status == 2 || solver_status == -2) ? 1 : 0;
-        if (Bt.iterations) glw(Bt.iterations)[b] = iters;
-        if (Bt.polish_rounds) glw(Bt.polish_rounds)[b] = rounds_total;
-        if (Bt.active_count) glw(Bt.active_count)[b] = polished ? na_last : 0;
-    }
+    if (lane == 0) store_scalars(Bt, b, true, cost, solver_status, iters, rounds_total, polished ? na_last : 0);
 
     if (Bt.active_lower && Bt.active_upper) {
-        // bits assembled in LDS, written out as whole words
-        wave_sync();
-        unsigned *bl = reinterpret_cast<unsigned *>(nt0);
-        unsigned *bu = bl + M.active_words;
-        for (int wd = lane; wd < 2 * M.active_words; wd += 64) bl[wd] = 0u;
-        wave_sync();
+        // at a polished point a working row is active where its multiplier is not zero, at an ADMM iterate by OSQP's rule; nt0 is free for the words
+        const ActiveBits bits(M, nt0, lane);
         if (!infeasible) {
 #pragma unroll
             for (int s = 0; s < NZS; ++s) {
@@ -1315,12 +1270,7 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
                 } else if (rb[s] > 0.0) {
                     side = (zb[s] - lw[s] < -yb[s]) ? -1 : ((uw[s] - zb[s] < yb[s]) ? 1 : 0);
                 }
-                if (side == 0) continue;
-                for (int p = GP(boxrow_ptr)[e]; p < GP(boxrow_ptr)[e + 1]; ++p) {
-                    const int rr = GP(boxrow_ref)[p];
-                    if (side < 0 && GP(boxrow_lo)[p] == lw[s]) atomicOr(&bl[rr >> 5], 1u << (rr & 31));
-                    if (side > 0 && GP(boxrow_hi)[p] == uw[s]) atomicOr(&bu[rr >> 5], 1u << (rr & 31));
-                }
+                if (side != 0) bits.mark_box(e, side, lw[s], uw[s]);
             }
 #pragma unroll
             for (int s = 0; s < NGS; ++s) {
@@ -1335,54 +1285,13 @@ __device__ void admm_solve_one(const LmpcDev &M, const LmpcBatchDev &Bt, const i
                 } else {
                     side = (zg[s] - lg[s] < -yg[s]) ? -1 : ((ug[s] - zg[s] < yg[s]) ? 1 : 0);
                 }
-                if (side == 0) continue;
-                const int rr = GP(g_refrow)[r];
-                if (side < 0) atomicOr(&bl[rr >> 5], 1u << (rr & 31));
-                else atomicOr(&bu[rr >> 5], 1u << (rr & 31));
+                if (side != 0) bits.mark_row(r, side);
             }
         }
-        wave_sync();
-        for (int wd = lane; wd < M.active_words; wd += 64) {
-            glw(Bt.active_lower)[(size_t)b * M.active_words + wd] = bl[wd];
-            glw(Bt.active_upper)[(size_t)b * M.active_words + wd] = bu[wd];
-        }
-        wave_sync();
+        bits.store(Bt, b, lane);
     }
 
-    if (Bt.seq_state || Bt.seq_input || Bt.seq_output) {
-        // OptSequence (LOptimizer.hpp:305-338): roll the model forward with the optimal inputs
-        wave_sync();
-        const gdp gA = GP(A), gB = GP(B), gC = GP(C), gBd = GP(Bd), gDd = GP(Dd), gdm = gl(Bt.dmeas ? Bt.dmeas : M.dmeas_s);
-        const gip gblk = GP(blk);
-        auto dm = [&](int k, int dd) -> double { return ref_at(gdm, Bt.dmeas_bs, Bt.dmeas_ks, b, k, dd); };
-        double *xs0 = arena, *xs1 = arena + nx;      // ping-pong state
-        if (lane < nx) xs0[lane] = infeasible ? qnan : gl(Bt.x0)[(size_t)b * nx + lane];
-        wave_sync();
-        for (int i = 0; i <= ph; ++i) {
-            const double *xc = (i & 1) ? xs1 : xs0;
-            double *xn = (i & 1) ? xs0 : xs1;
-            const int k = i > 0 ? i - 1 : 0;
-            if (Bt.seq_state && lane < nx) glw(Bt.seq_state)[((size_t)b * (ph + 1) + i) * nx + lane] = xc[lane];
-            if (Bt.seq_input && lane < nu) {
-                const int ii = (i + 1 <= ph) ? i + 1 : ph;
-                glw(Bt.seq_input)[((size_t)b * (ph + 1) + i) * nu + lane] = stage[gblk[ii] * nu + lane];
-            }
-            if (Bt.seq_output && lane < ny) {
-                double yv = 0;
-                for (int c = 0; c < nx; ++c) yv = fma(gC[lane + c * ny], xc[c], yv);
-                if (M.has_dist) for (int dd = 0; dd < ndu; ++dd) yv = fma(gDd[lane + dd * ny], dm(k, dd), yv);
-                glw(Bt.seq_output)[((size_t)b * (ph + 1) + i) * ny + lane] = yv;
-            }
-            if (i < ph && lane < nx) {
-                double s = 0;
-                for (int c = 0; c < nx; ++c) s = fma(gA[lane + c * nx], xc[c], s);
-                for (int c = 0; c < nu; ++c) s = fma(gB[lane + c * nx], stage[gblk[i + 1] * nu + c], s);
-                if (M.has_dist) for (int dd = 0; dd < ndu; ++dd) s = fma(gBd[lane + dd * nx], dm(i, dd), s);
-                xn[lane] = s;
-            }
-            wave_sync();
-        }
-    }
+    sequence_rollout(M, Bt, b, lane, stage, arena, infeasible);
     wave_sync();
     stamp();   // 3: unpacked
     if (Bt.dbg_cycles && lane == 0)

@@ -146,6 +146,11 @@ def test_forced_fallback_reaches_the_truth(family):
 # ---------------------------------------------------------------------------------------------
 # 4. warm starts: a wrong seed may cost rounds, never digits
 # ---------------------------------------------------------------------------------------------
+def _warm_seeds(g, words):
+    own = (SF.pack_bits(g["active_lower"], words), SF.pack_bits(g["active_upper"], words))
+    return {"the truth's sets": own, "empty sets": tuple(np.zeros_like(a) for a in own), "another instance's sets": tuple(np.roll(a, 1, axis=0) for a in own)}
+
+
 @pytest.mark.parametrize("family", ["large", "full"])
 def test_warm_starts_from_right_empty_and_wrong_sets(family):
     import torch
@@ -153,9 +158,7 @@ def test_warm_starts_from_right_empty_and_wrong_sets(family):
     g = Q.load(family)
     sp = w["sp"]
     c = _controller(sp, warm=True)
-    words = c.info()["active_words"]
-    own = (SF.pack_bits(g["active_lower"], words), SF.pack_bits(g["active_upper"], words))
-    seeds = {"the truth's sets": own, "empty sets": tuple(np.zeros_like(a) for a in own), "another instance's sets": tuple(np.roll(a, 1, axis=0) for a in own)}
+    seeds = _warm_seeds(g, c.info()["active_words"])
     rounds = {}
     for label, (wl, wu) in seeds.items():
         for shift in (False, True):
@@ -164,6 +167,24 @@ def test_warm_starts_from_right_empty_and_wrong_sets(family):
             _check(r, family, "warm from %s, warm_shift=%s" % (label, shift), keep=Q.compared_rows(sp))
             rounds[(label, shift)] = int(r.polish_rounds.sum().item())
     print("%s: polish rounds in all %s" % (family, rounds))
+
+
+def test_warm_starts_under_the_forced_fallback():
+    """the same seeds with a round cap of 1: the lean kernel gives up after its one round and the fallback kernel reads the warm start itself,
+    then writes the results.  Held as the cold forced fallback is, the share of instances that took ADMM iterations included: no seed is exempt from
+    it.  With the truth's own sets and warm_shift off the lean kernel finishes in its one round the 23 instances whose optimum holds at most 16 rows;
+    the other 41 of 64 reach the fallback (63 or 64 of 64 with the five other seeds)."""
+    import torch
+    w, x0, u0, yref = Q.inputs_of("large")
+    c = _controller(w["sp"], fused=0, warm=True, rounds=1)
+    for label, (wl, wu) in _warm_seeds(Q.load("large"), c.info()["active_words"]).items():
+        for shift in (False, True):
+            warm = (torch.from_numpy(np.ascontiguousarray(wl)).cuda(), torch.from_numpy(np.ascontiguousarray(wu)).cuda())
+            r = _solve(c, x0, u0, yref, warm=warm, warm_shift=shift)
+            it = r.iterations.cpu().numpy()
+            print("large, warm from %s, warm_shift=%s: %d of %d instances took ADMM iterations (max %d)" % (label, shift, int((it > 0).sum()), len(it), int(it.max())))
+            assert (it > 0).mean() > 0.5, (label, shift, (it > 0).mean())
+            _check(r, "large", "forced fallback, warm from %s, warm_shift=%s" % (label, shift))
 
 
 # ---------------------------------------------------------------------------------------------
