@@ -301,7 +301,7 @@ int mpcx_lmpc_sensitivity_host(mpcx_lmpc_t h, double *d_x0, double *d_u0, double
  * again, since this handle's last mpcx_lmpc_solve_batch: the batch must be the one that call solved.  Not differentiated here: the model (mpcx_lmpc_model_sensitivity_batch has it), the terminal weight, soft weights, the coefficients of scalar and linear rows.
  * Asynchronous on `stream`; neither form allocates or copies at launch: the kernel's operand Cq is uploaded by the set-up, the partial sums of
  * reduce = 1 by mpcx_lmpc_param_sens_reserve.  With reduce = 1 and both d_lower and d_upper NULL the bound rows are not computed at all.
- * Banks have no such call. */
+ * Banks (mpcx_lmpc_hetero_*): mpcx_lmpc_hetero_gradient_batch, per instance and summed per controller. */
 typedef struct mpcx_lmpc_param_sens {
     const mpcx_lmpc_batch *solved;
     const double *seed_cmd, *seed_input;          /* [B x nu], [B x (ph+1) x nu]; at least one */
@@ -332,7 +332,7 @@ int mpcx_lmpc_param_sensitivity_host(mpcx_lmpc_t h, const double *seed_cmd, cons
  * The multipliers of the optimum are recomputed from its own sequences, so every reference mode of the solved batch is served.
  * Not differentiated: soft weights, the terminal weight, its target and target map, the coefficients of scalar and linear rows; step 0.
  * Asynchronous on `stream`; the launch allocates nothing: the kernel's operand Xq is built and uploaded by mpcx_lmpc_model_sens_reserve or by
- * the first launch outside a capture after a set-up (a launch under capture without either: MPCX_E_STATE).  Banks have no such call. */
+ * the first launch outside a capture after a set-up (a launch under capture without either: MPCX_E_STATE).  Banks (mpcx_lmpc_hetero_*): mpcx_lmpc_hetero_gradient_batch. */
 typedef struct mpcx_lmpc_model_sens {
     const mpcx_lmpc_batch *solved;
     const double *seed_cmd, *seed_input;          /* [B x nu], [B x (ph+1) x nu]; at least one */
@@ -861,6 +861,40 @@ int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batc
  * words, unknown mode, a vector-Jacobian product without a seed, no model_index and a batch that is not the bank; MPCX_E_UNSUPPORTED: not even a
  * working set of one row fits the kernel's LDS plan. */
 int mpcx_lmpc_hetero_sensitivity_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_sens *s, const int32_t *model_index, void *stream);
+/* Gradients of a solved batch of a bank with respect to the weights, the bounds and the model of the controller each instance was solved with
+ * (DESIGN.md 4.10b): what mpcx_lmpc_param_sensitivity_batch and mpcx_lmpc_model_sensitivity_batch give for one controller, in one launch, every
+ * instance on its own controller; a second small launch adds the instances of each controller up.  One seed per instance (seed_cmd [B x nu] and /
+ * or seed_input [B x (ph+1) x nu], as MPCX_SENS_VJP takes them).
+ *   solved      the descriptor mpcx_lmpc_hetero_solve_batch filled, unchanged since: x0, u0, the references in their modes (MPCX_REF_SHARED:
+ *               each controller's own), seq_output, seq_input, active_lower, active_upper (all required), seq_state (required where a model
+ *               output is asked for) and status (optional: an unsolved instance gets flag 1).  The bank cannot tell whether the descriptor is
+ *               the one it solved: that is the caller's to keep
+ *   d_*         per instance: d_oweight [B x (ny x ph)], d_uweight, d_duweight [B x (nu x ph)], d_lower, d_upper [B x m_ref], d_A [B x (nx x nx)],
+ *               d_B, d_C, d_Bd, d_Dd, every matrix column-major as its setter takes it; layouts, the rules of the bound rows and what is not
+ *               differentiated as documented at mpcx_lmpc_param_sens and mpcx_lmpc_model_sens.  With d_A .. d_Dd all NULL the model part does
+ *               not run at all; d_Bd / d_Dd (and c_Bd / c_Dd) are ignored without exogenous inputs
+ *   c_*         per controller, [K x ..]: row k is the sum of the d_* rows of controller k's instances whose flag is 0, added in the order of
+ *               group_order[group_offsets[k] .. group_offsets[k+1]) without floating-point atomics (two launches give the same bits); n_used [K]
+ *               counts them.  group_order [B] and group_offsets [K+1] are the stable grouping of the instances by controller.  The sums read the
+ *               per-instance rows: a c_* needs its d_*; whether an instance counts is read from flags, where given, else from its rows
+ *   flags       the codes of mpcx_lmpc_sens -- 0 fine, 1 not solved or a model index outside [0, K), 2 dependent working set, 3 beyond the LDS
+ *               plan; every requested d_* row of a flagged instance is NaN
+ * All pointers are device pointers, every output may be NULL and is then written nowhere.  model_index as in mpcx_lmpc_hetero_solve_batch.
+ * Asynchronous on `stream`; allocates nothing.  MPCX_E_INVALID: null bank or descriptor, no solved batch, batch below 1, neither seed, a required
+ * member of `solved` missing, no model_index and a batch that is not the bank, a c_* without its d_* or without the group arrays, n_used without
+ * the group arrays or without flags and any d_*; MPCX_E_UNSUPPORTED: not even a working set of one row fits the kernel's LDS plan. */
+typedef struct mpcx_lmpc_bank_grad {
+    const mpcx_lmpc_batch *solved;
+    const double *seed_cmd, *seed_input;          /* at least one */
+    double *d_oweight, *d_uweight, *d_duweight, *d_lower, *d_upper;
+    double *d_A, *d_B, *d_C, *d_Bd, *d_Dd;
+    int32_t *flags;                               /* optional [B] */
+    const int32_t *group_order, *group_offsets;   /* [B], [K+1]; required iff any c_* or n_used is set */
+    double *c_oweight, *c_uweight, *c_duweight, *c_lower, *c_upper, *c_A, *c_B, *c_C, *c_Bd, *c_Dd;
+    int32_t *n_used;                              /* optional [K] */
+} mpcx_lmpc_bank_grad;
+int mpcx_lmpc_hetero_gradient_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_bank_grad *g, const int32_t *model_index, void *stream);
+int mpcx_lmpc_bank_grad_size(void);    /* sizeof(mpcx_lmpc_bank_grad) */
 /* The closed loop of a bank: a tick is mpcx_lmpc_hetero_solve_batch on the loop's own buffers followed by the advance kernel, captured as for a
  * controller (two graphs with carry_working_set).  The loop is the type mpcx_lmpc_loop_create returns: mpcx_lmpc_loop_run, _destroy, _debug_replay
  * and _debug_tick serve both.  The descriptor's rules are mpcx_lmpc_loop_create's; without a model_index the batch must be the bank.  model_index

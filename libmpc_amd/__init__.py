@@ -8,9 +8,9 @@ There is no CPU fallback: a missing libmpcx.so or GPU raises.
 from .lmpc import (LMPC, HorizonSlice, LParameters, Result, OptSequence, BatchResult, SensitivityResult, ParamSensitivityResult, ModelSensitivityResult, ClosedLoopResult, ResultStatus, SolutionStats, inf)
 from .nlmpc import NLMPC, NLMPCEvaluator, NLParameters, NLClosedLoopResult
 from ._capi import MpcxError
-from .autograd import lmpc_cmd, lmpc_cmd_params, lmpc_cmd_model
-from .bank import LMPCBank, LMPCHetero, group_by_model
+from .autograd import lmpc_cmd, lmpc_cmd_params, lmpc_cmd_model, lmpc_cmd_fleet
+from .bank import LMPCBank, LMPCHetero, BankGradientResult, group_by_model
 
 __all__ = ["LMPC", "NLMPC", "NLMPCEvaluator", "HorizonSlice", "LParameters", "NLParameters", "Result", "OptSequence",
-           "BatchResult", "SensitivityResult", "ParamSensitivityResult", "ModelSensitivityResult", "lmpc_cmd", "lmpc_cmd_params", "lmpc_cmd_model", "ClosedLoopResult", "NLClosedLoopResult", "ResultStatus", "MpcxError", "SolutionStats", "inf", "LMPCBank", "LMPCHetero", "group_by_model"]
+           "BatchResult", "SensitivityResult", "ParamSensitivityResult", "ModelSensitivityResult", "lmpc_cmd", "lmpc_cmd_params", "lmpc_cmd_model", "lmpc_cmd_fleet", "ClosedLoopResult", "NLClosedLoopResult", "ResultStatus", "MpcxError", "SolutionStats", "inf", "LMPCBank", "LMPCHetero", "BankGradientResult", "group_by_model"]
 __version__ = "0.1.0"

@@ -101,6 +101,15 @@ class ModelSens(C.Structure):
                 ("flags", C.c_void_p), ("n_used", C.c_void_p)]
 
 
+class BankGrad(C.Structure):
+    """mpcx_lmpc_bank_grad: gradients of a bank's solved batch on weights, bounds and models (device pointers; `solved` points to a Batch)"""
+    _fields_ = ([("solved", C.c_void_p), ("seed_cmd", C.c_void_p), ("seed_input", C.c_void_p)] +
+                [("d_" + n, C.c_void_p) for n in ("oweight", "uweight", "duweight", "lower", "upper", "A", "B", "C", "Bd", "Dd")] +
+                [("flags", C.c_void_p), ("group_order", C.c_void_p), ("group_offsets", C.c_void_p)] +
+                [("c_" + n, C.c_void_p) for n in ("oweight", "uweight", "duweight", "lower", "upper", "A", "B", "C", "Bd", "Dd")] +
+                [("n_used", C.c_void_p)])
+
+
 class Info(C.Structure):
     _fields_ = [("n_ref", C.c_int), ("m_ref", C.c_int), ("neq_ref", C.c_int), ("nz", C.c_int), ("mg", C.c_int),
                 ("active_words", C.c_int), ("kernel_variant", C.c_int),
@@ -142,7 +151,7 @@ EXPORTS = [
     "mpcx_comm_get_unique_id", "mpcx_comm_create", "mpcx_comm_destroy", "mpcx_comm_rank", "mpcx_comm_world", "mpcx_allgather_u",
     "mpcx_lmpc_hetero_create", "mpcx_lmpc_hetero_destroy", "mpcx_lmpc_hetero_get_info", "mpcx_lmpc_hetero_solve_batch",
     "mpcx_lmpc_hetero_time_solve_batch", "mpcx_lmpc_hetero_create_ex", "mpcx_lmpc_hetero_debug_get", "mpcx_lmpc_hetero_loop_create",
-    "mpcx_lmpc_hetero_sensitivity_batch",
+    "mpcx_lmpc_hetero_sensitivity_batch", "mpcx_lmpc_hetero_gradient_batch", "mpcx_lmpc_bank_grad_size",
     # profiling and testing aids (declared in include/mpcx.h under that heading)
     "mpcx_lmpc_set_total_batch", "mpcx_lmpc_debug_time_kernels", "mpcx_lmpc_debug_get", "mpcx_lmpc_debug_setup_counts", "mpcx_lmpc_debug_use_fused",
     "mpcx_lmpc_debug_force_generic", "mpcx_lmpc_debug_set_rounds", "mpcx_lmpc_debug_set_cycle_buffer", "mpcx_lmpc_debug_wave_reduce", "mpcx_lmpc_debug_ws_solve",
@@ -230,6 +239,7 @@ def lib():
         _lib.mpcx_lmpc_sensitivity_batch.argtypes = [C.c_void_p] * 3
         _lib.mpcx_lmpc_sensitivity_host.argtypes = [C.c_void_p] * 5
         _lib.mpcx_lmpc_hetero_sensitivity_batch.argtypes = [C.c_void_p] * 4
+        _lib.mpcx_lmpc_hetero_gradient_batch.argtypes = [C.c_void_p] * 4
         _lib.mpcx_lmpc_param_sensitivity_batch.argtypes = [C.c_void_p] * 3
         _lib.mpcx_lmpc_param_sens_reserve.argtypes = [C.c_void_p, C.c_int]
         _lib.mpcx_lmpc_param_sensitivity_host.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7

@@ -24,7 +24,14 @@ answers MPCX_E_STATE after a change or a new set-up); keep one controller per gr
 differentiates the same first move with respect to the model: what fitting A, B, C of a fleet's controller to logged or expert closed-loop
 behaviour needs.  Forward sets the model (and the disturbance matrices, where given), sets the controller up and solves; backward is one launch of
 the vector-Jacobian product and one of LMPC.modelSensitivityBatch with reduce=True (DESIGN.md 4.10).  The controller keeps every other setting;
-the rules of lmpc_cmd_params hold."""
+the rules of lmpc_cmd_params hold.
+
+    cmd = lmpc_cmd_fleet(controllers, x0, u0, yref, model, OWeight=..., A=..., ...)
+
+is the fleet's version of the three: K controllers, instance b solved by controller model[b], every parameter tensor with K in front.  Forward
+sets the given tensors on every controller, builds a fresh bank (LMPCHetero) from them and solves; backward is one vector-Jacobian launch
+ and one of LMPCHetero.gradientBatch with per_controller=True, whose per-controller rows are the gradients
+of the K-leading tensors."""
 from __future__ import annotations
 
 _FUNCTION = None
@@ -174,6 +181,88 @@ def lmpc_cmd_model(controller, x0, u0, yref, A, B, C, Bd=None, Dd=None, return_s
     if (Bd is None) != (Dd is None):
         raise ValueError("lmpc_cmd_model: Bd and Dd go together")
     cmd, status = _model_function().apply(controller, x0, u0, yref, as_t(A), as_t(B), as_t(C), as_t(Bd), as_t(Dd))
+    return (cmd, status) if return_status else cmd
+
+
+_FLEET_FUNCTION = None
+_FLEET_PARAMS = ("oweight", "uweight", "duweight", "A", "B", "C", "Bd", "Dd")
+
+
+def _fleet_function():
+    global _FLEET_FUNCTION
+    if _FLEET_FUNCTION is not None:
+        return _FLEET_FUNCTION
+    import torch
+
+    class LmpcCmdFleet(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, controllers, bank_model, device, x0, u0, yref, ow, uw, dw, A, B, Cm, Bd, Dd):
+            from .bank import LMPCHetero
+            host = lambda t, k: t[k].detach().cpu().numpy()
+            for k, c in enumerate(controllers):
+                if ow is not None and not c.setObjectiveWeights(host(ow, k), host(uw, k), host(dw, k)):
+                    raise ValueError("lmpc_cmd_fleet: controller %d refused the weights" % k)
+                if A is not None and not c.setStateSpaceModel(host(A, k), host(B, k), host(Cm, k)):
+                    raise ValueError("lmpc_cmd_fleet: controller %d refused the model" % k)
+                if Bd is not None and not c.setDisturbances(host(Bd, k), host(Dd, k)):
+                    raise ValueError("lmpc_cmd_fleet: controller %d refused the disturbance matrices" % k)
+            bank = LMPCHetero(controllers, device=device)
+            res = bank.optimizeBatch(x0.detach(), u0.detach(), model=bank_model[0], yref=None if yref is None else yref.detach(), want_active=True,
+                                     want_sequence=True)
+            ctx.bank, ctx.res = bank, res                      # (the bank lives as long as the graph: backward launches on it)
+            ctx.has_yref = yref is not None
+            ctx.mark_non_differentiable(res.status)
+            return res.cmd, res.status
+
+        @staticmethod
+        def backward(ctx, grad_cmd, _grad_status):
+            bank, res = ctx.bank, ctx.res
+            seed = grad_cmd.contiguous()
+            need = ctx.needs_input_grad
+            g = [None] * 14
+            want = tuple(n for n, k in zip(("x0", "u0", "yref"), need[3:6]) if k)
+            if want:
+                s = bank.sensitivityBatch(res.active_lower, res.active_upper, model=res._model, status=res.status, seed_cmd=seed, want=want)
+                g[3], g[4], g[5] = s.d_x0, s.d_u0, (s.d_yref if ctx.has_yref else None)
+            wantp = tuple(n for n, k in zip(_FLEET_PARAMS, need[6:14]) if k)
+            if wantp:
+                r = bank.gradientBatch(res, seed_cmd=seed, per_controller=True, want=wantp)
+                ctx.gradient = r                               # (testing aid: what the launch returned)
+                for i, n in enumerate(_FLEET_PARAMS):
+                    g[6 + i] = getattr(r, "c_" + n) if n in wantp else None
+            return tuple(g)
+
+    _FLEET_FUNCTION = LmpcCmdFleet
+    return _FLEET_FUNCTION
+
+
+def lmpc_cmd_fleet(controllers, x0, u0, yref, model=None, OWeight=None, UWeight=None, DeltaUWeight=None, A=None, B=None, C=None, Bd=None, Dd=None,
+                   return_status=False, device=0):
+    """cmd [B, nu] of a fleet: K configured controllers (libmpc_amd.LMPC; host-only handles are enough) of equal dimensions, instance b solved
+    by controller model[b] (None: instance b = controller b, B = K), at x0 [B, nx], u0 [B, nu] and the per-instance output reference yref
+    [B, ny] (None: each controller's own).  Each given parameter tensor has K in front -- OWeight [K, ny, ph], UWeight, DeltaUWeight [K, nu, ph]
+    (all three or none), A [K, nx, nx], B [K, nx, nu], C [K, ny, nx] (all three or none), Bd [K, nx, ndu], Dd [K, ny, ndu] (both or none) -- and
+    is set on every controller, which keeps it afterwards; cmd is differentiable with respect to all of them and to x0, u0, yref.  The gradient
+    of row k of a parameter tensor is the sum over controller k's instances in their order in the batch; an instance that was not solved or
+    whose working set is dependent contributes nothing to it.  A loss that needs no model gradient never runs the model part of the kernel.
+    The rules of lmpc_cmd_params hold; the bank of the forward pass is kept by the graph.  return_status: (cmd, status) instead."""
+    import torch
+    controllers = list(controllers)
+    if not controllers:
+        raise ValueError("lmpc_cmd_fleet: at least one controller")
+    for group, what in (((OWeight, UWeight, DeltaUWeight), "OWeight, UWeight and DeltaUWeight"), ((A, B, C), "A, B and C"), ((Bd, Dd), "Bd and Dd")):
+        if any(t is None for t in group) and not all(t is None for t in group):
+            raise ValueError("lmpc_cmd_fleet: %s go together" % what)
+    for t in (OWeight, UWeight, DeltaUWeight, A, B, C, Bd, Dd):
+        if t is not None and (len(t.shape) != 3 or t.shape[0] != len(controllers)):
+            raise ValueError("lmpc_cmd_fleet: every parameter tensor is [K, rows, columns], K the number of controllers")
+    dev = torch.device("cuda", int(device))
+    as_t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64)).to(device=dev, dtype=torch.float64)
+    x0, u0, yref = as_t(x0), as_t(u0), as_t(yref)
+    if yref is not None and yref.dim() != 2 and yref.requires_grad:
+        raise ValueError("lmpc_cmd_fleet differentiates a per-instance output reference [B, ny]; a per-step reference has no gradient here")
+    params = [as_t(t) for t in (OWeight, UWeight, DeltaUWeight, A, B, C, Bd, Dd)]
+    cmd, status = _fleet_function().apply(controllers, (model,), int(device), x0, u0, yref, *params)
     return (cmd, status) if return_status else cmd
 
 

@@ -12,6 +12,8 @@ A, B, C, weights, bounds) behind ONE set of kernels, each instance reading its o
 streams."""
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
@@ -32,6 +34,42 @@ def group_by_model(model, n_models: int):
     counts = np.bincount(model, minlength=n_models)
     offsets = np.concatenate([[0], np.cumsum(counts)])
     return order, offsets
+
+
+PARAM_OUTPUTS = ("oweight", "uweight", "duweight", "lower", "upper")
+MODEL_OUTPUTS = ("A", "B", "C", "Bd", "Dd")
+
+
+@dataclass
+class BankGradientResult:
+    """Gradients of sum(seed * output) of a bank's solved batch with respect to the weights, the bounds and the model of the controller each
+    instance was solved with (mpcx_lmpc_hetero_gradient_batch), device tensors.  Per instance: d_oweight [B, ny, ph],
+    d_uweight, d_duweight [B, nu, ph], d_lower, d_upper [B, m_ref], d_A [B, nx, nx], d_B [B, nx, nu], d_C [B, ny, nx], d_Bd [B, nx, ndu],
+    d_Dd [B, ny, ndu], indexed as the setters' matrices (None: not asked for; d_Bd, d_Dd None without exogenous inputs); the rows of a flagged
+    instance are NaN.  Per controller (per_controller=True): c_* the same with K in front, row k the sum over controller k's instances whose
+    flag is 0 in their order in the batch, and n_used [K] how many those were.  flags [B] as SensitivityResult's."""
+    d_oweight: "object" = None
+    d_uweight: "object" = None
+    d_duweight: "object" = None
+    d_lower: "object" = None
+    d_upper: "object" = None
+    d_A: "object" = None
+    d_B: "object" = None
+    d_C: "object" = None
+    d_Bd: "object" = None
+    d_Dd: "object" = None
+    flags: "object" = None
+    c_oweight: "object" = None
+    c_uweight: "object" = None
+    c_duweight: "object" = None
+    c_lower: "object" = None
+    c_upper: "object" = None
+    c_A: "object" = None
+    c_B: "object" = None
+    c_C: "object" = None
+    c_Bd: "object" = None
+    c_Dd: "object" = None
+    n_used: "object" = None
 
 
 class LMPCBank:
@@ -166,6 +204,7 @@ class LMPCHetero(_LoopFrontEnd):
                                            want_sequence=want_sequence, warm=warm, warm_shift=warm_shift)
         self.launch(b, mi, stream)
         res._inputs = keep
+        res._batch, res._model = b, mi         # the descriptor and the map: gradientBatch differentiates the batch they describe
         if sensitivities:
             res.sensitivities = self.sensitivityBatch(res.active_lower, res.active_upper, model=mi, status=res.status, stream=stream)
         return res
@@ -210,6 +249,90 @@ class LMPCHetero(_LoopFrontEnd):
         d, out, keep, mi = self.make_sensitivity(active_lower, active_upper, model, status, seed_cmd, seed_input, want)
         self.launch_sensitivity(d, mi, stream, keep)
         out._inputs = keep[:5] + (mi,)
+        return out
+
+    # -- gradients on weights, bounds and models of a solved batch (mpcx_lmpc_hetero_gradient_batch) --------------
+    def make_gradient(self, result, model=None, seed_cmd=None, seed_input=None, per_controller=False, want=PARAM_OUTPUTS + MODEL_OUTPUTS):
+        """Allocate outputs and fill the mpcx_lmpc_bank_grad descriptor for `result`: what optimizeBatch(..., want_active=True,
+        want_sequence=True) of this bank returned (or the Batch descriptor of make_batch, whose tensors the caller keeps alive), with the
+        `model` it was solved with.  per_controller: the sums over each controller's instances besides, the grouping (group_by_model) built
+        and uploaded here, so that the launch allocates nothing.  Returns (BankGrad, BankGradientResult, keepalive, model index on the
+        device | None)."""
+        b = getattr(result, "_batch", result)
+        if not isinstance(b, _capi.Batch):
+            raise ValueError("gradientBatch needs the result of optimizeBatch(want_active=True, want_sequence=True) or a Batch descriptor")
+        unknown = [n for n in want if n not in PARAM_OUTPUTS + MODEL_OUTPUTS]
+        if unknown or not want:
+            raise ValueError("want: names out of %s" % (PARAM_OUTPUTS + MODEL_OUTPUTS,))
+        with_model = any(n in want for n in ("A", "B", "C")) or (self.ndu > 0 and any(n in want for n in ("Bd", "Dd")))
+        if not (b.active_lower and b.active_upper and b.seq_output and b.seq_input and (b.seq_state or not with_model)):
+            raise ValueError("the batch must have been solved with want_active=True and want_sequence=True")
+        if seed_cmd is None and seed_input is None:
+            raise ValueError("a gradient needs seed_cmd or seed_input")
+        B = int(b.batch)
+        if model is None and B != self.count:
+            raise ValueError("model: without it the batch must be the bank (instance b = controller b)")
+        _, dev = self._torch()
+        mi = self._model_index(model, B)
+        sc = self._dev(torch, dev, seed_cmd, (B, self.nu))
+        si = self._dev(torch, dev, seed_input, (B, self.ph + 1, self.nu))
+        f64, K = torch.float64, self.count
+        # (the kernel writes each matrix column-major, as its setter reads it: allocated [columns, rows], handed out transposed)
+        shapes = {"oweight": (self.ph, self.ny), "uweight": (self.ph, self.nu), "duweight": (self.ph, self.nu), "lower": (self.m_ref,),
+                  "upper": (self.m_ref,), "A": (self.nx, self.nx), "B": (self.nu, self.nx), "C": (self.nx, self.ny), "Bd": (self.ndu, self.nx),
+                  "Dd": (self.ndu, self.ny)}
+        names = [n for n in PARAM_OUTPUTS + MODEL_OUTPUTS if n in want and int(np.prod(shapes[n])) > 0]
+        dt = {n: torch.empty((B,) + shapes[n], dtype=f64, device=dev) for n in names}
+        ct = {n: torch.empty((K,) + shapes[n], dtype=f64, device=dev) for n in names} if per_controller else {}
+        flags = torch.empty((B,), dtype=torch.int32, device=dev)
+        order = offsets = n_used = None
+        if per_controller:
+            idx = np.arange(B) if mi is None else mi.cpu().numpy()
+            o, off = group_by_model(idx, K)
+            order = torch.from_numpy(o.astype(np.int32)).to(dev)
+            offsets = torch.from_numpy(off.astype(np.int32)).to(dev)
+            n_used = torch.zeros((K,), dtype=torch.int32, device=dev)
+        tr = lambda t: t.transpose(-1, -2) if t.dim() == 3 else t
+        out = BankGradientResult(flags=flags, n_used=n_used, **{"d_" + n: tr(t) for n, t in dt.items()}, **{"c_" + n: tr(t) for n, t in ct.items()})
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        d = _capi.BankGrad()
+        d.solved = C.cast(C.pointer(b), C.c_void_p)
+        d.seed_cmd, d.seed_input, d.flags = ptr(sc), ptr(si), ptr(flags)
+        for n in PARAM_OUTPUTS + MODEL_OUTPUTS:
+            setattr(d, "d_" + n, ptr(dt.get(n)))
+            setattr(d, "c_" + n, ptr(ct.get(n)))
+        d.group_order, d.group_offsets, d.n_used = ptr(order), ptr(offsets), ptr(n_used)
+        keep = (b, result, sc, si, flags, order, offsets, n_used, mi) + tuple(dt.values()) + tuple(ct.values())
+        return d, out, keep, mi
+
+    def launch_gradient(self, desc, mi=None, stream=None, keep=None):
+        """One asynchronous launch (two kernels with per-controller sums) for a descriptor built by make_gradient(); streams as in
+        LMPC.launch()."""
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+            for t in (keep or ()):
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(s)
+        check(self._lib.mpcx_lmpc_hetero_gradient_batch(self._h, C.byref(desc), None if mi is None else C.c_void_p(mi.data_ptr()),
+                                                        C.c_void_p(s.cuda_stream)))
+
+    def gradientBatch(self, result, model=None, seed_cmd=None, seed_input=None, per_controller=False, stream=None,
+                      want=PARAM_OUTPUTS + MODEL_OUTPUTS) -> BankGradientResult:
+        """The gradient of sum(seed_cmd * cmd) + sum(seed_input * input sequence) of a solved batch with respect to OWeight, UWeight,
+        DeltaUWeight, to every bound of the QP and to every entry of A, B, C, Bd, Dd of the controller each instance was solved with: one
+        launch after the solve, on each instance's active set.  result: what optimizeBatch(..., want_active=True, want_sequence=True) of this
+        bank returned, unchanged since; model as it was given there (None: the one the result remembers).  per_controller: the sums over each
+        controller's instances as well (in a fixed order: the same bits every time).  want: which outputs to compute; without a model output
+        the model part of the kernel does not run."""
+        if model is None:
+            model = getattr(result, "_model", None)
+        d, out, keep, mi = self.make_gradient(result, model, seed_cmd, seed_input, per_controller, want)
+        self.launch_gradient(d, mi, stream, keep)
+        out._inputs = keep
         return out
 
     # -- the closed loop on the device (mpcx_lmpc_hetero_loop_create*; the loop itself is _LoopFrontEnd's) ---------------------

@@ -15,8 +15,9 @@
 //
 // One wavefront per instance, the whole kernel without a workgroup barrier.  Every matrix differs from instance to instance: there is no shared
 // operand for the matrix pipe.  The seeds of an instance (nu unit seeds in Jacobian mode) are served one after another on one factor of S.
-// The working-set decode, the factor of S, the solve on it and the seed scatter are lmpc_sens_common.hpp's, shared with the other sensitivity kernels.
-#include "lmpc_sens_common.hpp"
+// The working-set decode, the factor of S, the solve on it and the seed scatter are lmpc_sens_common.hpp's, shared with the other sensitivity kernels;
+// the roll-out of the direction is lmpc_bank_common.hpp's, shared with the bank's gradient kernel (lmpc_bank_grad.hip).
+#include "lmpc_bank_common.hpp"
 
 namespace mpcx {
 
@@ -29,7 +30,6 @@ struct LmpcBankSensDev {
     int cap;                                             // rows of S a wavefront's LDS slice holds
 };
 
-__host__ __device__ inline int bank_even(int n) { return (n + 1) & ~1; }
 // a wavefront's slice: S (packed lower triangle) | its original diagonal | one right-hand side | the working set's unified indices and the kind,
 // step and component of its general rows (ints) | blk (ints) | A, B, C | p, q | dx [(ph + 1) x nx] and P dx_ph | do [ph x ny] | gam [(ph + 1) x nx] |
 // the sums of d_u0.  Nothing a recursion over the horizon reads lies in HBM: a step of it costs LDS latency, not a trip to memory
@@ -37,36 +37,6 @@ __host__ __device__ inline size_t bank_wave_len(int cap, int nx, int nu, int ny,
 {
     return (size_t)cap * (cap + 1) / 2 + 2 * (size_t)cap + 2 * (size_t)cap + (size_t)(ph + 2) / 2 + (size_t)nx * (nx + nu) + (size_t)ny * nx +
            2 * (size_t)bank_even(nz) + (size_t)(ph + 2) * nx + (size_t)ph * ny + (size_t)(ph + 1) * nx + nu;
-}
-
-// the direction's roll-out through the instance's own model (As, Bs, Cs column-major and blk in LDS): dx [(ph + 1) x nx] by the chain of ph steps,
-// then the outputs of every step at once, do[(i - 1) ny + j] = Wy_i (C dx_i)[j] for i = 1 .. ph
-__device__ inline void bank_rollout(const double *As, const double *Bs, const double *Cs, gdp Wy, const int *blk, const double *q, int nx, int nu, int ny,
-                                    int ph, int lane, double *dx, double *dov)
-{
-    for (int a = lane; a < nx; a += 64) dx[a] = 0.0;
-    wave_sync();
-    for (int i = 1; i <= ph; ++i) {
-        const double *dv = q + blk[i] * nu, *xp = dx + (size_t)(i - 1) * nx;
-        for (int a = lane; a < nx; a += 64) {
-            double s = 0.0;
-#pragma unroll 4
-            for (int c = 0; c < nx; ++c) s = fma(As[a + (size_t)c * nx], xp[c], s);
-#pragma unroll 4
-            for (int j = 0; j < nu; ++j) s = fma(Bs[a + (size_t)j * nx], dv[j], s);
-            dx[(size_t)i * nx + a] = s;
-        }
-        wave_sync();
-    }
-    for (int t = lane; t < ph * ny; t += 64) {
-        const int i = t / ny + 1, j = t - (i - 1) * ny;
-        const double *xi = dx + (size_t)i * nx;
-        double s = 0.0;
-#pragma unroll 4
-        for (int c = 0; c < nx; ++c) s = fma(Cs[j + (size_t)c * ny], xi[c], s);
-        dov[t] = Wy[j + (size_t)i * ny] * s;
-    }
-    wave_sync();
 }
 
 __global__ __launch_bounds__(256) void lmpc_bank_sensitivity(const LmpcBankSensDev Sd)

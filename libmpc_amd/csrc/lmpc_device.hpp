@@ -222,6 +222,35 @@ struct LmpcBankSensArgs {
 // or its configuration failed
 int lmpc_bank_sens_launch(const LmpcDev &m, const LmpcBankSensArgs &a, void *stream);
 
+// Gradients of a bank's solved batch with respect to the weights, the bounds and the model of each instance's controller (lmpc_bank_grad.hip,
+// DESIGN.md 4.10b).  All device pointers; the references as LmpcBatchDev's accessors, a null array (bs = 0) being each controller's own.  One seed
+// per instance.  d_*: [B x ..] per instance, laid out as LmpcParamSensArgs / LmpcModelSensArgs; c_*: [K x ..] per controller, row k the sum of the
+// rows of controller k's instances whose flag is 0 in the order of group_order[group_offsets[k] .. group_offsets[k + 1]) (a second kernel that
+// reads the d_* arrays: every c_* needs its d_*)
+struct LmpcBankGradArgs {
+    int batch;
+    const uint32_t *active_lower, *active_upper;
+    const int32_t *status;
+    const double *seed_cmd, *seed_input;
+    const double *u0, *seq_state, *seq_output, *seq_input;      // of the solved batch; seq_state only where a model output is asked for
+    const double *yref; long yref_bs, yref_ks;
+    const double *uref; long uref_bs, uref_ks;
+    const double *duref; long duref_bs, duref_ks;
+    const double *dmeas; long dmeas_bs, dmeas_ks;
+    double *d_oweight, *d_uweight, *d_duweight, *d_lower, *d_upper;
+    double *d_A, *d_B, *d_C, *d_Bd, *d_Dd;        // column-major; d_Bd / d_Dd (and c_Bd / c_Dd) are ignored without exogenous inputs
+    int32_t *flags;
+    const LmpcDev *models;                        // the bank's model structs (device array)
+    const int32_t *model_index;
+    int n_models;
+    const int32_t *group_order, *group_offsets;   // [B], [n_models + 1]
+    double *c_oweight, *c_uweight, *c_duweight, *c_lower, *c_upper, *c_A, *c_B, *c_C, *c_Bd, *c_Dd;
+    int32_t *n_used;                              // [n_models]
+};
+// m: controller 0 (dimensions; the same for every controller of a bank).  0; -2: not even a working set of one row fits the LDS plan; -3: a launch
+// or its configuration failed
+int lmpc_bank_grad_launch(const LmpcDev &m, const LmpcBankGradArgs &a, void *stream);
+
 // Parameter sensitivities of a solved batch (lmpc_param_sens.hip).  All device pointers; the references as LmpcBatchDev's accessors
 struct LmpcParamSensArgs {
     int batch;

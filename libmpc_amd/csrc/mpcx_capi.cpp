@@ -2182,6 +2182,59 @@ int mpcx_lmpc_hetero_sensitivity_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_sen
     return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
 }
 
+int mpcx_lmpc_bank_grad_size(void) { return (int)sizeof(mpcx_lmpc_bank_grad); }
+
+int mpcx_lmpc_hetero_gradient_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_bank_grad *g, const int32_t *model_index, void *stream)
+{
+    if (!f) return fail(MPCX_E_INVALID, "null bank");
+    if (!g) return fail(MPCX_E_INVALID, "null gradient descriptor");
+    const mpcx_lmpc_batch *b = g->solved;
+    if (!b) return fail(MPCX_E_INVALID, "the solved batch is required");
+    if (b->batch < 1) return fail(MPCX_E_INVALID, "batch below 1");
+    if (!g->seed_cmd && !g->seed_input) return fail(MPCX_E_INVALID, "a gradient needs seed_cmd or seed_input");
+    if (!b->active_lower || !b->active_upper) return fail(MPCX_E_INVALID, "active_lower and active_upper of the solved batch are required");
+    if (!b->x0 || !b->u0) return fail(MPCX_E_INVALID, "x0 and u0 of the solved batch are required");
+    if (!b->seq_output || !b->seq_input) return fail(MPCX_E_INVALID, "the solved batch carries no sequences: seq_output and seq_input are required");
+    const bool with_model = f->d.ndu > 0 ? (g->d_A || g->d_B || g->d_C || g->d_Bd || g->d_Dd) : (g->d_A || g->d_B || g->d_C);
+    if (with_model && !b->seq_state) return fail(MPCX_E_INVALID, "a model output needs seq_state of the solved batch");
+    if (!model_index && b->batch != f->count) return fail(MPCX_E_INVALID, "without a model index the batch must be the bank: instance b uses controller b");
+    const double *const dv[10] = {g->d_oweight, g->d_uweight, g->d_duweight, g->d_lower, g->d_upper, g->d_A, g->d_B, g->d_C, g->d_Bd, g->d_Dd};
+    const double *const cv[10] = {g->c_oweight, g->c_uweight, g->c_duweight, g->c_lower, g->c_upper, g->c_A, g->c_B, g->c_C, g->c_Bd, g->c_Dd};
+    bool sums = g->n_used != nullptr, any_d = false;
+    for (int k = 0; k < 10; ++k) {
+        if (cv[k] && !dv[k]) return fail(MPCX_E_INVALID, "a per-controller sum needs the per-instance output it adds up");
+        sums = sums || cv[k]; any_d = any_d || dv[k];
+    }
+    if (sums && (!g->group_order || !g->group_offsets)) return fail(MPCX_E_INVALID, "per-controller sums need group_order and group_offsets");
+    if (g->n_used && !g->flags && !any_d) return fail(MPCX_E_INVALID, "n_used needs flags or a per-instance output");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    // references: per instance or per step from the caller; "shared" = each controller's own, read through the model
+    const double *const own[4] = {nullptr, nullptr, nullptr, nullptr};
+    mpcx::LmpcBatchDev B;
+    const int rc = make_batch(f->d, b, own, B);
+    if (rc != MPCX_OK) return rc;
+    mpcx::LmpcBankGradArgs a{};
+    a.batch = b->batch;
+    a.active_lower = b->active_lower; a.active_upper = b->active_upper; a.status = b->status;
+    a.seed_cmd = g->seed_cmd; a.seed_input = g->seed_input;
+    a.u0 = b->u0; a.seq_state = b->seq_state; a.seq_output = b->seq_output; a.seq_input = b->seq_input;
+    a.yref = B.yref; a.yref_bs = B.yref_bs; a.yref_ks = B.yref_ks;
+    a.uref = B.uref; a.uref_bs = B.uref_bs; a.uref_ks = B.uref_ks;
+    a.duref = B.duref; a.duref_bs = B.duref_bs; a.duref_ks = B.duref_ks;
+    a.dmeas = B.dmeas; a.dmeas_bs = B.dmeas_bs; a.dmeas_ks = B.dmeas_ks;
+    a.d_oweight = g->d_oweight; a.d_uweight = g->d_uweight; a.d_duweight = g->d_duweight; a.d_lower = g->d_lower; a.d_upper = g->d_upper;
+    a.d_A = g->d_A; a.d_B = g->d_B; a.d_C = g->d_C; a.d_Bd = g->d_Bd; a.d_Dd = g->d_Dd;
+    a.flags = g->flags;
+    a.models = f->models_d; a.model_index = model_index; a.n_models = f->count;
+    a.group_order = g->group_order; a.group_offsets = g->group_offsets;
+    a.c_oweight = g->c_oweight; a.c_uweight = g->c_uweight; a.c_duweight = g->c_duweight; a.c_lower = g->c_lower; a.c_upper = g->c_upper;
+    a.c_A = g->c_A; a.c_B = g->c_B; a.c_C = g->c_C; a.c_Bd = g->c_Bd; a.c_Dd = g->c_Dd;
+    a.n_used = g->n_used;
+    const int lr = mpcx::lmpc_bank_grad_launch(f->dev0, a, stream);
+    if (lr == -2) return fail(MPCX_E_UNSUPPORTED, "problem dimensions exceed the bank gradient kernel's LDS budget");
+    return lr == 0 ? MPCX_OK : fail(MPCX_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+}
+
 int mpcx_lmpc_hetero_time_solve_batch(mpcx_lmpc_hetero_t f, const mpcx_lmpc_batch *b, const int32_t *model_index, void *stream, int repeats, float *ms_mean)
 {
     if (!f || !b || !ms_mean || repeats < 1) return fail(MPCX_E_INVALID, "bad argument");
