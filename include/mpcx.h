@@ -400,6 +400,55 @@ int mpcx_lmpc_loop_run(mpcx_lmpc_loop_t l, void *stream);
 int mpcx_lmpc_loop_destroy(mpcx_lmpc_loop_t l);
 int mpcx_lmpc_loop_desc_size(void);               /* sizeof(mpcx_lmpc_loop_desc), for bindings that mirror the struct */
 
+/* The backward pass of that loop (no reference counterpart: the reference has neither the loop nor a derivative).  Given cotangents
+ * on the logged trajectories, one run returns the gradient of sum(seed_x * traj_x) + sum(seed_u * traj_u) of the loop's last completed run with
+ * respect to the initial state and last input, the output reference, the process noise, the plant, the controller's weights and its model.
+ * The adjoint recursion runs tick ticks - 1 down to 0 with lambda_ticks = seed_x[ticks], mu_ticks = 0 and the instance's plant A_p, B_p, Bd_p:
+ *     c_k = seed_u[k] + B_p' lambda_{k+1} + mu_{k+1}               the cotangent on cmd_k (which is also lastU of tick k + 1)
+ *     (gx, gu, gy, gtheta) = the vector-Jacobian products of tick k's solve seeded with c_k     (mpcx_lmpc_sensitivity_batch in MPCX_SENS_VJP mode,
+ *                                                                   mpcx_lmpc_param_sensitivity_batch, mpcx_lmpc_model_sensitivity_batch)
+ *     lambda_k = seed_x[k] + A_p' lambda_{k+1} + gx,  mu_k = gu
+ *     d_yref += gy,  d_theta += gtheta,  d_noise[k] = lambda_{k+1},  d_plant += lambda_{k+1} [x_k; cmd_k; d_k]'
+ * and d_x0 = lambda_0, d_u0 = mu_0.  The solve of tick k is computed again, cold, from traj_x[k], traj_u[k - 1] (the loop's u0 at tick 0) and the
+ * tick's references in the loop's modes (MPCX_REF_PREVIEW: the window at row k): the QP is strictly convex, so this is the point the forward run
+ * reached, with or without carried working sets.  Nothing is taped beyond the two trajectories; memory does not grow with ticks.  A backward tick
+ * (re-solve, the VJP launches, one adjoint kernel) is captured once as a linear chain; a run is a begin kernel, `ticks` replays and a finish step,
+ * with no host work in between and nothing allocated.
+ *   reduce      d_plant, the weights and the model: 0 a set per instance [B x ..]; 1 one set, the sum over the instances whose flag is 0, added in a
+ *               fixed order without floating-point atomics (two runs give the same bits), and n_used [1] = how many those were.  d_x0, d_u0,
+ *               d_yref and d_noise are per instance always
+ *   d_yref      what mpcx_lmpc_sens.d_yref means: a shift common to all steps, and here to all ticks; exact for MPCX_REF_PER_INSTANCE
+ *   d_plant     [B x nx (nx + nu + ndu)] (reduce = 1: one row): A_p | B_p | Bd_p, each column-major -- plant_batch's layout -- whichever plant the
+ *               loop has; the controller's model enters it only as the plant, its part in the solves is d_A .. d_Dd
+ *   flags       [B]: 0, or the OR over the ticks of the codes of mpcx_lmpc_sens.  An instance with a flag has NaN in every per-instance output
+ *               and enters no sum
+ * Every output may be NULL, and what nobody asks for is not computed: no model launch without one of d_A .. d_Dd, no sequences in the re-solve
+ * without weights or model.  MPCX_E_INVALID, ahead of any look at the loop's state, for a null descriptor, both seeds NULL, and a loop that is
+ * observed, offset-free, with targets, or a bank's: those are follow-ups.  MPCX_E_STATE under the loop's own invalidation rule (a setter since
+ * its creation).  `stream` of create: any non-default stream (one plain backward tick and the capture).  _run comes after a completed
+ * mpcx_lmpc_loop_run of the loop, on the same stream or synchronised with it; it uses the handle's one workspace and overwrites the loop's private
+ * solve buffers, not its trajectories: the concurrency rule of mpcx_lmpc_loop_run holds.  The seeds and the trajectories are read again by every
+ * run: refill them in place.  Destroy the gradient before its loop.
+ * Not differentiated: bounds, soft weights, the terminal weight, the coefficients of scalar and linear rows, dmeas, uref.  Banks and loops with an
+ * estimator have no backward pass yet. */
+typedef struct mpcx_lmpc_loop_grad_desc {
+    const double *seed_x;        /* device [(ticks+1) x B x nx] or NULL */
+    const double *seed_u;        /* device [ticks x B x nu] or NULL (not both NULL) */
+    int reduce;                  /* plant / weights / model: 0 per instance [B x ..], 1 summed over the instances with flag 0 */
+    double *d_x0, *d_u0, *d_yref;                     /* [B x nx], [B x nu], [B x ny] */
+    double *d_noise;                                  /* [ticks x B x nx] */
+    double *d_plant;                                  /* plant_batch's layout per instance: A | B | Bd, each column-major */
+    double *d_oweight, *d_uweight, *d_duweight;       /* layouts of mpcx_lmpc_param_sens */
+    double *d_A, *d_B, *d_C, *d_Bd, *d_Dd;            /* layouts of mpcx_lmpc_model_sens */
+    int32_t *flags;                                   /* [B]: 0, or the OR over ticks of the codes of mpcx_lmpc_sens */
+    int32_t *n_used;                                  /* [1], reduce = 1 */
+} mpcx_lmpc_loop_grad_desc;
+typedef struct mpcx_lmpc_loop_grad *mpcx_lmpc_loop_grad_t;
+int mpcx_lmpc_loop_grad_create(mpcx_lmpc_loop_t l, const mpcx_lmpc_loop_grad_desc *g, void *stream, mpcx_lmpc_loop_grad_t *out);
+int mpcx_lmpc_loop_grad_run(mpcx_lmpc_loop_grad_t g, void *stream);   /* after a completed mpcx_lmpc_loop_run of l, same stream or synchronised */
+int mpcx_lmpc_loop_grad_destroy(mpcx_lmpc_loop_grad_t g);
+int mpcx_lmpc_loop_grad_desc_size(void);          /* sizeof(mpcx_lmpc_loop_grad_desc), for bindings that mirror the struct */
+
 /* Output feedback for that loop (no reference counterpart: the reference has neither the loop nor an observer; its examples hand optimize() the
  * plant's state).  An observed loop carries the true state x and an estimate xhat per instance; the solve of tick k reads xhat_k and u_{k-1}, and
  * the advance kernel computes, everything from tick-k data (predictor form, so every reference and dmeas mode works unchanged):

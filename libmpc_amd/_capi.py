@@ -60,6 +60,13 @@ class LoopDesc(C.Structure):
                 ("plant_batch", C.c_void_p)]
 
 
+class LoopGradDesc(C.Structure):
+    """mpcx_lmpc_loop_grad_desc: the backward pass of a plain closed loop (device pointers throughout)"""
+    _fields_ = ([("seed_x", C.c_void_p), ("seed_u", C.c_void_p), ("reduce", C.c_int)] +
+                [("d_" + n, C.c_void_p) for n in ("x0", "u0", "yref", "noise", "plant", "oweight", "uweight", "duweight", "A", "B", "C", "Bd", "Dd")] +
+                [("flags", C.c_void_p), ("n_used", C.c_void_p)])
+
+
 class ObserverDesc(C.Structure):
     """mpcx_lmpc_observer_desc: the observer of an observed loop (gain is a host pointer, everything else device pointers)"""
     _fields_ = [("gain", C.c_void_p), ("gain_batch", C.c_void_p), ("xhat0", C.c_void_p), ("meas_noise", C.c_void_p),
@@ -138,6 +145,7 @@ EXPORTS = [
     "mpcx_lmpc_model_sensitivity_batch", "mpcx_lmpc_model_sens_size", "mpcx_lmpc_model_sens_reserve", "mpcx_lmpc_model_sensitivity_host", "mpcx_lmpc_solve_host", "mpcx_lmpc_get_info", "mpcx_version",
     "mpcx_lmpc_graph_create", "mpcx_lmpc_graph_launch", "mpcx_lmpc_graph_destroy",
     "mpcx_lmpc_loop_create", "mpcx_lmpc_loop_run", "mpcx_lmpc_loop_destroy", "mpcx_lmpc_loop_desc_size",
+    "mpcx_lmpc_loop_grad_create", "mpcx_lmpc_loop_grad_run", "mpcx_lmpc_loop_grad_destroy", "mpcx_lmpc_loop_grad_desc_size",
     "mpcx_lmpc_loop_create_observed", "mpcx_lmpc_hetero_loop_create_observed", "mpcx_lmpc_observer_desc_size", "mpcx_lmpc_kalman_gain",
     "mpcx_lmpc_loop_create_offset_free", "mpcx_lmpc_hetero_loop_create_offset_free", "mpcx_lmpc_disturbance_observer_desc_size",
     "mpcx_lmpc_loop_create_offset_free_target", "mpcx_lmpc_hetero_loop_create_offset_free_target", "mpcx_lmpc_target_desc_size",
@@ -262,6 +270,9 @@ def lib():
         _lib.mpcx_lmpc_kalman_gain.argtypes = [C.c_void_p] * 6
         _lib.mpcx_lmpc_loop_run.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_loop_destroy.argtypes = [C.c_void_p]
+        _lib.mpcx_lmpc_loop_grad_create.argtypes = [C.c_void_p] * 4
+        _lib.mpcx_lmpc_loop_grad_run.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mpcx_lmpc_loop_grad_destroy.argtypes = [C.c_void_p]
         _lib.mpcx_lmpc_loop_debug_replay.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_lmpc_loop_debug_tick.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mpcx_nlmpc_get_dims.argtypes = [C.c_void_p, C.c_void_p]

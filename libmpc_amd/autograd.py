@@ -31,7 +31,16 @@ the rules of lmpc_cmd_params hold.
 is the fleet's version of the three: K controllers, instance b solved by controller model[b], every parameter tensor with K in front.  Forward
 sets the given tensors on every controller, builds a fresh bank (LMPCHetero) from them and solves; backward is one vector-Jacobian launch
  and one of LMPCHetero.gradientBatch with per_controller=True, whose per-controller rows are the gradients
-of the K-leading tensors."""
+of the K-leading tensors.
+
+    traj_x, traj_u = lmpc_closed_loop(controller, x0, u0, ticks, yref=..., plant=..., noise=..., OWeight=..., A=..., ...)
+
+is the closed loop itself: `ticks` receding-horizon steps on the device (LMPC.make_loop / run_loop), differentiable with respect to every tensor
+argument.  Forward applies the given weights and model under the rules of lmpc_cmd_params / lmpc_cmd_model, builds the loop and runs it; backward
+is one LMPC.run_loop_gradient -- `ticks` graph replays of "re-solve, vector-Jacobian launches, adjoint kernel", no autograd node
+per tick and nothing taped beyond the two trajectories.  What a loss on a closed-loop trajectory needs: tuning weights against a tracking cost,
+fitting the controller's model or identifying the plant from logged runs, the sensitivity of a closed-loop cost to the initial state or the
+process noise."""
 from __future__ import annotations
 
 _FUNCTION = None
@@ -264,6 +273,127 @@ def lmpc_cmd_fleet(controllers, x0, u0, yref, model=None, OWeight=None, UWeight=
     params = [as_t(t) for t in (OWeight, UWeight, DeltaUWeight, A, B, C, Bd, Dd)]
     cmd, status = _fleet_function().apply(controllers, (model,), int(device), x0, u0, yref, *params)
     return (cmd, status) if return_status else cmd
+
+
+_LOOP_FUNCTION = None
+_LOOP_WANT = ("x0", "u0", "yref", "plant", "plant", "plant", "noise", "oweight", "uweight", "duweight", "A", "B", "C", "Bd", "Dd")
+
+
+class _LoopHolder:
+    """the loop of a forward pass and the gradient object of its backward pass: destroyed with the graph that keeps them"""
+
+    def __init__(self, controller, loop):
+        self.controller, self.loop, self.gradient = controller, loop, None
+
+    def close(self):
+        if self.gradient is not None:
+            self.controller.destroy_loop_gradient(self.gradient)
+            self.gradient = None
+        if self.loop is not None:
+            self.controller.destroy_loop(self.loop)
+            self.loop = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _loop_function():
+    global _LOOP_FUNCTION
+    if _LOOP_FUNCTION is not None:
+        return _LOOP_FUNCTION
+    import torch
+
+    class LmpcClosedLoop(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, controller, ticks, loop_kw, x0, u0, yref, pA, pB, pBd, noise, ow, uw, dw, A, B, Cm, Bd, Dd):
+            host = lambda t: t.detach().cpu().numpy()
+            if ow is not None and not controller.setObjectiveWeights(host(ow), host(uw), host(dw)):
+                raise ValueError("lmpc_closed_loop: the controller refused the weights")
+            if A is not None and not controller.setStateSpaceModel(host(A), host(B), host(Cm)):
+                raise ValueError("lmpc_closed_loop: the controller refused the model")
+            if Bd is not None and not controller.setDisturbances(host(Bd), host(Dd)):
+                raise ValueError("lmpc_closed_loop: the controller refused the disturbance matrices")
+            controller.setup()
+            det = lambda t: None if t is None else t.detach()
+            per_instance = pA is not None and pA.dim() == 3
+            kw = dict(loop_kw)
+            if pA is not None:
+                triple = (det(pA), det(pB), det(pBd))
+                if per_instance:
+                    kw["plants"] = triple
+                else:
+                    kw["plant"] = tuple(None if t is None else host(t) for t in triple)
+            loop = controller.make_loop(det(x0), det(u0), ticks, yref=det(yref), noise=det(noise), **kw)
+            ctx.holder = _LoopHolder(controller, loop)
+            ctx.per_instance = per_instance
+            controller.run_loop(loop)
+            torch.cuda.current_stream(controller.device).synchronize()
+            ctx.status = loop.result.status
+            return loop.result.x.clone(), loop.result.u.clone()
+
+        @staticmethod
+        def backward(ctx, grad_x, grad_u):
+            hold = ctx.holder
+            c = hold.controller
+            need = ctx.needs_input_grad[3:]
+            want = tuple(sorted({n for n, k in zip(_LOOP_WANT, need) if k}))
+            reduce = not ctx.per_instance
+            seed_x = None if grad_x is None else grad_x.contiguous()
+            seed_u = None if grad_u is None else grad_u.contiguous()
+            try:
+                r = hold.gradient = c.make_loop_gradient(hold.loop, seed_x=seed_x, seed_u=seed_u, reduce=reduce, want=want)
+                c.run_loop_gradient(r)
+                torch.cuda.current_stream(c.device).synchronize()
+            finally:
+                hold.close()
+            ctx.gradient = r                                   # (testing aid: what the run returned)
+            if reduce:
+                shared = lambda t: t
+            else:                                              # a set per instance: the shared tensors' gradients are sums over the instances with flag 0
+                ok = (r.flags == 0)
+                shared = lambda t: None if t is None else torch.where(ok.view(-1, 1, 1), t, torch.zeros_like(t)).sum(dim=0)
+            outs = (r.d_x0, r.d_u0, r.d_yref, r.d_plant_A, r.d_plant_B, r.d_plant_Bd, r.d_noise,
+                    shared(r.d_oweight), shared(r.d_uweight), shared(r.d_duweight), shared(r.d_A), shared(r.d_B), shared(r.d_C), shared(r.d_Bd), shared(r.d_Dd))
+            return (None, None, None) + tuple(g if k else None for g, k in zip(outs, need))
+
+    _LOOP_FUNCTION = LmpcClosedLoop
+    return _LOOP_FUNCTION
+
+
+def lmpc_closed_loop(controller, x0, u0, ticks, yref=None, plant=None, noise=None, OWeight=None, UWeight=None, DeltaUWeight=None,
+                     A=None, B=None, C=None, Bd=None, Dd=None, **loop_kw):
+    """(traj_x [ticks+1, B, nx], traj_u [ticks, B, nu]) of `ticks` closed-loop steps of `controller` (a libmpc_amd.LMPC) from x0 [B, nx] and the
+    last input u0 [B, nu], differentiable with respect to every tensor argument: x0, u0, the per-instance output reference yref [B, ny], the
+    process noise [ticks, B, nx], the plant, the weights OWeight [ny, ph], UWeight, DeltaUWeight [nu, ph] (all three or none) and the controller's
+    model A, B, C (all three or none), Bd, Dd (both or none).  plant = (A_p, B_p) or (A_p, B_p, Bd_p): [nx, .] one plant for the batch, its
+    gradient summed over the instances, or [B, nx, .] a plant per instance; None: the controller's own model -- and where A, B (Bd) are given they
+    are then the plant as well, so their gradients are the sum of the model's part and the plant's.  The gradients of plant and controller model are
+    separate outputs of the backward pass even when one tensor is passed for both; autograd adds them.  The gradients of shared tensors are sums
+    over the instances whose flag is 0; an instance that was not solved at some tick has NaN in its per-instance gradients.  loop_kw: further
+    arguments of LMPC.make_loop (uref, duref, dmeas, preview, warm), not differentiated.  The controller keeps the weights and the model
+    afterwards; call backward before it is changed again (the rules of lmpc_cmd_params)."""
+    import torch
+    _, dev = controller._torch()
+    as_t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64)).to(device=dev, dtype=torch.float64)
+    for group, what in (((OWeight, UWeight, DeltaUWeight), "OWeight, UWeight and DeltaUWeight"), ((A, B, C), "A, B and C"), ((Bd, Dd), "Bd and Dd")):
+        if any(t is None for t in group) and not all(t is None for t in group):
+            raise ValueError("lmpc_closed_loop: %s go together" % what)
+    for k in ("plant", "plants", "observer", "disturbance_observer", "target", "noise", "yref"):
+        if k in loop_kw:
+            raise ValueError("lmpc_closed_loop: %s= is not a loop_kw of this function" % k)
+    yref = as_t(yref)
+    if yref is not None and yref.dim() != 2 and yref.requires_grad:
+        raise ValueError("lmpc_closed_loop differentiates a per-instance output reference [B, ny]; a per-step reference has no gradient here")
+    if plant is None and A is not None:
+        plant = (A, B, Bd)
+    pA, pB, pBd = (tuple(plant) + (None,) * 3)[:3] if plant is not None else (None, None, None)
+    if plant is not None and (pA is None or pB is None):
+        raise ValueError("lmpc_closed_loop: plant is (A_p, B_p) or (A_p, B_p, Bd_p)")
+    return _loop_function().apply(controller, int(ticks), loop_kw, as_t(x0), as_t(u0), yref, as_t(pA), as_t(pB), as_t(pBd), as_t(noise),
+                                  as_t(OWeight), as_t(UWeight), as_t(DeltaUWeight), as_t(A), as_t(B), as_t(C), as_t(Bd), as_t(Dd))
 
 
 def lmpc_cmd(controller, x0, u0, yref=None, return_status=False, model=None):

@@ -405,6 +405,45 @@ int lmpc_loop_pack_plants(const LmpcLoopDev &L, void *stream);   // head of ever
 int lmpc_loop_pack_observer(const LmpcLoopDev &L, void *stream);  // head of every run of an observed loop, behind lmpc_loop_pack_plants: fills every other block the loop has
 int lmpc_loop_advance(const LmpcLoopDev &L, void *stream);
 
+// The backward pass of a plain closed loop (lmpc_loop_grad.hip): everything its kernels touch.  All device pointers; the same
+// struct at every backward tick.  The loop's own fields are copies of LmpcLoopDev's.
+constexpr int kLoopGradSlots = 8;                 // d_oweight, d_uweight, d_duweight, d_A, d_B, d_C, d_Bd, d_Dd
+struct LmpcLoopGradDev {
+    int batch, ticks, nx, nu, ndu, ny, ph;
+    int ipw, sg;                                  // instances per wavefront of the per-instance form; LDS stride of an instance's [lam | x | cmd | d | lam' | mu]
+    const double *plant;                          // the one plant for the batch, row-major per matrix (read by scalar loads) ...
+    const double *pk;                             // ... or the packed plant block of the loop's last run (null: the one plant)
+    const double *traj_x, *traj_u, *u0;           // the loop's logged trajectories and the caller's last input
+    const double *dmeas; long d_bs, d_tick;       // d_k as the loop reads it
+    double *x, *u;                                // what the re-solve reads as x0 / u0: staged from the trajectories
+    const double *pv_src[4]; double *pv_dst[4]; int pv_n[4];      // the loop's preview windows
+    const double *seed_x, *seed_u;                // [(ticks + 1) x B x nx], [ticks x B x nu]; either may be null
+    double *lam, *mu, *c;                         // lambda_{k+1} [B x nx], mu_{k+1} [B x nu], the cotangent on cmd_k [B x nu]
+    const double *gx, *gu, *gy;                   // the tick's vector-Jacobian products [B x nx], [B x nu], [B x ny]
+    const int32_t *tflags; int ntf;               // the tick's flags, [ntf x B]: one row per launch of the tick
+    const double *tick_out[kLoopGradSlots];       // the tick's per-instance weight and model gradients [B x len] (null: not asked for) ...
+    double *acc[kLoopGradSlots]; int len[kLoopGradSlots];         // ... and what they are added into
+    double *a_yref, *a_plant;                     // [B x ny], [B x nx (nx + nu + ndu)] accumulators, or null
+    double *d_noise, *d_x0, *d_u0;                // [ticks x B x nx], [B x nx], [B x nu], or null
+    int32_t *flags;                               // [B]: the OR over the ticks
+    int *state;                                   // [tick, blocks of the running adjoint kernel that are through]
+};
+// the reduced form's sums over the instances whose flag is 0: up to five arrays [B x len] -> partials [groups x plen] -> dst, the count last
+struct LmpcLoopGradSum {
+    const double *src[5]; double *dst[5]; int len[5];
+    const int32_t *flags; int batch;
+    double *part; int32_t *n_used;
+};
+constexpr int kLoopGradGroup = 64;                // instances a workgroup of the partial sums adds up
+inline size_t lmpc_loop_grad_plen(const LmpcLoopGradSum &s) { size_t n = 1; for (int k = 0; k < 5; ++k) n += (size_t)s.len[k]; return n; }
+inline size_t lmpc_loop_grad_groups(int batch) { return (size_t)((batch + kLoopGradGroup - 1) / kLoopGradGroup); }
+void lmpc_loop_grad_plan_lds(LmpcLoopGradDev &G); // fills sg (nx, nu, ndu before the call)
+int lmpc_loop_grad_prepare(const LmpcLoopGradDev &G);             // once per handle, outside any capture: 0, -2 (tiles larger than a CU's LDS), -3
+int lmpc_loop_grad_begin(const LmpcLoopGradDev &G, void *stream);
+int lmpc_loop_grad_adjoint(const LmpcLoopGradDev &G, void *stream);
+int lmpc_loop_grad_finish(const LmpcLoopGradDev &G, void *stream);                 // d_x0, d_u0, and NaN for the flagged instances
+int lmpc_loop_grad_sum(const LmpcLoopGradSum &s, void *stream);                     // 0, -3
+
 // Steady-state target maps (target_kernels.hip): the KKT system of each instance's target, one instance per wavefront, and the product with a map
 size_t target_map_lds_bytes(int nx, int nu, int ndu, int ny);         // the augmented matrix [K | rhs] of one instance
 // 0; -2: the augmented matrix exceeds lds_limit; -3: a launch or its configuration failed

@@ -1121,6 +1121,8 @@ struct mpcx_lmpc_loop {
     mpcx::LmpcLoopDev L{};
     hipGraphExec_t first = nullptr, next = nullptr;   // tick 0; every later tick (null: the same graph serves all)
     char *slab = nullptr;                        // every private buffer of the loop, one allocation
+    mpcx_lmpc_batch step{};                      // the cold step's descriptor and the loop's kind: what a backward pass (mpcx_lmpc_loop_grad_*) starts from
+    bool plain = true;
     ~mpcx_lmpc_loop()
     {
         if (first) (void)hipGraphExecDestroy(first);
@@ -1459,6 +1461,7 @@ static int loop_build(mpcx_lmpc_t h, mpcx_lmpc_hetero_t f, const int32_t *model_
 
     // the step's descriptors: tick 0 solves cold, the later ticks with the carried working sets
     const mpcx_lmpc_batch cold = step_descriptor(p, L, r);
+    l->step = cold; l->plain = !p.observed;
     mpcx_lmpc_batch warm = cold;
     warm.warm_active_lower = L.warm_lower; warm.warm_active_upper = L.warm_upper; warm.warm_shift = 1;
     const bool two = d->carry_working_set && d->ticks > 1;
@@ -1710,6 +1713,192 @@ int mpcx_lmpc_loop_destroy(mpcx_lmpc_loop_t l)
     if (!l) return MPCX_OK;
     (void)hipSetDevice(l->device);
     delete l;
+    return MPCX_OK;
+}
+
+// ---- the backward pass of the plain closed loop ---------------------------------------------------------------------
+// A backward tick is the owner's cold solve on the loop's own x / u buffers (staged from the trajectories by the begin and adjoint kernels), the VJP
+// launch seeded with the handle's c buffer, where asked for the weight and model launches (reduce = 0, into per-tick buffers), and
+// lmpc_loop_grad_adjoint; captured once as a linear chain on one stream.  A run is "begin kernel, the tick graph `ticks` times, finish kernel,
+// and with reduce = 1 the ordered sums".
+struct mpcx_lmpc_loop_grad {
+    mpcx_lmpc_loop_t loop = nullptr;
+    int device = 0;
+    mpcx::LmpcLoopGradDev G{};
+    mpcx::LmpcLoopGradSum sums[2] = {};          // reduce = 1: plant and weights; the model
+    bool sum[2] = {false, false};
+    hipGraphExec_t tick = nullptr;
+    char *slab = nullptr;
+    // what the tick's launches are given: the descriptors live as long as the handle (the weight and model descriptors point to `solve`)
+    mpcx_lmpc_batch solve{};
+    mpcx_lmpc_sens sens{};
+    mpcx_lmpc_param_sens param{};
+    mpcx_lmpc_model_sens model{};
+    bool want_param = false, want_model = false;
+    ~mpcx_lmpc_loop_grad()
+    {
+        if (tick) (void)hipGraphExecDestroy(tick);
+        if (slab) (void)hipFree(slab);
+    }
+    // the launches of one backward tick on `s`
+    int chain(void *s) const
+    {
+        int rc = mpcx_lmpc_solve_batch(loop->owner, &solve, s);
+        if (rc == MPCX_OK) rc = mpcx_lmpc_sensitivity_batch(loop->owner, &sens, s);
+        if (rc == MPCX_OK && want_param) rc = mpcx_lmpc_param_sensitivity_batch(loop->owner, &param, s);
+        if (rc == MPCX_OK && want_model) rc = mpcx_lmpc_model_sensitivity_batch(loop->owner, &model, s);
+        if (rc == MPCX_OK && mpcx::lmpc_loop_grad_adjoint(G, s) != 0) rc = fail(MPCX_E_DEVICE, "launch of the adjoint kernel failed");
+        return rc;
+    }
+};
+
+int mpcx_lmpc_loop_grad_desc_size(void) { return (int)sizeof(mpcx_lmpc_loop_grad_desc); }
+
+int mpcx_lmpc_loop_grad_create(mpcx_lmpc_loop_t l, const mpcx_lmpc_loop_grad_desc *d, void *stream, mpcx_lmpc_loop_grad_t *out)
+{
+    if (!l || !out) return fail(MPCX_E_INVALID, "null argument");
+    if (!d) return fail(MPCX_E_INVALID, "null gradient descriptor");
+    if (!d->seed_x && !d->seed_u) return fail(MPCX_E_INVALID, "a loop gradient needs seed_x or seed_u");
+    if (d->reduce != 0 && d->reduce != 1) return fail(MPCX_E_INVALID, "reduce must be 0 or 1");
+    if (l->bank) return fail(MPCX_E_INVALID, "a bank's loop has no backward pass yet (a follow-up): create the gradient on a controller's plain loop");
+    if (!l->plain) return fail(MPCX_E_INVALID, "an observed, offset-free or target loop has no backward pass yet (a follow-up): the estimator's adjoint is not built");
+    if (!stream) return fail(MPCX_E_INVALID, "a loop gradient is captured on a non-default stream");
+    int rc = loop_usable(l);
+    if (rc != MPCX_OK) return rc;
+    mpcx_lmpc_t h = l->owner;
+    const mpcx::LmpcLoopDev &L = l->L;
+    const mpcx_dims &dm = h->ctl.d;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    std::unique_ptr<mpcx_lmpc_loop_grad> g(new mpcx_lmpc_loop_grad);
+    g->loop = l; g->device = l->device;
+    mpcx::LmpcLoopGradDev &G = g->G;
+    G.batch = L.batch; G.ticks = L.ticks; G.nx = L.nx; G.nu = L.nu; G.ndu = L.ndu; G.ny = L.ny; G.ph = L.ph; G.ipw = L.ipw;
+    mpcx::lmpc_loop_grad_plan_lds(G);
+    G.plant = L.plant; G.pk = L.pk; G.traj_x = L.traj_x; G.traj_u = L.traj_u; G.u0 = L.u0;
+    G.dmeas = L.dmeas; G.d_bs = L.d_bs; G.d_tick = L.d_tick; G.x = L.x; G.u = L.u;
+    for (int a = 0; a < 4; ++a) { G.pv_src[a] = L.pv_src[a]; G.pv_dst[a] = L.pv_dst[a]; G.pv_n[a] = L.pv_n[a]; }
+    G.seed_x = d->seed_x; G.seed_u = d->seed_u;
+    G.d_noise = d->d_noise; G.d_x0 = d->d_x0; G.d_u0 = d->d_u0; G.a_yref = d->d_yref;
+
+    // the slots: the three weights, the five matrices (Bd and Dd only with exogenous inputs)
+    const size_t B = (size_t)L.batch;
+    const int nx = dm.nx, nu = dm.nu, ndu = dm.ndu, ny = dm.ny, ph = dm.ph;
+    double *const user[mpcx::kLoopGradSlots] = {d->d_oweight, d->d_uweight, d->d_duweight, d->d_A, d->d_B, d->d_C, ndu > 0 ? d->d_Bd : nullptr, ndu > 0 ? d->d_Dd : nullptr};
+    const int len[mpcx::kLoopGradSlots] = {ny * ph, nu * ph, nu * ph, nx * nx, nx * nu, ny * nx, nx * ndu, ny * ndu};
+    const int plen = nx * (nx + nu + ndu);
+    g->want_param = user[0] || user[1] || user[2];
+    g->want_model = user[3] || user[4] || user[5] || user[6] || user[7];
+    const bool seq = g->want_param || g->want_model;
+    const bool reduce = d->reduce == 1;
+
+    // the handle's buffers, one allocation (LoopSlab: sized in a first pass, handed out in a second)
+    double *tick_out[mpcx::kLoopGradSlots] = {}, *acc[mpcx::kLoopGradSlots] = {}, *a_plant = nullptr, *gx = nullptr, *gu = nullptr, *gy = nullptr;
+    double *seq_state = nullptr, *seq_output = nullptr, *seq_input = nullptr, *part[2] = {nullptr, nullptr};
+    int32_t *tflags = nullptr, *flags = nullptr;
+    auto carve = [&](LoopSlab &sl) {
+        G.lam = sl.take<double>(B * nx); G.mu = sl.take<double>(B * nu); G.c = sl.take<double>(B * nu);
+        gx = sl.take<double>(B * nx); gu = sl.take<double>(B * nu); gy = sl.take<double>(B * ny);
+        tflags = sl.take<int32_t>(3 * B);
+        flags = d->flags ? d->flags : sl.take<int32_t>(B);
+        G.state = sl.take<int>(2);
+        for (int k = 0; k < mpcx::kLoopGradSlots; ++k) {
+            if (!user[k]) continue;
+            tick_out[k] = sl.take<double>(B * len[k]);
+            acc[k] = reduce ? sl.take<double>(B * len[k]) : user[k];
+        }
+        if (d->d_plant) a_plant = reduce ? sl.take<double>(B * plen) : d->d_plant;
+        if (seq) {
+            seq_state = sl.take<double>(B * (ph + 1) * nx); seq_output = sl.take<double>(B * (ph + 1) * ny); seq_input = sl.take<double>(B * (ph + 1) * nu);
+        }
+        if (reduce) {
+            const size_t groups = mpcx::lmpc_loop_grad_groups(L.batch);
+            part[0] = sl.take<double>(groups * (size_t)(1 + plen + len[0] + len[1] + len[2]));
+            part[1] = sl.take<double>(groups * (size_t)(1 + len[3] + len[4] + len[5] + len[6] + len[7]));
+        }
+    };
+    LoopSlab slab;
+    carve(slab);
+    if (hipSetDevice(g->device) != hipSuccess) return fail(MPCX_E_DEVICE, "hipSetDevice failed");
+    if (hipMalloc(reinterpret_cast<void **>(&g->slab), slab.total) != hipSuccess) { g->slab = nullptr; return fail(MPCX_E_DEVICE, "allocation of the gradient's buffers failed"); }
+    if (hipMemset(g->slab, 0, slab.total) != hipSuccess) return fail(MPCX_E_DEVICE, "hipMemset failed");
+    slab.base = g->slab; slab.total = 0;
+    carve(slab);
+    G.gx = gx; G.gu = gu; G.gy = gy; G.tflags = tflags; G.flags = flags; G.a_plant = a_plant;
+    G.ntf = 1 + (g->want_param ? 1 : 0) + (g->want_model ? 1 : 0);
+    for (int k = 0; k < mpcx::kLoopGradSlots; ++k) { G.tick_out[k] = tick_out[k]; G.acc[k] = acc[k]; G.len[k] = len[k]; }
+
+    // the tick's descriptors: the loop's cold step with its active sets (the loop's own buffers, carried or not) and, for weights and model, sequences
+    g->solve = l->step;
+    g->solve.active_lower = const_cast<uint32_t *>(L.active_lower); g->solve.active_upper = const_cast<uint32_t *>(L.active_upper);
+    g->solve.warm_active_lower = g->solve.warm_active_upper = nullptr; g->solve.warm_shift = 0;
+    g->solve.seq_state = seq_state; g->solve.seq_output = seq_output; g->solve.seq_input = seq_input;
+    g->sens.batch = L.batch; g->sens.active_lower = L.active_lower; g->sens.active_upper = L.active_upper; g->sens.status = g->solve.status;
+    g->sens.mode = MPCX_SENS_VJP; g->sens.seed_cmd = G.c;
+    g->sens.d_x0 = gx; g->sens.d_u0 = gu; g->sens.d_yref = gy; g->sens.flags = tflags;
+    int row = 1;
+    if (g->want_param) {
+        g->param.solved = &g->solve; g->param.seed_cmd = G.c; g->param.reduce = 0;
+        g->param.d_oweight = tick_out[0]; g->param.d_uweight = tick_out[1]; g->param.d_duweight = tick_out[2];
+        g->param.flags = tflags + B * row++;
+    }
+    if (g->want_model) {
+        g->model.solved = &g->solve; g->model.seed_cmd = G.c; g->model.reduce = 0;
+        g->model.d_A = tick_out[3]; g->model.d_B = tick_out[4]; g->model.d_C = tick_out[5]; g->model.d_Bd = tick_out[6]; g->model.d_Dd = tick_out[7];
+        g->model.flags = tflags + B * row++;
+        rc = mpcx_lmpc_model_sens_reserve(h, 0);     // the model launch's operand, outside the capture
+        if (rc != MPCX_OK) return rc;
+    }
+    if (reduce) {
+        mpcx::LmpcLoopGradSum &s0 = g->sums[0], &s1 = g->sums[1];
+        s0.src[0] = a_plant; s0.dst[0] = d->d_plant; s0.len[0] = a_plant ? plen : 0;
+        for (int k = 0; k < 3; ++k) { s0.src[1 + k] = acc[k]; s0.dst[1 + k] = user[k]; s0.len[1 + k] = acc[k] ? len[k] : 0; }
+        for (int k = 0; k < 5; ++k) { s1.src[k] = acc[3 + k]; s1.dst[k] = user[3 + k]; s1.len[k] = acc[3 + k] ? len[3 + k] : 0; }
+        s0.flags = s1.flags = flags; s0.batch = s1.batch = L.batch;
+        s0.part = part[0]; s1.part = part[1];
+        s0.n_used = d->n_used; s1.n_used = nullptr;
+        g->sum[0] = a_plant || g->want_param || d->n_used; g->sum[1] = g->want_model;
+    }
+
+    // one plain backward tick first (it configures the kernels, which cannot be captured), then the capture
+    const int pr = mpcx::lmpc_loop_grad_prepare(G);
+    if (pr != 0) return pr == -2 ? fail(MPCX_E_UNSUPPORTED, "the adjoint kernel's tiles exceed a compute unit's LDS") : fail(MPCX_E_DEVICE, "hipFuncSetAttribute failed");
+    if (mpcx::lmpc_loop_grad_begin(G, s) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    rc = g->chain(s);
+    if (rc != MPCX_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(MPCX_E_DEVICE, "the warm-up backward tick failed");
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return fail(MPCX_E_DEVICE, "hipStreamBeginCapture failed");
+    rc = g->chain(s);
+    hipGraph_t graph = nullptr;
+    const hipError_t ec = hipStreamEndCapture(s, &graph);
+    if (rc == MPCX_OK && (ec != hipSuccess || !graph)) rc = fail(MPCX_E_DEVICE, "hipStreamEndCapture failed");
+    if (rc == MPCX_OK && hipGraphInstantiate(&g->tick, graph, nullptr, nullptr, 0) != hipSuccess) rc = fail(MPCX_E_DEVICE, "hipGraphInstantiate failed");
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc != MPCX_OK) return rc;
+    *out = g.release();
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_loop_grad_run(mpcx_lmpc_loop_grad_t g, void *stream)
+{
+    if (!g || !g->tick) return fail(MPCX_E_INVALID, "null loop gradient");
+    int rc = loop_usable(g->loop);
+    if (rc != MPCX_OK) return rc;
+    // (the weight and model launches differentiate "the batch this handle solved last": every tick's re-solve is that batch when they run)
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (mpcx::lmpc_loop_grad_begin(g->G, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the begin kernel failed");
+    for (int k = 0; k < g->G.ticks; ++k)
+        if (hipGraphLaunch(g->tick, s) != hipSuccess) return fail(MPCX_E_DEVICE, "hipGraphLaunch failed");
+    if (mpcx::lmpc_loop_grad_finish(g->G, stream) != 0) return fail(MPCX_E_DEVICE, "launch of the finish kernel failed");
+    for (int k = 0; k < 2; ++k)
+        if (g->sum[k] && mpcx::lmpc_loop_grad_sum(g->sums[k], stream) != 0) return fail(MPCX_E_DEVICE, "launch of the ordered sums failed");
+    return MPCX_OK;
+}
+
+int mpcx_lmpc_loop_grad_destroy(mpcx_lmpc_loop_grad_t g)
+{
+    if (!g) return MPCX_OK;
+    (void)hipSetDevice(g->device);
+    delete g;
     return MPCX_OK;
 }
 

@@ -185,6 +185,42 @@ class ClosedLoopResult:
     y: "object" = None
     dhat: "object" = None
     us: "object" = None
+    gradient: "object" = None           # a LoopGradientResult (LMPC.simulate(..., gradient=dict(...)))
+
+
+@dataclass
+class LoopGradientResult:
+    """Gradients of sum(seed_x * x) + sum(seed_u * u) of a closed-loop run (mpcx_lmpc_loop_grad_*), device tensors.  Per instance
+    always: d_x0 [B, nx], d_u0 [B, nu], d_yref [B, ny] (a shift of the output reference common to all steps and ticks), d_noise [ticks, B, nx].
+    Per instance [B, ..] or, reduced, without the leading B and summed over the instances whose flag is 0 (n_used [1]: how many): the plant
+    d_plant_A [nx, nx], d_plant_B [nx, nu], d_plant_Bd [nx, ndu] (views of one tensor; None without exogenous inputs), the weights d_oweight
+    [ny, ph], d_uweight, d_duweight [nu, ph] and the controller's model d_A, d_B, d_C, d_Bd, d_Dd, indexed as their setters take them.  flags [B]:
+    0, or the OR over the ticks of SensitivityResult's codes; every per-instance entry of a flagged instance is NaN.  What was not asked for is
+    None.  handle, seed_x, seed_u: the native object and the seeds as every run reads them (refill in place)."""
+    d_x0: "object" = None
+    d_u0: "object" = None
+    d_yref: "object" = None
+    d_noise: "object" = None
+    d_plant_A: "object" = None
+    d_plant_B: "object" = None
+    d_plant_Bd: "object" = None
+    d_oweight: "object" = None
+    d_uweight: "object" = None
+    d_duweight: "object" = None
+    d_A: "object" = None
+    d_B: "object" = None
+    d_C: "object" = None
+    d_Bd: "object" = None
+    d_Dd: "object" = None
+    flags: "object" = None
+    n_used: "object" = None
+    handle: "object" = None
+    seed_x: "object" = None
+    seed_u: "object" = None
+    keep: tuple = ()
+
+
+LOOP_GRADIENT_WANT = ("x0", "u0", "yref", "noise", "plant", "oweight", "uweight", "duweight", "A", "B", "C", "Bd", "Dd")
 
 
 @dataclass
@@ -932,18 +968,101 @@ class LMPC(_LoopFrontEnd):
                                observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0,
                                target=target)
 
+    def make_loop_gradient(self, loop: Loop, seed_x=None, seed_u=None, reduce=True, want=LOOP_GRADIENT_WANT, stream=None) -> LoopGradientResult:
+        """The backward pass of a plain loop of this controller (make_loop without observer), captured for run_loop_gradient
+        (mpcx_lmpc_loop_grad_create): the gradient of sum(seed_x * x) + sum(seed_u * u) of the loop's last run.  seed_x
+        [ticks+1, B, nx], seed_u [ticks, B, nu] (one may be None) are read again by every run: refill result.seed_x / result.seed_u in place.
+        want: which of LOOP_GRADIENT_WANT to compute -- without weights and model the backward ticks keep no sequences, without a model
+        matrix they launch no model kernel.  reduce: plant, weights and model summed over the instances whose flag is 0 (in a fixed order)
+        instead of a set per instance.  Destroy the gradient (destroy_loop_gradient) before its loop."""
+        torch, dev = self._torch()
+        unknown = set(want) - set(LOOP_GRADIENT_WANT)
+        if unknown:
+            raise ValueError(f"want: unknown outputs {sorted(unknown)}")
+        T, B = loop.ticks, int(loop.result.x.shape[1])
+        sx = self._dev(torch, dev, seed_x, (T + 1, B, self.nx))
+        su = self._dev(torch, dev, seed_u, (T, B, self.nu))
+        if sx is None and su is None:
+            raise ValueError("a loop gradient needs seed_x or seed_u")
+        f64 = torch.float64
+        lead = () if reduce else (B,)
+        new = lambda name, shape: torch.zeros(shape, dtype=f64, device=dev) if (name in want and all(n > 0 for n in shape)) else None
+        # (matrices are written column-major, as their setters read them: allocated [columns, rows], handed out transposed)
+        mat = lambda name, rows, cols: new(name, lead + (cols, rows))
+        tr = lambda t: None if t is None else t.transpose(-1, -2)
+        npl = self.nx + self.nu + self.ndu
+        plant = new("plant", lead + (npl, self.nx))
+        ow, uw, dw = mat("oweight", self.ny, self.ph), mat("uweight", self.nu, self.ph), mat("duweight", self.nu, self.ph)
+        gA, gB, gC = mat("A", self.nx, self.nx), mat("B", self.nx, self.nu), mat("C", self.ny, self.nx)
+        gBd, gDd = mat("Bd", self.nx, self.ndu), mat("Dd", self.ny, self.ndu)
+        out = LoopGradientResult(
+            d_x0=new("x0", (B, self.nx)), d_u0=new("u0", (B, self.nu)), d_yref=new("yref", (B, self.ny)), d_noise=new("noise", (T, B, self.nx)),
+            d_oweight=tr(ow), d_uweight=tr(uw), d_duweight=tr(dw), d_A=tr(gA), d_B=tr(gB), d_C=tr(gC), d_Bd=tr(gBd), d_Dd=tr(gDd),
+            flags=torch.zeros((B,), dtype=torch.int32, device=dev), n_used=torch.zeros((1,), dtype=torch.int32, device=dev) if reduce else None,
+            seed_x=sx, seed_u=su)
+        if plant is not None:
+            pt = tr(plant)
+            out.d_plant_A, out.d_plant_B = pt[..., :self.nx], pt[..., self.nx:self.nx + self.nu]
+            out.d_plant_Bd = pt[..., self.nx + self.nu:] if self.ndu > 0 else None
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        d = _capi.LoopGradDesc()
+        d.seed_x, d.seed_u, d.reduce = ptr(sx), ptr(su), int(bool(reduce))
+        d.d_x0, d.d_u0, d.d_yref, d.d_noise, d.d_plant = ptr(out.d_x0), ptr(out.d_u0), ptr(out.d_yref), ptr(out.d_noise), ptr(plant)
+        d.d_oweight, d.d_uweight, d.d_duweight = ptr(ow), ptr(uw), ptr(dw)
+        d.d_A, d.d_B, d.d_C, d.d_Bd, d.d_Dd = ptr(gA), ptr(gB), ptr(gC), ptr(gBd), ptr(gDd)
+        d.flags, d.n_used = ptr(out.flags), ptr(out.n_used)
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else torch.cuda.Stream(device=dev)
+        if s.cuda_stream == 0:
+            raise ValueError("a loop gradient is captured on a non-default stream")
+        s.wait_stream(cur)
+        h = C.c_void_p()
+        check(self._lib.mpcx_lmpc_loop_grad_create(loop.handle, C.byref(d), C.c_void_p(s.cuda_stream), C.byref(h)))
+        s.synchronize()
+        out.handle = h
+        out.keep = (loop, sx, su, plant, ow, uw, dw, gA, gB, gC, gBd, gDd, s)
+        return out
+
+    def run_loop_gradient(self, gradient: LoopGradientResult, stream=None) -> LoopGradientResult:
+        """One asynchronous backward pass over the last completed run of the gradient's loop: `ticks` graph replays between a begin and a
+        finish kernel; the result's tensors are filled once the stream has been synchronised.  Streams and the one-launch-in-flight rule as
+        for run_loop."""
+        torch, _ = self._torch()
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if s.cuda_stream != cur.cuda_stream:
+            s.wait_stream(cur)
+        check(self._lib.mpcx_lmpc_loop_grad_run(gradient.handle, C.c_void_p(s.cuda_stream)))
+        return gradient
+
+    def destroy_loop_gradient(self, gradient: LoopGradientResult):
+        if gradient.handle:
+            check(self._lib.mpcx_lmpc_loop_grad_destroy(gradient.handle))
+            gradient.handle = None
+
     def simulate(self, x0, lastU, ticks, plant=None, yref=None, uref=None, duref=None, dmeas=None, preview=False,
                  noise=None, warm=True, stream=None, plants=None, observer=None, xhat0=None, meas_noise=None,
-                 disturbance_observer=None, dhat0=None, target=None) -> ClosedLoopResult:
-        """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised."""
+                 disturbance_observer=None, dhat0=None, target=None, gradient=None) -> ClosedLoopResult:
+        """make_loop + run_loop + destroy_loop: one closed-loop run, synchronised.  gradient: dict(seed_x=, seed_u=, want=, reduce=) -- the
+        backward pass of that run as well (make_loop_gradient's arguments), returned as result.gradient."""
         loop = self.make_loop(x0, lastU, ticks, plant, yref, uref, duref, dmeas, preview, noise, warm, plants=plants,
                               observer=observer, xhat0=xhat0, meas_noise=meas_noise, disturbance_observer=disturbance_observer, dhat0=dhat0,
                               target=target)
         torch, _ = self._torch()
+        grad = None
         try:
+            if gradient is not None:
+                grad = self.make_loop_gradient(loop, **gradient)
             self.run_loop(loop, stream)
+            if grad is not None:
+                self.run_loop_gradient(grad, stream)
+                loop.result.gradient = grad
             (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
         finally:
+            if grad is not None:
+                self.destroy_loop_gradient(grad)
             self.destroy_loop(loop)
         return loop.result
 
